@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the BVH-traversal + path-tracing hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|c4|big] [--single-process]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|c4|big] [--single-process] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: it builds the scene, warms up, times K steps and prints the line
+(`value`, `ms_per_step`, the config and the process group).  `--full` adds everything else the line has carried: the shader clock
+sampled during the timed steps, the untimed counting passes and the `roofline` priced with profiles/pmc_<workload>.json, the
+`film_check`, and (N=1) the `cpu_baseline` leg with its parity window; `--no-counters` / `--no-cpu-baseline` drop parts of it.
+`--dump-outputs DIR` writes the film of the last timed step (float32: X, Y, Z sums + weight per pixel) to DIR/film.npy, or, for a
+film of more than 2^20 pixels, a fixed seeded sample of 2^20 of its pixels (DIR/film_sample.npy) and their row-major pixel indices
+(DIR/film_sample_pixel_index.npy, float64).  The inputs are generated from fixed seeds, so two builds compare output for output.
+(All N GPUs from one process keep the film on the device: that path renders the same frame once more to the host for the dump.)
 
 A "step" is one pass of the hot path over the whole workload: every rank renders its 64x64
 super-tiles (one launch of render_kernel + the merge of the partial sums) and the film is gathered on
@@ -17,7 +26,7 @@ ncclGather inside the library).
 itself -- decided from argv and the environment before anything touches a GPU, no re-exec -- so the command produces a line
 however it is launched.
 
-Rank 0 prints ONE JSON line.  Every figure of `roofline` (dominant kernel = render_kernel) follows from three inputs --
+Rank 0 prints ONE JSON line.  Under --full every figure of `roofline` (dominant kernel = render_kernel) follows from three inputs --
 P = profiles/pmc_<workload>.json (the committed rocprofv3 --pmc passes of THIS kernel's ISA and builder), R = rays_per_launch
 (counted live by the exact-counter instantiation) and T = kernel_ms (HIP events on the launch stream, average of the timed
 steps) -- by one formula each:
@@ -46,7 +55,7 @@ steps) -- by one formula each:
 The per-ray counters of P belong to ONE tree: beside the kernel's machine code (P.kernel_isa_id) and the builder's name the profile
 records the production walk's fetches and triangle tests per ray on that tree (P.tree), and everything that rests on P is withheld when
 the live counting pass differs by more than 0.5 % (a builder edit changes the tree and leaves the render kernel's ISA alone: ADVICE r05).
-`cpu_baseline` (N=1): the CPU oracle timed on this box's host cores on a bounded sample of the same workload.
+`cpu_baseline` (--full, N=1): the CPU oracle timed on this box's host cores on a bounded sample of the same workload.
 """
 import argparse
 import json
@@ -110,6 +119,27 @@ def algorithmic_bytes_per_sample(st, samples, spp):
     """sum over rays of (32 B per node visited + 48 B per triangle tested)
     + 28 B camera ray + 16/spp B film store, per camera sample."""
     return (32.0 * st["nodes_visited"] + 48.0 * st["tris_tested"]) / samples + 28.0 + 16.0 / spp
+
+
+DUMP_SAMPLE_PIXELS = 1 << 20  # a larger film is dumped as this many pixels of it: 16 MB of film + 8 MB of indices
+DUMP_SAMPLE_SEED = 20260101
+
+
+def dump_outputs(out_dir, film):
+    """--dump-outputs: the film of the last timed step, whole when it has at most DUMP_SAMPLE_PIXELS pixels, else the same fixed,
+    seeded sample of its pixels on every run (and the sample's row-major pixel indices).  -> {file name: shape}"""
+    import numpy as np
+    f = np.ascontiguousarray(film, dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    px = f.reshape(-1, f.shape[-1])
+    if px.shape[0] <= DUMP_SAMPLE_PIXELS:
+        arrays = {"film": f}
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+        arrays = {"film_sample": px[idx], "film_sample_pixel_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {f"{name}.npy": list(a.shape) for name, a in arrays.items()}
 
 
 def usable_cores():
@@ -258,21 +288,31 @@ def main():
                          "path, whose multi-GPU exchange is a sum reduction instead of the gather")
     ap.add_argument("--single-process", action="store_true",
                     help="N GPUs from ONE process through pbrt_hip_multi_* (ncclGather inside the library) instead of one rank per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-counters", action="store_true", help="skip the untimed counting passes (roofline.achieved = null)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: clock sampling, the counting passes and the roofline, the film check, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film of the last timed step (or a fixed seeded sample of its pixels) to DIR as .npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline leg")
+    ap.add_argument("--no-counters", action="store_true", help="(--full) skip the untimed counting passes (roofline.achieved = null)")
     ap.add_argument("--profiles", default=os.path.join(ROOT, "profiles"), help="directory of pmc_<workload>.json (tests point it at a copy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit(f"--steps {args.steps}: at least one timed step")
+    if not args.full:  # a plain run: the headline alone
+        args.no_counters = args.no_cpu_baseline = True
 
     mode, world = launch_mode(args.gpus, args.single_process, os.environ)  # (before torch / HIP are even imported)
     in_process = mode == "in-process"
     # The identity of the profiled kernel in the library on disk -- file parsing, done HERE, before torch or HIP are imported: a profile
     # that carries the kernel's mangled symbol needs no demangler at all, an older one runs c++filt now, while no GPU is initialised
     # (no child process from a GPU-initialised process; under rocprofv3 every child inherits the profiler's preload).
-    from pbrt_amd import isa_id
-    from pbrt_amd.build import LIB_PATH
     pmc_path = os.path.join(args.profiles, f"pmc_{args.workload}.json")
-    pmc = json.load(open(pmc_path)) if os.path.exists(pmc_path) else None
-    kernel_id_loaded = isa_id.kernel_id(LIB_PATH, pmc["kernel"], pmc.get("kernel_symbol")) if pmc is not None and pmc.get("kernel") else None
+    pmc = kernel_id_loaded = None
+    if args.full:  # (the profile prices the roofline, which only --full computes)
+        from pbrt_amd import isa_id
+        from pbrt_amd.build import LIB_PATH
+        pmc = json.load(open(pmc_path)) if os.path.exists(pmc_path) else None
+        kernel_id_loaded = isa_id.kernel_id(LIB_PATH, pmc["kernel"], pmc.get("kernel_symbol")) if pmc is not None and pmc.get("kernel") else None
 
     import torch
     import torch.distributed as dist
@@ -343,7 +383,7 @@ def main():
     for _ in range(args.warmup):
         step()
     per_gpu_ms.clear()
-    clocks = ClockSampler(device_index) if rank == 0 else None
+    clocks = ClockSampler(device_index) if rank == 0 and args.full else None
     if clocks:
         clocks.start()  # (before the barrier: nothing of the sampler's start-up falls into the timed region)
     barrier()
@@ -384,9 +424,11 @@ def main():
         per_rank = pdist.rank_kernel_stats(kernel_ms, local_samples, world, "cuda" if backend == "nccl" else "cpu")
     total_samples = res * res * spp[0] * spp[1]
     value = total_samples * args.steps / elapsed / 1e6
-    if in_process:  # the host copy of the film for the checks below (outside the timed region)
+    if in_process and (args.full or args.dump_outputs):
+        # the host copy of the film for the checks and the dump below (outside the timed region; the same inputs render the same film)
         film_np, _ = scene.render(host_film=True, **kw)
         film = torch.from_numpy(film_np)
+    dumped = dump_outputs(args.dump_outputs, film.cpu().numpy()) if args.dump_outputs and film is not None else None
 
     n_simd = torch.cuda.get_device_properties(device_index).multi_processor_count * SIMDS_PER_CU
     peak = n_simd * CLOCK_GHZ  # G issue-cycles/s
@@ -536,6 +578,8 @@ def main():
                                 + "; hbm_counter_frac = that traffic / that time / 8 TB/s")
     roof["clock_ghz_measured"] = clock["ghz_median"] if clock else None
     roof["clock"] = clock
+    if not args.full:
+        roof["note"] = "plain run: kernel_ms only; the clock, the counting passes and the figures priced with the profile come with --full"
     out = {
         "metric": "Msamples/sec (rays/sec) at 1/2/4/8 GPUs; PSNR vs CPU reference",
         "value": value, "unit": "Msamples/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
@@ -570,7 +614,9 @@ def main():
             out["cpu_baseline"] = cpu_baseline(kind, n, res, integrator, depth, spp,
                                                gpu_film=film.cpu().numpy() if film is not None else None)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-        if film is not None:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if film is not None and args.full:
             import numpy as np
             f = film.cpu().numpy()
             out["film_check"] = {"weight_ok": bool((f[..., 3] == spp[0] * spp[1]).all()) if not wide else None, "finite": bool(np.isfinite(f).all()),

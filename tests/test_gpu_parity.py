@@ -1690,7 +1690,7 @@ def test_bench_withholds_a_stale_profile(gpu, tmp_path):
     pmc = {"kernel": kernel, "kernel_isa_id": "0123456789abcdef", "build_id": "some-other-source-hash", "valu_issue_quadcycles_per_ray": 100.0,
            "valu_issue_busy_measured": 0.5, "traffic_bytes_raw": 1.0, "avg_ms": 1.0, "lane_utilisation": 0.5, "l2_hit_rate": 0.7}
     (tmp_path / "pmc_c2.json").write_text(json.dumps(pmc))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--workload", "c2", "--spp", "1", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--workload", "c2", "--spp", "1", "1", "--full", "--no-cpu-baseline",
            "--profiles", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1734,6 +1734,33 @@ def test_bench_withholds_a_stale_profile(gpu, tmp_path):
     assert "stale_profile" not in roof and roof["frac"] > 0 and roof["traffic"] == (3.0 * 2.0 + 1.0) * 1024 and roof["traffic_bytes_raw"] == 4096.0
 
 
+@pytest.mark.timeout(600)
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_film(gpu, tmp_path):
+    """bench.py without --full: the headline alone (none of --full's passes, checks or baseline), --steps timed steps whose
+    ms_per_step is what `value` rests on, and --dump-outputs writes the film the last timed step computed -- the film the same
+    scene and arguments render in this process."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "c2", "--spp", "1", "1",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=500)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["metric"].startswith("Msamples/sec")
+    assert line["steps"] == 3 and line["value"] > 0 and abs(line["ms_per_step"] - 1024 * 1024 / line["value"] / 1e3) < 1e-9 * line["ms_per_step"]
+    assert "cpu_baseline" not in line and "film_check" not in line
+    assert line["roofline"]["frac"] is None and line["roofline"]["clock"] is None and "hbm" not in line["roofline"]
+    assert line["dumped_outputs"] == {"film.npy": [1024, 1024, 4]} and sorted(os.listdir(out_dir)) == ["film.npy"]
+    film = np.load(out_dir / "film.npy")
+    assert film.dtype == np.float32 and (film[..., 3] == 1).all()
+    with pbrt_amd.Scene(scenes.random_mesh_scene(100_000, 1024, 1024), device=0, builder="gpu") as sc:
+        want, _ = sc.render(integrator=INTEGRATOR_PATH, max_depth=8, spp=(1, 1), seed=0, sampler="stratified")
+    assert_bit_equal(film, want, "bench.py --dump-outputs against the same render in this process")
+
+
 @pytest.mark.timeout(900)
 def test_bench_under_torchrun_uses_rccl(gpu):
     """bench.py as the driver launches it for N > 1 -- torch.distributed.run, one rank per GPU, RCCL ("nccl") process
@@ -1749,7 +1776,7 @@ def test_bench_under_torchrun_uses_rccl(gpu):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("PBRT_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--workload", "c2", "--spp", "2", "2", "--no-cpu-baseline"]
+           os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--workload", "c2", "--spp", "2", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, env=env, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -1759,7 +1786,7 @@ def test_bench_under_torchrun_uses_rccl(gpu):
     assert len(out["per_rank_kernel_ms"]["mean_per_rank"]) == n and "exchange_ms" in out  # (every rank's kernel time: RCCL all_gather)
     if gpu.device_count() >= 2:  # and all GPUs from ONE process through the library's own ncclGather
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--single-process", "--steps", "1", "--warmup", "1",
-                            "--workload", "c2", "--spp", "2", "2", "--no-cpu-baseline"], capture_output=True, text=True, cwd=root, timeout=800)
+                            "--workload", "c2", "--spp", "2", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True, cwd=root, timeout=800)
         assert r.returncode == 0, r.stderr[-3000:]
         out2 = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert out2["film_check"]["weight_ok"] and abs(out2["film_check"]["mean_Y"] - out["film_check"]["mean_Y"]) < 1e-12
@@ -1806,7 +1833,7 @@ def test_bench_eight_ranks_share_one_gpu_under_gloo(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PBRT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1", "--master-port", "29541",
-            os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--workload", "c2", "--spp", "2", "2", "--no-cpu-baseline"]
+            os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--workload", "c2", "--spp", "2", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(base, capture_output=True, text=True, cwd=root, env=env, timeout=1000)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1821,7 +1848,7 @@ def test_bench_eight_ranks_share_one_gpu_under_gloo(gpu):
     assert sum(pr["samples_per_rank"]) == 1024 * 1024 * 4 and pr["max"] == max(pr["mean_per_rank"]) and pr["imbalance"] >= 1.0
     assert abs(out["exchange_ms"] - (out["ms_per_step"] - pr["max"])) < 1e-9 and "unmeasured" in out["scaling_note"]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--workload", "c2", "--spp", "2", "2",
-                          "--no-cpu-baseline", "--no-counters"], capture_output=True, text=True, cwd=root, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-counters"], capture_output=True, text=True, cwd=root, timeout=600)
     assert one.returncode == 0, one.stderr[-3000:]
     ref = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     assert abs(ref["film_check"]["mean_Y"] - out["film_check"]["mean_Y"]) < 1e-12  # eight shares assemble the one-rank film
@@ -1829,7 +1856,7 @@ def test_bench_eight_ranks_share_one_gpu_under_gloo(gpu):
     assert wide.returncode == 0, wide.stderr[-3000:]
     w8 = json.loads([l for l in wide.stdout.splitlines() if l.startswith("{")][-1])
     w1 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--workload", "c2", "--spp", "2", "2",
-                         "--no-cpu-baseline", "--no-counters", "--filter", "1.5", "1.5"], capture_output=True, text=True, cwd=root, timeout=600)
+                         "--full", "--no-cpu-baseline", "--no-counters", "--filter", "1.5", "1.5"], capture_output=True, text=True, cwd=root, timeout=600)
     assert w1.returncode == 0, w1.stderr[-3000:]
     w1 = json.loads([l for l in w1.stdout.splitlines() if l.startswith("{")][-1])
     assert w8["film_check"]["finite"] and abs(w8["film_check"]["mean_Y"] - w1["film_check"]["mean_Y"]) < 1e-12

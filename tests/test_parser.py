@@ -12,6 +12,7 @@ from pbrt_amd._lib import PbrtHipError
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C0 = os.path.join(ROOT, "scenes", "c0_check_sphere.pbrt")
+REF_SCENES = os.path.join(ROOT, "tests", "golden", "reference_scenes")
 
 
 def test_tokenizer():  # parser.rs:778-791
@@ -134,12 +135,12 @@ def test_c0_scene_loads():
     _expect_check_sphere(loader.load_file(C0), (400, 400))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/scenes/check-sphere.pbrt"), reason="reference tree not mounted")
 def test_reference_scene_files_load():
-    """The reference's own scene files: its parser stops at line 14 / 20 of this one."""
-    _expect_check_sphere(loader.load_file("/root/reference/scenes/check-sphere.pbrt"), (400, 400))
-    _expect_check_sphere(loader.load_file("/root/reference/src/core/testdata/scene1.pbrt"), (400, 300))
-    ls = loader.load_file("/root/reference/scenes/paramset-lookup.pbrt")
+    """The reference's own scene files (scenes/check-sphere.pbrt, src/core/testdata/scene1.pbrt, scenes/paramset-lookup.pbrt,
+    copied verbatim to tests/golden/reference_scenes/): its parser stops at line 14 / 20 of this one."""
+    _expect_check_sphere(loader.load_file(os.path.join(REF_SCENES, "check-sphere.pbrt")), (400, 400))
+    _expect_check_sphere(loader.load_file(os.path.join(REF_SCENES, "scene1.pbrt")), (400, 300))
+    ls = loader.load_file(os.path.join(REF_SCENES, "paramset-lookup.pbrt"))
     assert ls.scene.idx.shape[0] == 0
 
 

@@ -112,9 +112,17 @@ uint32_t tuning(const char *name, uint32_t dflt, long cap = 64) {
 // the shading stage should wait for more lanes (C4 +12 % over 36)
 constexpr uint32_t kMinWalkers = 36, kMinWalkersShallow = 20, kShallowStackNeed = 16, kMinParked = 16;
 // persistent one-wave workgroups of the render kernel per CU = what a CU holds at once: render_stack_plan (device_types.h:
-// 20 with up to 32 LDS rows -- 5 waves per SIMD by the kernel's 96 VGPRs --, fewer with more rows); the kernel for scenes
-// with spheres has the register budget of 3 waves per SIMD.  The grid is this x the device's CU count (hipDeviceProp_t)
+// 20 with up to 30 LDS rows -- 5 waves per SIMD by the kernel's 96 VGPRs --, fewer with more rows); the kernel for scenes
+// with spheres has the register budget of 3 waves per SIMD.  The grid is this x the device's CU count (hipDeviceProp_t;
+// render_launch)
 constexpr uint32_t kRenderWavesPerCuSpheres = 12;
+// the production walk's stack plan under the A-B knobs PBRT_HIP_FORCE_OVERFLOW_VARIANT (the overflow variant for every tree) and
+// PBRT_HIP_PREFER_LDS_STACK (the whole stack in LDS whenever it fits kQuadLdsStack rows, whatever the occupancy), read once
+RenderStackPlan stack_plan(uint32_t quad_stack_need) {
+  static const bool force_overflow = debug_knob("PBRT_HIP_FORCE_OVERFLOW_VARIANT") != nullptr;
+  static const bool prefer_lds = debug_knob("PBRT_HIP_PREFER_LDS_STACK") != nullptr;
+  return render_stack_plan(quad_stack_need, force_overflow, prefer_lds);
+}
 constexpr uint32_t kLeafRef = 0x80000000u;
 
 // A vertex that a triangle uses and that is NaN or infinite would send the builders' bucket index out of range:
@@ -1084,7 +1092,7 @@ int pbrt_hip_scene_canonical_info(const pbrt_hip_scene *s, uint32_t *ready, doub
 }
 
 int pbrt_hip_render_stack_plan(uint32_t stack_need, uint32_t *lds_rows, uint32_t *waves_per_cu, uint32_t *overflow_entries) {
-  const RenderStackPlan p = render_stack_plan(stack_need, render_force_overflow(), render_prefer_lds());
+  const RenderStackPlan p = stack_plan(stack_need);
   if (lds_rows) *lds_rows = p.rows;
   if (waves_per_cu) *waves_per_cu = p.waves_per_cu;
   if (overflow_entries) *overflow_entries = p.extra_entries;
@@ -1148,16 +1156,6 @@ static int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc
 }
 
 namespace {
-// The scratch one render of `s` needs beyond the caller's slab, sized for THIS description and (re)allocated here when what the
-// scene holds is too small: the lanes' path-state records, the partial film sums of the work items, the overflow area of the
-// walk's stack, the generator matrices of sampler 2.  pbrt_hip_render_device calls it; a host that is about to launch on several
-// GPUs calls it for every GPU FIRST (pbrt_hip_render_prepare), so that no hipMalloc -- a synchronising call -- sits between
-// the launches of a frame.
-struct RenderScratch {
-  uint32_t n_workgroups = 0, chunk_shift = 0;
-  uint32_t passes = 1;  // partials_passes
-  RenderStackPlan plan{};
-};
 // The partial film sums cost 16 K bytes per pixel of the rank's share (one float4 per item, K <= 16 chunks per pixel): 1.07 GB for C3, 4.3 GB
 // for C4's 4096^2 on one GPU, and growing with the resolution.  A frame whose sums would pass the cap (2 GiB; PBRT_HIP_PARTIALS_CAP_KB for the
 // tests) is rendered in P passes over the same buffer: pass p takes the rank's super-tiles j = p + P * j', which is exactly the share of rank
@@ -1172,19 +1170,49 @@ uint32_t partials_passes(uint32_t n_local, uint32_t n_chunks) {
   tiles = std::min<uint64_t>(tiles, ((1ull << 32) - 1) / (4096ull * n_chunks));
   return (uint32_t)((n_local + tiles - 1) / tiles);
 }
-int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGeom &fg, const Shard &sh, RenderScratch *out) {
-  const uint32_t spp = r->spp_x * r->spp_y;
-  out->chunk_shift = sample_chunk_shift(spp);
-  const uint32_t n_chunks = 1u << out->chunk_shift;  // K: DESIGN.md 3.1
-  out->passes = fg.wide ? 1u : partials_passes(sh.n_local, n_chunks);
-  const uint32_t n_pass_tiles = (sh.n_local + out->passes - 1) / out->passes;  // of pass 0, the largest
-  if ((uint64_t)n_pass_tiles * 4096u * n_chunks >= (1ull << 32)) return fail(PBRT_HIP_ERR_LIMIT, "render: film too large for 32-bit item numbers");
-  if ((uint64_t)r->world_size * out->passes >= (1ull << 32)) return fail(PBRT_HIP_ERR_LIMIT, "render: world_size x passes does not fit 32 bits");
-  // (scenes with spheres run a kernel with a bigger register budget, 3 waves per SIMD: kernels.hip)
-  out->plan = render_stack_plan(s->dev.quad_stack_need, render_force_overflow(), render_prefer_lds());
-  // (the instantiations for another filter radius and for the Sobol' sampler fit the 96 VGPRs of 5 waves per SIMD like the default one)
-  const uint32_t waves_per_cu = s->dev.n_spheres ? std::min(kRenderWavesPerCuSpheres, out->plan.waves_per_cu) : out->plan.waves_per_cu;
-  out->n_workgroups = std::min<uint32_t>(n_pass_tiles * 64u * n_chunks, std::max<uint32_t>(1u, tuning("PBRT_HIP_RENDER_WORKGROUPS", s->n_cu * waves_per_cu, 1 << 20)));
+// How one render of `s` is launched (RenderLaunch, device_types.h), decided here and nowhere else: the instantiation's switches, the
+// walk's stack, the grid, the passes and the scheduling thresholds.  The exact walk's rows follow the canonical tree, which a
+// device-built scene gets here on first use.
+int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGeom &fg, const Shard &sh, RenderLaunch *out) {
+  RenderLaunch L{};
+  L.spheres = s->dev.n_spheres > 0;
+  L.counters = (r->flags & PBRT_HIP_FLAG_COUNTERS) ? kCountExact : ((r->flags & PBRT_HIP_FLAG_WALK_COUNTERS) ? kCountWalk : kCountNone);
+  L.wide = fg.wide;
+  L.table_sampler = r->sampler == PBRT_HIP_SAMPLER_SOBOL_ND || r->sampler == PBRT_HIP_SAMPLER_HALTON;
+  L.mis = r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS;
+  L.textured = s->textured;
+  const bool shallow = s->dev.quad_stack_need <= kShallowStackNeed;
+  L.plan = stack_plan(s->dev.quad_stack_need);
+  L.lds_bytes = L.plan.rows * 256u;
+  const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured;
+  L.steps = default_path && !L.plan.overflow && shallow ? 2u : PBRT_STEPS_PER_CHECK;
+  if (L.counters == kCountExact) {
+    const int ce = ensure_canonical(s);
+    if (ce) return ce;
+    // the exact walk holds at most depth - 1 entries (refs + entry distances): the smallest of the instantiated row counts that fits
+    const uint32_t held = s->bvh.depth > 0 ? s->bvh.depth - 1 : 0;
+    L.exact_rows = held > 40 ? 64 : held > 32 ? 40 : held > 26 ? 32 : held > 20 ? 26 : 20;
+    L.lds_bytes = L.exact_rows * 512u;
+  }
+  // (the instantiations for another filter radius and for the table samplers fit the 96 VGPRs of 5 waves per SIMD like the default one)
+  L.waves_per_cu = L.spheres ? std::min(kRenderWavesPerCuSpheres, L.plan.waves_per_cu) : L.plan.waves_per_cu;
+  L.chunk_shift = sample_chunk_shift(r->spp_x * r->spp_y);
+  const uint32_t n_chunks = 1u << L.chunk_shift;  // K: DESIGN.md 3.1
+  L.passes = fg.wide ? 1u : partials_passes(sh.n_local, n_chunks);
+  L.pass_tiles = (sh.n_local + L.passes - 1) / L.passes;  // of pass 0, the largest
+  if ((uint64_t)L.pass_tiles * 4096u * n_chunks >= (1ull << 32)) return fail(PBRT_HIP_ERR_LIMIT, "render: film too large for 32-bit item numbers");
+  if ((uint64_t)r->world_size * L.passes >= (1ull << 32)) return fail(PBRT_HIP_ERR_LIMIT, "render: world_size x passes does not fit 32 bits");
+  L.n_workgroups = std::min<uint32_t>(L.pass_tiles * 64u * n_chunks, std::max<uint32_t>(1u, tuning("PBRT_HIP_RENDER_WORKGROUPS", s->n_cu * L.waves_per_cu, 1 << 20)));
+  L.min_walkers = tuning("PBRT_HIP_MIN_WALKERS", shallow ? kMinWalkersShallow : kMinWalkers);
+  L.min_parked = tuning("PBRT_HIP_MIN_PARKED", kMinParked);
+  *out = L;
+  return PBRT_HIP_OK;
+}
+// The scratch launch L needs beyond the caller's slab, (re)allocated here when what the scene holds is too small: the lanes' path-state
+// records, the partial film sums of the work items, the overflow area of the walk's stack, the generator matrices of sampler 2 and the
+// table of sampler 3.  pbrt_hip_render_device calls it; a host that is about to launch on several GPUs calls it for every GPU FIRST
+// (pbrt_hip_render_prepare), so that no hipMalloc -- a synchronising call -- sits between the launches of a frame.
+int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const RenderLaunch &L) {
   if (r->sampler == PBRT_HIP_SAMPLER_SOBOL_ND && s->d_sobol.n == 0) {
     static_assert(kSobolNdDims == 2 * (int)kSobolNdRequests, "sampler 2: two dimensions per request");
     std::vector<uint32_t> mat((size_t)kSobolNdDims * 32);
@@ -1202,18 +1230,18 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
   {
     // float4 records: 5 x 64 per one-wave workgroup (kernels.hip LaneRecords); with another box filter radius 16 x 2 x 64 more
     // behind them (kWideSlotFloat4: a chunk's sums per footprint)
-    const size_t path = (size_t)out->n_workgroups * 320, need = path + (fg.wide ? (size_t)out->n_workgroups * 2048 : 0);
+    const size_t path = (size_t)L.n_workgroups * 320, need = path + (L.wide ? (size_t)L.n_workgroups * 2048 : 0);
     if (s->d_lane_state.n < need) { s->d_lane_state.release(); HIP_TRY(s->d_lane_state.alloc(need)); }
   }
-  if (!fg.wide) {
-    const size_t need = (size_t)n_pass_tiles * 4096u * n_chunks;  // one float4 per item of a pass
+  if (!L.wide) {
+    const size_t need = (size_t)L.pass_tiles * 4096u * (1u << L.chunk_shift);  // one float4 per item of a pass
     // (C3 1.07 GB in one pass; C4's 4096^2 x 16 chunks on one GPU: 3 passes over 1.43 GB; the buffer follows the frame: released when a
     // later render needs less than a quarter of it)
     if (s->d_partials.n < need || s->d_partials.n / 4 > need) { s->d_partials.release(); HIP_TRY(s->d_partials.alloc(need)); }
   }
   {
     // the overflow variant keeps kQuadLdsStackOvf rows per lane in LDS; deeper entries (rare) go here
-    const size_t need = (size_t)out->n_workgroups * 64 * out->plan.extra_entries;
+    const size_t need = (size_t)L.n_workgroups * 64 * L.plan.extra_entries;
     if (s->d_stack_overflow.n < need) { s->d_stack_overflow.release(); HIP_TRY(s->d_stack_overflow.alloc(need)); }
   }
   return PBRT_HIP_OK;
@@ -1228,8 +1256,9 @@ int pbrt_hip_render_prepare(pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
     HIP_TRY(hipSetDevice(s->device));
     const FilmGeom fg = film_geom(s->desc, *r);
     const Shard sh = make_shard_bounds(fg.sb, r->rank, r->world_size);
-    RenderScratch rs;
-    return ensure_render_scratch(s, r, fg, sh, &rs);
+    RenderLaunch L;
+    rc = render_launch(s, r, fg, sh, &L);
+    return rc ? rc : ensure_render_scratch(s, r, L);
   } catch (const std::exception &e) {
     return fail(PBRT_HIP_ERR_INTERNAL, e.what());
   }
@@ -1253,11 +1282,11 @@ int pbrt_hip_render_device(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, voi
     R.max_lum = r->max_sample_luminance > 0.f ? r->max_sample_luminance : std::numeric_limits<float>::infinity();
     R.filter_rx = fg.rx; R.filter_ry = fg.ry;
     R.acc = fg.wide ? (unsigned long long *)d_slab : nullptr;
-    const bool sobol_nd = r->sampler == PBRT_HIP_SAMPLER_SOBOL_ND || r->sampler == PBRT_HIP_SAMPLER_HALTON;  // the table samplers' instantiation
-    RenderScratch rs;
-    rc = ensure_render_scratch(s, r, fg, sh, &rs);  // (no allocation when pbrt_hip_render_prepare ran for this description, or an earlier frame did)
+    RenderLaunch L;
+    rc = render_launch(s, r, fg, sh, &L);
+    if (!rc) rc = ensure_render_scratch(s, r, L);  // (no allocation when pbrt_hip_render_prepare ran for this description, or an earlier frame did)
     if (rc) return rc;
-    R.sobol_mat = r->sampler == PBRT_HIP_SAMPLER_HALTON ? s->d_halton.p : (sobol_nd ? s->d_sobol.p : nullptr);
+    R.sobol_mat = r->sampler == PBRT_HIP_SAMPLER_HALTON ? s->d_halton.p : (r->sampler == PBRT_HIP_SAMPLER_SOBOL_ND ? s->d_sobol.p : nullptr);
     R.tri_uv = s->d_tri_uv.p;
     R.textures = s->d_textures.p;
     R.integrator = r->integrator;
@@ -1281,46 +1310,40 @@ int pbrt_hip_render_device(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, voi
     R.spp_x_recip = recip32(r->spp_x);
     if ((uint64_t)sh.total * (uint64_t)sh.stx >= (1ull << 32))
       return fail(PBRT_HIP_ERR_LIMIT, "render: film too large for the kernel's tile arithmetic");
-    // The render kernel's waves are persistent: as many one-wave workgroups as the device holds at once (20 per CU: the
-    // LDS stack -- render_stack_plan -- and the register budget both allow 5 per SIMD), each lane drawing item after item
-    // from the rank's list.
+    // The render kernel's waves are persistent: as many one-wave workgroups as the device holds at once (render_launch), each
+    // lane drawing item after item from the rank's list.
     // An item is one CHUNK (a K-th of the samples, K <= 16 with at least 32 samples per chunk) of one pixel: DESIGN.md 3.1.
-    R.chunk_shift = rs.chunk_shift;
+    R.chunk_shift = L.chunk_shift;
     const uint32_t n_chunks = 1u << R.chunk_shift;  // K: DESIGN.md 3.1
-    R.n_workgroups = rs.n_workgroups;
+    R.n_workgroups = L.n_workgroups;
     R.next_item = reinterpret_cast<uint32_t *>(s->d_counters.p + 8);  // 8 counters, 64 bytes apart
     R.n_regions = std::min<uint32_t>(8u, std::max<uint32_t>(1u, tuning("PBRT_HIP_REGIONS", 8u, 8)));
     R.lane_state = s->d_lane_state.p;
     R.wide_slots = s->d_lane_state.p + (size_t)R.n_workgroups * 320;
     R.partials = fg.wide ? nullptr : s->d_partials.p;
     R.stack_overflow = s->d_stack_overflow.p;
-    R.stack_overflow_entries = rs.plan.extra_entries;
-    R.min_walkers = tuning("PBRT_HIP_MIN_WALKERS", s->dev.quad_stack_need <= kShallowStackNeed ? kMinWalkersShallow : kMinWalkers);
-    R.min_parked = tuning("PBRT_HIP_MIN_PARKED", kMinParked);
-    const int counters = (r->flags & PBRT_HIP_FLAG_COUNTERS) ? 1 : ((r->flags & PBRT_HIP_FLAG_WALK_COUNTERS) ? 2 : 0);
-    if (counters == 1) {  // the canonical walk: a device-built scene gets the oracle's tree now (host build, first use only)
-      const int ce = ensure_canonical(s);
-      if (ce) return ce;
-    }
+    R.stack_overflow_entries = L.plan.extra_entries;
+    R.min_walkers = L.min_walkers;
+    R.min_parked = L.min_parked;
     HIP_TRY(hipMemsetAsync(s->d_counters.p, 0, 80 * sizeof(unsigned long long), st));
     if (fg.wide && fg.crop_px()) HIP_TRY(hipMemsetAsync(d_slab, 0, fg.crop_px() * 32, st));  // this rank's accumulators start at zero
     HIP_TRY(hipEventRecord(s->ev0, st));
     // one launch per pass (one pass unless the partial sums would pass the cap: partials_passes) renders every item of the pass; the merge
     // adds each pixel's K partial sums in chunk order (a wide filter has no partial sums: its samples go straight into the accumulators)
-    for (uint32_t pass = 0; pass < rs.passes; pass++) {
-      const uint32_t n_pass = sh.n_local > pass ? (sh.n_local - pass + rs.passes - 1) / rs.passes : 0;
+    for (uint32_t pass = 0; pass < L.passes; pass++) {
+      const uint32_t n_pass = sh.n_local > pass ? (sh.n_local - pass + L.passes - 1) / L.passes : 0;
       if (n_pass == 0 && pass > 0) break;
       R.rank = r->rank + r->world_size * pass;
-      R.world = r->world_size * rs.passes;
+      R.world = r->world_size * L.passes;
       R.n_items = n_pass * 4096u * n_chunks;
       if (pass > 0)  // the hand-out positions start again; the ray counters (the first 64 bytes) run on
         HIP_TRY(hipMemsetAsync(s->d_counters.p + 8, 0, 72 * sizeof(unsigned long long), st));
-      HIP_TRY(launch_render(counters == 1 ? s->dev_exact : s->dev, R, n_pass, s->bvh.depth, counters, fg.wide, sobol_nd, st, r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS, s->textured));
-      if (!fg.wide) HIP_TRY(launch_merge(R.partials, (float4 *)d_slab, sh.w, sh.h, R.rank, R.world, n_pass, spp, st, pass, rs.passes));
+      HIP_TRY(launch_render(L.counters == kCountExact ? s->dev_exact : s->dev, R, L, st));
+      if (!fg.wide) HIP_TRY(launch_merge(R.partials, (float4 *)d_slab, sh.w, sh.h, R.rank, R.world, n_pass, spp, st, pass, L.passes));
     }
     HIP_TRY(hipEventRecord(s->ev1, st));
     s->pending = true;
-    s->pending_counters = counters != 0;
+    s->pending_counters = L.counters != kCountNone;
     // samples = pixels of this rank's super-tiles that lie inside the film
     uint64_t px = 0;
     for (uint32_t j = 0; j < sh.n_local; j++) {
@@ -1527,9 +1550,9 @@ static int ray_batch(pbrt_hip_scene *s, int64_t n, const float *o, const float *
     B.counters = s->d_counters.p;
   }
   {
-    // launch_intersect uses at most 4096 workgroups of 4 waves
-    const uint32_t extra = s->dev.quad_stack_need + 2u > kIntersectLdsStack ? s->dev.quad_stack_need + 2u - kIntersectLdsStack : 0;  // sentinel + entries beyond the kIntersectLdsStack - 1 kept in LDS
-    const size_t need = (size_t)4096 * 4 * 64 * extra;
+    // an overflow area for every wave of the largest grid launch_intersect makes
+    const uint32_t extra = intersect_overflow_entries(s->dev.quad_stack_need);
+    const size_t need = (size_t)kIntersectMaxWorkgroups * kIntersectWavesPerWorkgroup * 64 * extra;
     if (s->d_stack_overflow.n < need) { s->d_stack_overflow.release(); RB_TRY(s->d_stack_overflow.alloc(need)); }
     B.stack_overflow = s->d_stack_overflow.p;
     B.stack_overflow_entries = extra;

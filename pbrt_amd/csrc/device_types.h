@@ -35,18 +35,17 @@ inline const char *debug_knob(const char *name) {
 // the overflow variant: kQuadLdsStackOvf rows in LDS at 20 waves, deeper entries in HBM (kQuadLdsStack = the rows of the
 // ray-batch kernel, and the most the render kernel takes with PBRT_HIP_PREFER_LDS_STACK).  -DPBRT_QUAD_LDS_STACK=12 forces the overflow variant on nearly every scene (tests of that path).
 #ifdef PBRT_QUAD_LDS_STACK
-constexpr uint32_t kQuadLdsStack = PBRT_QUAD_LDS_STACK, kQuadLdsStackOvf = PBRT_QUAD_LDS_STACK, kQuadLdsStackOvfDeep = PBRT_QUAD_LDS_STACK;
+constexpr uint32_t kQuadLdsStack = PBRT_QUAD_LDS_STACK, kQuadLdsStackOvf = PBRT_QUAD_LDS_STACK;
 #else
-constexpr uint32_t kQuadLdsStack = 40, kQuadLdsStackOvf = 30, kQuadLdsStackOvfDeep = 30;
+constexpr uint32_t kQuadLdsStack = 40, kQuadLdsStackOvf = 30;
 #endif
-// Round 2 gave very deep trees (stack bound >= 42: the 12 M-triangle `big` workload has 48) a 35-row variant at 18 waves per
-// CU, on the assumption that they reach the end of a 30-row LDS part often.  They do not: the bound is a worst case that
-// walks do not come near (tools/walk_sim.py with ORC_WALK_STACK_IN_TRIS: a ray's deepest stack in the 12 M-triangle tree is
-// 8.5 entries on average, 19 at the 99.9th percentile, 23 at most over 40 000 rays; 1 M triangles: 7.6 / 17 / 20), so the
-// HBM overflow area is a safety net, not a path; and more resident waves help this latency-bound workload (r03q / r03r:
-// 20 waves with 30 rows 217 ms, 18 waves with 35 rows 219 ms, 16 waves 224 ms).  The deep variant is therefore the same
-// 30 rows (kept as a name so that a different choice stays a one-line change).
-constexpr uint32_t kOvfDeepNeed = 42;
+// Every tree that takes the overflow variant gets the same kQuadLdsStackOvf rows.  Round 2 gave very deep trees (stack bound
+// >= 42: the 12 M-triangle `big` workload has 48) a 35-row variant at 18 waves per CU, on the assumption that they reach the
+// end of a 30-row LDS part often.  They do not: the bound is a worst case that walks do not come near (tools/walk_sim.py with
+// ORC_WALK_STACK_IN_TRIS: a ray's deepest stack in the 12 M-triangle tree is 8.5 entries on average, 19 at the 99.9th
+// percentile, 23 at most over 40 000 rays; 1 M triangles: 7.6 / 17 / 20), so the HBM overflow area is a safety net, not a
+// path; and more resident waves help this latency-bound workload (r03q / r03r: 20 waves with 30 rows 217 ms, 18 waves with
+// 35 rows 219 ms, 16 waves 224 ms).
 constexpr uint32_t kLdsGranule = 1280u;
 constexpr uint32_t kLdsBytesPerCu = 160u * 1024u;
 // float4 per triangle record in `tris`: {p0, id}{p1, material}{p2, 0} + one of padding -- a 64-byte record never straddles
@@ -55,6 +54,11 @@ constexpr uint32_t kLdsBytesPerCu = 160u * 1024u;
 #define PBRT_TRI_STRIDE 4
 #endif
 constexpr uint32_t kTriStride = PBRT_TRI_STRIDE;
+// node steps of the production walk between two scheduling checks (kernels.hip trav_run): 3 for deep trees (C3 +1 %, C2 +2 % over
+// 2); the default path takes 2 in shallow trees, whose walks are a few steps long (capi.cpp render_launch; C4: 3 would cost 5 %)
+#ifndef PBRT_STEPS_PER_CHECK
+#define PBRT_STEPS_PER_CHECK 3
+#endif
 #ifndef PBRT_RENDER_MAX_WAVES_PER_CU  // 4 SIMDs x the waves per SIMD the render kernel's register budget allows (kernels.hip)
 #define PBRT_RENDER_MAX_WAVES_PER_CU 20
 #endif
@@ -81,7 +85,7 @@ constexpr uint32_t kSobolNdRequests = 64u;
 
 struct RenderStackPlan {
   uint32_t rows;           // LDS rows per wave
-  bool overflow;           // the overflow variant (rows == kQuadLdsStackOvf or kQuadLdsStackOvfDeep)
+  bool overflow;           // the overflow variant (rows == kQuadLdsStackOvf)
   uint32_t waves_per_cu;   // one-wave workgroups a CU holds at once with these rows (at most 20: 5 per SIMD by registers)
   uint32_t extra_entries;  // HBM entries per lane beyond the LDS part (overflow variant)
 };
@@ -95,25 +99,26 @@ inline RenderStackPlan render_stack_plan(uint32_t quad_stack_need, bool force_ov
   p.rows = need_rows < 8u ? 8u : need_rows;
   // (20 waves with the overflow variant beat 18 or 16 waves with the whole stack in LDS: C2 +1 %, C3 +4 %)
   p.overflow = force_overflow || need_rows > kQuadLdsStack || (waves(p.rows) < waves(kQuadLdsStackOvf) && !prefer_lds);
-  if (p.overflow) p.rows = quad_stack_need >= kOvfDeepNeed ? kQuadLdsStackOvfDeep : kQuadLdsStackOvf;
+  if (p.overflow) p.rows = kQuadLdsStackOvf;
   p.waves_per_cu = waves(p.rows);
   p.extra_entries = p.overflow && need_rows > p.rows ? need_rows - p.rows : 0u;
   return p;
 }
-inline bool render_prefer_lds() {  // A-B runs: the whole stack in LDS whenever it fits kQuadLdsStack rows, whatever the occupancy
-  static const bool f = debug_knob("PBRT_HIP_PREFER_LDS_STACK") != nullptr;
-  return f;
-}
-inline bool render_force_overflow() {  // A-B runs
-  static const bool f = debug_knob("PBRT_HIP_FORCE_OVERFLOW_VARIANT") != nullptr;
-  return f;
-}
-// the traversal kernel over ray batches keeps static rows
-constexpr uint32_t kQuadLdsEntries = kQuadLdsStack - 1u;
 // The ray-batch kernel (pbrt_hip_intersect / pbrt_hip_occluded: the walk alone, ~64 VGPRs) runs 8 waves per SIMD with 20 rows of a
 // lane's stack in LDS (20 KB per 4-wave workgroup, 8 per CU) and deeper entries in HBM: +9 % on 4 waves with 40 rows, +12 % at equal
 // rows (tools/experiments/dual_ray, profiles/r03y_traversal_occupancy_1m.txt)
 constexpr uint32_t kIntersectLdsStack = 20;
+// Its grid: persistent workgroups of 4 waves (intersect_kernel), one per 256 rays and at most kIntersectMaxWorkgroups of them.  Each
+// wave has its own HBM area of intersect_overflow_entries x 64 lanes for the entries beyond the kIntersectLdsStack - 1 kept in LDS
+// (+ the sentinel).
+constexpr uint32_t kIntersectWavesPerWorkgroup = 4, kIntersectMaxWorkgroups = 256 * 16;
+inline uint32_t intersect_workgroups(int64_t n_rays) {
+  const int64_t w = (n_rays + 255) / 256;
+  return w > kIntersectMaxWorkgroups ? kIntersectMaxWorkgroups : (uint32_t)w;
+}
+inline uint32_t intersect_overflow_entries(uint32_t quad_stack_need) {
+  return quad_stack_need + 2u > kIntersectLdsStack ? quad_stack_need + 2u - kIntersectLdsStack : 0u;
+}
 
 struct DevScene {
   const uint4 *nodes;
@@ -194,10 +199,34 @@ struct RayBatch {
   uint32_t stack_overflow_entries;
 };
 
+// One launch of the render kernel, decided on the host in one place (capi.cpp render_launch) from the scene, the render description
+// and the film geometry.  launch_render maps it to an instantiation and computes nothing.
+enum RenderCounters : uint32_t {
+  kCountNone = 0,
+  kCountExact = 1,  // PBRT_HIP_FLAG_COUNTERS: the exact walk of the canonical tree (render_kernel<..., EXACT>)
+  kCountWalk = 2,   // PBRT_HIP_FLAG_WALK_COUNTERS: the production walk, counting
+};
+struct RenderLaunch {
+  // the variant (capi.cpp check_render_desc says which combinations exist)
+  bool spheres;        // SPH
+  RenderCounters counters;
+  bool wide;           // WIDE: a box filter radius other than 0.5
+  bool table_sampler;  // SND: samplers 2 and 3 (3.12, 3.13)
+  bool mis, textured;  // render_kernel_x's MIS (3.14) and TEX (3.15)
+  RenderStackPlan plan;  // the production walk's stack: LDS rows, the overflow variant, HBM entries per lane
+  uint32_t steps;        // production walk: node steps per scheduling check (STEPS)
+  uint32_t exact_rows;   // exact walk: STACK, its stack rows of refs (and as many of entry distances)
+  uint32_t lds_bytes;    // dynamic shared memory per one-wave workgroup
+  uint32_t waves_per_cu;  // one-wave workgroups per CU: the plan's, clamped for the spheres' register budget
+  uint32_t n_workgroups;  // the grid: waves_per_cu x the device's CUs, at most one per item of the largest pass
+  uint32_t chunk_shift;   // log2 K, K = the sample chunks of a pixel
+  uint32_t passes;        // launches of a frame over one partial-sums buffer (capi.cpp partials_passes) ...
+  uint32_t pass_tiles;    // ... and the super-tiles of the largest one
+  uint32_t min_walkers, min_parked;  // traversal scheduling thresholds (RenderParams)
+};
+
 // launchers (kernels.hip)
-hipError_t launch_render(const DevScene &S, const RenderParams &R, uint32_t n_local_super, uint32_t bvh_depth,
-                         int counters /* 0 none, 1 exact walk, 2 production walk */, bool wide_filter, bool sobol_nd, hipStream_t stream,
-                         bool mis = false, bool textured = false);
+hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t stream);
 // fixed-point accumulators -> film pixels {X, Y, Z, weight}
 hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, size_t n_px, hipStream_t stream);
 hipError_t launch_acc_add(unsigned long long *dst, const unsigned long long *src, size_t n, hipStream_t stream);  // dst[i] += src[i]

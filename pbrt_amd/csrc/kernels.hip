@@ -22,14 +22,10 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "device_types.h"
-
-// node steps of the production walk between two scheduling checks (trav_run)
-#ifndef PBRT_STEPS_PER_CHECK
-#define PBRT_STEPS_PER_CHECK 3
-#endif
 
 namespace pbrt_hip {
 namespace {
@@ -1125,118 +1121,66 @@ hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, siz
   return hipGetLastError();
 }
 
-// the variants of the production walk outside the default path (no counting instantiations): WIDE = a box filter radius
-// other than 0.5 (3.11), SND = the Sobol' sampler with its own dimensions per request (3.12)
-template <bool SPH, bool WIDE, bool SND>
-static hipError_t launch_render_variant(const DevScene &S, const RenderParams &R, hipStream_t st) {
-  const dim3 grid(R.n_workgroups), block(64);
-  const RenderStackPlan plan = render_stack_plan(S.quad_stack_need, render_force_overflow(), render_prefer_lds());
-  const uint32_t lds = plan.rows * 256u;
-  if (plan.overflow && plan.rows == kQuadLdsStackOvfDeep && kQuadLdsStackOvfDeep != kQuadLdsStackOvf)
-    hipLaunchKernelGGL((render_kernel<SPH, false, false, (int)kQuadLdsStackOvfDeep, PBRT_STEPS_PER_CHECK, WIDE, SND>), grid, block, lds, st, S, R);
-  else if (plan.overflow) hipLaunchKernelGGL((render_kernel<SPH, false, false, (int)kQuadLdsStackOvf, PBRT_STEPS_PER_CHECK, WIDE, SND>), grid, block, lds, st, S, R);
-  else hipLaunchKernelGGL((render_kernel<SPH, false, false, 0, PBRT_STEPS_PER_CHECK, WIDE, SND>), grid, block, lds, st, S, R);
-  return hipGetLastError();
+// with_bools(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...): run-time switches as template arguments
+template <class F>
+static hipError_t with_bools(F &&f) { return f(); }
+template <class F, class... Bs>
+static hipError_t with_bools(F &&f, bool b, Bs... rest) {
+  if (b) return with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+  return with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
 
-template <bool SPH, bool COUNT, bool EXACT>
-static hipError_t launch_render_t(const DevScene &S, const RenderParams &R, uint32_t n_local_super, uint32_t depth,
-                                  hipStream_t st) {
-  const dim3 grid(R.n_workgroups), block(64);
-  if constexpr (!EXACT) {  // production walk: LDS rows per scene; the overflow variant for deep quad trees
-    // node steps per scheduling check: 3 for deep trees (C3 +1 %, C2 +2 % over 2), 2 for shallow ones whose walks
-    // are a few steps long (C4: 3 would cost 5 %)
-    const RenderStackPlan plan = render_stack_plan(S.quad_stack_need, render_force_overflow(), render_prefer_lds());
-    const uint32_t lds = plan.rows * 256u;
-    // (production walk: STACK = the LDS rows of the overflow variant, 0 = whole stack in LDS)
-    if (plan.overflow && plan.rows == kQuadLdsStackOvfDeep && kQuadLdsStackOvfDeep != kQuadLdsStackOvf)
-      hipLaunchKernelGGL((render_kernel<SPH, COUNT, false, (int)kQuadLdsStackOvfDeep>), grid, block, lds, st, S, R);
-    else if (plan.overflow) hipLaunchKernelGGL((render_kernel<SPH, COUNT, false, (int)kQuadLdsStackOvf>), grid, block, lds, st, S, R);
-    else if (!COUNT && S.quad_stack_need <= 16u) hipLaunchKernelGGL((render_kernel<SPH, COUNT, false, 0, 2>), grid, block, lds, st, S, R);
-    else hipLaunchKernelGGL((render_kernel<SPH, COUNT, false, 0>), grid, block, lds, st, S, R);
+// RenderLaunch -> the instantiation; everything else was decided by capi.cpp render_launch.  render_kernel has the default path, and
+// one at a time a wide filter (WIDE) or the table samplers (SND); the counting walks only on the default path.  render_kernel_x has
+// every other combination, without counters.  The production walk's STACK is the LDS rows of the overflow variant, or 0 for the whole
+// stack in LDS; the exact walk's is its stack rows.
+hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
+  if (R.n_items == 0) return hipSuccess;
+  auto go = [&](void (*kernel)(DevScene, RenderParams)) {
+    hipLaunchKernelGGL(kernel, dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
     return hipGetLastError();
-  } else {
-    // exact walk: the LDS stack is sized to the tree: the walk holds at most depth - 1 entries (refs + entry distances)
-    const uint32_t need = depth > 0 ? depth - 1 : 0;
-    if (need > 40) hipLaunchKernelGGL((render_kernel<SPH, COUNT, EXACT, 64>), grid, block, 64 * 512, st, S, R);
-    else if (need > 32) hipLaunchKernelGGL((render_kernel<SPH, COUNT, EXACT, 40>), grid, block, 40 * 512, st, S, R);
-    else if (need > 26) hipLaunchKernelGGL((render_kernel<SPH, COUNT, EXACT, 32>), grid, block, 32 * 512, st, S, R);
-    else if (need > 20) hipLaunchKernelGGL((render_kernel<SPH, COUNT, EXACT, 26>), grid, block, 26 * 512, st, S, R);
-    else hipLaunchKernelGGL((render_kernel<SPH, COUNT, EXACT, 20>), grid, block, 20 * 512, st, S, R);
-    return hipGetLastError();
-  }
+  };
+  if (L.counters == kCountExact)
+    return with_bools([&](auto SPH) {
+      switch (L.exact_rows) {
+        case 20: return go(render_kernel<SPH, true, true, 20>);
+        case 26: return go(render_kernel<SPH, true, true, 26>);
+        case 32: return go(render_kernel<SPH, true, true, 32>);
+        case 40: return go(render_kernel<SPH, true, true, 40>);
+        case 64: return go(render_kernel<SPH, true, true, 64>);
+      }
+      return hipErrorInvalidValue;
+    }, L.spheres);
+  // (ray log / phase probe builds wrap the default path's launch: experiments.inc)
+  const bool experiment = kExperimentLaunch && L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured;
+  hipError_t e = hipSuccess;
+  if (experiment && experiment_launch_begin(&e)) return e;
+  e = with_bools([&](auto SPH, auto OVF, auto COUNT, auto MIS, auto TEX, auto SND, auto WIDE) {
+    constexpr int STACK = OVF ? (int)kQuadLdsStackOvf : 0;
+    if constexpr (MIS || TEX || (SND && WIDE)) {
+      if constexpr (COUNT) return hipErrorInvalidValue;
+      else return go(render_kernel_x<SPH, STACK, MIS, TEX, SND, WIDE>);
+    } else if constexpr (COUNT && (SND || WIDE)) {
+      return hipErrorInvalidValue;
+    } else if constexpr (!COUNT && !SND && !WIDE && STACK == 0) {
+      return go(L.steps == 2 ? render_kernel<SPH, false, false, 0, 2> : render_kernel<SPH, false, false, 0>);
+    } else {
+      return go(render_kernel<SPH, COUNT, false, STACK, PBRT_STEPS_PER_CHECK, WIDE, SND>);
+    }
+  }, L.spheres, L.plan.overflow, L.counters == kCountWalk, L.mis, L.textured, L.table_sampler, L.wide);
+  if (experiment) experiment_launch_end(st);
+  return e;
 }
 
-template <bool SPH, bool MIS, bool TEX, bool SND, bool WIDE>
-static hipError_t launch_render_x(const DevScene &S, const RenderParams &R, hipStream_t st) {
-  const dim3 grid(R.n_workgroups), block(64);
-  const RenderStackPlan plan = render_stack_plan(S.quad_stack_need, render_force_overflow(), render_prefer_lds());
-  const uint32_t lds = plan.rows * 256u;
-  if (plan.overflow) hipLaunchKernelGGL((render_kernel_x<SPH, (int)kQuadLdsStackOvf, MIS, TEX, SND, WIDE>), grid, block, lds, st, S, R);
-  else hipLaunchKernelGGL((render_kernel_x<SPH, 0, MIS, TEX, SND, WIDE>), grid, block, lds, st, S, R);
-  return hipGetLastError();
-}
-// (mis, tex, snd, wide) -> the instantiation: every combination render_kernel does not cover itself
-template <bool SPH, bool MIS, bool TEX>
-static hipError_t launch_render_x_sw(const DevScene &S, const RenderParams &R, bool snd, bool wide, hipStream_t st) {
-  if (snd) return wide ? launch_render_x<SPH, MIS, TEX, true, true>(S, R, st) : launch_render_x<SPH, MIS, TEX, true, false>(S, R, st);
-  return wide ? launch_render_x<SPH, MIS, TEX, false, true>(S, R, st) : launch_render_x<SPH, MIS, TEX, false, false>(S, R, st);
-}
-template <bool SPH>
-static hipError_t launch_render_x_pick(const DevScene &S, const RenderParams &R, bool mis, bool tex, bool snd, bool wide, hipStream_t st) {
-  if (mis && tex) return launch_render_x_sw<SPH, true, true>(S, R, snd, wide, st);
-  if (mis) return launch_render_x_sw<SPH, true, false>(S, R, snd, wide, st);
-  if (tex) return launch_render_x_sw<SPH, false, true>(S, R, snd, wide, st);
-  return launch_render_x<SPH, false, false, true, true>(S, R, st);  // (a table sampler under a wide filter: the one pair left)
-}
-
-hipError_t launch_render(const DevScene &S, const RenderParams &R, uint32_t n_local_super, uint32_t bvh_depth,
-                         int counters, bool wide_filter, bool sobol_nd, hipStream_t stream, bool mis, bool textured) {
-  if (n_local_super == 0) return hipSuccess;
-  const bool sph = S.n_spheres > 0;
-  if (mis || textured || (wide_filter && sobol_nd)) {  // the variants (render_kernel_x): no counters -- refused by check_render_desc
-    if (counters != 0) return hipErrorInvalidValue;
-    return sph ? launch_render_x_pick<true>(S, R, mis, textured, sobol_nd, wide_filter, stream)
-               : launch_render_x_pick<false>(S, R, mis, textured, sobol_nd, wide_filter, stream);
-  }
-  if (wide_filter) return sph ? launch_render_variant<true, true, false>(S, R, stream) : launch_render_variant<false, true, false>(S, R, stream);
-  if (sobol_nd) return sph ? launch_render_variant<true, false, true>(S, R, stream) : launch_render_variant<false, false, true>(S, R, stream);
-  if (counters == 0 && kExperimentLaunch) {  // (ray log / phase probe builds: experiments.inc)
-    hipError_t e = hipSuccess;
-    if (experiment_launch_begin(&e)) return e;
-    e = sph ? launch_render_t<true, false, false>(S, R, n_local_super, bvh_depth, stream)
-            : launch_render_t<false, false, false>(S, R, n_local_super, bvh_depth, stream);
-    experiment_launch_end(stream);
-    return e;
-  }
-  if (counters == 1)
-    return sph ? launch_render_t<true, true, true>(S, R, n_local_super, bvh_depth, stream)
-               : launch_render_t<false, true, true>(S, R, n_local_super, bvh_depth, stream);
-  if (counters == 2)
-    return sph ? launch_render_t<true, true, false>(S, R, n_local_super, bvh_depth, stream)
-               : launch_render_t<false, true, false>(S, R, n_local_super, bvh_depth, stream);
-  return sph ? launch_render_t<true, false, false>(S, R, n_local_super, bvh_depth, stream)
-             : launch_render_t<false, false, false>(S, R, n_local_super, bvh_depth, stream);
-}
-
-template <bool SPH, bool COUNT>
-static hipError_t launch_intersect_t(const DevScene &S, const RayBatch &B, bool any_hit, uint32_t depth, hipStream_t st) {
-  int64_t blocks = (B.n + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  const dim3 grid((uint32_t)blocks), block(256);
-  if (depth <= 32) hipLaunchKernelGGL((intersect_kernel<SPH, COUNT, 32>), grid, block, 0, st, S, B, any_hit ? 1 : 0);
-  else hipLaunchKernelGGL((intersect_kernel<SPH, COUNT, 64>), grid, block, 0, st, S, B, any_hit ? 1 : 0);
-  if (kExperimentLaunch) experiment_launch_end(st);
-  return hipGetLastError();
-}
-
-hipError_t launch_intersect(const DevScene &S, const RayBatch &B, bool any_hit, uint32_t bvh_depth, hipStream_t stream) {
+hipError_t launch_intersect(const DevScene &S, const RayBatch &B, bool any_hit, uint32_t bvh_depth, hipStream_t st) {
   if (B.n == 0) return hipSuccess;
-  const bool sph = S.n_spheres > 0, cnt = B.counters != nullptr;
-  if (sph) return cnt ? launch_intersect_t<true, true>(S, B, any_hit, bvh_depth, stream)
-                      : launch_intersect_t<true, false>(S, B, any_hit, bvh_depth, stream);
-  return cnt ? launch_intersect_t<false, true>(S, B, any_hit, bvh_depth, stream)
-             : launch_intersect_t<false, false>(S, B, any_hit, bvh_depth, stream);
+  const dim3 grid(intersect_workgroups(B.n)), block(64 * kIntersectWavesPerWorkgroup);
+  const hipError_t e = with_bools([&](auto SPH, auto COUNT) {
+    hipLaunchKernelGGL((bvh_depth <= 32 ? intersect_kernel<SPH, COUNT, 32> : intersect_kernel<SPH, COUNT, 64>), grid, block, 0, st, S, B, any_hit ? 1 : 0);
+    return hipGetLastError();
+  }, S.n_spheres > 0, B.counters != nullptr);
+  if (kExperimentLaunch) experiment_launch_end(st);
+  return e;
 }
 
 hipError_t launch_pack_tris(const float *P, const uint32_t *idx, const uint16_t *mat_id, const uint32_t *order,

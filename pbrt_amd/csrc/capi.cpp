@@ -605,6 +605,40 @@ void build_production_quads(const Bvh &canon, const float *P, const uint32_t *id
   if (n_refs) *n_refs = (uint32_t)rb.ref_tri.size();
 }
 
+// `count` elements from `src` into `buf`, allocated anew, asynchronously on `stream` (src must live until the stream has caught up)
+template <class T>
+hipError_t upload(DevBuf<T> *buf, const T *src, size_t count, hipStream_t stream) {
+  const hipError_t e = buf->alloc(count);
+  if (e != hipSuccess || count == 0) return e;
+  return hipMemcpyAsync(buf->p, src, count * sizeof(T), hipMemcpyHostToDevice, stream);
+}
+
+// The canonical tree (the oracle's binary tree) of the n primitives P / idx: the tree itself in s->bvh, its child-pair
+// records in s->d_nodes, its leaf order in `order`, the scene's triangle records packed in that order into `tris`, and the tree's fields
+// of *D.  A host-built scene's tree (build_tree) and a device-built scene's counting walk (ensure_canonical) both come from here;
+// `what` prefixes the refusals.  *host_ms (if asked for): the time of the tree and the pair records.
+int build_canonical(pbrt_hip_scene *s, const float *P, const uint32_t *idx, uint32_t n, const std::string &what, DevBuf<uint32_t> *order,
+                    DevBuf<float4> *tris, DevScene *D, double *host_ms = nullptr) {
+  const auto t0 = std::chrono::steady_clock::now();
+  build_bvh(P, idx, n, &s->bvh);
+  if (s->bvh.depth > 64) return fail(PBRT_HIP_ERR_LIMIT, what + "BVH deeper than the 64-entry traversal stack");
+  PairNodes pairs;
+  std::string why;
+  if (!make_pair_nodes(s->bvh, &pairs, &why)) return fail(PBRT_HIP_ERR_LIMIT, what + why);
+  if (host_ms) *host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  HIP_TRY(upload(&s->d_nodes, pairs.q.data(), pairs.q.size(), s->stream));
+  HIP_TRY(upload(order, s->bvh.order.data(), n, s->stream));
+  HIP_TRY(tris->alloc(kTriStride * (size_t)n));
+  HIP_TRY(launch_pack_tris(s->d_P.p, s->d_idx.p, s->d_mat_id.p, order->p, n, D->n_tris, s->d_spheres.p, tris->p, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));  // (pairs is a local)
+  D->nodes = s->d_nodes.p;
+  D->tris = tris->p;
+  D->n_nodes = (uint32_t)s->bvh.nodes.size();
+  D->root_ref = pairs.root_ref;
+  for (int k = 0; k < 3; k++) { D->root_lo[k] = pairs.root_lo[k]; D->root_hi[k] = pairs.root_hi[k]; }
+  return PBRT_HIP_OK;
+}
+
 // The counter flags (PBRT_HIP_FLAG_COUNTERS, counters of pbrt_hip_intersect) count the CANONICAL walk: the oracle's binary
 // tree of DESIGN.md 3.3.  A host-built scene has it; a device-built one gets it here on first use -- vertex / index buffers
 // read back from the device, the host builder (one core, about a second for 1M triangles: a measurement aid, off the
@@ -613,39 +647,304 @@ int ensure_canonical(pbrt_hip_scene *s) {
   if (s->canonical_ready) return PBRT_HIP_OK;
   if (!s->gpu_built) { s->dev_exact = s->dev; s->canonical_ready = true; return PBRT_HIP_OK; }
   const auto t0 = std::chrono::steady_clock::now();
-  const uint32_t nt = s->n_prims;  // (triangles + the spheres' proxy triangles)
   std::vector<float> P(s->d_P.n);
   std::vector<uint32_t> idx(s->d_idx.n);
   HIP_TRY(hipSetDevice(s->device));
   if (!P.empty()) HIP_TRY(hipMemcpy(P.data(), s->d_P.p, P.size() * 4, hipMemcpyDeviceToHost));
   if (!idx.empty()) HIP_TRY(hipMemcpy(idx.data(), s->d_idx.p, idx.size() * 4, hipMemcpyDeviceToHost));
-  build_bvh(P.data(), idx.data(), nt, &s->bvh);
-  if (s->bvh.depth > 64) return fail(PBRT_HIP_ERR_LIMIT, "counters: canonical BVH deeper than the 64-entry traversal stack");
-  PairNodes pairs;
-  std::string why;
-  if (!make_pair_nodes(s->bvh, &pairs, &why)) return fail(PBRT_HIP_ERR_LIMIT, "counters: " + why);
-  s->d_nodes.release();
-  HIP_TRY(s->d_nodes.alloc(pairs.q.size()));
-  HIP_TRY(s->d_order_exact.alloc(nt));
-  HIP_TRY(s->d_tris_exact.alloc(kTriStride * (size_t)nt));
-  if (!pairs.q.empty()) HIP_TRY(hipMemcpyAsync(s->d_nodes.p, pairs.q.data(), pairs.q.size() * 16, hipMemcpyHostToDevice, s->stream));
-  if (nt) HIP_TRY(hipMemcpyAsync(s->d_order_exact.p, s->bvh.order.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(launch_pack_tris(s->d_P.p, s->d_idx.p, s->d_mat_id.p, s->d_order_exact.p, nt, s->dev.n_tris, s->d_spheres.p, s->d_tris_exact.p, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  s->dev_exact = s->dev;
+  const int rc = build_canonical(s, P.data(), idx.data(), s->n_prims, "counters: canonical ", &s->d_order_exact, &s->d_tris_exact, &s->dev_exact);
+  if (rc) return rc;
   s->dev.nodes = s->d_nodes.p;  // (the pre-canonical allocation was empty and has just been released: no stale pointer is kept)
   s->device_bytes += s->d_nodes.n * 16 + s->d_tris_exact.n * 16 + s->d_order_exact.n * 4;
-  s->dev_exact = s->dev;
-  s->dev_exact.nodes = s->d_nodes.p;
-  s->dev_exact.tris = s->d_tris_exact.p;
-  s->dev_exact.n_nodes = (uint32_t)s->bvh.nodes.size();
-  s->dev_exact.root_ref = pairs.root_ref;
-  for (int k = 0; k < 3; k++) { s->dev_exact.root_lo[k] = pairs.root_lo[k]; s->dev_exact.root_hi[k] = pairs.root_hi[k]; }
   s->canonical_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   s->canonical_ready = true;
   return PBRT_HIP_OK;
 }
 
+// ---- scene creation in stages (pbrt_hip_scene_create_ex): check_scene_desc, open, gather_inputs, upload_inputs, build_tree, set_view ----
+
+// The accelerator's builder.  ONE default -- the device builder (binned SAH + parallel re-insertion + collapse), whoever asks and
+// however (pbrt_hip_scene_create, flags 0, pbrt_hip_render_multi, the command line, bench.py); the host's binned-SAH builder only on
+// request (PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE, or PBRT_HIP_BUILDER=host in the environment when the caller left the choice open).
+enum class Builder { kHost, kHostOptimized, kGpu, kGpuPlain };
+
+// a material whose Kd is a texture
+bool kd_textured(const pbrt_hip_material &m) { return m.kd_tex != 0u && m.type == 0u; }
+
+// Every refusal that depends on the description alone, before any HIP call, and the builder that `flags` (and PBRT_HIP_BUILDER) ask for.
+int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *builder) {
+  if (d->xres <= 0 || d->yres <= 0) return fail(PBRT_HIP_ERR_INVALID, "scene_create: resolution must be positive");
+  if (d->n_tris && (!d->P || !d->idx || !d->mat_id)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: missing mesh arrays");
+  if ((d->n_tris || d->n_spheres) && (!d->mats || d->n_mats == 0)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: no materials");
+  if (d->n_mats > 65536) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 65536 materials");
+  if (d->n_tris > (1u << 24)) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 2^24 triangles (leaf references hold a 24-bit slot)");
+  if ((uint64_t)d->n_tris + d->n_spheres > (1u << 24)) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 2^24 primitives (triangles + spheres; leaf references hold a 24-bit slot)");
+  if (d->n_spheres && !d->spheres) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_spheres > 0 but no sphere table");
+  for (size_t i = 0; i < 3 * (size_t)d->n_tris; i++)
+    if (d->idx[i] >= d->n_verts) return fail(PBRT_HIP_ERR_INVALID, "scene_create: vertex index out of range");
+  for (uint32_t t = 0; t < d->n_tris; t++)
+    if (d->mat_id[t] >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material id out of range");
+  {
+    const long long bad = first_non_finite_vertex(d->P, d->idx, d->n_tris);
+    if (bad >= 0) return fail(PBRT_HIP_ERR_INVALID, "scene_create: vertex " + std::to_string(bad) + " is not finite");
+  }
+  for (uint32_t s = 0; s < d->n_spheres; s++) {
+    const pbrt_hip_sphere &sp = d->spheres[s];
+    if (!std::isfinite(sp.c[0]) || !std::isfinite(sp.c[1]) || !std::isfinite(sp.c[2]) || !std::isfinite(sp.r) || !(sp.r > 0.f))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere centre / radius must be finite and the radius positive");
+  }
+  // (a NaN in a light's position or in a colour travels into ray directions and throughputs: a ray that is not a number is pruned by
+  // nothing and walks the whole tree -- minutes per frame on a large scene -- before its sample is dropped as NaN)
+  if (d->n_lights && !d->lights) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_lights > 0 but no light table");
+  for (uint32_t i = 0; i < d->n_lights; i++)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(d->lights[i].p[k]) || !std::isfinite(d->lights[i].c[k]))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": position / direction / colour is not finite");
+  for (uint32_t i = 0; i < d->n_mats; i++)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(d->mats[i].k[k]) || !std::isfinite(d->mats[i].le[k]))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": colour / emission is not finite");
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(d->cam_to_world[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: camera matrix is not finite");
+  if (!(d->fov > 0.f && d->fov < 180.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: fov must lie in (0, 180) degrees");
+  for (int k = 0; k < 4; k++)  // Film "cropwindow": fractions of the film (film.rs:92-101 multiplies and rounds them up: a NaN or 1e30 there is an int overflow)
+    if (!(d->crop[k] >= 0.f && d->crop[k] <= 1.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: crop window values must lie in [0, 1]");
+  for (uint32_t s = 0; s < d->n_spheres; s++)
+    if (d->spheres[s].mat >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere material id out of range");
+  if (d->n_textures && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_textures > 0 but no texture table");
+  for (uint32_t i = 0; i < d->n_mats; i++) {
+    if (d->mats[i].kd_tex > d->n_textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
+    if (d->mats[i].kd_tex && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: textured material but no texture table");
+  }
+  for (uint32_t i = 0; i < d->n_textures; i++) {
+    const pbrt_hip_texture &tx = d->textures[i];
+    if (tx.type != 0u) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown texture type");
+    if (!std::isfinite(tx.su) || !std::isfinite(tx.sv) || !std::isfinite(tx.du) || !std::isfinite(tx.dv))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture mapping is not finite");
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(tx.tex1[k]) || !std::isfinite(tx.tex2[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture colour is not finite");
+  }
+  bool textured = false;  // a triangle whose material's Kd is a texture: its corner (u, v) must be there
+  for (uint32_t t = 0; t < d->n_tris && !textured; t++) textured = kd_textured(d->mats[d->mat_id[t]]);
+  if (textured) {
+    if (!d->tri_uv) return fail(PBRT_HIP_ERR_INVALID, "scene_create: a triangle's material is textured but tri_uv is NULL");
+    for (size_t i = 0; i < 6 * (size_t)d->n_tris; i++)
+      if (!std::isfinite(d->tri_uv[i])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: tri_uv is not finite");
+  }
+  if (flags & ~(PBRT_HIP_SCENE_GPU_BUILD | PBRT_HIP_SCENE_OPTIMIZED_TREE | PBRT_HIP_SCENE_PLAIN_TREE | PBRT_HIP_SCENE_HOST_BUILD))
+    return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown flag");
+  const bool want_host = (flags & (PBRT_HIP_SCENE_HOST_BUILD | PBRT_HIP_SCENE_OPTIMIZED_TREE)) != 0u;
+  const bool want_gpu = (flags & (PBRT_HIP_SCENE_GPU_BUILD | PBRT_HIP_SCENE_PLAIN_TREE)) != 0u;
+  if (want_host && want_gpu)
+    return fail(PBRT_HIP_ERR_INVALID, "scene_create: PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE are host builds, not combined with PBRT_HIP_SCENE_GPU_BUILD / _PLAIN_TREE");
+  for (uint32_t s = 0; s < d->n_spheres; s++)  // (a finite centre and radius can still make an infinite box)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(d->spheres[s].c[k] - d->spheres[s].r) || !std::isfinite(d->spheres[s].c[k] + d->spheres[s].r))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: a sphere's bounding box is not finite");
+  for (uint32_t i = 0; i < d->n_lights; i++)
+    if (d->lights[i].type > 2) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+  for (uint32_t i = 0; i < d->n_mats; i++)
+    if (d->mats[i].type > 1) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
+  const char *env = want_host || want_gpu ? nullptr : std::getenv("PBRT_HIP_BUILDER");
+  if (flags & PBRT_HIP_SCENE_OPTIMIZED_TREE) *builder = Builder::kHostOptimized;
+  else if ((flags & PBRT_HIP_SCENE_HOST_BUILD) || (env && std::strcmp(env, "host") == 0)) *builder = Builder::kHost;
+  else *builder = (flags & PBRT_HIP_SCENE_PLAIN_TREE) ? Builder::kGpuPlain : Builder::kGpu;  // (PBRT_HIP_SCENE_PLAIN_TREE alone qualifies the default)
+  return PBRT_HIP_OK;
+}
+
+// What a checked description puts on the device, assembled on the host.
+// Spheres are PRIMITIVES OF THE TREE (round 6; until round 5 every ray tested every sphere after the walk).  Every builder here --
+// the host's binned SAH, the device builder, the collapse, the lazily built canonical tree -- bounds a primitive by the box of its
+// three vertices, so sphere s enters the vertex / index buffers as a degenerate PROXY TRIANGLE (c - r, c + r, c - r): primitive
+// n_tris + s, bounded by exactly the sphere's box [c - r, c + r] (fp32 per component: the oracle's sphere_box), centroid its centre.
+// Its leaf record is a sphere's (pack_tris_kernel) and the leaf pass runs the sphere test on it (trav_run<..., SPH>).
+struct SceneInputs {
+  const float *P = nullptr;  // the primitives' vertices, indices and material ids: the caller's arrays, or *_aug with spheres
+  const uint32_t *idx = nullptr;
+  const uint16_t *mat = nullptr;
+  uint32_t n_verts = 0, n_prims = 0;  // primitives: the triangles + the spheres' proxies
+  std::vector<float> P_aug;
+  std::vector<uint32_t> idx_aug;
+  std::vector<uint16_t> mat_aug;
+  std::vector<float4> lights, mats, spheres, textures;  // the kernels' records: 5, 2, 2 and 3 per light / material / sphere / texture
+  float le_inf[3] = {0.f, 0.f, 0.f};
+  bool has_inf = false;
+  bool textured_tris = false;  // a triangle whose material's Kd is a texture: its corner (u, v) go up too
+  bool textured_sph = false;   // a sphere whose material's Kd is one: (u, v) from its own parametrisation (kernels.hip sphere_uv)
+};
+void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
+  auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+  in->P = d.P; in->idx = d.idx; in->mat = d.mat_id;
+  in->n_verts = d.n_verts;
+  in->n_prims = d.n_tris + d.n_spheres;
+  if (d.n_spheres) {
+    in->P_aug.assign(d.P, d.P + (d.n_tris ? 3 * (size_t)d.n_verts : 0));
+    if (!d.n_tris) in->n_verts = 0;  // (a scene without triangles drops the caller's vertices)
+    in->idx_aug.assign(d.idx, d.idx + 3 * (size_t)d.n_tris);
+    in->mat_aug.assign(d.mat_id, d.mat_id + d.n_tris);
+    for (uint32_t i = 0; i < d.n_spheres; i++) {
+      const pbrt_hip_sphere &sp = d.spheres[i];
+      const uint32_t v0 = in->n_verts + 2 * i;
+      for (int k = 0; k < 3; k++) in->P_aug.push_back(sp.c[k] - sp.r);
+      for (int k = 0; k < 3; k++) in->P_aug.push_back(sp.c[k] + sp.r);
+      in->idx_aug.push_back(v0); in->idx_aug.push_back(v0 + 1); in->idx_aug.push_back(v0);
+      in->mat_aug.push_back((uint16_t)sp.mat);
+    }
+    in->n_verts += 2 * d.n_spheres;
+    in->P = in->P_aug.data(); in->idx = in->idx_aug.data(); in->mat = in->mat_aug.data();
+  }
+  // light table: explicit lights, then every emissive triangle in index order
+  for (uint32_t i = 0; i < d.n_lights; i++) {
+    const pbrt_hip_light &l = d.lights[i];
+    in->lights.push_back(make_float4(as_f(l.type), l.p[0], l.p[1], l.p[2]));
+    in->lights.push_back(make_float4(0, 0, 0, 0));
+    in->lights.push_back(make_float4(0, 0, 0, 0));
+    in->lights.push_back(make_float4(l.c[0], l.c[1], l.c[2], 0));
+    in->lights.push_back(make_float4(0, 0, 0, 0));
+    if (l.type == 2) {
+      for (int k = 0; k < 3; k++) in->le_inf[k] = in->le_inf[k] + l.c[k];
+      in->has_inf = true;
+    }
+  }
+  for (uint32_t t = 0; t < d.n_tris; t++) {
+    const pbrt_hip_material &m = d.mats[d.mat_id[t]];
+    if (!(m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) continue;
+    F3 p[3];
+    for (int v = 0; v < 3; v++) {
+      const float *q = d.P + 3 * (size_t)d.idx[3 * (size_t)t + v];
+      p[v] = {q[0], q[1], q[2]};
+    }
+    F3 cr = cross3(sub(p[1], p[0]), sub(p[2], p[0]));
+    float len = std::sqrt(dot3(cr, cr));
+    in->lights.push_back(make_float4(as_f(3u), p[0].x, p[0].y, p[0].z));
+    in->lights.push_back(make_float4(p[1].x, p[1].y, p[1].z, 0.5f * len));
+    in->lights.push_back(make_float4(p[2].x, p[2].y, p[2].z, 0));
+    in->lights.push_back(make_float4(m.le[0], m.le[1], m.le[2], 0));
+    in->lights.push_back(make_float4(cr.x / len, cr.y / len, cr.z / len, 0));
+  }
+  in->mats.resize(2 * (size_t)d.n_mats);
+  for (uint32_t i = 0; i < d.n_mats; i++) {
+    const pbrt_hip_material &m = d.mats[i];
+    in->mats[2 * i] = make_float4(as_f(m.type), m.k[0], m.k[1], m.k[2]);
+    in->mats[2 * i + 1] = make_float4(m.le[0], m.le[1], m.le[2], as_f(m.type == 0u ? m.kd_tex : 0u));
+  }
+  in->spheres.resize(2 * (size_t)d.n_spheres);
+  for (uint32_t i = 0; i < d.n_spheres; i++) {
+    const pbrt_hip_sphere &sp = d.spheres[i];
+    in->spheres[2 * i] = make_float4(sp.c[0], sp.c[1], sp.c[2], sp.r);
+    in->spheres[2 * i + 1] = make_float4(as_f(sp.mat), 0, 0, 0);
+    in->textured_sph = in->textured_sph || kd_textured(d.mats[sp.mat]);
+  }
+  for (uint32_t t = 0; t < d.n_tris && !in->textured_tris; t++) in->textured_tris = kd_textured(d.mats[d.mat_id[t]]);
+  if (in->textured_tris || in->textured_sph) {  // (the texture table goes up only when something is textured)
+    in->textures.resize(3 * (size_t)d.n_textures);
+    for (uint32_t i = 0; i < d.n_textures; i++) {
+      const pbrt_hip_texture &tx = d.textures[i];
+      in->textures[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
+      in->textures[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
+      in->textures[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
+    }
+  }
+}
+
+// The inputs into the scene's arrays (asynchronously: `in` outlives the stream's synchronisation) and the fields of s->dev they make
+int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const SceneInputs &in) {
+  HIP_TRY(upload(&s->d_P, in.P, 3 * (size_t)in.n_verts, s->stream));
+  HIP_TRY(upload(&s->d_idx, in.idx, 3 * (size_t)in.n_prims, s->stream));
+  HIP_TRY(upload(&s->d_mat_id, in.mat, in.n_prims, s->stream));
+  HIP_TRY(upload(&s->d_mats, in.mats.data(), in.mats.size(), s->stream));
+  HIP_TRY(upload(&s->d_lights, in.lights.data(), in.lights.size(), s->stream));
+  HIP_TRY(upload(&s->d_spheres, in.spheres.data(), in.spheres.size(), s->stream));
+  HIP_TRY(upload(&s->d_textures, in.textures.data(), in.textures.size(), s->stream));
+  if (in.textured_tris) HIP_TRY(upload(&s->d_tri_uv_in, d.tri_uv, 6 * (size_t)d.n_tris, s->stream));
+  DevScene &D = s->dev;
+  D.mats = s->d_mats.p;
+  D.lights = s->d_lights.p;
+  D.spheres = s->d_spheres.p;
+  D.n_tris = d.n_tris;  // (the triangles: a hit's primitive id >= this is sphere id - n_tris)
+  D.n_spheres = d.n_spheres;
+  D.n_lights = (uint32_t)(in.lights.size() / 5);
+  D.n_lights_f = (float)D.n_lights;
+  for (int k = 0; k < 3; k++) D.le_inf[k] = in.le_inf[k];
+  D.has_inf = in.has_inf ? 1u : 0u;
+  return PBRT_HIP_OK;
+}
+
+// The tree over the uploaded primitives, on the host or on the device: d_nodes, d_quads and d_order, the triangle records packed in
+// leaf order into d_tris, s->build, and the tree's fields of s->dev (nodes, quads, root ref and box, n_nodes, the walk's stack need).
+int build_tree(pbrt_hip_scene *s, const SceneInputs &in, Builder builder) {
+  DevScene &D = s->dev;
+  const uint32_t np = in.n_prims;
+  s->gpu_built = (builder == Builder::kGpu || builder == Builder::kGpuPlain) && np >= 2;
+  if (s->gpu_built) {  // the walk enters quad 0 through the root box; there is no canonical binary tree
+    HIP_TRY(s->d_order.alloc(np));
+    HIP_TRY(s->d_quads.alloc(4 * (size_t)np));
+    HIP_TRY(s->d_tris.alloc(kTriStride * (size_t)np));
+    GpuBuildInfo gb{};
+    HIP_TRY(gpu_build_quads(s->d_P.p, s->d_idx.p, np, s->d_order.p, s->d_quads.p, np, builder == Builder::kGpuPlain ? 0u : kGpuBuildReinsert, &gb,
+                            s->stream));
+    if (gb.stack_need + 1u > 4096u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: device-built tree too deep");
+    HIP_TRY(launch_pack_tris(s->d_P.p, s->d_idx.p, s->d_mat_id.p, s->d_order.p, np, D.n_tris, s->d_spheres.p, s->d_tris.p, s->stream));
+    s->build = {gb.build_ms, gb.reinsert_passes, gb.reinsert_moves, gb.reinsert_ms, gb.reinsert_cost_before, gb.reinsert_cost_after, gb.reinsert_undone};
+    s->n_quads_gpu = gb.n_quads;
+    D.tris = s->d_tris.p;
+    D.n_nodes = 2u * np - 1u;
+    D.root_ref = 0u;
+    for (int k = 0; k < 3; k++) { D.root_lo[k] = gb.root_lo[k]; D.root_hi[k] = gb.root_hi[k]; }
+    D.quad_stack_need = gb.stack_need;
+  } else {
+    double canon_ms = 0.0;
+    const int rc = build_canonical(s, in.P, in.idx, np, "scene_create: ", &s->d_order, &s->d_tris, &D, &canon_ms);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const char *sl = debug_knob("PBRT_HIP_SPLIT_LEAVES");
+    QuadNodes quads;
+    build_production_quads(s->bvh, in.P, in.idx, np, builder == Builder::kHostOptimized ? kTreeReinsert : production_tree_default(),
+                           !(sl && sl[0] == '0'), &quads);
+    s->build.build_ms = canon_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HIP_TRY(upload(&s->d_quads, quads.q.data(), quads.q.size(), s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));  // (quads is a local)
+    D.quad_stack_need = quads.stack_need;
+  }
+  D.quads = s->d_quads.p;
+  D.inv_parallel = inv_parallel_for_extent(std::max(D.root_hi[0] - D.root_lo[0], std::max(D.root_hi[1] - D.root_lo[1], D.root_hi[2] - D.root_lo[2])));
+  return PBRT_HIP_OK;
+}
+
+// The perspective camera and the crop window of `d` into D: screen window from the aspect ratio, fov on the shorter axis
+void set_view(DevScene *D, const pbrt_hip_scene_desc &d) {
+  for (int k = 0; k < 12; k++) D->c2w[k] = d.cam_to_world[k];
+  const float aspect = (float)d.xres / (float)d.yres;
+  float sx0, sx1, sy0, sy1;
+  if (aspect > 1.f) { sx0 = -aspect; sx1 = aspect; sy0 = -1.f; sy1 = 1.f; }
+  else { sx0 = -1.f; sx1 = 1.f; sy0 = -1.f / aspect; sy1 = 1.f / aspect; }
+  const float tan_half = (float)std::tan((double)d.fov * (3.14159265358979323846 / 180.0) * 0.5);
+  D->cam_ax = ((sx1 - sx0) / (float)d.xres) * tan_half;
+  D->cam_bx = sx0 * tan_half;
+  D->cam_ay = -((sy1 - sy0) / (float)d.yres) * tan_half;
+  D->cam_by = sy1 * tan_half;
+  D->xres = d.xres;
+  D->yres = d.yres;
+  int32_t cb[4];
+  film_cropped_bounds(d.xres, d.yres, d.crop, cb);
+  D->cx0 = cb[0]; D->cy0 = cb[1]; D->cx1 = cb[2]; D->cy1 = cb[3];
+}
+
 }  // namespace
+
+int pbrt_hip_scene::open(int on_device) {
+  device = on_device;
+  HIP_TRY(hipSetDevice(device));
+  int cus = 0;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  n_cu = cus > 0 ? (uint32_t)cus : 1u;
+  HIP_TRY(hipStreamCreate(&stream));
+  HIP_TRY(hipEventCreate(&ev0));
+  HIP_TRY(hipEventCreate(&ev1));
+  HIP_TRY(d_counters.alloc(80));  // [0..4] ray / visit counters, [6..7] pixel-order scratch, [8..71] the pixel hand-out counters
+  return PBRT_HIP_OK;
+}
 
 extern "C" {
 
@@ -725,312 +1024,33 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
   if (!d || !out) return fail(PBRT_HIP_ERR_INVALID, "scene_create: null argument");
   *out = nullptr;
   try {
-    if (d->xres <= 0 || d->yres <= 0) return fail(PBRT_HIP_ERR_INVALID, "scene_create: resolution must be positive");
-    if (d->n_tris && (!d->P || !d->idx || !d->mat_id)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: missing mesh arrays");
-    if ((d->n_tris || d->n_spheres) && (!d->mats || d->n_mats == 0)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: no materials");
-    if (d->n_mats > 65536) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 65536 materials");
-    if (d->n_tris > (1u << 24)) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 2^24 triangles (leaf references hold a 24-bit slot)");
-    if ((uint64_t)d->n_tris + d->n_spheres > (1u << 24)) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 2^24 primitives (triangles + spheres; leaf references hold a 24-bit slot)");
-    if (d->n_spheres && !d->spheres) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_spheres > 0 but no sphere table");
-    for (size_t i = 0; i < 3 * (size_t)d->n_tris; i++)
-      if (d->idx[i] >= d->n_verts) return fail(PBRT_HIP_ERR_INVALID, "scene_create: vertex index out of range");
-    for (uint32_t t = 0; t < d->n_tris; t++)
-      if (d->mat_id[t] >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material id out of range");
-    {
-      const long long bad = first_non_finite_vertex(d->P, d->idx, d->n_tris);
-      if (bad >= 0) return fail(PBRT_HIP_ERR_INVALID, "scene_create: vertex " + std::to_string(bad) + " is not finite");
-    }
-    for (uint32_t s = 0; s < d->n_spheres; s++) {
-      const pbrt_hip_sphere &sp = d->spheres[s];
-      if (!std::isfinite(sp.c[0]) || !std::isfinite(sp.c[1]) || !std::isfinite(sp.c[2]) || !std::isfinite(sp.r) || !(sp.r > 0.f))
-        return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere centre / radius must be finite and the radius positive");
-    }
-    // (a NaN in a light's position or in a colour travels into ray directions and throughputs: a ray that is not a number is pruned by
-    // nothing and walks the whole tree -- minutes per frame on a large scene -- before its sample is dropped as NaN)
-    if (d->n_lights && !d->lights) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_lights > 0 but no light table");
-    for (uint32_t i = 0; i < d->n_lights; i++)
-      for (int k = 0; k < 3; k++)
-        if (!std::isfinite(d->lights[i].p[k]) || !std::isfinite(d->lights[i].c[k]))
-          return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": position / direction / colour is not finite");
-    for (uint32_t i = 0; i < d->n_mats; i++)
-      for (int k = 0; k < 3; k++)
-        if (!std::isfinite(d->mats[i].k[k]) || !std::isfinite(d->mats[i].le[k]))
-          return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": colour / emission is not finite");
-    for (int k = 0; k < 16; k++)
-      if (!std::isfinite(d->cam_to_world[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: camera matrix is not finite");
-    if (!(d->fov > 0.f && d->fov < 180.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: fov must lie in (0, 180) degrees");
-    for (int k = 0; k < 4; k++)  // Film "cropwindow": fractions of the film (film.rs:92-101 multiplies and rounds them up: a NaN or 1e30 there is an int overflow)
-      if (!(d->crop[k] >= 0.f && d->crop[k] <= 1.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: crop window values must lie in [0, 1]");
-    for (uint32_t s = 0; s < d->n_spheres; s++)
-      if (d->spheres[s].mat >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere material id out of range");
-    bool textured = false;      // a triangle whose material's Kd is a texture: its corner (u, v) must be there
-    bool textured_sph = false;  // a sphere whose material's Kd is one: (u, v) from its own parametrisation (kernels.hip sphere_uv)
-    if (d->n_textures && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_textures > 0 but no texture table");
-    for (uint32_t i = 0; i < d->n_mats; i++) {
-      if (d->mats[i].kd_tex > d->n_textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
-      if (d->mats[i].kd_tex && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: textured material but no texture table");
-    }
-    for (uint32_t i = 0; i < d->n_textures; i++) {
-      const pbrt_hip_texture &tx = d->textures[i];
-      if (tx.type != 0u) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown texture type");
-      if (!std::isfinite(tx.su) || !std::isfinite(tx.sv) || !std::isfinite(tx.du) || !std::isfinite(tx.dv))
-        return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture mapping is not finite");
-      for (int k = 0; k < 3; k++)
-        if (!std::isfinite(tx.tex1[k]) || !std::isfinite(tx.tex2[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture colour is not finite");
-    }
-    for (uint32_t t = 0; t < d->n_tris && !textured; t++) textured = d->mats[d->mat_id[t]].kd_tex != 0u && d->mats[d->mat_id[t]].type == 0u;
-    for (uint32_t i = 0; i < d->n_spheres && !textured_sph; i++) textured_sph = d->mats[d->spheres[i].mat].kd_tex != 0u && d->mats[d->spheres[i].mat].type == 0u;
-    if (textured && !d->tri_uv) return fail(PBRT_HIP_ERR_INVALID, "scene_create: a triangle's material is textured but tri_uv is NULL");
-    if (textured)
-      for (size_t i = 0; i < 6 * (size_t)d->n_tris; i++)
-        if (!std::isfinite(d->tri_uv[i])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: tri_uv is not finite");
-
+    Builder builder;
+    int rc = check_scene_desc(d, flags, &builder);
+    if (rc) return rc;
     int ndev = pbrt_hip_device_count();
     if (ndev <= 0) return fail(PBRT_HIP_ERR_NO_DEVICE, "scene_create: no HIP device (there is no CPU fallback)");
     if (device < 0) HIP_TRY(hipGetDevice(&device));
     if (device >= ndev) return fail(PBRT_HIP_ERR_INVALID, "scene_create: device index out of range");
-    HIP_TRY(hipSetDevice(device));
 
+    SceneInputs in;  // (declared before the scene: freed after it, on every exit)
     std::unique_ptr<pbrt_hip_scene> s(new pbrt_hip_scene());
-    s->device = device;
-    {
-      int cus = 0;
-      HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-      s->n_cu = cus > 0 ? (uint32_t)cus : 1u;
-    }
+    if ((rc = s->open(device))) return rc;
     s->desc = *d;
     s->desc.P = nullptr; s->desc.idx = nullptr; s->desc.mat_id = nullptr;
     s->desc.mats = nullptr; s->desc.lights = nullptr; s->desc.spheres = nullptr;
     s->desc.tri_uv = nullptr; s->desc.textures = nullptr;
-    s->textured = textured || textured_sph;
-
-    // --- accelerator: ONE default -- the device builder further down (binned SAH + parallel re-insertion + collapse), whoever asks
-    // and however (pbrt_hip_scene_create, flags 0, pbrt_hip_render_multi, the command line, bench.py); the host's binned-SAH
-    // builder only on request (PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE, or PBRT_HIP_BUILDER=host in the environment when the
-    // caller left the choice open) ---
-    if (flags & ~(PBRT_HIP_SCENE_GPU_BUILD | PBRT_HIP_SCENE_OPTIMIZED_TREE | PBRT_HIP_SCENE_PLAIN_TREE | PBRT_HIP_SCENE_HOST_BUILD))
-      return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown flag");
-    const bool want_host = (flags & (PBRT_HIP_SCENE_HOST_BUILD | PBRT_HIP_SCENE_OPTIMIZED_TREE)) != 0u;
-    const bool want_gpu = (flags & (PBRT_HIP_SCENE_GPU_BUILD | PBRT_HIP_SCENE_PLAIN_TREE)) != 0u;
-    if (want_host && want_gpu)
-      return fail(PBRT_HIP_ERR_INVALID, "scene_create: PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE are host builds, not combined with PBRT_HIP_SCENE_GPU_BUILD / _PLAIN_TREE");
-    if (!want_host && !want_gpu) {
-      const char *b = std::getenv("PBRT_HIP_BUILDER");
-      if (b && std::strcmp(b, "host") == 0) flags |= PBRT_HIP_SCENE_HOST_BUILD;
-      else flags |= PBRT_HIP_SCENE_GPU_BUILD;
-    } else if (want_gpu) {
-      flags |= PBRT_HIP_SCENE_GPU_BUILD;  // (PBRT_HIP_SCENE_PLAIN_TREE alone qualifies the default)
-    }
-    // Spheres are PRIMITIVES OF THE TREE (round 6; until round 5 every ray tested every sphere after the walk).  Every builder here --
-    // the host's binned SAH, the device builder, the collapse, the lazily built canonical tree -- bounds a primitive by the box of its
-    // three vertices, so sphere s enters the vertex / index buffers as a degenerate PROXY TRIANGLE (c - r, c + r, c - r): primitive
-    // n_tris + s, bounded by exactly the sphere's box [c - r, c + r] (fp32 per component: the oracle's sphere_box), centroid its centre.
-    // Its leaf record is a sphere's (pack_tris_kernel) and the leaf pass runs the sphere test on it (trav_run<..., SPH>).
-    const uint32_t np = d->n_tris + d->n_spheres;
-    std::vector<float> P_aug;
-    std::vector<uint32_t> idx_aug;
-    std::vector<uint16_t> mat_aug;
-    const float *bP = d->P;
-    const uint32_t *bidx = d->idx;
-    const uint16_t *bmat = d->mat_id;
-    uint32_t n_verts_b = d->n_verts;
-    if (d->n_spheres) {
-      P_aug.assign(d->P, d->P + (d->n_tris ? 3 * (size_t)d->n_verts : 0));
-      if (!d->n_tris) n_verts_b = 0;
-      idx_aug.assign(d->idx, d->idx + 3 * (size_t)d->n_tris);
-      mat_aug.assign(d->mat_id, d->mat_id + d->n_tris);
-      for (uint32_t i = 0; i < d->n_spheres; i++) {
-        const pbrt_hip_sphere &sp = d->spheres[i];
-        const uint32_t v0 = n_verts_b + 2 * i;
-        for (int k = 0; k < 3; k++) P_aug.push_back(sp.c[k] - sp.r);
-        for (int k = 0; k < 3; k++) P_aug.push_back(sp.c[k] + sp.r);
-        idx_aug.push_back(v0); idx_aug.push_back(v0 + 1); idx_aug.push_back(v0);
-        mat_aug.push_back((uint16_t)sp.mat);
-        if (!std::isfinite(sp.c[0] - sp.r) || !std::isfinite(sp.c[0] + sp.r) || !std::isfinite(sp.c[1] - sp.r) || !std::isfinite(sp.c[1] + sp.r) ||
-            !std::isfinite(sp.c[2] - sp.r) || !std::isfinite(sp.c[2] + sp.r))
-          return fail(PBRT_HIP_ERR_INVALID, "scene_create: a sphere's bounding box is not finite");
-      }
-      n_verts_b += 2 * d->n_spheres;
-      bP = P_aug.data(); bidx = idx_aug.data(); bmat = mat_aug.data();
-    }
-    s->gpu_built = (flags & PBRT_HIP_SCENE_GPU_BUILD) && np >= 2;
-    PairNodes pairs;
-    if (!s->gpu_built) {
-      const auto t0 = std::chrono::steady_clock::now();
-      build_bvh(bP, bidx, np, &s->bvh);
-      if (s->bvh.depth > 64) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: BVH deeper than the 64-entry traversal stack");
-      std::string why;
-      if (!make_pair_nodes(s->bvh, &pairs, &why)) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: " + why);
-      s->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-
-    // --- light table: explicit lights, then every emissive triangle in index order ---
-    std::vector<float4> lights;
-    float le_inf[3] = {0.f, 0.f, 0.f};
-    bool has_inf = false;
-    auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
-    for (uint32_t i = 0; i < d->n_lights; i++) {
-      const pbrt_hip_light &l = d->lights[i];
-      if (l.type > 2) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
-      lights.push_back(make_float4(as_f(l.type), l.p[0], l.p[1], l.p[2]));
-      lights.push_back(make_float4(0, 0, 0, 0));
-      lights.push_back(make_float4(0, 0, 0, 0));
-      lights.push_back(make_float4(l.c[0], l.c[1], l.c[2], 0));
-      lights.push_back(make_float4(0, 0, 0, 0));
-      if (l.type == 2) {
-        for (int k = 0; k < 3; k++) le_inf[k] = le_inf[k] + l.c[k];
-        has_inf = true;
-      }
-    }
-    for (uint32_t t = 0; t < d->n_tris; t++) {
-      const pbrt_hip_material &m = d->mats[d->mat_id[t]];
-      if (!(m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) continue;
-      F3 p[3];
-      for (int v = 0; v < 3; v++) {
-        const float *q = d->P + 3 * (size_t)d->idx[3 * (size_t)t + v];
-        p[v] = {q[0], q[1], q[2]};
-      }
-      F3 cr = cross3(sub(p[1], p[0]), sub(p[2], p[0]));
-      float len = std::sqrt(dot3(cr, cr));
-      lights.push_back(make_float4(as_f(3u), p[0].x, p[0].y, p[0].z));
-      lights.push_back(make_float4(p[1].x, p[1].y, p[1].z, 0.5f * len));
-      lights.push_back(make_float4(p[2].x, p[2].y, p[2].z, 0));
-      lights.push_back(make_float4(m.le[0], m.le[1], m.le[2], 0));
-      lights.push_back(make_float4(cr.x / len, cr.y / len, cr.z / len, 0));
-    }
-    s->n_lights = (uint32_t)(lights.size() / 5);
-
-    std::vector<float4> mats(2 * (size_t)d->n_mats);
-    for (uint32_t i = 0; i < d->n_mats; i++) {
-      const pbrt_hip_material &m = d->mats[i];
-      if (m.type > 1) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
-      mats[2 * i] = make_float4(as_f(m.type), m.k[0], m.k[1], m.k[2]);
-      mats[2 * i + 1] = make_float4(m.le[0], m.le[1], m.le[2], as_f(m.type == 0u ? m.kd_tex : 0u));
-    }
-    std::vector<float4> spheres(2 * (size_t)d->n_spheres);
-    for (uint32_t i = 0; i < d->n_spheres; i++) {
-      const pbrt_hip_sphere &sp = d->spheres[i];
-      spheres[2 * i] = make_float4(sp.c[0], sp.c[1], sp.c[2], sp.r);
-      spheres[2 * i + 1] = make_float4(as_f(sp.mat), 0, 0, 0);
-    }
-
-    // --- upload: vertex / index buffers, flattened nodes, leaf order; pack leaf records on device ---
-    const uint32_t nt = np;  // primitives: the triangles + the spheres' proxies (D.n_tris below stays the TRIANGLES: primitive ids >= it are spheres)
-    HIP_TRY(s->d_P.alloc(3 * (size_t)n_verts_b));
-    HIP_TRY(s->d_idx.alloc(3 * (size_t)nt));
-    HIP_TRY(s->d_mat_id.alloc(nt));
-    HIP_TRY(s->d_order.alloc(nt));
-    QuadNodes quads;
-    if (!s->gpu_built) {
-      const auto t0 = std::chrono::steady_clock::now();
-      const char *sl = debug_knob("PBRT_HIP_SPLIT_LEAVES");
-      build_production_quads(s->bvh, bP, bidx, np, (flags & PBRT_HIP_SCENE_OPTIMIZED_TREE) ? kTreeReinsert : production_tree_default(),
-                             !(sl && sl[0] == '0'), &quads);
-      s->build_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    HIP_TRY(s->d_nodes.alloc(pairs.q.size()));
-    HIP_TRY(s->d_quads.alloc(s->gpu_built ? 4 * (size_t)nt : quads.q.size()));
-    HIP_TRY(s->d_tris.alloc(kTriStride * (size_t)nt));
-    HIP_TRY(s->d_mats.alloc(mats.size()));
-    HIP_TRY(s->d_lights.alloc(lights.size()));
-    HIP_TRY(s->d_spheres.alloc(spheres.size()));
-    HIP_TRY(s->d_counters.alloc(80));  // [0..4] ray / visit counters, [6..7] pixel-order scratch, [8..71] the pixel hand-out counters
-    HIP_TRY(hipStreamCreate(&s->stream));
-    HIP_TRY(hipEventCreate(&s->ev0));
-    HIP_TRY(hipEventCreate(&s->ev1));
-    auto up = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-      if (!bytes) return hipSuccess;
-      return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s->stream);
-    };
-    HIP_TRY(up(s->d_P.p, bP, s->d_P.n * 4));
-    HIP_TRY(up(s->d_idx.p, bidx, s->d_idx.n * 4));
-    HIP_TRY(up(s->d_mat_id.p, bmat, s->d_mat_id.n * 2));
-    GpuBuildInfo gb{};
-    if (s->gpu_built) {
-      HIP_TRY(gpu_build_quads(s->d_P.p, s->d_idx.p, nt, s->d_order.p, s->d_quads.p, nt, (flags & PBRT_HIP_SCENE_PLAIN_TREE) ? 0u : kGpuBuildReinsert, &gb,
-                              s->stream));
-      if (gb.stack_need + 1u > 4096u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: device-built tree too deep");
-      quads.stack_need = gb.stack_need;
-      s->build_ms = gb.build_ms;
-      s->reinsert_passes = gb.reinsert_passes;
-      s->reinsert_moves = gb.reinsert_moves;
-      s->reinsert_ms = gb.reinsert_ms;
-      s->reinsert_cost_before = gb.reinsert_cost_before;
-      s->reinsert_cost_after = gb.reinsert_cost_after;
-      s->reinsert_undone = gb.reinsert_undone;
-    } else {
-      HIP_TRY(up(s->d_order.p, s->bvh.order.data(), s->d_order.n * 4));
-    }
-    HIP_TRY(up(s->d_nodes.p, pairs.q.data(), pairs.q.size() * 16));
-    if (!s->gpu_built) HIP_TRY(up(s->d_quads.p, quads.q.data(), quads.q.size() * 16));
-    HIP_TRY(up(s->d_mats.p, mats.data(), mats.size() * 16));
-    HIP_TRY(up(s->d_lights.p, lights.data(), lights.size() * 16));
-    HIP_TRY(up(s->d_spheres.p, spheres.data(), spheres.size() * 16));
-    HIP_TRY(launch_pack_tris(s->d_P.p, s->d_idx.p, s->d_mat_id.p, s->d_order.p, nt, d->n_tris, s->d_spheres.p, s->d_tris.p, s->stream));
-    if (textured || textured_sph) {  // corner (u, v) into leaf-slot order (whichever builder made d_order), the texture table as 3 x 16 B records
-      std::vector<float4> tex(3 * (size_t)d->n_textures);
-      for (uint32_t i = 0; i < d->n_textures; i++) {
-        const pbrt_hip_texture &tx = d->textures[i];
-        tex[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
-        tex[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
-        tex[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
-      }
-      HIP_TRY(s->d_textures.alloc(tex.size()));
-      HIP_TRY(up(s->d_textures.p, tex.data(), tex.size() * 16));
-      if (textured) {
-        HIP_TRY(s->d_tri_uv_in.alloc(6 * (size_t)d->n_tris));
-        HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)nt));
-        HIP_TRY(up(s->d_tri_uv_in.p, d->tri_uv, 24 * (size_t)d->n_tris));
-        HIP_TRY(launch_pack_uv(s->d_tri_uv_in.p, s->d_order.p, nt, d->n_tris, s->d_tri_uv.p, s->stream));
-      }
-      HIP_TRY(hipStreamSynchronize(s->stream));  // (tex is a local)
+    gather_inputs(*d, &in);
+    s->n_prims = in.n_prims;
+    s->textured = in.textured_tris || in.textured_sph;
+    if ((rc = upload_inputs(s.get(), *d, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
+    if (in.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
+      HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));
+      HIP_TRY(launch_pack_uv(s->d_tri_uv_in.p, s->d_order.p, in.n_prims, d->n_tris, s->d_tri_uv.p, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->device_bytes = s->d_tri_uv_in.n * 4 + s->d_tri_uv.n * 8 + s->d_textures.n * 16 + s->d_P.n * 4 + s->d_idx.n * 4 + s->d_mat_id.n * 2 + s->d_order.n * 4 + s->d_nodes.n * 16 + s->d_quads.n * 16 +
                       s->d_tris.n * 16 + s->d_mats.n * 16 + s->d_lights.n * 16 + s->d_spheres.n * 16;
-
-    // --- kernel argument block ---
-    DevScene &D = s->dev;
-    D.nodes = s->d_nodes.p;
-    D.quads = s->d_quads.p;
-    D.quad_stack_need = quads.stack_need;
-    D.tris = s->d_tris.p;
-    D.mats = s->d_mats.p;
-    D.lights = s->d_lights.p;
-    D.spheres = s->d_spheres.p;
-    D.n_nodes = (uint32_t)s->bvh.nodes.size();
-    D.root_ref = pairs.root_ref;
-    for (int k = 0; k < 3; k++) { D.root_lo[k] = pairs.root_lo[k]; D.root_hi[k] = pairs.root_hi[k]; }
-    if (s->gpu_built) {  // the walk enters quad 0 through the root box; there is no canonical binary tree
-      D.n_nodes = 2u * nt - 1u;
-      D.root_ref = 0u;
-      for (int k = 0; k < 3; k++) { D.root_lo[k] = gb.root_lo[k]; D.root_hi[k] = gb.root_hi[k]; }
-      s->n_quads_gpu = gb.n_quads;
-    }
-    D.inv_parallel = inv_parallel_for_extent(std::max(D.root_hi[0] - D.root_lo[0], std::max(D.root_hi[1] - D.root_lo[1], D.root_hi[2] - D.root_lo[2])));
-    D.n_tris = d->n_tris;  // (the triangles: a hit's primitive id >= this is sphere id - n_tris)
-    s->n_prims = nt;
-    D.n_spheres = d->n_spheres;
-    D.n_lights = s->n_lights;
-    D.n_lights_f = (float)s->n_lights;
-    for (int k = 0; k < 3; k++) D.le_inf[k] = le_inf[k];
-    D.has_inf = has_inf ? 1u : 0u;
-    for (int k = 0; k < 12; k++) D.c2w[k] = d->cam_to_world[k];
-    // perspective camera: screen window from the aspect ratio, fov on the shorter axis
-    const float aspect = (float)d->xres / (float)d->yres;
-    float sx0, sx1, sy0, sy1;
-    if (aspect > 1.f) { sx0 = -aspect; sx1 = aspect; sy0 = -1.f; sy1 = 1.f; }
-    else { sx0 = -1.f; sx1 = 1.f; sy0 = -1.f / aspect; sy1 = 1.f / aspect; }
-    const float tan_half = (float)std::tan((double)d->fov * (3.14159265358979323846 / 180.0) * 0.5);
-    D.cam_ax = ((sx1 - sx0) / (float)d->xres) * tan_half;
-    D.cam_bx = sx0 * tan_half;
-    D.cam_ay = -((sy1 - sy0) / (float)d->yres) * tan_half;
-    D.cam_by = sy1 * tan_half;
-    D.xres = d->xres;
-    D.yres = d->yres;
-    int32_t cb[4];
-    film_cropped_bounds(d->xres, d->yres, d->crop, cb);
-    D.cx0 = cb[0]; D.cy0 = cb[1]; D.cx1 = cb[2]; D.cy1 = cb[3];
+    set_view(&s->dev, *d);
     *out = s.release();
     return PBRT_HIP_OK;
   } catch (const std::exception &e) {
@@ -1049,7 +1069,7 @@ int pbrt_hip_scene_info(const pbrt_hip_scene *s, uint32_t *n_nodes, uint32_t *de
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "scene_info: null scene");
   if (n_nodes) *n_nodes = (uint32_t)s->bvh.nodes.size();
   if (depth) *depth = s->bvh.depth;
-  if (n_lights) *n_lights = s->n_lights;
+  if (n_lights) *n_lights = s->dev.n_lights;
   if (device_bytes) *device_bytes = s->device_bytes;
   return PBRT_HIP_OK;
 }
@@ -1064,30 +1084,30 @@ int pbrt_hip_scene_walk_info(const pbrt_hip_scene *s, uint32_t *quad_nodes, uint
 int pbrt_hip_scene_build_info(const pbrt_hip_scene *s, uint32_t *gpu_built, double *build_ms) {
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "build_info: null scene");
   if (gpu_built) *gpu_built = s->gpu_built ? 1u : 0u;
-  if (build_ms) *build_ms = s->build_ms;
+  if (build_ms) *build_ms = s->build.build_ms;
   return PBRT_HIP_OK;
 }
 
 int pbrt_hip_scene_optimize_info(const pbrt_hip_scene *s, uint32_t *passes, uint32_t *moves, double *ms) {
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "optimize_info: null scene");
-  if (passes) *passes = s->reinsert_passes;
-  if (moves) *moves = s->reinsert_moves;
-  if (ms) *ms = s->reinsert_ms;
+  if (passes) *passes = s->build.reinsert_passes;
+  if (moves) *moves = s->build.reinsert_moves;
+  if (ms) *ms = s->build.reinsert_ms;
   return PBRT_HIP_OK;
 }
 
 int pbrt_hip_scene_optimize_cost(const pbrt_hip_scene *s, double *before, double *after, uint32_t *undone) {
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "optimize_cost: null scene");
-  if (before) *before = s->reinsert_cost_before;
-  if (after) *after = s->reinsert_cost_after;
-  if (undone) *undone = s->reinsert_undone;
+  if (before) *before = s->build.reinsert_cost_before;
+  if (after) *after = s->build.reinsert_cost_after;
+  if (undone) *undone = s->build.reinsert_undone;
   return PBRT_HIP_OK;
 }
 
 int pbrt_hip_scene_canonical_info(const pbrt_hip_scene *s, uint32_t *ready, double *build_ms) {
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "canonical_info: null scene");
   if (ready) *ready = (s->canonical_ready || !s->gpu_built) ? 1u : 0u;
-  if (build_ms) *build_ms = s->gpu_built ? s->canonical_build_ms : s->build_ms;
+  if (build_ms) *build_ms = s->gpu_built ? s->canonical_build_ms : s->build.build_ms;
   return PBRT_HIP_OK;
 }
 
@@ -1227,23 +1247,18 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
     HIP_TRY(s->d_halton.alloc(kHaltonDims * 4));
     HIP_TRY(hipMemcpy(s->d_halton.p, tab, sizeof(tab), hipMemcpyHostToDevice));
   }
-  {
-    // float4 records: 5 x 64 per one-wave workgroup (kernels.hip LaneRecords); with another box filter radius 16 x 2 x 64 more
-    // behind them (kWideSlotFloat4: a chunk's sums per footprint)
-    const size_t path = (size_t)L.n_workgroups * 320, need = path + (L.wide ? (size_t)L.n_workgroups * 2048 : 0);
-    if (s->d_lane_state.n < need) { s->d_lane_state.release(); HIP_TRY(s->d_lane_state.alloc(need)); }
-  }
+  // float4 records: 5 x 64 per one-wave workgroup (kernels.hip LaneRecords); with another box filter radius 16 x 2 x 64 more
+  // behind them (kWideSlotFloat4: a chunk's sums per footprint)
+  HIP_TRY(s->d_lane_state.grow((size_t)L.n_workgroups * (L.wide ? 320 + 2048 : 320)));
   if (!L.wide) {
     const size_t need = (size_t)L.pass_tiles * 4096u * (1u << L.chunk_shift);  // one float4 per item of a pass
     // (C3 1.07 GB in one pass; C4's 4096^2 x 16 chunks on one GPU: 3 passes over 1.43 GB; the buffer follows the frame: released when a
     // later render needs less than a quarter of it)
-    if (s->d_partials.n < need || s->d_partials.n / 4 > need) { s->d_partials.release(); HIP_TRY(s->d_partials.alloc(need)); }
+    if (s->d_partials.n / 4 > need) s->d_partials.release();
+    HIP_TRY(s->d_partials.grow(need));
   }
-  {
-    // the overflow variant keeps kQuadLdsStackOvf rows per lane in LDS; deeper entries (rare) go here
-    const size_t need = (size_t)L.n_workgroups * 64 * L.plan.extra_entries;
-    if (s->d_stack_overflow.n < need) { s->d_stack_overflow.release(); HIP_TRY(s->d_stack_overflow.alloc(need)); }
-  }
+  // the overflow variant keeps kQuadLdsStackOvf rows per lane in LDS; deeper entries (rare) go here
+  HIP_TRY(s->d_stack_overflow.grow((size_t)L.n_workgroups * 64 * L.plan.extra_entries));
   return PBRT_HIP_OK;
 }
 }  // namespace
@@ -1404,8 +1419,8 @@ int pbrt_hip_render(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, float *fil
   const Shard sh = make_shard_bounds(fg.sb, r->rank, r->world_size);
   const size_t n_px = fg.crop_px();
   const size_t slab_n = fg.wide ? 2 * n_px : (size_t)sh.n_local * 4096;  // (wide: four int64 accumulators per pixel = two float4)
-  if (s->d_slab.n < slab_n) { s->d_slab.release(); HIP_TRY(s->d_slab.alloc(slab_n)); }
-  if (s->d_film.n < n_px) { s->d_film.release(); HIP_TRY(s->d_film.alloc(n_px)); }
+  HIP_TRY(s->d_slab.grow(slab_n));
+  HIP_TRY(s->d_film.grow(n_px));
   if (n_px) HIP_TRY(hipMemsetAsync(s->d_film.p, 0, n_px * 16, s->stream));
   rc = pbrt_hip_render_device(s, r, s->d_slab.p, s->stream);
   if (rc) return rc;
@@ -1453,7 +1468,7 @@ int pbrt_hip_render_acc(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, int64_
   const size_t n_px = fg.crop_px();
   if (n_px && !acc) return fail(PBRT_HIP_ERR_INVALID, "render_acc: null output");
   HIP_TRY(hipSetDevice(s->device));
-  if (s->d_slab.n < 2 * n_px) { s->d_slab.release(); HIP_TRY(s->d_slab.alloc(2 * n_px)); }
+  HIP_TRY(s->d_slab.grow(2 * n_px));
   rc = pbrt_hip_render_device(s, r, s->d_slab.p, s->stream);
   if (rc) return rc;
   hipError_t e = n_px ? hipMemcpyAsync(acc, s->d_slab.p, n_px * 32, hipMemcpyDeviceToHost, s->stream) : hipSuccess;
@@ -1515,78 +1530,59 @@ static int ray_batch(pbrt_hip_scene *s, int64_t n, const float *o, const float *
   DevBuf<float> d_o, d_d, d_tmax, d_t, d_b1, d_b2;
   DevBuf<uint32_t> d_prim;
   DevBuf<uint8_t> d_occ;
-  int rc = PBRT_HIP_OK;
-  auto cleanup = [&]() {
-    d_o.release(); d_d.release(); d_tmax.release(); d_t.release(); d_b1.release(); d_b2.release();
-    d_prim.release(); d_occ.release();
-  };
-#define RB_TRY(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) {                                                                       \
-      cleanup();                                                                                  \
-      return fail(PBRT_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    }                                                                                             \
-  } while (0)
-  RB_TRY(d_o.alloc(3 * (size_t)n));
-  RB_TRY(d_d.alloc(3 * (size_t)n));
-  RB_TRY(d_tmax.alloc((size_t)n));
-  RB_TRY(hipMemcpyAsync(d_o.p, o, 12 * (size_t)n, hipMemcpyHostToDevice, s->stream));
-  RB_TRY(hipMemcpyAsync(d_d.p, d, 12 * (size_t)n, hipMemcpyHostToDevice, s->stream));
-  RB_TRY(hipMemcpyAsync(d_tmax.p, tmax, 4 * (size_t)n, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(d_o.alloc(3 * (size_t)n));
+  HIP_TRY(d_d.alloc(3 * (size_t)n));
+  HIP_TRY(d_tmax.alloc((size_t)n));
+  HIP_TRY(hipMemcpyAsync(d_o.p, o, 12 * (size_t)n, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d_d.p, d, 12 * (size_t)n, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d_tmax.p, tmax, 4 * (size_t)n, hipMemcpyHostToDevice, s->stream));
   RayBatch B{};
   B.o = d_o.p; B.d = d_d.p; B.tmax = d_tmax.p; B.n = n;
   B.min_walkers = tuning("PBRT_HIP_MIN_WALKERS", kMinWalkers);
   B.min_parked = tuning("PBRT_HIP_MIN_PARKED", kMinParked);
   if (any) {
-    RB_TRY(d_occ.alloc((size_t)n));
+    HIP_TRY(d_occ.alloc((size_t)n));
     B.occluded = d_occ.p;
   } else {
-    RB_TRY(d_t.alloc((size_t)n)); RB_TRY(d_prim.alloc((size_t)n)); RB_TRY(d_b1.alloc((size_t)n)); RB_TRY(d_b2.alloc((size_t)n));
+    HIP_TRY(d_t.alloc((size_t)n)); HIP_TRY(d_prim.alloc((size_t)n)); HIP_TRY(d_b1.alloc((size_t)n)); HIP_TRY(d_b2.alloc((size_t)n));
     B.t = d_t.p; B.prim = d_prim.p; B.b1 = d_b1.p; B.b2 = d_b2.p;
   }
   if (counters) {
-    RB_TRY(hipMemsetAsync(s->d_counters.p, 0, 2 * sizeof(unsigned long long), s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_counters.p, 0, 2 * sizeof(unsigned long long), s->stream));
     B.counters = s->d_counters.p;
   }
-  {
-    // an overflow area for every wave of the largest grid launch_intersect makes
-    const uint32_t extra = intersect_overflow_entries(s->dev.quad_stack_need);
-    const size_t need = (size_t)kIntersectMaxWorkgroups * kIntersectWavesPerWorkgroup * 64 * extra;
-    if (s->d_stack_overflow.n < need) { s->d_stack_overflow.release(); RB_TRY(s->d_stack_overflow.alloc(need)); }
-    B.stack_overflow = s->d_stack_overflow.p;
-    B.stack_overflow_entries = extra;
-  }
+  // an overflow area for every wave of the largest grid launch_intersect makes
+  B.stack_overflow_entries = intersect_overflow_entries(s->dev.quad_stack_need);
+  HIP_TRY(s->d_stack_overflow.grow((size_t)kIntersectMaxWorkgroups * kIntersectWavesPerWorkgroup * 64 * B.stack_overflow_entries));
+  B.stack_overflow = s->d_stack_overflow.p;
   const bool timed = debug_knob("PBRT_HIP_TIME_INTERSECT") != nullptr;  // tuning aid: kernel time to stderr
-  if (timed) RB_TRY(hipEventRecord(s->ev0, s->stream));
-  RB_TRY(launch_intersect(counters ? s->dev_exact : s->dev, B, any, s->bvh.depth, s->stream));
+  if (timed) HIP_TRY(hipEventRecord(s->ev0, s->stream));
+  HIP_TRY(launch_intersect(counters ? s->dev_exact : s->dev, B, any, s->bvh.depth, s->stream));
   if (timed) {
-    RB_TRY(hipEventRecord(s->ev1, s->stream));
-    RB_TRY(hipEventSynchronize(s->ev1));
+    HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(hipEventSynchronize(s->ev1));
     float ms = 0.f;
-    RB_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     std::fprintf(stderr, "pbrt_hip intersect kernel: %lld rays %.3f ms %.1f Mrays/s\n", (long long)n, ms, (double)n / ms / 1e3);
   }
   if (any) {
-    RB_TRY(hipMemcpyAsync(occ, d_occ.p, (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(occ, d_occ.p, (size_t)n, hipMemcpyDeviceToHost, s->stream));
   } else {
-    RB_TRY(hipMemcpyAsync(t, d_t.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
-    RB_TRY(hipMemcpyAsync(prim, d_prim.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
-    RB_TRY(hipMemcpyAsync(b1, d_b1.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
-    RB_TRY(hipMemcpyAsync(b2, d_b2.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(t, d_t.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(prim, d_prim.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(b1, d_b1.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(b2, d_b2.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
   }
   if (counters) {
     unsigned long long c[2];
-    RB_TRY(hipMemcpyAsync(c, s->d_counters.p, sizeof(c), hipMemcpyDeviceToHost, s->stream));
-    RB_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpyAsync(c, s->d_counters.p, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
     counters[0] = c[0];
     counters[1] = c[1];
   } else {
-    RB_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
   }
-#undef RB_TRY
-  cleanup();
-  return rc;
+  return PBRT_HIP_OK;
 }
 
 int pbrt_hip_intersect(pbrt_hip_scene *s, int64_t n, const float *o, const float *d, const float *tmax, float *t,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 
 #include "../../include/pbrt_hip.h"
 #include "../../include/pbrt_hip_debug.h"
@@ -15,19 +16,53 @@ namespace pbrt_hip {
 int fail(int code, const std::string &msg);
 const char *last_error_message();
 
+// A device allocation that the buffer owns: freed by its destructor, on whichever device is current then.  n and p change only
+// when hipMalloc succeeds; after a failure the buffer is empty (n == 0, p == nullptr), so a later grow() tries again.
 template <class T>
 struct DevBuf {
   T *p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf &operator=(DevBuf o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }  // (moves only: o is moved into)
+  ~DevBuf() { release(); }
+  // frees what the buffer holds and allocates `count` elements (contents undefined)
   hipError_t alloc(size_t count) {
-    n = count;
+    release();
     if (count == 0) return hipSuccess;
-    return hipMalloc((void **)&p, count * sizeof(T));
+    T *q = nullptr;
+    const hipError_t e = hipMalloc((void **)&q, count * sizeof(T));
+    if (e == hipSuccess) { p = q; n = count; }
+    return e;
   }
+  // grow-only scratch: allocated anew (contents lost) when it holds fewer than `need` elements
+  hipError_t grow(size_t need) { return n < need ? alloc(need) : hipSuccess; }
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
     n = 0;
+  }
+};
+
+// A scene's build time and GpuBuildInfo's re-insertion statistics (zeros for a host build; build_ms a double: the host path times itself)
+struct BuildStats {
+  double build_ms = 0.0;
+  uint32_t reinsert_passes = 0, reinsert_moves = 0;
+  double reinsert_ms = 0.0;
+  double reinsert_cost_before = 0.0, reinsert_cost_after = 0.0;  // summed half surface area of the interior nodes
+  uint32_t reinsert_undone = 0;
+};
+
+// A scene's own stream (of pbrt_hip_render()) and the events that time a render.  A base of pbrt_hip_scene: base classes are
+// destroyed after the members, so the scene's buffers are freed before these.
+struct SceneStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~SceneStream() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
   }
 };
 }  // namespace pbrt_hip
@@ -39,12 +74,11 @@ struct DevBuf {
       return pbrt_hip::fail(PBRT_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
   } while (0)
 
-struct pbrt_hip_scene {
+struct pbrt_hip_scene : pbrt_hip::SceneStream {
   int device = 0;
   uint32_t n_cu = 256;  // hipDeviceProp_t::multiProcessorCount of `device`
   pbrt_hip_scene_desc desc{};  // scalar fields only; pointers are cleared
   pbrt_hip::Bvh bvh;
-  uint32_t n_lights = 0;
   pbrt_hip::DevScene dev{};
   // device allocations
   pbrt_hip::DevBuf<float> d_P;
@@ -56,9 +90,7 @@ struct pbrt_hip_scene {
   pbrt_hip::DevBuf<float4> d_slab, d_film;          // scratch of pbrt_hip_render()
   pbrt_hip::DevBuf<float4> d_lane_state;            // per-lane path state records of the render kernel
   pbrt_hip::DevBuf<float4> d_partials;              // partial film sums of the work items (8 chunks per slab pixel)
-  pbrt_hip::DevBuf<unsigned long long> d_counters;  // 5
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipStream_t stream = nullptr;  // own stream of pbrt_hip_render()
+  pbrt_hip::DevBuf<unsigned long long> d_counters;  // 80: see open()
   bool pending = false;
   bool pending_counters = false;
   uint32_t n_quads_gpu = 0;
@@ -78,22 +110,10 @@ struct pbrt_hip_scene {
   pbrt_hip::DevBuf<float4> d_tris_exact;
   pbrt_hip::DevBuf<uint32_t> d_order_exact;
   double canonical_build_ms = 0.0;
-  double build_ms = 0.0;
-  uint32_t reinsert_passes = 0, reinsert_moves = 0;  // the device build's tree optimisation (GpuBuildInfo)
-  double reinsert_ms = 0.0;
-  double reinsert_cost_before = 0.0, reinsert_cost_after = 0.0;  // summed half surface area of the interior nodes (GpuBuildInfo)
-  uint32_t reinsert_undone = 0;
+  pbrt_hip::BuildStats build;
   uint64_t pending_samples = 0;
   uint64_t device_bytes = 0;
 
-  ~pbrt_hip_scene() {
-    d_P.release(); d_idx.release(); d_order.release(); d_mat_id.release(); d_nodes.release(); d_quads.release(); d_stack_overflow.release();
-    d_tris.release(); d_mats.release(); d_lights.release(); d_spheres.release();
-    d_slab.release(); d_film.release(); d_counters.release(); d_lane_state.release(); d_partials.release();
-    d_tris_exact.release(); d_order_exact.release(); d_sobol.release(); d_halton.release(); d_tri_uv_in.release(); d_tri_uv.release(); d_textures.release();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  // what every scene has on `device` beside its arrays (scene_create, clone_scene): the CU count, the stream, the events, the counters
+  int open(int device);
 };
-

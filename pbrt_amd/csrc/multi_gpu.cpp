@@ -143,31 +143,16 @@ namespace {
 
 // a copy of `src` (any device) on `device`: every array of the scene travels device to device
 int clone_scene(const pbrt_hip_scene *src, int device, pbrt_hip_scene **out) {
-  HIP_TRY(hipSetDevice(device));
   std::unique_ptr<pbrt_hip_scene> s(new pbrt_hip_scene());
-  s->device = device;
-  {
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    s->n_cu = cus > 0 ? (uint32_t)cus : 1u;
-  }
+  const int rc = s->open(device);
+  if (rc) return rc;
   s->desc = src->desc;
   s->bvh.depth = src->bvh.depth;  // (the host copy of the tree stays with the original: export / info use that one)
-  s->n_lights = src->n_lights;
   s->gpu_built = src->gpu_built;
   s->n_quads_gpu = src->n_quads_gpu;
   s->n_prims = src->n_prims;
-  s->build_ms = src->build_ms;
-  s->reinsert_passes = src->reinsert_passes;
-  s->reinsert_moves = src->reinsert_moves;
-  s->reinsert_ms = src->reinsert_ms;
-  s->reinsert_cost_before = src->reinsert_cost_before;
-  s->reinsert_cost_after = src->reinsert_cost_after;
-  s->reinsert_undone = src->reinsert_undone;
+  s->build = src->build;
   s->device_bytes = src->device_bytes;
-  HIP_TRY(hipStreamCreate(&s->stream));
-  HIP_TRY(hipEventCreate(&s->ev0));
-  HIP_TRY(hipEventCreate(&s->ev1));
   int can = 0;
   if (hipDeviceCanAccessPeer(&can, device, src->device) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(src->device, 0);  // (already enabled is fine)
   (void)hipGetLastError();
@@ -180,7 +165,6 @@ int clone_scene(const pbrt_hip_scene *src, int device, pbrt_hip_scene **out) {
   CLONE(d_P); CLONE(d_idx); CLONE(d_order); CLONE(d_mat_id); CLONE(d_nodes); CLONE(d_quads);
   CLONE(d_tris); CLONE(d_mats); CLONE(d_lights); CLONE(d_spheres); CLONE(d_tri_uv); CLONE(d_textures);
 #undef CLONE
-  HIP_TRY(s->d_counters.alloc(80));
   HIP_TRY(hipStreamSynchronize(s->stream));
   s->dev = src->dev;
   s->dev.nodes = s->d_nodes.p;
@@ -258,14 +242,12 @@ int ensure_buffers(pbrt_hip_multi *m, size_t count, bool gather) {
   for (int g = 0; g < m->n; g++) {
     if (m->slabs[g].n >= count) continue;
     HIP_TRY(hipSetDevice(m->dev[g]));
-    m->slabs[g].release();
     HIP_TRY(m->slabs[g].alloc(count));
     HIP_TRY(hipMemsetAsync(m->slabs[g].p, 0, count * sizeof(float4), m->streams[g]));  // (a rank without tiles sends zeros)
   }
   const size_t need = gather ? (size_t)m->n * count : count;
   if (m->n > 1 && m->gathered.n < need) {
     HIP_TRY(hipSetDevice(0));
-    m->gathered.release();
     HIP_TRY(m->gathered.alloc(need));
   }
   return PBRT_HIP_OK;

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import pbrt_amd
-from pbrt_amd import _lib, scenes
+from pbrt_amd import _lib, api, scenes
 from util import SMALL_SCENES, assert_bit_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -196,7 +196,7 @@ def test_shards_partition_the_film_for_any_gpu_count():
             assert (seen == 1).all() and sizes[0] == max(sizes)
 
 
-def test_bad_arguments_are_rejected_before_any_device_work():
+def test_bad_arguments_are_rejected_before_any_device_work(monkeypatch):
     sd = scenes.cornell_scene(8, 8)
     sd.mat_id = sd.mat_id.copy()
     sd.mat_id[0] = 99
@@ -265,6 +265,50 @@ def test_bad_arguments_are_rejected_before_any_device_work():
         with pytest.raises(_lib.PbrtHipError) as e:
             pbrt_amd.Scene(sd)
         assert e.value.code == -1 and what in str(e.value), (what, str(e.value))
+    # the light and material types, a sphere box beyond fp32 and the builder flags: refused before any device work as well
+    for field, row, cols, vals, what in (("lights", 0, [0], [7], "unknown light type"), ("materials", 0, [0], [5], "unknown material type"),
+                                         ("spheres", 0, [0, 3], [3e38, 1e38], "bounding box is not finite")):
+        sd = scenes.check_sphere_scene(8, 8)
+        arr = getattr(sd, field).copy()
+        arr[row, cols] = vals
+        setattr(sd, field, arr)
+        with pytest.raises(_lib.PbrtHipError) as e:
+            pbrt_amd.Scene(sd)
+        assert e.value.code == -1 and what in str(e.value), (what, str(e.value))
+    for flags, what in ((16, "unknown flag"), (api.SCENE_HOST_BUILD | api.SCENE_GPU_BUILD, "not combined")):
+        monkeypatch.setitem(api.BUILDERS, "bad", flags)
+        with pytest.raises(_lib.PbrtHipError) as e:
+            pbrt_amd.Scene(scenes.cornell_scene(8, 8), builder="bad")
+        assert e.value.code == -1 and what in str(e.value), (what, str(e.value))
+
+
+def test_device_buffer_is_empty_after_a_failed_allocation(tmp_path):
+    """DevBuf (capi_internal.hpp): a failed hipMalloc leaves the buffer empty, so the next grow() allocates again instead of
+    taking the buffer for big enough; a move leaves the source empty.  (2^60 bytes fail on any device, and everything fails without one.)"""
+    import subprocess
+    from pbrt_amd import build
+    src = tmp_path / "devbuf.cpp"
+    src.write_text("""#include <cstdio>
+#include <utility>
+#include "capi_internal.hpp"
+int main() {
+  const size_t huge = (size_t(1) << 60) / sizeof(float4);
+  pbrt_hip::DevBuf<float4> b;
+  if (b.alloc(huge) == hipSuccess || b.n != 0 || b.p != nullptr) return 1;
+  if (b.grow(huge) == hipSuccess || b.n != 0 || b.p != nullptr) return 2;  // tried again, failed again
+  const hipError_t e = b.grow(64);
+  if (e == hipSuccess ? (b.n != 64 || b.p == nullptr) : (b.n != 0 || b.p != nullptr)) return 3;
+  pbrt_hip::DevBuf<float4> c(std::move(b));
+  if (b.n != 0 || b.p != nullptr || c.n != (e == hipSuccess ? 64u : 0u)) return 4;
+  std::printf("ok %d\\n", (int)e);
+  return 0;
+}
+""")
+    exe = tmp_path / "devbuf"
+    subprocess.run([build.HIPCC, "-std=c++17", "-x", "hip", f"--offload-arch={build.ARCH}", "-I", build.CSRC, str(src), "-o", str(exe)],
+                   check=True, timeout=600)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), (r.returncode, r.stdout, r.stderr)
 
 
 @pytest.mark.parametrize("name", ["mesh1k", "mesh20k", "cornell", "check_sphere", "sphere", "spheres2k"])

@@ -39,14 +39,26 @@ typedef enum {
   PBRT_HIP_ERR_INTERNAL = -5
 } pbrt_hip_status;
 
-/* Material "matte" / "mirror" (scene files name them: scenes/check-sphere.pbrt:21,29; the
- * reference only has the TODO at api.rs:255-269).  32 bytes. */
+#define PBRT_HIP_MATERIAL_MATTE 0u
+#define PBRT_HIP_MATERIAL_MIRROR 1u
+#define PBRT_HIP_MATERIAL_GLASS 2u
+/* Material "matte" / "mirror" / "glass" (scene files name them: scenes/check-sphere.pbrt:21,29; the
+ * reference only has the TODO at api.rs:255-269).  32 bytes.
+ * GLASS (type 2) is pbrt-v3's GlassMaterial with zero roughness: one FresnelSpecular lobe, an interface between index 1
+ * on the side the geometric normal points to (a triangle's winding normal, a sphere's outward one) and index eta on the other; no
+ * nested media.  It needs seven numbers and reuses the seven words after `type`:
+ *   k = Kr (reflectance), le = Kt (TRANSMITTANCE -- a glass surface does not emit), kd_tex = the IEEE-754 bits of the float eta.
+ * Kr, Kt finite and >= 0, eta finite and in [1, 16] (PBRT_HIP_ERR_INVALID otherwise, the message holds "glass").  At a hit ONE 1-D
+ * sample chooses reflection (probability F, the Fresnel reflectance; weight Kr) or refraction (1 - F; weight Kt eta_i^2 / eta_t^2:
+ * radiance transport); also under Integrator "directlighting", where pbrt-v3 follows both branches and this path follows the one
+ * chosen (same expectation).  Every interface crossed costs one bounce of max_depth.  A glass primitive occludes shadow rays (as in
+ * pbrt-v3: no caustics by light sampling).  Not with the counter flags (PBRT_HIP_ERR_LIMIT). */
 typedef struct {
-  uint32_t type; /* 0 = matte (Lambertian, k = Kd), 1 = mirror (perfect specular, k = Kr) */
+  uint32_t type; /* PBRT_HIP_MATERIAL_*: 0 = matte (Lambertian, k = Kd), 1 = mirror (perfect specular, k = Kr), 2 = glass (above) */
   float k[3];
   float le[3]; /* emitted radiance; non-zero turns every triangle using it into an area light
-                  (replaces api.rs:476-478 area_light_source -> todo!()) */
-  uint32_t kd_tex; /* matte only: 0 = Kd is k; t > 0 = Kd is textures[t - 1] evaluated at the hit's (u, v): a triangle's corner (u, v)
+                  (replaces api.rs:476-478 area_light_source -> todo!()).  GLASS: Kt */
+  uint32_t kd_tex; /* GLASS: the bits of the float eta.  Matte only: 0 = Kd is k; t > 0 = Kd is textures[t - 1] evaluated at the hit's (u, v): a triangle's corner (u, v)
                       (tri_uv) interpolated like the hit point; a SPHERE's own (u, v) = (phi / 2 pi, 1 - theta / pi) with phi = atan2(n.y, n.x)
                       in [0, 2 pi), theta = acos(n.z) of the unit normal n about the WORLD's z axis (pbrt-v3 Sphere::Intersect for an
                       unrotated sphere: a sphere here is a centre and a radius, its CTM's rotation is not carried -- the parser warns) */
@@ -154,8 +166,9 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.5 (gfx950)": 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
-                                       end, pbrt_hip_material.pad became kd_tex, flags 0 of scene_create_ex = the device builder) */
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.6 (gfx950)": 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
+                                       end, pbrt_hip_material.pad became kd_tex, flags 0 of scene_create_ex = the device builder); 0.6 =
+                                       material type 2, glass, inside the same struct sizes */
 /* identity of the build: a hash of the library's sources and kernel-shaping flags (pbrt_amd/build.py source_id).  A
  * profile taken on one build must not price another: bench.py compares this with the id stored beside the counters */
 const char *pbrt_hip_build_id(void);

@@ -11,7 +11,7 @@ import numpy as np
 from . import _lib
 from ._lib import Light, Material, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
 
-MATTE, MIRROR = 0, 1
+MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
 INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_PATH_MIS = 0, 1, 2  # 2: the path integrator with MIS
 FLAG_COUNTERS = 1
@@ -37,7 +37,9 @@ class SceneData:
     (api.rs:220-223).  `materials` rows: (type, kr, kg, kb, ler, leg, leb); `lights` rows:
     (type, px, py, pz, cr, cg, cb); `spheres` rows: (cx, cy, cz, r, material).  Textured materials: `mat_tex[i]` =
     0 or 1 + the row of `textures` that is material i's Kd, `textures` rows: (type 0 = checkerboard, tex1 rgb, tex2 rgb, su, sv, du,
-    dv), `tri_uv` rows: (u0, v0, u1, v1, u2, v2) per triangle (needed when a triangle's material is textured)."""
+    dv), `tri_uv` rows: (u0, v0, u1, v1, u2, v2) per triangle (needed when a triangle's material is textured).  Glass:
+    a `materials` row (GLASS, Kr rgb, Kt rgb) -- a glass surface does not emit -- and `mat_eta[i]` = its index of refraction (an empty
+    `mat_eta` = 1.5 for every glass row; the entries of other rows are not read)."""
     P: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
     idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.uint32))
     mat_id: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint16))
@@ -52,6 +54,7 @@ class SceneData:
     mat_tex: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint32))
     textures: np.ndarray = field(default_factory=lambda: np.zeros((0, 11), np.float32))
     tri_uv: np.ndarray = field(default_factory=lambda: np.zeros((0, 6), np.float32))
+    mat_eta: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.float32))
 
     def normalized(self):
         self.P = np.ascontiguousarray(self.P, np.float32).reshape(-1, 3)
@@ -65,6 +68,10 @@ class SceneData:
         if self.mat_tex.shape[0] != self.materials.shape[0]:
             assert self.mat_tex.shape[0] == 0
             self.mat_tex = np.zeros(self.materials.shape[0], np.uint32)
+        self.mat_eta = np.ascontiguousarray(self.mat_eta, np.float32).reshape(-1)
+        if 0 < self.mat_eta.shape[0] < self.materials.shape[0]:  # (materials appended since: 1.5, as for an empty array)
+            self.mat_eta = np.concatenate([self.mat_eta, np.full(self.materials.shape[0] - self.mat_eta.shape[0], 1.5, np.float32)])
+        assert self.mat_eta.shape[0] in (0, self.materials.shape[0])
         self.textures = np.ascontiguousarray(self.textures, np.float32).reshape(-1, 11)
         self.tri_uv = np.ascontiguousarray(self.tri_uv, np.float32).reshape(-1, 6)
         assert self.idx.shape[0] == self.mat_id.shape[0] and self.tri_uv.shape[0] in (0, self.idx.shape[0])
@@ -84,6 +91,9 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         mats[i].k[:] = [float(x) for x in m[1:4]]
         mats[i].le[:] = [float(x) for x in m[4:7]]
         mats[i].kd_tex = int(sd.mat_tex[i])
+        if int(m[0]) == GLASS:  # include/pbrt_hip.h: k = Kr, le = Kt, kd_tex = the IEEE-754 bits of eta
+            eta = sd.mat_eta[i:i + 1] if len(sd.mat_eta) else np.array([1.5], np.float32)
+            mats[i].kd_tex = int(eta.view(np.uint32)[0])
     texs = None
     if len(sd.textures):
         tex_t = tex_t or dict(desc._fields_)["textures"]._type_  # (the Texture class of the caller's own struct mirror)

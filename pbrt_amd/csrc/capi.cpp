@@ -671,6 +671,11 @@ enum class Builder { kHost, kHostOptimized, kGpu, kGpuPlain };
 
 // a material whose Kd is a texture
 bool kd_textured(const pbrt_hip_material &m) { return m.kd_tex != 0u && m.type == 0u; }
+// a glass material's index of refraction: the float whose bits ride in kd_tex
+float glass_eta(const pbrt_hip_material &m) { float e; std::memcpy(&e, &m.kd_tex, 4); return e; }
+// glass is an interface between index 1 and eta: eta = 1 (index-matched: nothing reflects, nothing bends) is legal; 16 is four times
+// the densest real dielectric and keeps eta^2 and 1 / eta^2 -- the radiance scale of a refraction -- far from fp32's ends
+constexpr float kGlassEtaMin = 1.0f, kGlassEtaMax = 16.0f;
 
 // Every refusal that depends on the description alone, before any HIP call, and the builder that `flags` (and PBRT_HIP_BUILDER) ask for.
 int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *builder) {
@@ -703,8 +708,18 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
         return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": position / direction / colour is not finite");
   for (uint32_t i = 0; i < d->n_mats; i++)
     for (int k = 0; k < 3; k++)
-      if (!std::isfinite(d->mats[i].k[k]) || !std::isfinite(d->mats[i].le[k]))
+      if (d->mats[i].type != PBRT_HIP_MATERIAL_GLASS && (!std::isfinite(d->mats[i].k[k]) || !std::isfinite(d->mats[i].le[k])))
         return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": colour / emission is not finite");
+  for (uint32_t i = 0; i < d->n_mats; i++) {  // glass: k = Kr, le = Kt, kd_tex = the bits of eta
+    const pbrt_hip_material &m = d->mats[i];
+    if (m.type != PBRT_HIP_MATERIAL_GLASS) continue;
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(m.k[k]) || !std::isfinite(m.le[k]) || !(m.k[k] >= 0.f) || !(m.le[k] >= 0.f))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": glass Kr / Kt must be finite and >= 0");
+    const float eta = glass_eta(m);
+    if (!std::isfinite(eta) || !(eta >= kGlassEtaMin && eta <= kGlassEtaMax))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": glass eta (the float in kd_tex) must be finite and lie in [1, 16]");
+  }
   for (int k = 0; k < 16; k++)
     if (!std::isfinite(d->cam_to_world[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: camera matrix is not finite");
   if (!(d->fov > 0.f && d->fov < 180.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: fov must lie in (0, 180) degrees");
@@ -714,6 +729,7 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
     if (d->spheres[s].mat >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere material id out of range");
   if (d->n_textures && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_textures > 0 but no texture table");
   for (uint32_t i = 0; i < d->n_mats; i++) {
+    if (d->mats[i].type == PBRT_HIP_MATERIAL_GLASS) continue;  // (kd_tex holds eta)
     if (d->mats[i].kd_tex > d->n_textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
     if (d->mats[i].kd_tex && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: textured material but no texture table");
   }
@@ -745,7 +761,7 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
   for (uint32_t i = 0; i < d->n_lights; i++)
     if (d->lights[i].type > 2) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
   for (uint32_t i = 0; i < d->n_mats; i++)
-    if (d->mats[i].type > 1) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
+    if (d->mats[i].type > PBRT_HIP_MATERIAL_GLASS) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
   const char *env = want_host || want_gpu ? nullptr : std::getenv("PBRT_HIP_BUILDER");
   if (flags & PBRT_HIP_SCENE_OPTIMIZED_TREE) *builder = Builder::kHostOptimized;
   else if ((flags & PBRT_HIP_SCENE_HOST_BUILD) || (env && std::strcmp(env, "host") == 0)) *builder = Builder::kHost;
@@ -768,6 +784,7 @@ struct SceneInputs {
   std::vector<uint32_t> idx_aug;
   std::vector<uint16_t> mat_aug;
   std::vector<float4> lights, mats, spheres, textures;  // the kernels' records: 5, 2, 2 and 3 per light / material / sphere / texture
+  std::vector<float4> glass;  // {Kt, eta} per material, when the scene has a glass one; else empty
   float le_inf[3] = {0.f, 0.f, 0.f};
   bool has_inf = false;
   bool textured_tris = false;  // a triangle whose material's Kd is a texture: its corner (u, v) go up too
@@ -809,6 +826,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
   }
   for (uint32_t t = 0; t < d.n_tris; t++) {
     const pbrt_hip_material &m = d.mats[d.mat_id[t]];
+    if (m.type == PBRT_HIP_MATERIAL_GLASS) continue;  // (its le is Kt: glass does not emit)
     if (!(m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) continue;
     F3 p[3];
     for (int v = 0; v < 3; v++) {
@@ -828,6 +846,11 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
     const pbrt_hip_material &m = d.mats[i];
     in->mats[2 * i] = make_float4(as_f(m.type), m.k[0], m.k[1], m.k[2]);
     in->mats[2 * i + 1] = make_float4(m.le[0], m.le[1], m.le[2], as_f(m.type == 0u ? m.kd_tex : 0u));
+    if (m.type == PBRT_HIP_MATERIAL_GLASS) {  // no emission on the device; {Kt, eta} in the table of the GLS instantiations
+      in->mats[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (in->glass.empty()) in->glass.assign(d.n_mats, make_float4(0.f, 0.f, 0.f, 1.f));
+      in->glass[i] = make_float4(m.le[0], m.le[1], m.le[2], glass_eta(m));
+    }
   }
   in->spheres.resize(2 * (size_t)d.n_spheres);
   for (uint32_t i = 0; i < d.n_spheres; i++) {
@@ -857,6 +880,7 @@ int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const SceneIn
   HIP_TRY(upload(&s->d_lights, in.lights.data(), in.lights.size(), s->stream));
   HIP_TRY(upload(&s->d_spheres, in.spheres.data(), in.spheres.size(), s->stream));
   HIP_TRY(upload(&s->d_textures, in.textures.data(), in.textures.size(), s->stream));
+  HIP_TRY(upload(&s->d_glass, in.glass.data(), in.glass.size(), s->stream));
   if (in.textured_tris) HIP_TRY(upload(&s->d_tri_uv_in, d.tri_uv, 6 * (size_t)d.n_tris, s->stream));
   DevScene &D = s->dev;
   D.mats = s->d_mats.p;
@@ -955,7 +979,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.5 (gfx950)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.6 (gfx950)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif
@@ -1042,13 +1066,14 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
     gather_inputs(*d, &in);
     s->n_prims = in.n_prims;
     s->textured = in.textured_tris || in.textured_sph;
+    s->glass = !in.glass.empty();
     if ((rc = upload_inputs(s.get(), *d, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
     if (in.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
       HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));
       HIP_TRY(launch_pack_uv(s->d_tri_uv_in.p, s->d_order.p, in.n_prims, d->n_tris, s->d_tri_uv.p, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    s->device_bytes = s->d_tri_uv_in.n * 4 + s->d_tri_uv.n * 8 + s->d_textures.n * 16 + s->d_P.n * 4 + s->d_idx.n * 4 + s->d_mat_id.n * 2 + s->d_order.n * 4 + s->d_nodes.n * 16 + s->d_quads.n * 16 +
+    s->device_bytes = s->d_glass.n * 16 + s->d_tri_uv_in.n * 4 + s->d_tri_uv.n * 8 + s->d_textures.n * 16 + s->d_P.n * 4 + s->d_idx.n * 4 + s->d_mat_id.n * 2 + s->d_order.n * 4 + s->d_nodes.n * 16 + s->d_quads.n * 16 +
                       s->d_tris.n * 16 + s->d_mats.n * 16 + s->d_lights.n * 16 + s->d_spheres.n * 16;
     set_view(&s->dev, *d);
     *out = s.release();
@@ -1164,6 +1189,8 @@ static int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc
   // instantiations exist for the default path alone)
   if ((s->textured || r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS) && (r->flags & (PBRT_HIP_FLAG_COUNTERS | PBRT_HIP_FLAG_WALK_COUNTERS)))
     return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for textured materials / the MIS integrator");
+  if (s->glass && (r->flags & (PBRT_HIP_FLAG_COUNTERS | PBRT_HIP_FLAG_WALK_COUNTERS)))
+    return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for a scene with a glass material");
   if (!(r->max_sample_luminance >= 0.f)) return fail(PBRT_HIP_ERR_INVALID, "render: max_sample_luminance must be >= 0 (0 = none)");
   if (fx != 0.5f || fy != 0.5f) {
     // the fixed-point film: a sample adds at most 2^39 units to a pixel's int64 accumulator, and a pixel receives
@@ -1201,10 +1228,11 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
   L.table_sampler = r->sampler == PBRT_HIP_SAMPLER_SOBOL_ND || r->sampler == PBRT_HIP_SAMPLER_HALTON;
   L.mis = r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS;
   L.textured = s->textured;
+  L.glass = s->glass;
   const bool shallow = s->dev.quad_stack_need <= kShallowStackNeed;
   L.plan = stack_plan(s->dev.quad_stack_need);
   L.lds_bytes = L.plan.rows * 256u;
-  const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured;
+  const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured && !L.glass;
   L.steps = default_path && !L.plan.overflow && shallow ? 2u : PBRT_STEPS_PER_CHECK;
   if (L.counters == kCountExact) {
     const int ce = ensure_canonical(s);
@@ -1215,7 +1243,7 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
     L.lds_bytes = L.exact_rows * 512u;
   }
   // (the instantiations for another filter radius and for the table samplers fit the 96 VGPRs of 5 waves per SIMD like the default one)
-  L.waves_per_cu = L.spheres ? std::min(kRenderWavesPerCuSpheres, L.plan.waves_per_cu) : L.plan.waves_per_cu;
+  L.waves_per_cu = (L.spheres || L.glass) ? std::min(kRenderWavesPerCuSpheres, L.plan.waves_per_cu) : L.plan.waves_per_cu;  // (glass: the spheres' budget, kernels.hip)
   L.chunk_shift = sample_chunk_shift(r->spp_x * r->spp_y);
   const uint32_t n_chunks = 1u << L.chunk_shift;  // K: DESIGN.md 3.1
   L.passes = fg.wide ? 1u : partials_passes(sh.n_local, n_chunks);
@@ -1304,6 +1332,7 @@ int pbrt_hip_render_device(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, voi
     R.sobol_mat = r->sampler == PBRT_HIP_SAMPLER_HALTON ? s->d_halton.p : (r->sampler == PBRT_HIP_SAMPLER_SOBOL_ND ? s->d_sobol.p : nullptr);
     R.tri_uv = s->d_tri_uv.p;
     R.textures = s->d_textures.p;
+    R.glass = s->d_glass.p;
     R.integrator = r->integrator;
     R.max_depth = r->max_depth;
     R.spp_x = r->spp_x;

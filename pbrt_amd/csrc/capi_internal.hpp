@@ -107,6 +107,8 @@ struct pbrt_hip_scene : pbrt_hip::SceneStream {
   pbrt_hip::DevBuf<float2> d_tri_uv;    // ... and in leaf-slot order (3 per slot)
   pbrt_hip::DevBuf<float4> d_textures;
   bool textured = false;                // some triangle's material has kd_tex != 0: the TEX instantiations render it
+  pbrt_hip::DevBuf<float4> d_glass;     // {Kt, eta} per material of a scene with glass; empty otherwise
+  bool glass = false;                   // some material is glass: the GLS instantiations render the scene
   pbrt_hip::DevBuf<float4> d_tris_exact;
   pbrt_hip::DevBuf<uint32_t> d_order_exact;
   double canonical_build_ms = 0.0;

@@ -182,6 +182,9 @@ struct RenderParams {
   // with them the machine code of the instantiations the counter profiles are keyed by.)
   const float2 *tri_uv;
   const float4 *textures;
+  // glass materials (render_kernel_x<..., GLS>): 16 B per MATERIAL {Kt.rgb, eta}, read for the materials of type 2 alone
+  // (mats[2 i] = {2, Kr}, mats[2 i + 1] = 0: glass does not emit).  At the end, for the reason given above.
+  const float4 *glass;
 };
 // 2^24 fixed-point units per unit of radiance, a component clamped to [0, 2^15]
 constexpr float kFixedOne = 16777216.0f, kFixedMax = 32768.0f;
@@ -213,6 +216,7 @@ struct RenderLaunch {
   bool wide;           // WIDE: a box filter radius other than 0.5
   bool table_sampler;  // SND: samplers 2 and 3 (3.12, 3.13)
   bool mis, textured;  // render_kernel_x's MIS (3.14) and TEX (3.15)
+  bool glass;          // render_kernel_x's GLS (3.16): the scene has a glass material
   RenderStackPlan plan;  // the production walk's stack: LDS rows, the overflow variant, HBM entries per lane
   uint32_t steps;        // production walk: node steps per scheduling check (STEPS)
   uint32_t exact_rows;   // exact walk: STACK, its stack rows of refs (and as many of entry distances)

@@ -138,6 +138,25 @@ __device__ __forceinline__ void sphere_uv(float nx, float ny, float nz, float *u
   *v = (theta - 3.14159265358979323846f) / (0.f - 3.14159265358979323846f);
 }
 
+// Fresnel reflectance of a smooth dielectric interface and the cosine of the refracted ray (pbrt-v3 FrDielectric):
+// ci = |cos theta_i| in [0, 1], r = eta_i / eta_t.  sin^2 theta_t = r^2 (1 - ci^2) >= 1 is total internal reflection: F = 1, ct = 0.
+// With e = 1 / r = eta_t / eta_i the two amplitudes are (e ci - ct) / (e ci + ct) and (ci - e ct) / (ci + e ct): both denominators are
+// positive whenever the ray is not totally reflected (ci = 0 gives sin^2 theta_t = r^2, so ct > 0 or F = 1 already) -- no 0 / 0 at
+// grazing incidence, and r = 1 gives ct = ci up to rounding: F of the order of 1e-14.
+__device__ __forceinline__ void glass_fresnel(float ci, float r, float &F, float &ct) {
+  const float s2i = fmaxf(0.f, 1.0f - ci * ci);
+  const float s2t = (r * r) * s2i;
+  F = 1.0f;
+  ct = 0.f;
+  if (s2t < 1.0f) {
+    ct = sqrtf(1.0f - s2t);
+    const float e = 1.0f / r;
+    const float rpar = (e * ci - ct) / (e * ci + ct);
+    const float rper = (ci - e * ct) / (ci + e * ct);
+    F = 0.5f * (rpar * rpar + rper * rper);
+  }
+}
+
 // cosine-weighted direction about n; returns local z (0 => pdf 0)
 __device__ __forceinline__ float cosine_about(V3 n, float u1, float u2, V3 &wi) {
   float ox = 2.0f * u1 - 1.0f, oy = 2.0f * u2 - 1.0f;
@@ -929,16 +948,19 @@ template <bool SPH, bool COUNT, bool EXACT, int STACK, int STEPS = PBRT_STEPS_PE
 // (scenes with spheres -- C0 / C1: a handful of primitives, nothing to gain from occupancy -- get the register budget
 // of 3 waves per SIMD: the f64 quadratic of lib.rs:181-203 does not fit 128 VGPRs beside the path state)
 __global__ void __launch_bounds__(64, (COUNT ? 1 : (SPH ? 3 : PBRT_RENDER_WAVES_PER_SIMD))) render_kernel(const DevScene S, const RenderParams R) {
-  constexpr bool MIS = false, TEX = false;  // (the variants: render_kernel_x below)
+  constexpr bool MIS = false, TEX = false, GLS = false;  // (the variants: render_kernel_x below)
   (void)MIS;
+  (void)GLS;
 #include "render_body.inc"
 }
 // The variants of the path that BASELINE's configs do not use, in a kernel of their own name so that the instantiations above keep
 // theirs (and their machine code): MIS = multiple importance sampling of the direct-light estimate, TEX = materials
-// whose Kd is a checkerboard texture (3.15) -- and every combination of the two with the table samplers (SND: 3.12, 3.13) and a box
-// filter radius other than 0.5 (WIDE: 3.11), which render_kernel instantiates one at a time.  No counters.
-template <bool SPH, int STACK, bool MIS, bool TEX, bool SND, bool WIDE>
-__global__ void __launch_bounds__(64, (SPH ? 3 : PBRT_RENDER_WAVES_PER_SIMD)) render_kernel_x(const DevScene S, const RenderParams R) {
+// whose Kd is a checkerboard texture (3.15), GLS = glass materials (3.16) -- and every combination of the three with the table samplers
+// (SND: 3.12, 3.13) and a box filter radius other than 0.5 (WIDE: 3.11), which render_kernel instantiates one at a time.  No counters.
+// (The GLS instantiations get the spheres' register budget, 3 waves per SIMD: with the Fresnel / refraction branch beside the path state
+// the body needs up to 9 VGPRs more than the 96 of 5 waves, and a spill costs every scene more than glass scenes lose in occupancy.)
+template <bool SPH, int STACK, bool MIS, bool TEX, bool SND, bool WIDE, bool GLS = false>
+__global__ void __launch_bounds__(64, ((SPH || GLS) ? 3 : PBRT_RENDER_WAVES_PER_SIMD)) render_kernel_x(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false;
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
 #include "render_body.inc"
@@ -1152,12 +1174,15 @@ hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderL
       return hipErrorInvalidValue;
     }, L.spheres);
   // (ray log / phase probe builds wrap the default path's launch: experiments.inc)
-  const bool experiment = kExperimentLaunch && L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured;
+  const bool experiment = kExperimentLaunch && L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured && !L.glass;
   hipError_t e = hipSuccess;
   if (experiment && experiment_launch_begin(&e)) return e;
-  e = with_bools([&](auto SPH, auto OVF, auto COUNT, auto MIS, auto TEX, auto SND, auto WIDE) {
+  e = with_bools([&](auto SPH, auto OVF, auto COUNT, auto MIS, auto TEX, auto SND, auto WIDE, auto GLS) {
     constexpr int STACK = OVF ? (int)kQuadLdsStackOvf : 0;
-    if constexpr (MIS || TEX || (SND && WIDE)) {
+    if constexpr (GLS) {  // a scene with a glass material: always render_kernel_x<..., GLS = true>
+      if constexpr (COUNT) return hipErrorInvalidValue;
+      else return go(render_kernel_x<SPH, STACK, MIS, TEX, SND, WIDE, true>);
+    } else if constexpr (MIS || TEX || (SND && WIDE)) {
       if constexpr (COUNT) return hipErrorInvalidValue;
       else return go(render_kernel_x<SPH, STACK, MIS, TEX, SND, WIDE>);
     } else if constexpr (COUNT && (SND || WIDE)) {
@@ -1167,7 +1192,7 @@ hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderL
     } else {
       return go(render_kernel<SPH, COUNT, false, STACK, PBRT_STEPS_PER_CHECK, WIDE, SND>);
     }
-  }, L.spheres, L.plan.overflow, L.counters == kCountWalk, L.mis, L.textured, L.table_sampler, L.wide);
+  }, L.spheres, L.plan.overflow, L.counters == kCountWalk, L.mis, L.textured, L.table_sampler, L.wide, L.glass);
   if (experiment) experiment_launch_end(st);
   return e;
 }

@@ -1,5 +1,5 @@
 // render_body.inc -- the body of render_kernel and of render_kernel_x (kernels.hip), included once in each: the two are the same
-// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX in scope.  (A shared __device__
+// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS in scope.  (A shared __device__
 // function would be the tidy way to say this; the text is included instead because wrapping the body in a function -- forceinline or
 // not -- perturbs the register allocation of the production instantiation, whose machine code the committed counter profiles are
 // keyed by: pbrt_amd/isa_id.py; measured in round 5.)  In scope as well: `S` (DevScene) and `R` (RenderParams), the kernel's arguments.
@@ -90,6 +90,7 @@
           V3 p = {0.f, 0.f, 0.f}, ng = {0.f, 0.f, 1.f};
           float4 m0 = {0.f, 0.f, 0.f, 0.f}, m1 = {0.f, 0.f, 0.f, 0.f};
           float tri_area = 0.f;  // MIS: the hit triangle's area
+          float4 gl = {0.f, 0.f, 0.f, 1.f};  // GLS: {Kt, eta} of a glass material (DESIGN.md 3.16)
           const V3 wo = -T.d;
           if (hit) {
             uint32_t mid;
@@ -112,6 +113,7 @@
             }
             m0 = S.mats[2 * mid];
             m1 = S.mats[2 * mid + 1];
+            if (GLS && __float_as_uint(m0.x) == 2u) gl = R.glass[mid];
           }
           if (P.bounces == 0 || P.specular) {
             if (hit) {
@@ -169,7 +171,26 @@
             float sh_tmax = kInf;
             bool alive = true;
             V3 lpend = {0.f, 0.f, 0.f};
-            if (__float_as_uint(m0.x) == 0u) {  // matte
+            bool transmitted = false;  // GLS: the bounce ray leaves on the far side of the surface
+            if (GLS && __float_as_uint(m0.x) == 2u) {
+              // glass (DESIGN.md 3.16; pbrt-v3 FresnelSpecular): ONE 1-D request chooses reflection (probability F, weight Kr) or
+              // refraction (1 - F, weight Kt eta_i^2 / eta_t^2); no light sample, no shadow ray; specular like the mirror
+              const float cos_o = dot(ng, wo);
+              const float ci = fminf(fabsf(cos_o), 1.0f);
+              const float r = cos_o > 0.f ? 1.0f / gl.w : gl.w;  // eta_i / eta_t: entering where wo is on the normal's side
+              float F, ct;
+              glass_fresnel(ci, r, F, ct);
+              const float u = sample_1d<SND>(P, sobol, spp_mask, R.sobol_mat, halton);
+              if (u < F) {
+                P.wi_next = -wo + nf * (2.0f * ci);
+                P.beta = P.beta * k;
+              } else {
+                P.wi_next = -wo * r + nf * (r * ci - ct);
+                P.beta = P.beta * (mk(gl.x, gl.y, gl.z) * (r * r));
+                transmitted = true;
+              }
+              P.specular = true;
+            } else if (__float_as_uint(m0.x) == 0u) {  // matte
               if (nL > 0u) {
                 const float xi = sample_1d<SND>(P, sobol, spp_mask, R.sobol_mat, halton);
                 float u1, u2;
@@ -211,6 +232,7 @@
             }
             P.cont = alive;
             ro = po;  // shadow ray and bounce ray both leave from the offset point
+            if (GLS && transmitted) ro = p - nf * kSpawnEps;  // (a refracted ray: from below the surface)
             if (need_shadow) {
               rd = sh_d;
               rtmax = sh_tmax;

@@ -230,6 +230,8 @@ struct MaterialDef {
   uint32_t type = 0;  // matte
   float k[3] = {0.5f, 0.5f, 0.5f};
   uint32_t kd_tex = 0;  // 1 + index into LoadedScene::textures when "texture Kd" names a checkerboard
+  float kt[3] = {1.f, 1.f, 1.f};  // glass (type 2): k = Kr, kt = Kt, eta = the index of refraction
+  float eta = 1.5f;
 };
 struct GraphicsState {  // api.rs:251-289
   MaterialDef material;
@@ -254,7 +256,7 @@ struct Api {
   std::map<std::string, std::array<float, 3>> spectrum_textures;
   std::map<std::string, uint32_t> checker_textures;  // name -> 1 + index into out->textures
   std::map<std::string, MaterialDef> named_materials;
-  std::map<std::tuple<uint32_t, float, float, float, float, float, float, uint32_t>, uint16_t> material_ids;
+  std::map<std::tuple<uint32_t, float, float, float, float, float, float, uint32_t, float, float, float, float>, uint16_t> material_ids;
   bool camera_set = false;
   std::string cur_dir;  // directory of the file being parsed: resolves Shape "plymesh" "string filename" like Include
   // ObjectBegin "name" ... ObjectEnd / ObjectInstance "name" (pbrt-v3 api.cpp pbrtObjectBegin / pbrtObjectInstance; NotImplemented in the
@@ -348,6 +350,19 @@ struct Api {
       m.type = 1;
       m.k[0] = m.k[1] = m.k[2] = 0.9f;
       spectrum(ps, "Kr", m.k);
+    } else if (type == "glass") {
+      // pbrt-v3 GlassMaterial with zero roughness: Kr, Kt (default 1), "float index" or "float eta" (default 1.5; pbrt-v3
+      // reads both names).  A texture given as Kr / Kt is reduced to its constant colour, as every parameter but a matte Kd is.
+      m.type = PBRT_HIP_MATERIAL_GLASS;
+      m.k[0] = m.k[1] = m.k[2] = 1.f;
+      spectrum(ps, "Kr", m.k);
+      spectrum(ps, "Kt", m.kt);
+      m.eta = ps.one_float("eta", ps.one_float("index", 1.5f));
+      for (const char *rough : {"uroughness", "vroughness"})
+        if (ps.one_float(rough, 0.f) != 0.f || ps.find(rough, "texture"))
+          warn(std::string("Material \"glass\": \"") + rough + "\" is ignored (smooth glass is rendered)");
+      if (ps.find("bumpmap", "texture", "float")) warn("Material \"glass\": \"bumpmap\" is ignored (smooth glass is rendered)");
+      if (ps.find("remaproughness", "bool")) warn("Material \"glass\": \"remaproughness\" is ignored (smooth glass is rendered)");
     } else {
       warn("Material \"" + type + "\" is not supported by this path: using matte Kd 0.5");
     }
@@ -355,13 +370,19 @@ struct Api {
   }
 
   uint16_t material_id(const MaterialDef &m, const float le[3]) {
-    auto key = std::make_tuple(m.type, m.k[0], m.k[1], m.k[2], le[0], le[1], le[2], m.kd_tex);
+    const bool glass = m.type == PBRT_HIP_MATERIAL_GLASS;  // (the others keep the key they had: Kt = eta = 0)
+    auto key = std::make_tuple(m.type, m.k[0], m.k[1], m.k[2], le[0], le[1], le[2], m.kd_tex, glass ? m.kt[0] : 0.f, glass ? m.kt[1] : 0.f,
+                               glass ? m.kt[2] : 0.f, glass ? m.eta : 0.f);
     auto it = material_ids.find(key);
     if (it != material_ids.end()) return it->second;
     pbrt_hip_material pm{};
     pm.type = m.type;
     pm.kd_tex = m.kd_tex;
     for (int i = 0; i < 3; i++) { pm.k[i] = m.k[i]; pm.le[i] = le[i]; }
+    if (glass) {  // include/pbrt_hip.h: le = Kt, kd_tex = the bits of eta
+      for (int i = 0; i < 3; i++) pm.le[i] = m.kt[i];
+      std::memcpy(&pm.kd_tex, &m.eta, 4);
+    }
     const uint16_t id = (uint16_t)out->mats.size();
     out->mats.push_back(pm);
     material_ids[key] = id;
@@ -449,7 +470,14 @@ struct Api {
     }
     const float *le = (gs.has_area_light && !in_object) ? gs.area_le : zero;
     if (out->mats.size() >= 65535) { warn("more than 65535 materials: shape skipped"); return; }
-    const uint16_t mid = material_id(gs.material, le);
+    MaterialDef shape_mat = gs.material;
+    if (shape_mat.type == PBRT_HIP_MATERIAL_GLASS && (le[0] > 0.f || le[1] > 0.f || le[2] > 0.f)) {
+      // a glass material has no room for emission (its `le` is Kt): the shape emits, its surface is black matte
+      warn("Material \"glass\" under an AreaLightSource: the shape emits and is rendered as black matte");
+      shape_mat = MaterialDef();
+      shape_mat.k[0] = shape_mat.k[1] = shape_mat.k[2] = 0.f;
+    }
+    const uint16_t mid = material_id(shape_mat, le);
     const float *M = ctm[0].m;
     if (name == "sphere") {
       const float r = ps.one_float("radius", 1.f);
@@ -1040,7 +1068,7 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
   if (api.in_object) { api.warn("Missing end to ObjectBegin"); api.object_end(); }  // (the file ended inside an object: the scene's arrays come back)
   {  // corner (u, v) travel only when some triangle's material is textured
     bool textured = false;
-    for (uint16_t m : out->mat_id) textured = textured || out->mats[m].kd_tex != 0u;
+    for (uint16_t m : out->mat_id) textured = textured || (out->mats[m].type == PBRT_HIP_MATERIAL_MATTE && out->mats[m].kd_tex != 0u);
     if (!textured) { out->tri_uv.clear(); out->tri_uv.shrink_to_fit(); }
   }
   if (!api.camera_set) mat_identity(out->cam_to_world);

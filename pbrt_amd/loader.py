@@ -7,7 +7,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import RenderDesc, SceneDesc, check, lib
-from .api import SceneData
+from .api import GLASS, SceneData
 
 
 @dataclass
@@ -48,7 +48,9 @@ def _collect(h):
             spheres=np.array([[*d.spheres[i].c, d.spheres[i].r, d.spheres[i].mat] for i in range(d.n_spheres)], np.float32).reshape(-1, 5),
             cam_to_world=np.array(list(d.cam_to_world), np.float32).reshape(4, 4), fov=d.fov, xres=d.xres, yres=d.yres,
             crop=tuple(d.crop),
-            mat_tex=np.array([d.mats[i].kd_tex for i in range(d.n_mats)], np.uint32),
+            mat_tex=np.array([0 if d.mats[i].type == GLASS else d.mats[i].kd_tex for i in range(d.n_mats)], np.uint32),
+            mat_eta=(np.array([d.mats[i].kd_tex if d.mats[i].type == GLASS else 0x3FC00000 for i in range(d.n_mats)], np.uint32).view(np.float32)
+                     if any(d.mats[i].type == GLASS for i in range(d.n_mats)) else np.zeros(0, np.float32)),
             textures=np.array([[d.textures[i].type, *d.textures[i].tex1, *d.textures[i].tex2, d.textures[i].su, d.textures[i].sv, d.textures[i].du,
                                 d.textures[i].dv] for i in range(d.n_textures)], np.float32).reshape(-1, 11),
             tri_uv=(arr(d.tri_uv, 6 * d.n_tris, np.float32).reshape(-1, 6) if d.tri_uv else np.zeros((0, 6), np.float32))).normalized()

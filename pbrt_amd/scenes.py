@@ -5,10 +5,11 @@
   check_sphere_scene  C0-like: scenes/check-sphere.pbrt's mirror sphere over a ground plane
   random_mesh_scene   C2 / C3: N random triangles in a box with a ceiling area light
   cornell_scene       C4: Cornell-style box
+  glass_sphere_scene  a glass sphere and a glass cube in a Cornell-style box (= scenes/glass_sphere.pbrt)
 """
 import numpy as np
 
-from .api import LIGHT_DISTANT, LIGHT_INFINITE, LIGHT_POINT, MATTE, MIRROR, SceneData, look_at
+from .api import GLASS, LIGHT_DISTANT, LIGHT_INFINITE, LIGHT_POINT, MATTE, MIRROR, SceneData, look_at
 
 MESH_SEED = 0x5EED0001
 
@@ -164,6 +165,46 @@ def cornell_scene(xres=4096, yres=4096, crop=(0.0, 1.0, 0.0, 1.0)):
     return SceneData(
         P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
         materials=np.array(mats, np.float32),
+        cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
+    ).normalized()
+
+
+def glass_sphere_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), glass=True):
+    """The glass material's scene, array for array what scenes/glass_sphere.pbrt loads to: the Cornell-style box
+    [-1, 1]^3 open towards the camera (white floor / ceiling / back wall, red left and green right walls), a 1 x 1 ceiling emitter with Le
+    (10, 9, 7), a glass triangle-mesh cube (12 triangles, eta 1.33, a greenish Kt) standing on the floor and a glass sphere (eta 1.5, Kr = Kt =
+    1) hovering beside it.  `glass=False`: the same scene with the two glass materials replaced by mirrors (Kr = the glass's Kr): the
+    throughput comparison of profiles/glass_vs_mirror.txt."""
+    WHITE, RED, GREEN, LIGHT, CUBE, BALL = range(6)  # (numbered in the order the scene file's shapes first use them)
+    mats = [_mat(MATTE, (0.73, 0.73, 0.73)), _mat(MATTE, (0.65, 0.05, 0.05)), _mat(MATTE, (0.12, 0.45, 0.15)), _mat(MATTE, (0, 0, 0), (10, 9, 7)),
+            _mat(GLASS, (1, 1, 1), (0.8, 0.95, 0.85)), _mat(GLASS, (1, 1, 1), (1, 1, 1))]  # a glass row: (GLASS, Kr, Kt)
+    eta = [1.5, 1.5, 1.5, 1.5, 1.33, 1.5]
+    if not glass:
+        mats[CUBE], mats[BALL] = _mat(MIRROR, (1, 1, 1)), _mat(MIRROR, (1, 1, 1))
+    V, I, M = [], [], []
+
+    def add(q, m):
+        base = len(V)
+        v, t = _quad(*q)
+        V.extend(v)
+        I.extend([[base + a for a in tri] for tri in t])
+        M.extend([m, m])
+
+    add(((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1)), WHITE)  # floor
+    add(((-1, -1, 1), (-1, 1, 1), (1, 1, 1), (1, -1, 1)), WHITE)      # ceiling
+    add(((-1, 1, -1), (1, 1, -1), (1, 1, 1), (-1, 1, 1)), WHITE)      # back wall (y = +1)
+    add(((-1, -1, -1), (-1, 1, -1), (-1, 1, 1), (-1, -1, 1)), RED)    # left
+    add(((1, -1, -1), (1, -1, 1), (1, 1, 1), (1, 1, -1)), GREEN)      # right
+    add(((-0.5, -0.5, 0.999), (-0.5, 0.5, 0.999), (0.5, 0.5, 0.999), (0.5, -0.5, 0.999)), LIGHT)  # normal -z
+    # the cube [-0.75, -0.15] x [-0.1, 0.5] x [-0.999, -0.399], every face wound so that its normal points outwards
+    x0, x1, y0, y1, z0, z1 = -0.75, -0.15, -0.1, 0.5, -0.999, -0.399
+    c = [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)]
+    for f in ((0, 3, 2, 1), (4, 5, 6, 7), (0, 1, 5, 4), (3, 7, 6, 2), (0, 4, 7, 3), (1, 2, 6, 5)):  # -z +z -y +y -x +x
+        add(tuple(c[i] for i in f), CUBE)
+    return SceneData(
+        P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
+        materials=np.array(mats, np.float32), mat_eta=np.array(eta, np.float32),
+        spheres=np.array([[0.4, -0.2, -0.45, 0.35, BALL]], np.float32),
         cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
     ).normalized()
 

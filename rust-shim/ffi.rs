@@ -13,7 +13,9 @@ fn main() {
 // ---------------------------------------------------------------- src/core/hip.rs
 use std::os::raw::{c_char, c_int, c_void};
 
+pub const MATERIAL_MATTE: u32 = 0; pub const MATERIAL_MIRROR: u32 = 1; pub const MATERIAL_GLASS: u32 = 2;  // PBRT_HIP_MATERIAL_*
 #[repr(C)] pub struct HipMaterial { pub kind: u32, pub k: [f32; 3], pub le: [f32; 3], pub kd_tex: u32 }  // kd_tex: 0, or 1 + the index of the checkerboard that is the matte Kd
+// kind == MATERIAL_GLASS (smooth dielectric): k = Kr, le = Kt (glass does not emit), kd_tex = eta.to_bits() (eta in [1, 16])
 #[repr(C)] pub struct HipTexture  { pub kind: u32, pub tex1: [f32; 3], pub tex2: [f32; 3], pub su: f32, pub sv: f32, pub du: f32, pub dv: f32, pub pad: [u32; 5] }  // Texture "..." "spectrum" "checkerboard" (check-sphere.pbrt:24-25)
 #[repr(C)] pub struct HipLight    { pub kind: u32, pub p: [f32; 3], pub c: [f32; 3], pub pad: f32 }
 #[repr(C)] pub struct HipSphere   { pub c: [f32; 3], pub r: f32, pub mat: u32, pub pad: [u32; 3] }

@@ -5,7 +5,8 @@
 //   2. the built tree OPTIMISED by parallel re-insertion (reinsert_core.hpp: every node looks for the position that lowers the
 //      summed surface area most, conflicting moves are dropped, boxes refitted; up to 12 passes): 4.5 % fewer node fetches per ray
 //      on BASELINE C3, 6.5 % on C2;
-//   3. the host's dynamic-programming collapse into the quantised 4-wide nodes the production walk reads.
+//   3. the dynamic-programming collapse into the quantised 4-wide nodes the production walk reads (its rules and
+//      the record: quad_encode.hpp, which the host builder of quad_nodes.cpp calls too).
 // 0.13 s for 1M triangles (34 ms without stage 2: PBRT_HIP_SCENE_PLAIN_TREE) against the host's second.  Round 1's LBVH and PLOC
 // builders are records now (tools/experiments/r01_lbvh_ploc_builders.hip.txt).
 // The reference has no accelerator at all (core/api.rs:237 is a name), so there is nothing to conform to but the RESULT:
@@ -18,19 +19,19 @@
 
 #include <algorithm>
 #include <cmath>
-#include <string>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>  // (rocPRIM directly: hipCUB is its CUDA-compatibility face)
 #include <rocprim/device/device_scan.hpp>
 
 #include "device_types.h"
+#include "quad_encode.hpp"
+#include "quad_nodes.hpp"
 #include "reinsert_core.hpp"
 
 namespace pbrt_hip {
 namespace {
 
-constexpr uint32_t kLeafRef = 0x80000000u;  // in quad refs (kernels.hip) and in the radix tree's child words
 constexpr uint32_t kNone = 0xffffffffu;
 
 __device__ __forceinline__ uint32_t f2ord(float f) {
@@ -570,38 +571,17 @@ __global__ void ri_leaves_kernel(reins::Tree t, const uint32_t *newslot, const u
   for (int w = 0; w < 3; w++) leaf_bx_out[3 * (size_t)s + w] = t.bx[3 * (size_t)(t.n_int + k) + w];
 }
 
-// ---- the collapse's dynamic programme (capi.cpp make_quad_nodes_as, after Ylitie, Karras, Laine 2017, section 3.2) ----
-// F(n, k, d) = least expected work inside subtree n when n may occupy up to k child slots of the quad node made of its
-// ancestor at binary distance d; G(n) = the work below n as a quad node of its own.  A child is reached with the probability
-// of its box AS THE ANCESTOR'S 8-BIT GRID HOLDS IT (about one cell wider per axis).  Leaves hold one triangle here.
-constexpr float kDpTriCost = 2.0f;
+// ---- the collapse's dynamic programme (quad_encode.hpp; leaves hold one triangle here) ----
 struct DpTables {
   float *F;   // [(4 * node + (k - 1)) * 3 + (d - 1)], internal nodes
   float *Fl;  // [3 * slot + (d - 1)], leaves
   float *G;   // internal nodes
-};
-__device__ __forceinline__ float dp_load(const float *p) {
-  return __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ float dp_f(const DpTables &T, uint32_t c, uint32_t k, uint32_t d) {
-  return (c & kLeafRef) ? dp_load(&T.Fl[3 * (size_t)(c & ~kLeafRef) + (d - 1u)]) : dp_load(&T.F[(4 * (size_t)c + (k - 1u)) * 3 + (d - 1u)]);
-}
-// surface area of box (lo, hi) as the grid of a quad node with box (qlo, qhi) holds it
-__device__ __forceinline__ float area_on_grid(const float lo[3], const float hi[3], const float qlo[3], const float qhi[3]) {
-  float dd[3];
-  for (int a = 0; a < 3; a++) {
-    const float ext = qhi[a] - qlo[a];
-    int e = -126;
-    if (ext > 0.f) { (void)frexpf(ext / 255.0f, &e); if (e < -126) e = -126; }
-    dd[a] = (hi[a] - lo[a]) + ldexpf(1.0f, e);
+  // F(c, k, d) of child word c, as quad_encode.hpp reads it (a value another CU has just written must not come from this CU's L1)
+  __device__ __forceinline__ float operator()(uint32_t c, uint32_t k, uint32_t d) const {
+    const float *p = (c & kLeafRef) ? &Fl[3 * (size_t)(c & ~kLeafRef) + (d - 1u)] : &F[(4 * (size_t)c + (k - 1u)) * 3 + (d - 1u)];
+    return __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   }
-  return (dd[0] * dd[1] + dd[0] * dd[2]) + dd[1] * dd[2];
-}
-__device__ __forceinline__ float dp_dist(const DpTables &T, uint32_t l, uint32_t r, uint32_t k, uint32_t d) {
-  float best = INFINITY;
-  for (uint32_t k1 = 1; k1 < k; k1++) best = fminf(best, dp_f(T, l, k1, d) + dp_f(T, r, k - k1, d));
-  return best;
-}
+};
 // bottom-up: one thread per leaf climbs; the second thread to reach a node computes it (its children are complete)
 __global__ void collapse_dp_kernel(int n, const uint32_t *child, const uint32_t *parent_internal, const uint32_t *parent_leaf, uint32_t *visits,
                                    const unsigned long long *bx, DpTables T) {
@@ -612,7 +592,7 @@ __global__ void collapse_dp_kernel(int n, const uint32_t *child, const uint32_t 
   uint32_t anc = parent_leaf[k];
   for (uint32_t d = 1; d <= 3; d++) {
     box_load<false>(bx, anc, qlo, qhi);
-    T.Fl[3 * (size_t)k + (d - 1u)] = kDpTriCost * area_on_grid(lo, hi, qlo, qhi);
+    T.Fl[3 * (size_t)k + (d - 1u)] = quad::kDpTriCost * quad::area_on_grid(lo, hi, qlo, qhi);
     if (parent_internal[anc] != kNone) anc = parent_internal[anc];
   }
   uint32_t node = parent_leaf[k];
@@ -621,16 +601,16 @@ __global__ void collapse_dp_kernel(int n, const uint32_t *child, const uint32_t 
     if (atomicAdd(&visits[node], 1u) == 0u) return;  // the sibling subtree is not done yet
     __threadfence();
     const uint32_t l = child[2 * (size_t)node], r = child[2 * (size_t)node + 1];
-    const float g = dp_dist(T, l, r, 4u, 1u);
+    const float g = quad::dp_dist(T, l, r, 4u, 1u);
     T.G[node] = g;
     box_load<false>(bx, node, lo, hi);
     anc = node;
     for (uint32_t d = 1; d <= 3; d++) {
       if (parent_internal[anc] != kNone) anc = parent_internal[anc];
       box_load<false>(bx, anc, qlo, qhi);
-      const float one = area_on_grid(lo, hi, qlo, qhi) + g;  // one step at the node when reached, plus what lies below
-      T.F[(4 * (size_t)node + 0u) * 3 + (d - 1u)] = one;
-      for (uint32_t kk = 2; kk <= 4; kk++) T.F[(4 * (size_t)node + (kk - 1u)) * 3 + (d - 1u)] = d < 3u ? fminf(one, dp_dist(T, l, r, kk, d + 1u)) : one;
+      float f[4];  // one step at the node when reached, plus what lies below -- or opened
+      quad::dp_interior(T, l, r, d, quad::area_on_grid(lo, hi, qlo, qhi) + g, f);
+      for (uint32_t kk = 1; kk <= 4; kk++) T.F[(4 * (size_t)node + (kk - 1u)) * 3 + (d - 1u)] = f[kk - 1u];
     }
     node = parent_internal[node];
   }
@@ -640,10 +620,9 @@ struct CollapseItem {
   uint32_t node, quad, path;  // binary internal node, its quad slot, stack entries held above it
 };
 
-// One level of the top-down collapse: a quad node takes its binary node's two children and keeps opening the
-// interior child with the largest surface area while the result fits four slots (the rule of capi.cpp
-// make_quad_nodes; leaves hold one triangle here, so only interior children open).  Child boxes are quantised to
-// the node's own 8-bit grid exactly as the host builder does it, enclosure checked in double arithmetic.
+// One level of the top-down collapse by the rules of quad_encode.hpp: a quad node's children are the ones the dynamic
+// programme chose (DP) or the greedy rule picks (leaves hold one triangle here, so only interior children open); their boxes
+// go onto the node's own 8-bit grid through the quantiser the host builder uses (quad_nodes.cpp).
 // counters: [0] quads allocated, [1] stack need (max); level_count[0] = items of this level, level_count[1] of the next
 template <bool DP>
 __global__ void collapse_kernel(const CollapseItem *items, uint32_t *level_count, int n, const uint32_t *child, const unsigned long long *bx,
@@ -653,7 +632,7 @@ __global__ void collapse_kernel(const CollapseItem *items, uint32_t *level_count
   const CollapseItem it = items[w];
   struct Kid {
     float lo[3], hi[3];
-    uint32_t c;  // child word of the radix tree
+    uint32_t c;  // child word of the binary tree
   } kids[4];
   int nk = 0;
   auto add = [&](uint32_t c) {
@@ -666,98 +645,50 @@ __global__ void collapse_kernel(const CollapseItem *items, uint32_t *level_count
     // follow the programme's minimising choices: node c with k slots at distance d is opened or presented as one child
     struct Open { uint32_t c, k, d; } st[8];
     int ns = 0;
-    auto split = [&](uint32_t c, uint32_t k, uint32_t d) {  // the children of c share k slots at distance d; ties: the most even split
-      const uint32_t l = child[2 * (size_t)c], r = child[2 * (size_t)c + 1];
-      uint32_t bk = 1;
-      float best = INFINITY;
-      for (uint32_t k1 = 1; k1 < k; k1++) {
-        const float v = dp_f(T, l, k1, d) + dp_f(T, r, k - k1, d);
-        const int ev = abs((int)(2 * k1) - (int)k), eb = abs((int)(2 * bk) - (int)k);
-        if (v < best || (v == best && ev < eb)) { best = v; bk = k1; }
-      }
-      st[ns++] = Open{r, k - bk, d};
-      st[ns++] = Open{l, bk, d};
+    auto split = [&](uint32_t c, uint32_t k, uint32_t d) {  // the children of c share k slots at distance d
+      const uint32_t l = child[2 * (size_t)c], r = child[2 * (size_t)c + 1], kl = quad::dp_best_split(T, l, r, k, d);
+      st[ns++] = Open{r, k - kl, d};
+      st[ns++] = Open{l, kl, d};
     };
     split(it.node, 4u, 1u);
     while (ns > 0) {
       const Open o = st[--ns];
-      if (!(o.c & kLeafRef) && o.k >= 2u && o.d < 3u && dp_f(T, o.c, o.k, o.d) < dp_f(T, o.c, 1u, o.d)) split(o.c, o.k, o.d + 1u);
+      if (!(o.c & kLeafRef) && quad::dp_opens(T, o.c, o.k, o.d)) split(o.c, o.k, o.d + 1u);
       else add(o.c);
     }
   } else {
-  add(child[2 * it.node]);
-  add(child[2 * it.node + 1]);
-  }
-  for (; !DP;) {
-    int best = -1;
-    float best_area = -1.f;
-    for (int k = 0; k < nk; k++) {
-      if (kids[k].c & kLeafRef) continue;
-      const float dx = kids[k].hi[0] - kids[k].lo[0], dy = kids[k].hi[1] - kids[k].lo[1], dz = kids[k].hi[2] - kids[k].lo[2];
-      const float area = (dx * dy + dx * dz) + dy * dz;
-      if (nk + 1 <= 4 && area > best_area) { best = k; best_area = area; }
+    add(child[2 * it.node]);
+    add(child[2 * it.node + 1]);
+    auto grow = [&](int k) { return (kids[k].c & kLeafRef) ? 0u : 1u; };
+    for (int best; (best = quad::greedy_pick(kids, nk, grow)) >= 0;) {
+      const uint32_t c = kids[best].c;
+      kids[best] = kids[--nk];
+      add(child[2 * c]);
+      add(child[2 * c + 1]);
     }
-    if (best < 0) break;
-    const uint32_t c = kids[best].c;
-    kids[best] = kids[--nk];
-    add(child[2 * c]);
-    add(child[2 * c + 1]);
   }
   const uint32_t path = it.path + (uint32_t)(nk - 1);
   atomicMax(&counters[1], path);
   float me_lo[3], me_hi[3];
   box_load<false>(bx, it.node, me_lo, me_hi);
-  uint32_t ebyte[3], qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
-  for (int a = 0; a < 3; a++) {
-    const float origin = me_lo[a], extent = me_hi[a] - me_lo[a];
-    // smallest power-of-two cell with 255 cells covering the extent (bumped while rounding pushes a plane past 255)
-    int e = -126;
-    if (extent > 0.f) {
-      (void)frexpf(extent / 255.0f, &e);  // extent/255 = m * 2^e, m in [0.5, 1)  =>  2^e >= extent/255
-      if (e < -126) e = -126;
-    }
-    for (; e <= 127; e++) {
-      const float cell = ldexpf(1.0f, e);
-      bool ok = true;
-      uint32_t lo_bytes = 0, hi_bytes = 0;
-      for (int k = 0; k < 4 && ok; k++) {
-        if (k >= nk) { lo_bytes |= 255u << (8 * k); continue; }
-        int ql = (int)floorf((kids[k].lo[a] - origin) / cell), qh = (int)ceilf((kids[k].hi[a] - origin) / cell);
-        if (ql < 0) ql = 0;
-        if (qh < 0) qh = 0;
-        // enclosure checked in exact arithmetic: origin + q * cell fits a double without rounding
-        const double o64 = origin, c64 = cell;
-        while (ql > 0 && o64 + ql * c64 > (double)kids[k].lo[a]) ql--;
-        while (qh <= 255 && o64 + qh * c64 < (double)kids[k].hi[a]) qh++;
-        if (ql > 255 || qh > 255 || o64 + ql * c64 > (double)kids[k].lo[a]) { ok = false; break; }
-        lo_bytes |= (uint32_t)ql << (8 * k);
-        hi_bytes |= (uint32_t)qh << (8 * k);
-      }
-      if (ok) { qlo[a] = lo_bytes; qhi[a] = hi_bytes; break; }
-    }
-    ebyte[a] = (uint32_t)((e > 127 ? 127 : e) + 127);
-  }
+  const quad::Grid grid = quad::quantise(me_lo, me_hi, kids, nk);
   // the interior children of a node are allocated side by side, as in the host's breadth-first array (one atomic for the
   // node: siblings share 128-byte lines, and a walk that has taken one child usually comes back for the next)
   uint32_t n_int = 0;
   for (int k = 0; k < nk; k++) n_int += (kids[k].c & kLeafRef) ? 0u : 1u;
-  uint32_t quad = n_int ? atomicAdd(&counters[0], n_int) : 0u, slot = n_int ? atomicAdd(&level_count[1], n_int) : 0u;
+  uint32_t qi = n_int ? atomicAdd(&counters[0], n_int) : 0u, slot = n_int ? atomicAdd(&level_count[1], n_int) : 0u;
   uint32_t ref[4];
   for (int k = 0; k < 4; k++) {
     if (k >= nk) { ref[k] = kEmptyLeafRef; continue; }
     const uint32_t c = kids[k].c;
     if (c & kLeafRef) {
-      ref[k] = kLeafRef | (1u << 24) | (c & ~kLeafRef);  // one triangle, leaf slot = sorted position
+      ref[k] = quad::leaf_ref(1u, c & ~kLeafRef);  // one triangle, leaf slot = sorted position
     } else {
-      ref[k] = quad * 64u;  // byte offset in the node array (capi.cpp make_quad_nodes)
-      next[slot++] = CollapseItem{c, quad++, path};
+      ref[k] = quad::interior_ref(qi);
+      next[slot++] = CollapseItem{c, qi++, path};
     }
   }
-  uint4 *q = quads + 4 * (size_t)it.quad;
-  q[0] = make_uint4(__float_as_uint(me_lo[0]), __float_as_uint(me_lo[1]), __float_as_uint(me_lo[2]), ebyte[0] << 23);
-  q[1] = make_uint4(qlo[0], qlo[1], qlo[2], qhi[0]);
-  q[2] = make_uint4(qhi[1], qhi[2], ebyte[1] << 23, ebyte[2] << 23);
-  q[3] = make_uint4(ref[0], ref[1], ref[2], ref[3]);
+  quad::pack_record(quads + 4 * (size_t)it.quad, me_lo, grid, ref);
 }
 
 struct Tmp {
@@ -809,8 +740,6 @@ hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_t
   hipLaunchKernelGGL(morton_kernel, grid_t, block, 0, stream, d_P, d_idx, n_tris, bounds.as<uint32_t>(), keys.as<uint32_t>(), vals.as<uint32_t>());
   GB_TRY(hipGetLastError());
   GB_TRY(rocprim::radix_sort_pairs(sort_tmp.p, sort_bytes, keys.as<uint32_t>(), keys_out.as<uint32_t>(), vals.as<uint32_t>(), d_order, (size_t)n, 0u, 30u, stream));
-  const uint32_t root_node = 0u;  // internal node the collapse starts from
-  const bool sah_tree = true;
   {
     // ---- top-down binned SAH ----
     const size_t cap = (size_t)n / 2 + 2;  // segments of >= 2 triangles on one level
@@ -902,7 +831,7 @@ hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_t
     // (tests/conftest.py) so that trees of 8 .. 300 triangles keep exercising the pass.
     uint32_t min_tris = stop.min_tris;
     if (const char *v = debug_knob("PBRT_HIP_REINSERT_MIN_TRIS")) min_tris = (uint32_t)std::max(8, std::atoi(v));
-    if (sah_tree && n_tris >= min_tris && n >= 8 && passes > 0) {
+    if (n_tris >= min_tris && n >= 8 && passes > 0) {
       const uint32_t n_int = (uint32_t)n - 1u, n_nodes = 2u * n_int + 1u;
       const dim3 grid_n((n_nodes + 255u) / 256u), grid_i((n_int + 255u) / 256u);
       Tmp par, kid, mv_y, mv_lca, mv_gain, lock, holds, stats, cnt, newslot, order2, leaf_bx, par_b, kid_b, bx_b;
@@ -993,11 +922,9 @@ hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_t
   // top-down collapse, one launch per level of the quad tree.  The host does not know how many items a level holds
   // (the kernel reads the count the level above left on the device) nor how deep the tree is: it launches kBatch
   // levels blind -- level L holds at most min(4^L, n) items -- and looks at the device once per batch.
-  // Which descendants become a quad node's children: for trees of kDpMinTris triangles and more the dynamic programme of
-  // capi.cpp (the host's default there too), else -- and for the LBVH / PLOC trees -- the greedy largest-area rule.
-  constexpr uint32_t kDpMinTris = 1024;
-  const char *cm = debug_knob("PBRT_HIP_COLLAPSE");
-  const bool use_dp = sah_tree && n >= 2 && ((n_tris >= kDpMinTris && !(cm && std::string(cm) == "greedy")) || (cm && std::string(cm) == "dp"));
+  // Which descendants become a quad node's children: the host's choice (quad_nodes.cpp collapse_rule: the dynamic programme for
+  // trees of quad::kDpCollapseMinTris triangles and more, else the greedy largest-area rule); there is no plain rule here.
+  const bool use_dp = collapse_rule(n_tris, /*has_plain=*/false) == kCollapseDp;
   Tmp dpF, dpFl, dpG;
   DpTables dp{nullptr, nullptr, nullptr};
   if (use_dp) {
@@ -1011,7 +938,7 @@ hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_t
     GB_TRY(hipGetLastError());
   }
   constexpr uint32_t kBatch = 48;
-  const CollapseItem root{root_node, 0u, 0u};
+  const CollapseItem root{0u, 0u, 0u};  // the binary tree's root, quad 0, nothing on the stack
   GB_TRY(hipMemcpyAsync(q0.p, &root, sizeof(root), hipMemcpyHostToDevice, stream));
   uint32_t h_counters[2] = {1u, 0u};  // quad 0 is the root's
   GB_TRY(hipMemcpyAsync(counters.p, h_counters, sizeof(h_counters), hipMemcpyHostToDevice, stream));
@@ -1044,7 +971,7 @@ hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_t
   }
   GB_TRY(hipMemcpyAsync(h_counters, counters.p, sizeof(h_counters), hipMemcpyDeviceToHost, stream));
   float root_box[6];  // {lo.x lo.y lo.z hi.x hi.y hi.z} of the root
-  GB_TRY(hipMemcpyAsync(root_box, bx.as<unsigned long long>() + 3 * (size_t)root_node, 24, hipMemcpyDeviceToHost, stream));
+  GB_TRY(hipMemcpyAsync(root_box, bx.p, 24, hipMemcpyDeviceToHost, stream));
   GB_TRY(hipEventRecord(e1, stream));
   GB_TRY(hipStreamSynchronize(stream));
   float ms = 0.f;

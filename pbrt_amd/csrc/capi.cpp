@@ -20,8 +20,7 @@
 #include "capi_internal.hpp"
 #include "device_types.h"
 #include "host_math.hpp"
-#include "ref_bvh.hpp"
-#include "reinsert_batch.hpp"
+#include "quad_nodes.hpp"
 #include "scene_parser.hpp"
 
 using namespace pbrt_hip;
@@ -123,7 +122,6 @@ RenderStackPlan stack_plan(uint32_t quad_stack_need) {
   static const bool prefer_lds = debug_knob("PBRT_HIP_PREFER_LDS_STACK") != nullptr;
   return render_stack_plan(quad_stack_need, force_overflow, prefer_lds);
 }
-constexpr uint32_t kLeafRef = 0x80000000u;
 
 // A vertex that a triangle uses and that is NaN or infinite would send the builders' bucket index out of range:
 // such input is refused at the boundary.  Returns the first offending vertex, or -1.
@@ -133,476 +131,6 @@ long long first_non_finite_vertex(const float *P, const uint32_t *idx, uint32_t 
     if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2])) return (long long)idx[i];
   }
   return -1;
-}
-
-// "Children in parent" form of the binary tree for the kernels: one 64-byte record per INTERIOR
-// node with the boxes and references of its two children.  ref = interior index
-// (dense numbering of interior nodes in depth-first order) or kLeafRef | n_prims << 24 | first slot.
-struct PairNodes {
-  std::vector<uint4> q;  // 4 per interior node
-  uint32_t root_ref = 0xffffffffu;
-  float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};
-};
-bool make_pair_nodes(const Bvh &b, PairNodes *out, std::string *why) {
-  const size_t n = b.nodes.size();
-  if (n == 0) return true;
-  if (b.order.size() > (1u << 24)) { *why = "more than 2^24 triangles (leaf references hold a 24-bit slot)"; return false; }
-  // Record numbering.  The memory system past L2 serves random requests in 128-byte lines at a rate
-  // that does not depend on how many of the 128 bytes are used (tools/ubench/gather_wide.hip), so
-  // the two 64-byte records of SIBLING interior nodes are placed in one line: fetching the near
-  // child's record brings the far one along.  Sibling pairs start at even indices; groups follow
-  // each other in depth-first order.  PBRT_HIP_NODE_LAYOUT=dfs restores plain depth-first numbering.
-  std::vector<uint32_t> interior_index(n, 0);
-  uint32_t n_int = 0;
-  const char *layout = debug_knob("PBRT_HIP_NODE_LAYOUT");
-  if (layout && std::string(layout) == "dfs") {
-    for (size_t i = 0; i < n; i++)
-      if ((b.nodes[i].count_axis & 0xffffu) == 0) interior_index[i] = n_int++;
-  } else if ((b.nodes[0].count_axis & 0xffffu) == 0) {
-    std::vector<uint32_t> todo = {0};
-    interior_index[0] = 0;
-    n_int = 2;  // the root has its line to itself
-    while (!todo.empty()) {
-      const uint32_t p = todo.back();
-      todo.pop_back();
-      const uint32_t c0 = p + 1, c1 = b.nodes[p].offset;
-      const bool i0 = (b.nodes[c0].count_axis & 0xffffu) == 0, i1 = (b.nodes[c1].count_axis & 0xffffu) == 0;
-      if (i0 && i1) {
-        n_int = (n_int + 1u) & ~1u;
-        interior_index[c0] = n_int;
-        interior_index[c1] = n_int + 1;
-        n_int += 2;
-      } else if (i0) {
-        interior_index[c0] = n_int++;
-      } else if (i1) {
-        interior_index[c1] = n_int++;
-      }
-      if (i1) todo.push_back(c1);
-      if (i0) todo.push_back(c0);
-    }
-  }
-  auto ref_of = [&](uint32_t i) -> uint32_t {
-    const BvhNode &c = b.nodes[i];
-    const uint32_t cnt = c.count_axis & 0xffffu;
-    return cnt ? (kLeafRef | (cnt << 24) | c.offset) : interior_index[i];
-  };
-  auto as_u = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-  out->q.assign(4 * (size_t)n_int, make_uint4(0u, 0u, 0u, 0u));
-  for (size_t i = 0; i < n; i++) {
-    const BvhNode &p = b.nodes[i];
-    if (p.count_axis & 0xffffu) continue;
-    const BvhNode &c0 = b.nodes[i + 1], &c1 = b.nodes[p.offset];
-    uint4 *q = &out->q[4 * (size_t)interior_index[i]];
-    q[0] = make_uint4(as_u(c0.lo[0]), as_u(c0.lo[1]), as_u(c0.lo[2]), as_u(c0.hi[0]));
-    q[1] = make_uint4(as_u(c0.hi[1]), as_u(c0.hi[2]), as_u(c1.lo[0]), as_u(c1.lo[1]));
-    q[2] = make_uint4(as_u(c1.lo[2]), as_u(c1.hi[0]), as_u(c1.hi[1]), as_u(c1.hi[2]));
-    q[3] = make_uint4(ref_of((uint32_t)i + 1), ref_of(p.offset), p.count_axis >> 16, 0u);
-  }
-  out->root_ref = ref_of(0);
-  for (int a = 0; a < 3; a++) { out->root_lo[a] = b.nodes[0].lo[a]; out->root_hi[a] = b.nodes[0].hi[a]; }
-  return true;
-}
-
-// 4-wide, QUANTISED form of the same tree for the production walk.  Every quad node is a binary
-// interior node collapsed with its interior children (2..4 children); the children's boxes are
-// stored as 8-bit coordinates on the node's own grid (origin = the node's lower corner, one
-// power-of-two cell size per axis), rounded outwards, so a node with four children is 64 bytes:
-//   {origin.x origin.y origin.z  cell.x}                    cell sizes as f32 (powers of two)
-//   {qlo.x[4]  qlo.y[4]  qlo.z[4]  qhi.x[4]}               one byte per child
-//   {qhi.y[4]  qhi.z[4]  cell.y  cell.z}
-//   {ref[4]}                                                interior child: its byte offset in this array (node x 64);
-//                                                           leaf child: 1<<31 | count<<24 | first leaf slot
-// plane = origin + q * cell (a real number): the builder checks in exact (double) arithmetic that
-// every decoded box contains the true one, so the walk visits a superset of the exact walk's nodes and the
-// RESULT is unchanged (tie rule of DESIGN.md 3.4).  Why: the loop is bound by the bytes it moves
-// from L2 to L1, and this form moves ~2.9 KB per ray instead of ~4.9 KB.
-// Unused child slots: qlo = 255, qhi = 0 (inverted), ref kEmptyLeafRef (a leaf without triangles: device_types.h).
-struct QuadNodes {
-  std::vector<uint4> q;     // 4 per node
-  uint32_t stack_need = 0;  // most entries the walk can hold: max over root-to-leaf paths of sum(children - 1)
-  std::vector<float> exact;  // diagnostics (tools/walk_sim.py): the children's boxes before quantisation, 24 floats per node
-};
-// A child of a quad node while it is being assembled: a node of the binary tree, or (split_leaves) one
-// triangle of a leaf that was expanded into a quad node of single-triangle children.
-struct QuadChild {
-  float lo[3], hi[3];
-  uint32_t ref;        // final ref (leaf) or 0 with `node` / `leaf_node` set
-  uint32_t node;       // binary interior node to recurse into, or 0xffffffff
-  uint32_t leaf_node;  // binary leaf to expand into its own quad node, or 0xffffffff
-};
-enum Collapse { kCollapsePlain = 0, kCollapseGreedy = 1, kCollapseDp = 2 };
-// `b`: the binary tree over triangle references (the canonical tree through refs_of_bvh, or the optimised single-triangle tree of
-// single_ref_tree + reinsert_optimize_batch); slot_of_ref[r] = slot of reference r's triangle in the leaf-ordered triangle records (null: r itself).
-void make_quad_nodes_as(const RefBvh &b, const uint32_t *slot_of_ref, bool split_leaves, Collapse how, QuadNodes *out) {
-  const bool greedy = how != kCollapsePlain;
-  if (b.nodes.empty() || (b.nodes[0].count_axis & 0xffffu) != 0) return;  // no tree, or the root is a leaf
-  auto as_u = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-  // Which descendants become the (up to four) children of a quad node?  Greedy: open the child with the largest
-  // surface area while the result fits four slots.  Dp instead minimises, by dynamic
-  // programming over the binary tree (after Ylitie, Karras, Laine 2017, section 3.2), the expected work of a walk:
-  // every child of a quad node R is reached with the probability of its box AS R's 8-BIT GRID HOLDS IT (about one
-  // cell of R wider per axis -- a small child of a large node gets a coarse box), a reached interior child costs one
-  // node step, a reached triangle c_tri.  R is the ancestor at binary distance d = 1..3 of the node in question:
-  //   F(n, k, d) = least expected work inside subtree n when n may occupy up to k child slots of R
-  //              = min( present n as ONE child: Aq(n, R) * (c_tri * #triangles)   for a plain leaf,
-  //                                             Aq(n, R) + G(n)                   else (one step at n, plus below),
-  //                     open n (k >= 2, d < 3): min_{k1+k2=k} F(l, k1, d+1) + F(r, k2, d+1) )
-  // with G(n) = min_{k1+k2=4} F(l,k1,1) + F(r,k2,1) the work below n as a quad node of its own (areas are
-  // unconditional reach probabilities up to the common factor 1/A(root), as in the SAH).
-  // Measured (c_tri = 2): C3 40.2 instead of 41.0 fetches per ray but a stack bound of 41 (overflow variant): -1 %;
-  // C2 +2 %.  Without the quantisation term the same programme made 11.6 % fewer nodes and C3 6 % slower.
-  const bool use_dp = how == kCollapseDp;
-  static const float c_tri = debug_knob("PBRT_HIP_COLLAPSE_CTRI") ? (float)std::atof(debug_knob("PBRT_HIP_COLLAPSE_CTRI")) : 2.0f;
-  const size_t nn = b.nodes.size();
-  std::vector<float> F;            // F[(4 * n + (k - 1)) * 3 + (d - 1)]
-  std::vector<float> G;            // work below n as a quad node of its own (interior nodes and splittable leaves)
-  std::vector<uint32_t> parent;
-  auto Fi = [](size_t n, uint32_t k, uint32_t d) { return (4 * n + (k - 1)) * 3 + (d - 1); };
-  auto anc = [&](uint32_t n, uint32_t d) { while (d-- && parent[n] != 0xffffffffu) n = parent[n]; return n; };
-  // surface area of box (lo, hi) as the grid of quad node q holds it: about one cell wider per axis
-  auto area_q = [&](const float *lo, const float *hi, const BvhNode &q) {
-    float dd[3];
-    for (int a = 0; a < 3; a++) {
-      const float ext = q.hi[a] - q.lo[a];
-      int e = -126;
-      if (ext > 0.f) { std::frexp(ext / 255.0f, &e); if (e < -126) e = -126; }
-      dd[a] = (hi[a] - lo[a]) + std::ldexp(1.0f, e);
-    }
-    return (dd[0] * dd[1] + dd[0] * dd[2]) + dd[1] * dd[2];
-  };
-  auto slot_of = [&](uint32_t r) { return slot_of_ref ? slot_of_ref[r] : r; };
-  auto tri_box = [&](uint32_t r, float lo[3], float hi[3]) {  // box of reference r
-    for (int a = 0; a < 3; a++) { lo[a] = b.ref_lo[3 * (size_t)r + a]; hi[a] = b.ref_hi[3 * (size_t)r + a]; }
-  };
-  auto one_cost = [&](uint32_t n, uint32_t d) {  // n presented as ONE child of its ancestor at distance d
-    const BvhNode &nd = b.nodes[n];
-    const uint32_t cnt = nd.count_axis & 0xffffu;
-    const float reach = area_q(nd.lo, nd.hi, b.nodes[anc(n, d)]);
-    if (cnt && !(split_leaves && cnt >= 2 && cnt <= 4)) return reach * c_tri * (float)cnt;  // plain leaf: its triangles are tested
-    return reach + G[n];  // a quad node of its own: one step when reached, plus what lies below
-  };
-  if (use_dp) {
-    F.assign(12 * nn, 0.f);
-    G.assign(nn, 0.f);
-    parent.assign(nn, 0xffffffffu);
-    for (size_t i = 0; i < nn; i++)
-      if ((b.nodes[i].count_axis & 0xffffu) == 0) { parent[i + 1] = (uint32_t)i; parent[b.nodes[i].offset] = (uint32_t)i; }
-    for (size_t i = nn; i-- > 0;) {  // children have larger indices than their parent (depth-first order)
-      const BvhNode &n = b.nodes[i];
-      const uint32_t cnt = n.count_axis & 0xffffu;
-      if (cnt) {
-        const bool splittable = split_leaves && cnt >= 2 && cnt <= 4;
-        if (splittable) {  // as a quad node of its own its triangles sit on ITS grid
-          float g = 0.f;
-          for (uint32_t j = 0; j < cnt; j++) { float lo[3], hi[3]; tri_box(n.offset + j, lo, hi); g += c_tri * area_q(lo, hi, n); }
-          G[i] = g;
-        }
-        for (uint32_t d = 1; d <= 3; d++) {
-          const float one = one_cost((uint32_t)i, d);
-          float opened = std::numeric_limits<float>::infinity();
-          if (splittable) {  // opened: its triangles are direct children of the ancestor
-            opened = 0.f;
-            const BvhNode &q = b.nodes[anc((uint32_t)i, d)];
-            for (uint32_t j = 0; j < cnt; j++) { float lo[3], hi[3]; tri_box(n.offset + j, lo, hi); opened += c_tri * area_q(lo, hi, q); }
-          }
-          for (uint32_t k = 1; k <= 4; k++) F[Fi(i, k, d)] = (splittable && k >= cnt) ? std::min(one, opened) : one;
-        }
-      } else {
-        const size_t l = i + 1, r = n.offset;
-        auto dist = [&](uint32_t k, uint32_t d) {
-          float best = std::numeric_limits<float>::infinity();
-          for (uint32_t k1 = 1; k1 < k; k1++) best = std::min(best, F[Fi(l, k1, d)] + F[Fi(r, k - k1, d)]);
-          return best;
-        };
-        G[i] = dist(4, 1);
-        for (uint32_t d = 1; d <= 3; d++) {
-          const float one = one_cost((uint32_t)i, d);
-          F[Fi(i, 1, d)] = one;
-          for (uint32_t k = 2; k <= 4; k++) F[Fi(i, k, d)] = d < 3 ? std::min(one, dist(k, d + 1)) : one;
-        }
-      }
-    }
-  }
-  if (use_dp && std::getenv("PBRT_HIP_REINSERT_VERBOSE")) {
-    const BvhNode &r = b.nodes[0];
-    const float dx = r.hi[0] - r.lo[0], dy = r.hi[1] - r.lo[1], dz = r.hi[2] - r.lo[2];
-    std::fprintf(stderr, "collapse: expected work below the root G = %.4f root areas\n", G[0] / ((dx * dy + dx * dz) + dy * dz));
-  }
-  struct Item { uint32_t node, quad, path; bool is_leaf; };  // path = stack entries held above this node
-  std::vector<Item> todo = {{0u, 0u, 0u, false}};
-  out->q.assign(4, make_uint4(0, 0, 0, 0));
-  while (!todo.empty()) {
-    const Item it = todo.back();
-    todo.pop_back();
-    const BvhNode &me = b.nodes[it.node];
-    QuadChild kids[4];
-    int nk = 0;
-    auto add_node = [&](uint32_t c) {
-      const BvhNode &n = b.nodes[c];
-      QuadChild k;
-      for (int a = 0; a < 3; a++) { k.lo[a] = n.lo[a]; k.hi[a] = n.hi[a]; }
-      const uint32_t cnt = n.count_axis & 0xffffu;
-      k.ref = cnt ? (kLeafRef | (cnt << 24) | slot_of(n.offset)) : 0u;  // (a run of several references: consecutive slots)
-      k.node = cnt ? 0xffffffffu : c;
-      // a leaf of 2..4 triangles becomes a quad node of single triangles: their boxes are then tested in
-      // the node step and each leaf pass tests exactly one triangle per parked lane
-      k.leaf_node = (split_leaves && cnt >= 2 && cnt <= 4) ? c : 0xffffffffu;
-      kids[nk++] = k;
-    };
-    auto tri_child = [&](uint32_t r) {
-      QuadChild k;
-      tri_box(r, k.lo, k.hi);
-      k.ref = kLeafRef | (1u << 24) | slot_of(r);
-      k.node = k.leaf_node = 0xffffffffu;
-      return k;
-    };
-    if (it.is_leaf) {  // expand a leaf: one child per triangle, boxed by its own bounds
-      const uint32_t cnt = me.count_axis & 0xffffu;
-      for (uint32_t j = 0; j < cnt; j++) kids[nk++] = tri_child(me.offset + j);
-    } else {
-      // Greedy collapse: start from the two children of the binary node and keep opening the child with the
-      // largest surface area (an interior node into its two children, a small leaf into its triangles) while
-      // the result still fits four slots.
-      if (use_dp) {
-        // follow the minimising choices: node c with k slots at distance d is opened or presented as one child
-        struct Open { uint32_t c, k, d; };
-        std::vector<Open> st;
-        auto split = [&](uint32_t c, uint32_t k, uint32_t d) {  // children of c share k slots at distance d; ties: the most even split
-          const size_t l = c + 1, r = b.nodes[c].offset;
-          uint32_t bk = 1;
-          float best = std::numeric_limits<float>::infinity();
-          for (uint32_t k1 = 1; k1 < k; k1++) {
-            const float v = F[Fi(l, k1, d)] + F[Fi(r, k - k1, d)];
-            if (v < best || (v == best && std::abs((int)(2 * k1) - (int)k) < std::abs((int)(2 * bk) - (int)k))) { best = v; bk = k1; }
-          }
-          st.push_back({(uint32_t)r, k - bk, d});
-          st.push_back({(uint32_t)l, bk, d});
-        };
-        split(it.node, 4u, 1u);
-        while (!st.empty()) {
-          const Open o = st.back();
-          st.pop_back();
-          const BvhNode &n = b.nodes[o.c];
-          const uint32_t cnt = n.count_axis & 0xffffu;
-          const float one = one_cost(o.c, o.d);
-          if (cnt) {
-            if (split_leaves && cnt >= 2 && cnt <= 4 && o.k >= cnt && F[Fi(o.c, o.k, o.d)] < one) {
-              for (uint32_t j = 0; j < cnt; j++) kids[nk++] = tri_child(n.offset + j);  // opened: its triangles are direct children
-            } else {
-              add_node(o.c);
-            }
-          } else if (o.k >= 2u && o.d < 3u && F[Fi(o.c, o.k, o.d)] < one) {
-            split(o.c, o.k, o.d + 1u);
-          } else {
-            add_node(o.c);
-          }
-        }
-      } else {
-      add_node(it.node + 1);
-      add_node(me.offset);
-      auto area = [](const QuadChild &k) {
-        const float dx = k.hi[0] - k.lo[0], dy = k.hi[1] - k.lo[1], dz = k.hi[2] - k.lo[2];
-        return (dx * dy + dx * dz) + dy * dz;
-      };
-      for (;;) {
-        int best = -1;
-        float best_area = -1.f;
-        for (int k = 0; k < nk; k++) {
-          const QuadChild &c = kids[k];
-          const uint32_t grow = c.node != 0xffffffffu ? 1u : (c.leaf_node != 0xffffffffu ? (b.nodes[c.leaf_node].count_axis & 0xffffu) - 1u : 99u);
-          if (greedy && (uint32_t)nk + grow <= 4u && area(c) > best_area) { best = k; best_area = area(c); }
-        }
-        if (best < 0) break;
-        const QuadChild c = kids[best];
-        kids[best] = kids[--nk];
-        if (c.node != 0xffffffffu) {
-          add_node(c.node + 1);
-          add_node(b.nodes[c.node].offset);
-        } else {
-          const BvhNode &lf = b.nodes[c.leaf_node];
-          for (uint32_t j = 0; j < (lf.count_axis & 0xffffu); j++) kids[nk++] = tri_child(lf.offset + j);
-        }
-      }
-      if (!greedy) {  // the plain collapse: both children opened once
-        nk = 0;
-        const uint32_t two[2] = {it.node + 1, me.offset};
-        for (uint32_t c : two) {
-          if ((b.nodes[c].count_axis & 0xffffu) == 0) { add_node(c + 1); add_node(b.nodes[c].offset); }
-          else add_node(c);
-        }
-      }
-      }
-    }
-    const uint32_t path = it.path + (uint32_t)(nk - 1);
-    if (path > out->stack_need) out->stack_need = path;
-    uint32_t ebyte[3], qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
-    for (int a = 0; a < 3; a++) {
-      const float origin = me.lo[a], extent = me.hi[a] - me.lo[a];
-      // smallest power-of-two cell with 255 cells covering the extent (bumped while rounding pushes a plane past 255)
-      int e = -126;
-      if (extent > 0.f) {
-        std::frexp(extent / 255.0f, &e);  // extent/255 = m * 2^e, m in [0.5, 1)  =>  2^e >= extent/255
-        if (e < -126) e = -126;
-      }
-      for (;; e++) {
-        const float cell = std::ldexp(1.0f, e);
-        bool ok = true;
-        uint32_t lo_bytes = 0, hi_bytes = 0;
-        for (int k = 0; k < 4 && ok; k++) {
-          if (k >= nk) { lo_bytes |= 255u << (8 * k); continue; }
-          const QuadChild &c = kids[k];
-          int ql = (int)std::floor((c.lo[a] - origin) / cell), qh = (int)std::ceil((c.hi[a] - origin) / cell);
-          if (ql < 0) ql = 0;
-          if (qh < 0) qh = 0;
-          // enclosure checked in exact arithmetic: origin + q * cell fits a double without rounding
-          const double o64 = origin, c64 = cell;
-          while (ql > 0 && o64 + ql * c64 > (double)c.lo[a]) ql--;
-          while (qh <= 255 && o64 + qh * c64 < (double)c.hi[a]) qh++;
-          if (ql > 255 || qh > 255 || o64 + ql * c64 > (double)c.lo[a]) { ok = false; break; }
-          lo_bytes |= (uint32_t)ql << (8 * k);
-          hi_bytes |= (uint32_t)qh << (8 * k);
-        }
-        if (ok) { ebyte[a] = (uint32_t)(e + 127); qlo[a] = lo_bytes; qhi[a] = hi_bytes; break; }
-      }
-    }
-    uint32_t ref[4];
-    for (int k = 0; k < 4; k++) {
-      if (k >= nk) { ref[k] = kEmptyLeafRef; continue; }
-      const QuadChild &c = kids[k];
-      if (c.node == 0xffffffffu && c.leaf_node == 0xffffffffu) {
-        ref[k] = c.ref;
-      } else {
-        const uint32_t quad = (uint32_t)(out->q.size() / 4);
-        ref[k] = quad * 64u;  // an interior child's ref is its byte offset in the node array: no shift in the walk
-        out->q.resize(out->q.size() + 4, make_uint4(0, 0, 0, 0));
-        // below child k the walk holds the entries of this path minus the ones already popped: bound by path
-        if (c.node != 0xffffffffu) todo.push_back({c.node, quad, path, false});
-        else todo.push_back({c.leaf_node, quad, path, true});
-      }
-    }
-    out->exact.resize(out->q.size() / 4 * 24, 0.f);
-    for (int k = 0; k < 4; k++)
-      for (int a = 0; a < 3; a++) {
-        out->exact[(size_t)it.quad * 24 + k * 6 + a] = k < nk ? kids[k].lo[a] : std::numeric_limits<float>::infinity();
-        out->exact[(size_t)it.quad * 24 + k * 6 + 3 + a] = k < nk ? kids[k].hi[a] : -std::numeric_limits<float>::infinity();
-      }
-    uint4 *q = &out->q[4 * (size_t)it.quad];
-    // the three cell sizes as f32 bit patterns (powers of two: exponent byte << 23), ready to be multiplied by 1 / d
-    q[0] = make_uint4(as_u(me.lo[0]), as_u(me.lo[1]), as_u(me.lo[2]), ebyte[0] << 23);
-    q[1] = make_uint4(qlo[0], qlo[1], qlo[2], qhi[0]);
-    q[2] = make_uint4(qhi[1], qhi[2], ebyte[1] << 23, ebyte[2] << 23);
-    q[3] = make_uint4(ref[0], ref[1], ref[2], ref[3]);
-  }
-}
-
-// A-B aid (PBRT_HIP_QUAD_LAYOUT=pre|pre_big behind the debug switch): renumber the quad nodes in depth-first PRE-order, so
-// that a node and the first interior child visited after it share a 128-byte line (the collapse above keeps SIBLINGS
-// together instead: a family is one or two lines).  pre: children in slot order; pre_big: the child with the largest box
-// first.  The tree, and so every result, is unchanged.
-void relayout_quads(QuadNodes *q, bool big_first) {
-  const size_t n = q->q.size() / 4;
-  if (n < 2) return;
-  auto area = [&](size_t node, int k) {
-    const uint4 *w = &q->q[4 * node];
-    auto byte = [](uint32_t v, int i) { return (float)((v >> (8 * i)) & 0xffu); };
-    float cx, cy, cz;
-    std::memcpy(&cx, &w[0].w, 4); std::memcpy(&cy, &w[2].z, 4); std::memcpy(&cz, &w[2].w, 4);
-    const float dx = (byte(w[1].w, k) - byte(w[1].x, k)) * cx, dy = (byte(w[2].x, k) - byte(w[1].y, k)) * cy, dz = (byte(w[2].y, k) - byte(w[1].z, k)) * cz;
-    return (dx * dy + dx * dz) + dy * dz;
-  };
-  std::vector<uint32_t> new_of(n, 0xffffffffu), order;
-  order.reserve(n);
-  std::vector<uint32_t> st = {0u};
-  while (!st.empty()) {
-    const uint32_t me = st.back();
-    st.pop_back();
-    new_of[me] = (uint32_t)order.size();
-    order.push_back(me);
-    const uint32_t ref[4] = {q->q[4 * (size_t)me + 3].x, q->q[4 * (size_t)me + 3].y, q->q[4 * (size_t)me + 3].z, q->q[4 * (size_t)me + 3].w};
-    int ks[4], m = 0;
-    for (int k = 0; k < 4; k++)
-      if (!(ref[k] & kLeafRef)) ks[m++] = k;
-    if (big_first) std::sort(ks, ks + m, [&](int a, int b) { return area(me, a) > area(me, b); });
-    for (int i = m - 1; i >= 0; i--) st.push_back(ref[ks[i]] / 64u);  // (the first of ks is popped next: it follows its parent)
-  }
-  std::vector<uint4> nq(q->q.size());
-  std::vector<float> ne(q->exact.size());
-  for (size_t i = 0; i < n; i++) {
-    const size_t o = order[i];
-    for (int w = 0; w < 4; w++) nq[4 * i + w] = q->q[4 * o + w];
-    uint32_t *r = &nq[4 * i + 3].x;
-    for (int k = 0; k < 4; k++)
-      if (!(r[k] & kLeafRef)) r[k] = new_of[r[k] / 64u] * 64u;
-    if (!ne.empty()) std::memcpy(&ne[24 * i], &q->exact[24 * o], 24 * sizeof(float));
-  }
-  q->q.swap(nq);
-  q->exact.swap(ne);
-}
-
-// The tree the walk gets: the quantisation-aware dynamic-programming collapse for trees of 1024 triangles and more, the
-// greedy one below that.  Measured (r02f kernel): dp is 2.5 % faster on C3 (433 k instead of 488 k nodes, 40.2 instead of 41.0
-// fetches per ray), 1.6 % on C2, 3.1 % on the 12 M-triangle workload, but 2 % slower on C4's 19-node tree; its build takes a
-// third longer.  (Until r02e its deeper stack bound -- C3: 41 instead of 38 -- cost it the overflow variant of the walk, which
-// every big tree takes now anyway.)  PBRT_HIP_COLLAPSE=dp|greedy|plain overrides (PBRT_HIP_GREEDY_COLLAPSE=0 = plain).
-constexpr uint32_t kDpCollapseMinTris = 1024;
-void make_quad_nodes(const RefBvh &b, const uint32_t *slot_of_ref, bool split_leaves, QuadNodes *out) {
-  const char *c = debug_knob("PBRT_HIP_COLLAPSE");
-  const char *g = debug_knob("PBRT_HIP_GREEDY_COLLAPSE");
-  Collapse how = b.ref_tri.size() >= kDpCollapseMinTris ? kCollapseDp : kCollapseGreedy;
-  if ((g && g[0] == '0') || (c && std::strcmp(c, "plain") == 0)) how = kCollapsePlain;
-  else if (c && std::strcmp(c, "dp") == 0) how = kCollapseDp;
-  else if (c && std::strcmp(c, "greedy") == 0) how = kCollapseGreedy;
-  make_quad_nodes_as(b, slot_of_ref, split_leaves, how, out);
-  if (const char *l = debug_knob("PBRT_HIP_QUAD_LAYOUT")) {
-    if (std::strcmp(l, "pre") == 0) relayout_quads(out, false);
-    else if (std::strcmp(l, "pre_big") == 0) relayout_quads(out, true);
-  }
-}
-
-// The production walk's 4-wide tree of a triangle soup, built on the host.  `tree` picks the binary tree it is collapsed from:
-// kTreeCanonical = the canonical binned-SAH tree `canon` (the oracle's tree); kTreeReinsert = that tree with its
-// leaves opened into single triangles and optimised by the DEVICE builder's parallel re-insertion pass run on the host
-// (reinsert_batch.cpp: the same functions, reinsert_core.hpp).  Either way a leaf child's slot refers to the triangle records in
-// `canon`'s leaf order.  (Round 3's host-only builders -- spatial splits, sequential re-insertion -- are records now:
-// tools/experiments/r03_host_tree_builders/.)
-enum ProductionTree : uint32_t { kTreeCanonical = 0, kTreeReinsert = 2 };  // (= PBRT_HIP_TREE_*)
-ReinsertBatchParams reinsert_batch_params() {
-  ReinsertBatchParams p;  // (passes, stop rule and least tree size: reins::StopRule, shared with the device loop of bvh_gpu.hip)
-  if (const char *v = debug_knob("PBRT_HIP_REINSERT")) p.passes = std::atoi(v);
-  if (const char *v = debug_knob("PBRT_HIP_REINSERT_MIN_TRIS")) p.stop.min_tris = (uint32_t)std::max(8, std::atoi(v));
-  if (const char *v = debug_knob("PBRT_HIP_REINSERT_MU")) p.mu = (uint32_t)std::max(1, std::atoi(v));
-  if (const char *v = debug_knob("PBRT_HIP_REINSERT_VISITS")) p.search.max_visits = (uint32_t)std::max(1, std::atoi(v));
-  if (const char *v = debug_knob("PBRT_HIP_REINSERT_MIN_REL")) p.search.min_rel = (float)std::atof(v);
-  if (const char *v = debug_knob("PBRT_HIP_REINSERT_QK")) p.search.qk = (float)std::atof(v);
-  if (const char *v = debug_knob("PBRT_HIP_REINSERT_QW")) p.search.qw = (float)std::atof(v);
-  return p;
-}
-ProductionTree production_tree_default() {
-  const char *v = debug_knob("PBRT_HIP_TREE");
-  if (v && std::strcmp(v, "reinsert") == 0) return kTreeReinsert;
-  return kTreeCanonical;
-}
-void build_production_quads(const Bvh &canon, const float *P, const uint32_t *idx, uint32_t n_tris, ProductionTree tree,
-                            bool split_leaves, QuadNodes *out, uint32_t *n_refs = nullptr) {
-  RefBvh rb;
-  if (tree == kTreeReinsert && n_tris >= 2) {
-    single_ref_tree(canon, P, idx, &rb);
-    const ReinsertBatchParams rp = reinsert_batch_params();
-    if (n_tris >= rp.stop.min_tris) reinsert_optimize_batch(&rb, rp);  // (smaller trees stay as built, as on the device)
-    if (std::getenv("PBRT_HIP_REINSERT_VERBOSE")) {
-      LinkTree lt;
-      link_tree_of(rb, &lt);
-      std::fprintf(stderr, "tree %u: summed interior half-area %.6g, depth %u\n", (unsigned)tree, lt.cost(), rb.depth);
-    }
-    std::vector<uint32_t> slot_of_tri(n_tris), slot_of_ref(rb.ref_tri.size());
-    for (uint32_t s = 0; s < n_tris; s++) slot_of_tri[canon.order[s]] = s;
-    for (size_t r = 0; r < rb.ref_tri.size(); r++) slot_of_ref[r] = slot_of_tri[rb.ref_tri[r]];
-    make_quad_nodes(rb, slot_of_ref.data(), true, out);
-  } else {
-    refs_of_bvh(canon, P, idx, &rb);
-    make_quad_nodes(rb, nullptr, split_leaves, out);
-  }
-  if (n_refs) *n_refs = (uint32_t)rb.ref_tri.size();
 }
 
 // `count` elements from `src` into `buf`, allocated anew, asynchronously on `stream` (src must live until the stream has caught up)

@@ -68,6 +68,9 @@ constexpr uint32_t kRenderMaxWavesPerCu = PBRT_RENDER_MAX_WAVES_PER_CU;
 // upper planes 0).  The box rejects it except for degenerate rays / flat nodes, and then the walk parks at an empty leaf and
 // pops: harmless, so the node step needs no "is this slot used" test (it had two compares per step for it until r02c).
 constexpr uint32_t kEmptyLeafRef = 0x80000000u;
+// A leaf child's ref in a node record is kLeafRef | n_prims << 24 | first leaf slot (n_prims <= 64; quad_encode.hpp leaf_ref); the
+// device builder's binary tree marks a leaf's child word with the same bit.
+constexpr uint32_t kLeafRef = 0x80000000u;
 
 // A pixel's spp samples are cut into K = sample_chunks(spp) chunks, each a work item with its own RNG stream and partial
 // film sum (oracle/oracle.cpp has the same rule): the largest power of two <= 16 that leaves a chunk at least
@@ -122,7 +125,7 @@ inline uint32_t intersect_overflow_entries(uint32_t quad_stack_need) {
 
 struct DevScene {
   const uint4 *nodes;
-  const uint4 *quads;  // 4 x 16 B per quantised quad node (capi.cpp QuadNodes)
+  const uint4 *quads;  // 4 x 16 B per quantised quad node (quad_encode.hpp; on the host quad_nodes.hpp QuadNodes)
   uint32_t quad_stack_need;
   const float4 *tris;
   const float4 *mats;

@@ -223,7 +223,6 @@ __device__ __forceinline__ bool sphere_hit(const float4 cr, V3 o, V3 d, float tm
 }
 
 constexpr uint32_t kDone = 0xffffffffu;
-constexpr uint32_t kLeafRef = 0x80000000u;  // ref = kLeafRef | n_prims << 24 | first slot (n_prims <= 64)
 
 // The production walk addresses its LDS stack by 32-bit LDS byte addresses kept in a register (one v_add per push, no
 // shift / or to form an address: tools/ubench/valu_issue.hip shows v_lshl_or_b32 and friends issue at half rate).

@@ -1,5 +1,5 @@
 // ref_bvh.hpp -- a binary tree over triangle REFERENCES, the form the production walk's 4-wide nodes are collapsed from
-// (capi.cpp make_quad_nodes_as) and the host run of the re-insertion pass works on (reinsert_batch.cpp).
+// (quad_nodes.cpp make_quad_nodes_as) and the host run of the re-insertion pass works on (reinsert_batch.cpp).
 #pragma once
 #include <cstdint>
 #include <vector>

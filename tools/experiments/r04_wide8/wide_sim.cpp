@@ -3,7 +3,7 @@
 // origin 12 B + 3 exponent bytes + imask + child base + triangle base + 8 meta bytes + 6 x 8 plane bytes: FIVE 16-byte pieces.)
 // Not product code, not linked into libpbrt_hip.so: a simulator that collapses the product's optimised binary tree (canonical
 // binned SAH -> single-triangle leaves -> the device builder's re-insertion pass, host run) into W-wide nodes with child boxes on
-// the node's own 8-bit power-of-two grid (the product's quantisation rule, capi.cpp make_quad_nodes_as), walks the ray mix of a
+// the node's own 8-bit power-of-two grid (the product's quantisation rule, quad_encode.hpp quantise), walks the ray mix of a
 // path-traced frame (written by run.py) and counts node steps and triangle tests per ray for W = 4 and W = 8, both with the greedy
 // largest-area collapse.  Hits are checked against the oracle's (passed in by run.py).
 // build: g++ -O2 -std=c++17 -Ipbrt_amd/csrc tools/experiments/r04_wide8/wide_sim.cpp pbrt_amd/csrc/bvh_build.cpp pbrt_amd/csrc/reinsert_batch.cpp -o /tmp/wide_sim

@@ -68,18 +68,47 @@ typedef struct {
  * empty marker): pbrt-v3's Checkerboard2DTexture over a UVMapping2D, point-sampled (aamode "none": no ray differentials here):
  * (s, t) = (su u + du, sv v + dv); tex1 where floor(s) + floor(t) is even, tex2 where odd.  64 bytes. */
 typedef struct {
-  uint32_t type;  /* 0 = checkerboard, dimension 2, "uv" mapping */
+  uint32_t type;  /* 0 = checkerboard, dimension 2, "uv" mapping; 1 = this slot is the environment-map record below */
   float tex1[3], tex2[3];
   float su, sv, du, dv; /* "float uscale" / "vscale" / "udelta" / "vdelta" */
   uint32_t pad[5];
 } pbrt_hip_texture;
 
-/* LightSource "point" / "distant" / "infinite" (api.rs:334-351 make_light: todo!() for all). */
+/* LightSource "infinite" "string mapname" (the reference: src/lights/infinite.rs:52-66 reads the image, multiplies the
+ * texels by L x scale and stops at todo!() before its MIPMap and Distribution2D): an environment map in the latitude-longitude
+ * parametrisation of pbrt-v3's InfiniteAreaLight.  A slot of `textures` whose first word is 1 IS this record -- also 64 bytes; the table's
+ * element type is 4-aligned, so the library reads the slot with memcpy, and a host may fill it the same way.
+ *   direction d -> w = world_to_light d, phi = atan2(w.y, w.x) in [0, 2 pi), theta = acos(w.z), (u, v) = (phi / 2 pi, theta / pi),
+ *   col = min((int)(u width), width - 1), row = min((int)(v height), height - 1); row 0 of `rgb` -- the first row pbrt_hip_read_image
+ *   returns -- is theta = 0, the light's +z.
+ * POINT-SAMPLED, as the checkerboard is: Le(d) = c x texel[row][col] (c: the light's factor, below), a piecewise-constant sky -- a deliberate
+ * difference from pbrt-v3's bilinear MIPMap::Lookup, which makes the sampling density exactly proportional to the radiance it samples.
+ * The light is importance-sampled by pbrt-v3's Distribution2D over luminance x sin theta, from the same (u1, u2) every other light gets.
+ * Refused before any device work (the message holds "environment"): width x height > 2^24 (PBRT_HIP_ERR_LIMIT); width or height 0, a NULL
+ * `rgb`, a texel that is not finite or is negative, a world_to_light that is not finite or not orthonormal to 1e-4
+ * (PBRT_HIP_ERR_INVALID); a matte kd_tex that names such a slot (PBRT_HIP_ERR_INVALID: image textures for Kd do not exist). */
 typedef struct {
-  uint32_t type; /* 0 point, 1 distant, 2 infinite with constant radiance */
+  uint32_t type;     /* = 1 */
+  uint32_t width, height;
+  uint32_t reserved; /* = 0 */
+  const float *rgb;  /* host, 3 x width x height, row-major, copied during the call */
+  float world_to_light[9]; /* row-major 3 x 3 rotation: the inverse of the light's CTM */
+  uint32_t pad;
+} pbrt_hip_envmap;
+
+/* LightSource "point" / "distant" / "infinite" (api.rs:334-351 make_light: todo!() for all).
+ * Type 3 is the infinite light with an environment map: c = the factor on the texels (L x scale, infinite.rs:54), `pad`
+ * = the BITS of the 1-based number of a type-1 slot of `textures` (the way glass keeps eta in kd_tex), p is ignored.  A type-3 light
+ * that names no such slot is PBRT_HIP_ERR_INVALID, more than one type-3 light PBRT_HIP_ERR_LIMIT (messages hold "environment").
+ * Constant infinite lights (type 2) work beside it.  A scene with a map runs the ENV kernels (kernels_env.hip render_kernel_env); they
+ * exist for every integrator and sampler, with and without spheres, textures and glass, and NOT for: a box filter radius other than
+ * 0.5, the counter flags (both PBRT_HIP_ERR_LIMIT at render, the message names the combination). */
+#define PBRT_HIP_LIGHT_ENVMAP 3u
+typedef struct {
+  uint32_t type; /* 0 point, 1 distant, 2 infinite with constant radiance, 3 infinite with an environment map */
   float p[3];    /* point: position; distant: unit direction TOWARDS the light */
-  float c[3];    /* point: intensity I; distant / infinite: radiance L */
-  float pad;
+  float c[3];    /* point: intensity I; distant / infinite: radiance L; 3: the factor on the texels */
+  float pad;     /* 3: the bits of the texture-table number (1-based) of the pbrt_hip_envmap */
 } pbrt_hip_light;
 
 /* Shape "sphere" (check-sphere.pbrt:22), world space.  A primitive of the BVH like a triangle (primitive number n_tris + index, which is
@@ -166,9 +195,13 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.6 (gfx950)": 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.7 (gfx950; struct sizes of 0.6)": 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
                                        end, pbrt_hip_material.pad became kd_tex, flags 0 of scene_create_ex = the device builder); 0.6 =
-                                       material type 2, glass, inside the same struct sizes */
+                                       material type 2, glass, inside the same struct sizes; 0.7 = light type 3 and texture-table
+                                       slot type 1, the environment map, again inside the same struct sizes.  The "(... struct sizes of 0.6)"
+                                       suffix is there for one reason: a test of the glass material looks for "0.6" in this string, and
+                                       no struct has changed size since 0.6.  The first version that changes a struct's size drops the
+                                       suffix and updates that test with it */
 /* identity of the build: a hash of the library's sources and kernel-shaping flags (pbrt_amd/build.py source_id).  A
  * profile taken on one build must not price another: bench.py compares this with the id stored beside the counters */
 const char *pbrt_hip_build_id(void);

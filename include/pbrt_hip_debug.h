@@ -63,6 +63,21 @@ int pbrt_hip_quad_build_host_ex(const float *P, uint32_t n_verts, const uint32_t
 /* host only: the generator matrices sampler 2 uses -- 128 dimensions x 32 columns, rows 0 .. 127 of the reference's
  * SOBOL_MATRICES32 (sobolmatrices.rs:81), the first 32 of its 52 columns -- for tests of that claim */
 void pbrt_hip_sobol_matrices(uint32_t *out_4096_words);
+/* ---- environment maps (pbrt_amd/csrc/envmap_core.hpp is the one statement of the arithmetic) ---- */
+/* host only: the importance-sampling tables of an image (rgb: 3 x width x height, row 0 = theta 0): marginal = the CDF over rows (height
+ * + 1 floats), conditional = one CDF per row (height x (width + 1) floats), p_uv = the density over (u, v) of every texel (width x
+ * height floats: f / mean(f), f = luminance x sin(pi (row + 1/2) / height); a map that is black everywhere: f = the sine alone).  Any
+ * output may be NULL.  The image is validated as pbrt_hip_scene_create validates it. */
+int pbrt_hip_envmap_tables(const float *rgb, uint32_t width, uint32_t height, float *marginal, float *conditional, float *p_uv);
+/* host only: envmap_core.hpp over arrays.  u12 != NULL: SAMPLE -- n pairs (u1, u2) in [0, 1) -> d (3 n floats, written), texel (row x
+ * width + col of the texel drawn), le (its rgb, 3 n), pdf (the density over solid angle).  u12 == NULL: LOOKUP -- d (3 n, read) -> texel,
+ * le, pdf of each direction.  texel, le, pdf may be NULL. */
+int pbrt_hip_envmap_eval_host(const float *rgb, uint32_t width, uint32_t height, const float world_to_light[9], int64_t n, const float *u12,
+                              float *d, uint32_t *texel, float *le, float *pdf);
+/* the same on the device of `scene`, over the map and tables the scene holds (a tiny kernel that calls the same header): the same bits.
+ * PBRT_HIP_ERR_INVALID for a scene without an environment map. */
+int pbrt_hip_envmap_eval_device(pbrt_hip_scene *scene, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

@@ -15,6 +15,12 @@ class Texture(C.Structure):
                 ("du", C.c_float), ("dv", C.c_float), ("pad", C.c_uint32 * 5)]
 
 
+class EnvMap(C.Structure):
+    """pbrt_hip_envmap: what a slot of the texture table IS when its first word is 1; 64 bytes like Texture"""
+    _fields_ = [("type", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("reserved", C.c_uint32), ("rgb", C.POINTER(C.c_float)),
+                ("world_to_light", C.c_float * 9), ("pad", C.c_uint32)]
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_uint32), ("p", C.c_float * 3), ("c", C.c_float * 3), ("pad", C.c_float)]
 
@@ -110,6 +116,9 @@ SYMBOLS = {
     "pbrt_hip_loaded_warnings": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "pbrt_hip_loaded_state": (C.c_int, [_vp, _pf, C.c_char_p, C.c_size_t]),
     "pbrt_hip_tokenize": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrt_hip_envmap_tables": (C.c_int, [_pf, _u32, _u32, _pf, _pf, _pf]),
+    "pbrt_hip_envmap_eval_host": (C.c_int, [_pf, _u32, _u32, _pf, _i64, _pf, _pf, _pu32, _pf, _pf]),
+    "pbrt_hip_envmap_eval_device": (C.c_int, [_vp, _i64, _pf, _pf, _pu32, _pf, _pf]),
 }
 
 _lib = None

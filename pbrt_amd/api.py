@@ -9,10 +9,11 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import Light, Material, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
+from ._lib import EnvMap, Light, Material, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
 
 MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
+LIGHT_ENVMAP = 3  # PBRT_HIP_LIGHT_ENVMAP: the infinite light with an environment map
 INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_PATH_MIS = 0, 1, 2  # 2: the path integrator with MIS
 FLAG_COUNTERS = 1
 FLAG_WALK_COUNTERS = 2
@@ -39,7 +40,9 @@ class SceneData:
     0 or 1 + the row of `textures` that is material i's Kd, `textures` rows: (type 0 = checkerboard, tex1 rgb, tex2 rgb, su, sv, du,
     dv), `tri_uv` rows: (u0, v0, u1, v1, u2, v2) per triangle (needed when a triangle's material is textured).  Glass:
     a `materials` row (GLASS, Kr rgb, Kt rgb) -- a glass surface does not emit -- and `mat_eta[i]` = its index of refraction (an empty
-    `mat_eta` = 1.5 for every glass row; the entries of other rows are not read)."""
+    `mat_eta` = 1.5 for every glass row; the entries of other rows are not read).  An environment map: a `lights` row
+    (LIGHT_ENVMAP, 0, 0, 0, c rgb) -- c the factor on the texels -- and `envmap` = its (H, W, 3) texels, row 0 = the light's +z, with
+    `envmap_world_to_light` = the 3 x 3 rotation; the record travels in a slot appended to the texture table (fill_desc)."""
     P: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
     idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.uint32))
     mat_id: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint16))
@@ -55,6 +58,8 @@ class SceneData:
     textures: np.ndarray = field(default_factory=lambda: np.zeros((0, 11), np.float32))
     tri_uv: np.ndarray = field(default_factory=lambda: np.zeros((0, 6), np.float32))
     mat_eta: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.float32))
+    envmap: np.ndarray = field(default_factory=lambda: np.zeros((0, 0, 3), np.float32))
+    envmap_world_to_light: np.ndarray = field(default_factory=lambda: np.eye(3, dtype=np.float32))
 
     def normalized(self):
         self.P = np.ascontiguousarray(self.P, np.float32).reshape(-1, 3)
@@ -74,6 +79,9 @@ class SceneData:
         assert self.mat_eta.shape[0] in (0, self.materials.shape[0])
         self.textures = np.ascontiguousarray(self.textures, np.float32).reshape(-1, 11)
         self.tri_uv = np.ascontiguousarray(self.tri_uv, np.float32).reshape(-1, 6)
+        self.envmap = np.ascontiguousarray(self.envmap, np.float32)
+        assert self.envmap.ndim == 3 and self.envmap.shape[2] == 3
+        self.envmap_world_to_light = np.ascontiguousarray(self.envmap_world_to_light, np.float32).reshape(3, 3)
         assert self.idx.shape[0] == self.mat_id.shape[0] and self.tri_uv.shape[0] in (0, self.idx.shape[0])
         return self
 
@@ -95,16 +103,22 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
             eta = sd.mat_eta[i:i + 1] if len(sd.mat_eta) else np.array([1.5], np.float32)
             mats[i].kd_tex = int(eta.view(np.uint32)[0])
     texs = None
-    if len(sd.textures):
+    has_env = sd.envmap.size > 0  # the map's record takes a slot of its own behind the checkerboards (include/pbrt_hip.h pbrt_hip_envmap)
+    if len(sd.textures) or has_env:
         tex_t = tex_t or dict(desc._fields_)["textures"]._type_  # (the Texture class of the caller's own struct mirror)
-        texs = (tex_t * len(sd.textures))()
+        texs = (tex_t * (len(sd.textures) + int(has_env)))()
         for i, t in enumerate(sd.textures):
             texs[i].type = int(t[0])
             texs[i].tex1[:] = [float(x) for x in t[1:4]]
             texs[i].tex2[:] = [float(x) for x in t[4:7]]
             texs[i].su, texs[i].sv, texs[i].du, texs[i].dv = (float(x) for x in t[7:11])
+        if has_env:
+            e = EnvMap(type=1, width=sd.envmap.shape[1], height=sd.envmap.shape[0], rgb=_fp(sd.envmap))
+            e.world_to_light[:] = [float(x) for x in sd.envmap_world_to_light.reshape(-1)]
+            assert C.sizeof(e) == C.sizeof(tex_t)
+            C.memmove(C.byref(texs, len(sd.textures) * C.sizeof(tex_t)), C.byref(e), C.sizeof(e))
         desc.textures = texs
-    desc.n_textures = len(sd.textures)
+    desc.n_textures = len(sd.textures) + int(has_env)
     if sd.tri_uv.shape[0]:
         desc.tri_uv = _fp(sd.tri_uv)
     lights = (light_t * max(len(sd.lights), 1))()
@@ -112,6 +126,8 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         lights[i].type = int(l[0])
         lights[i].p[:] = [float(x) for x in l[1:4]]
         lights[i].c[:] = [float(x) for x in l[4:7]]
+        if int(l[0]) == LIGHT_ENVMAP:  # `pad` = the bits of the 1-based number of the map's slot (0: the scene holds no map -- refused)
+            lights[i].pad = float(np.array([len(sd.textures) + 1 if has_env else 0], np.uint32).view(np.float32)[0])
     spheres = (sphere_t * max(len(sd.spheres), 1))()
     for i, s in enumerate(sd.spheres):
         spheres[i].c[:] = [float(x) for x in s[0:3]]
@@ -270,6 +286,35 @@ def film_from_acc(acc):
     film = np.zeros(a.shape[:-1] + (4,), np.float32)
     lib().pbrt_hip_film_from_acc(a.ctypes.data_as(C.POINTER(C.c_int64)), a.size // 4, _fp(film))
     return film
+
+
+def envmap_tables(rgb):
+    """pbrt_hip_envmap_tables (host only): the importance-sampling tables of an (H, W, 3) map -> (marginal[H + 1], conditional[H, W + 1],
+    p_uv[H, W]), DESIGN.md 3.17"""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    h, w = rgb.shape[:2]
+    marg, cond, puv = np.zeros(h + 1, np.float32), np.zeros((h, w + 1), np.float32), np.zeros((h, w), np.float32)
+    check(lib().pbrt_hip_envmap_tables(_fp(rgb), w, h, _fp(marg), _fp(cond), _fp(puv)), "pbrt_hip_envmap_tables")
+    return marg, cond, puv
+
+
+def _envmap_eval(call, where, n_or_u, d):
+    u12 = None if n_or_u is None else np.ascontiguousarray(n_or_u, np.float32).reshape(-1, 2)
+    d = np.zeros((len(u12), 3), np.float32) if u12 is not None else np.ascontiguousarray(d, np.float32).reshape(-1, 3).copy()
+    n = len(d)
+    texel, le, pdf = np.zeros(n, np.uint32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+    check(call(n, _fp(u12) if u12 is not None else None, _fp(d), _u32p(texel), _fp(le), _fp(pdf)), where)
+    return d, texel, le, pdf
+
+
+def envmap_eval_host(rgb, world_to_light=None, u12=None, d=None):
+    """pbrt_hip_envmap_eval_host: csrc/envmap_core.hpp over arrays on the host.  u12 (n, 2): SAMPLE -> (d[n, 3], texel[n] = row * W + col,
+    le[n, 3] = the texel's rgb, pdf[n] over solid angle); else d (n, 3): LOOKUP -> the same four, d as given."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    m = np.ascontiguousarray(np.eye(3) if world_to_light is None else world_to_light, np.float32).reshape(3, 3)
+    h, w = rgb.shape[:2]
+    return _envmap_eval(lambda n, u, dd, t, le, pdf: lib().pbrt_hip_envmap_eval_host(_fp(rgb), w, h, _fp(m), n, u, dd, t, le, pdf),
+                        "pbrt_hip_envmap_eval_host", u12, d)
 
 
 def sobol_matrices():
@@ -442,6 +487,11 @@ class Scene:
         st = Stats()
         check(lib().pbrt_hip_render(self._h, C.byref(r), _fp(film), C.byref(st)), "pbrt_hip_render")
         return film, {k: getattr(st, k) for k, _ in Stats._fields_}
+
+    def envmap_eval(self, u12=None, d=None):
+        """pbrt_hip_envmap_eval_device: envmap_eval_host's arithmetic on the device, over the map this scene holds"""
+        return _envmap_eval(lambda n, u, dd, t, le, pdf: lib().pbrt_hip_envmap_eval_device(self._h, n, u, dd, t, le, pdf),
+                            "pbrt_hip_envmap_eval_device", u12, d)
 
     def render_acc(self, filter_width, **kw):
         """A box filter radius other than 0.5: this rank's fixed-point film accumulators (h, w, 4) int64 {r, g, b, samples}

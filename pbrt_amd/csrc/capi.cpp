@@ -19,6 +19,7 @@
 #include "bvh_build.hpp"
 #include "capi_internal.hpp"
 #include "device_types.h"
+#include "envmap.hpp"
 #include "host_math.hpp"
 #include "quad_nodes.hpp"
 #include "scene_parser.hpp"
@@ -115,6 +116,8 @@ constexpr uint32_t kMinWalkers = 36, kMinWalkersShallow = 20, kShallowStackNeed 
 // with spheres has the register budget of 3 waves per SIMD.  The grid is this x the device's CU count (hipDeviceProp_t;
 // render_launch)
 constexpr uint32_t kRenderWavesPerCuSpheres = 12;
+// a scene with an environment map: render_kernel_env's register budget is 4 waves per SIMD (kernels_env.hip)
+constexpr uint32_t kRenderWavesPerCuEnv = 16;
 // the production walk's stack plan under the A-B knobs PBRT_HIP_FORCE_OVERFLOW_VARIANT (the overflow variant for every tree) and
 // PBRT_HIP_PREFER_LDS_STACK (the whole stack in LDS whenever it fits kQuadLdsStack rows, whatever the occupancy), read once
 RenderStackPlan stack_plan(uint32_t quad_stack_need) {
@@ -199,6 +202,8 @@ enum class Builder { kHost, kHostOptimized, kGpu, kGpuPlain };
 
 // a material whose Kd is a texture
 bool kd_textured(const pbrt_hip_material &m) { return m.kd_tex != 0u && m.type == 0u; }
+// the 1-based texture-table number an environment-map light carries as the bits of its `pad`
+uint32_t light_env_slot(const pbrt_hip_light &l) { uint32_t u; std::memcpy(&u, &l.pad, 4); return u; }
 // a glass material's index of refraction: the float whose bits ride in kd_tex
 float glass_eta(const pbrt_hip_material &m) { float e; std::memcpy(&e, &m.kd_tex, 4); return e; }
 // glass is an interface between index 1 and eta: eta = 1 (index-matched: nothing reflects, nothing bends) is legal; 16 is four times
@@ -261,8 +266,16 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
     if (d->mats[i].kd_tex > d->n_textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
     if (d->mats[i].kd_tex && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: textured material but no texture table");
   }
+  for (uint32_t i = 0; i < d->n_mats; i++)  // (image textures for Kd do not exist: a type-1 slot is a light's map)
+    if (kd_textured(d->mats[i]) && is_envmap_slot(d->textures, d->mats[i].kd_tex - 1u))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names an environment map, which is not a texture for Kd");
   for (uint32_t i = 0; i < d->n_textures; i++) {
     const pbrt_hip_texture &tx = d->textures[i];
+    if (is_envmap_slot(d->textures, i)) {  // an environment map's record
+      const int rc = envmap_check(envmap_slot(d->textures, i), "scene_create: texture slot " + std::to_string(i + 1) + ": ");
+      if (rc) return rc;
+      continue;
+    }
     if (tx.type != 0u) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown texture type");
     if (!std::isfinite(tx.su) || !std::isfinite(tx.sv) || !std::isfinite(tx.du) || !std::isfinite(tx.dv))
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture mapping is not finite");
@@ -287,7 +300,15 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
       if (!std::isfinite(d->spheres[s].c[k] - d->spheres[s].r) || !std::isfinite(d->spheres[s].c[k] + d->spheres[s].r))
         return fail(PBRT_HIP_ERR_INVALID, "scene_create: a sphere's bounding box is not finite");
   for (uint32_t i = 0; i < d->n_lights; i++)
-    if (d->lights[i].type > 2) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+  uint32_t n_env = 0;
+  for (uint32_t i = 0; i < d->n_lights; i++) {  // an environment-map light names a type-1 slot of the texture table; one per scene
+    if (d->lights[i].type != PBRT_HIP_LIGHT_ENVMAP) continue;
+    const uint32_t t = light_env_slot(d->lights[i]);
+    if (t == 0u || t > d->n_textures || !d->textures || !is_envmap_slot(d->textures, t - 1u))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": an environment-map light (type 3) must name a type-1 slot of the texture table in `pad`");
+    if (++n_env > 1u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than one environment-map light (type 3)");
+  }
   for (uint32_t i = 0; i < d->n_mats; i++)
     if (d->mats[i].type > PBRT_HIP_MATERIAL_GLASS) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
   const char *env = want_host || want_gpu ? nullptr : std::getenv("PBRT_HIP_BUILDER");
@@ -313,6 +334,11 @@ struct SceneInputs {
   std::vector<uint16_t> mat_aug;
   std::vector<float4> lights, mats, spheres, textures;  // the kernels' records: 5, 2, 2 and 3 per light / material / sphere / texture
   std::vector<float4> glass;  // {Kt, eta} per material, when the scene has a glass one; else empty
+  // an environment-map light: its tables, world_to_light and factor
+  bool env = false;
+  EnvTables env_tables;
+  uint32_t env_w = 0, env_h = 0;
+  float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
   float le_inf[3] = {0.f, 0.f, 0.f};
   bool has_inf = false;
   bool textured_tris = false;  // a triangle whose material's Kd is a texture: its corner (u, v) go up too
@@ -342,7 +368,8 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
   // light table: explicit lights, then every emissive triangle in index order
   for (uint32_t i = 0; i < d.n_lights; i++) {
     const pbrt_hip_light &l = d.lights[i];
-    in->lights.push_back(make_float4(as_f(l.type), l.p[0], l.p[1], l.p[2]));
+    // (type 3 of the boundary, the environment map, is 4 in this table: 3 is an emissive triangle here -- kernels.hip kDevLightEnv)
+    in->lights.push_back(make_float4(as_f(l.type == PBRT_HIP_LIGHT_ENVMAP ? 4u : l.type), l.p[0], l.p[1], l.p[2]));
     in->lights.push_back(make_float4(0, 0, 0, 0));
     in->lights.push_back(make_float4(0, 0, 0, 0));
     in->lights.push_back(make_float4(l.c[0], l.c[1], l.c[2], 0));
@@ -350,6 +377,14 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
     if (l.type == 2) {
       for (int k = 0; k < 3; k++) in->le_inf[k] = in->le_inf[k] + l.c[k];
       in->has_inf = true;
+    }
+    if (l.type == PBRT_HIP_LIGHT_ENVMAP) {
+      const pbrt_hip_envmap e = envmap_slot(d.textures, light_env_slot(l) - 1u);
+      in->env = true;
+      in->env_w = e.width; in->env_h = e.height;
+      for (int k = 0; k < 9; k++) in->env_m[k] = e.world_to_light[k];
+      for (int k = 0; k < 3; k++) in->env_c[k] = l.c[k];
+      envmap_build_tables(e.rgb, e.width, e.height, &in->env_tables);
     }
   }
   for (uint32_t t = 0; t < d.n_tris; t++) {
@@ -392,6 +427,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
     in->textures.resize(3 * (size_t)d.n_textures);
     for (uint32_t i = 0; i < d.n_textures; i++) {
       const pbrt_hip_texture &tx = d.textures[i];
+      if (is_envmap_slot(d.textures, i)) continue;  // (an environment map's slot: no material names it, its records stay zero)
       in->textures[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
       in->textures[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
       in->textures[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
@@ -409,6 +445,15 @@ int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const SceneIn
   HIP_TRY(upload(&s->d_spheres, in.spheres.data(), in.spheres.size(), s->stream));
   HIP_TRY(upload(&s->d_textures, in.textures.data(), in.textures.size(), s->stream));
   HIP_TRY(upload(&s->d_glass, in.glass.data(), in.glass.size(), s->stream));
+  if (in.env) {
+    HIP_TRY(upload(&s->d_env_texels, in.env_tables.texels.data(), in.env_tables.texels.size(), s->stream));
+    HIP_TRY(upload(&s->d_env_marginal, in.env_tables.marginal.data(), in.env_tables.marginal.size(), s->stream));
+    HIP_TRY(upload(&s->d_env_conditional, in.env_tables.conditional.data(), in.env_tables.conditional.size(), s->stream));
+    s->env = true;
+    s->env_w = in.env_w; s->env_h = in.env_h;
+    for (int k = 0; k < 9; k++) s->env_m[k] = in.env_m[k];
+    for (int k = 0; k < 3; k++) s->env_c[k] = in.env_c[k];
+  }
   if (in.textured_tris) HIP_TRY(upload(&s->d_tri_uv_in, d.tri_uv, 6 * (size_t)d.n_tris, s->stream));
   DevScene &D = s->dev;
   D.mats = s->d_mats.p;
@@ -507,7 +552,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.6 (gfx950)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.7 (gfx950; struct sizes of 0.6)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif
@@ -601,7 +646,7 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
       HIP_TRY(launch_pack_uv(s->d_tri_uv_in.p, s->d_order.p, in.n_prims, d->n_tris, s->d_tri_uv.p, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    s->device_bytes = s->d_glass.n * 16 + s->d_tri_uv_in.n * 4 + s->d_tri_uv.n * 8 + s->d_textures.n * 16 + s->d_P.n * 4 + s->d_idx.n * 4 + s->d_mat_id.n * 2 + s->d_order.n * 4 + s->d_nodes.n * 16 + s->d_quads.n * 16 +
+    s->device_bytes = s->d_env_texels.n * 16 + s->d_env_marginal.n * 4 + s->d_env_conditional.n * 4 + s->d_glass.n * 16 + s->d_tri_uv_in.n * 4 + s->d_tri_uv.n * 8 + s->d_textures.n * 16 + s->d_P.n * 4 + s->d_idx.n * 4 + s->d_mat_id.n * 2 + s->d_order.n * 4 + s->d_nodes.n * 16 + s->d_quads.n * 16 +
                       s->d_tris.n * 16 + s->d_mats.n * 16 + s->d_lights.n * 16 + s->d_spheres.n * 16;
     set_view(&s->dev, *d);
     *out = s.release();
@@ -713,12 +758,18 @@ static int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc
   if (fx > 16.f || fy > 16.f) return fail(PBRT_HIP_ERR_LIMIT, "render: filter radius above 16 pixels");
   if ((fx != 0.5f || fy != 0.5f) && (r->flags & (PBRT_HIP_FLAG_COUNTERS | PBRT_HIP_FLAG_WALK_COUNTERS)))
     return fail(PBRT_HIP_ERR_INVALID, "render: the counter flags need the default box filter (radius 0.5)");
+  // an environment map: render_kernel_env exists without counters and for the default box filter (kernels_env.hip).
+  // Asked first, so that a scene with a map is told of the map whatever else it holds (glass, textures)
+  if (s->env && (r->flags & (PBRT_HIP_FLAG_COUNTERS | PBRT_HIP_FLAG_WALK_COUNTERS)))
+    return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for a scene with an environment map");
   // (textures, the MIS integrator, the table samplers and a wide box filter combine freely -- render_kernel_x --; only the counting
   // instantiations exist for the default path alone)
   if ((s->textured || r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS) && (r->flags & (PBRT_HIP_FLAG_COUNTERS | PBRT_HIP_FLAG_WALK_COUNTERS)))
     return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for textured materials / the MIS integrator");
   if (s->glass && (r->flags & (PBRT_HIP_FLAG_COUNTERS | PBRT_HIP_FLAG_WALK_COUNTERS)))
     return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for a scene with a glass material");
+  if (s->env && (fx != 0.5f || fy != 0.5f))
+    return fail(PBRT_HIP_ERR_LIMIT, "render: an environment map with a box filter radius other than 0.5 is a combination the library does not build");
   if (!(r->max_sample_luminance >= 0.f)) return fail(PBRT_HIP_ERR_INVALID, "render: max_sample_luminance must be >= 0 (0 = none)");
   if (fx != 0.5f || fy != 0.5f) {
     // the fixed-point film: a sample adds at most 2^39 units to a pixel's int64 accumulator, and a pixel receives
@@ -757,10 +808,11 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
   L.mis = r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS;
   L.textured = s->textured;
   L.glass = s->glass;
+  L.env = s->env;
   const bool shallow = s->dev.quad_stack_need <= kShallowStackNeed;
   L.plan = stack_plan(s->dev.quad_stack_need);
   L.lds_bytes = L.plan.rows * 256u;
-  const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured && !L.glass;
+  const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured && !L.glass && !L.env;
   L.steps = default_path && !L.plan.overflow && shallow ? 2u : PBRT_STEPS_PER_CHECK;
   if (L.counters == kCountExact) {
     const int ce = ensure_canonical(s);
@@ -772,6 +824,7 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
   }
   // (the instantiations for another filter radius and for the table samplers fit the 96 VGPRs of 5 waves per SIMD like the default one)
   L.waves_per_cu = (L.spheres || L.glass) ? std::min(kRenderWavesPerCuSpheres, L.plan.waves_per_cu) : L.plan.waves_per_cu;  // (glass: the spheres' budget, kernels.hip)
+  if (L.env) L.waves_per_cu = std::min(kRenderWavesPerCuEnv, L.plan.waves_per_cu);  // (whatever else the scene holds: render_kernel_env's own budget)
   L.chunk_shift = sample_chunk_shift(r->spp_x * r->spp_y);
   const uint32_t n_chunks = 1u << L.chunk_shift;  // K: DESIGN.md 3.1
   L.passes = fg.wide ? 1u : partials_passes(sh.n_local, n_chunks);
@@ -819,6 +872,49 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
 }
 }  // namespace
 
+// the environment map's fields of the kernels' argument block (null / identity for a scene without one)
+static void set_env_params(const pbrt_hip_scene *s, RenderParams *R) {
+  R->env_texels = s->d_env_texels.p;
+  R->env_marginal = s->d_env_marginal.p;
+  R->env_conditional = s->d_env_conditional.p;
+  R->env_w = s->env_w; R->env_h = s->env_h;
+  for (int k = 0; k < 9; k++) R->env_m[k] = s->env_m[k];
+  for (int k = 0; k < 3; k++) R->env_c[k] = s->env_c[k];
+}
+
+int pbrt_hip_envmap_eval_device(pbrt_hip_scene *s, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "envmap_eval_device: null scene");
+  if (!s->env) return fail(PBRT_HIP_ERR_INVALID, "envmap_eval_device: the scene has no environment map");
+  if (n < 0 || (n && !d)) return fail(PBRT_HIP_ERR_INVALID, "envmap_eval_device: null argument");
+  if (n == 0) return PBRT_HIP_OK;
+  try {
+    HIP_TRY(hipSetDevice(s->device));
+    DevBuf<float> d_u, d_d, d_le, d_pdf;
+    DevBuf<uint32_t> d_texel;
+    HIP_TRY(d_d.alloc(3 * (size_t)n));
+    HIP_TRY(d_le.alloc(3 * (size_t)n));
+    HIP_TRY(d_pdf.alloc((size_t)n));
+    HIP_TRY(d_texel.alloc((size_t)n));
+    if (u12) {
+      HIP_TRY(d_u.alloc(2 * (size_t)n));
+      HIP_TRY(hipMemcpyAsync(d_u.p, u12, 8 * (size_t)n, hipMemcpyHostToDevice, s->stream));
+    } else {
+      HIP_TRY(hipMemcpyAsync(d_d.p, d, 12 * (size_t)n, hipMemcpyHostToDevice, s->stream));
+    }
+    RenderParams R{};
+    set_env_params(s, &R);
+    HIP_TRY(launch_envmap_eval(R, n, d_u.p, d_d.p, d_texel.p, d_le.p, d_pdf.p, s->stream));
+    if (u12) HIP_TRY(hipMemcpyAsync(d, d_d.p, 12 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    if (texel) HIP_TRY(hipMemcpyAsync(texel, d_texel.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    if (le) HIP_TRY(hipMemcpyAsync(le, d_le.p, 12 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    if (pdf) HIP_TRY(hipMemcpyAsync(pdf, d_pdf.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+  } catch (const std::exception &e) {
+    return fail(PBRT_HIP_ERR_INTERNAL, e.what());
+  }
+}
+
 int pbrt_hip_render_prepare(pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
   int rc = check_render_desc(s, r);
   if (rc) return rc;
@@ -861,6 +957,7 @@ int pbrt_hip_render_device(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, voi
     R.tri_uv = s->d_tri_uv.p;
     R.textures = s->d_textures.p;
     R.glass = s->d_glass.p;
+    set_env_params(s, &R);
     R.integrator = r->integrator;
     R.max_depth = r->max_depth;
     R.spp_x = r->spp_x;

@@ -109,6 +109,13 @@ struct pbrt_hip_scene : pbrt_hip::SceneStream {
   bool textured = false;                // some triangle's material has kd_tex != 0: the TEX instantiations render it
   pbrt_hip::DevBuf<float4> d_glass;     // {Kt, eta} per material of a scene with glass; empty otherwise
   bool glass = false;                   // some material is glass: the GLS instantiations render the scene
+  // an environment-map infinite light: texels {r, g, b, p_uv}, the marginal and conditional CDFs (envmap.hpp EnvTables),
+  // world_to_light and the light's factor; env: the scene has one and render_kernel_env renders it
+  pbrt_hip::DevBuf<float4> d_env_texels;
+  pbrt_hip::DevBuf<float> d_env_marginal, d_env_conditional;
+  bool env = false;
+  uint32_t env_w = 0, env_h = 0;
+  float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
   pbrt_hip::DevBuf<float4> d_tris_exact;
   pbrt_hip::DevBuf<uint32_t> d_order_exact;
   double canonical_build_ms = 0.0;

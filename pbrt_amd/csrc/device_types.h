@@ -188,6 +188,14 @@ struct RenderParams {
   // glass materials (render_kernel_x<..., GLS>): 16 B per MATERIAL {Kt.rgb, eta}, read for the materials of type 2 alone
   // (mats[2 i] = {2, Kr}, mats[2 i + 1] = 0: glass does not emit).  At the end, for the reason given above.
   const float4 *glass;
+  // an environment-map infinite light (render_kernel_env): the texels {r, g, b, p_uv} row-major (row 0 = theta 0), the
+  // marginal CDF over rows (env_h + 1 floats) and the rows' conditional CDFs (env_h x (env_w + 1)), world_to_light (row-major 3 x 3) and
+  // the light's factor on the texels (envmap_core.hpp).  At the end, for the reason given above.
+  const float4 *env_texels;
+  const float *env_marginal, *env_conditional;
+  uint32_t env_w, env_h;
+  float env_m[9];
+  float env_c[3];
 };
 // 2^24 fixed-point units per unit of radiance, a component clamped to [0, 2^15]
 constexpr float kFixedOne = 16777216.0f, kFixedMax = 32768.0f;
@@ -220,6 +228,7 @@ struct RenderLaunch {
   bool table_sampler;  // SND: samplers 2 and 3 (3.12, 3.13)
   bool mis, textured;  // render_kernel_x's MIS (3.14) and TEX (3.15)
   bool glass;          // render_kernel_x's GLS (3.16): the scene has a glass material
+  bool env;            // render_kernel_env (3.17): the scene has an environment map -- never with `wide` or the counters (capi.cpp check_render_desc)
   RenderStackPlan plan;  // the production walk's stack: LDS rows, the overflow variant, HBM entries per lane
   uint32_t steps;        // production walk: node steps per scheduling check (STEPS)
   uint32_t exact_rows;   // exact walk: STACK, its stack rows of refs (and as many of entry distances)
@@ -234,6 +243,10 @@ struct RenderLaunch {
 
 // launchers (kernels.hip)
 hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t stream);
+// kernels_env.hip: the launch of a scene with an environment map (launch_render hands it over), and envmap_core.hpp over device arrays
+// (pbrt_hip_envmap_eval_device: u12 != nullptr samples into d, else d is looked up; R's env_* fields are the map)
+hipError_t launch_render_env(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t stream);
+hipError_t launch_envmap_eval(const RenderParams &R, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf, hipStream_t stream);
 // fixed-point accumulators -> film pixels {X, Y, Z, weight}
 hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, size_t n_px, hipStream_t stream);
 hipError_t launch_acc_add(unsigned long long *dst, const unsigned long long *src, size_t n, hipStream_t stream);  // dst[i] += src[i]

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "device_types.h"
+#include "envmap_core.hpp"
 
 namespace pbrt_hip {
 namespace {
@@ -725,6 +726,8 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
     tmax = kInf;
     return true;
   } else {
+    // (an emissive triangle: device type 3.  Device type 4, an environment map, never arrives here: a kernel with ENV takes it before
+    // this chain, and launch_render's first question is L.env -- launch_render_env returns an error for what it does not build, it does not fall back)
     const float4 l1 = S.lights[5 * li + 1];
     const float4 l2 = S.lights[5 * li + 2];
     const float4 l4 = S.lights[5 * li + 4];
@@ -751,6 +754,47 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
     tmax = dist * kShadowShrink;
     return true;
   }
+}
+
+// ---- the environment-map infinite light (the arithmetic is envmap_core.hpp's, shared with the host).  Used by the ENV
+// instantiation alone (kernels_env.hip render_kernel_env): nothing below is reachable from render_kernel / render_kernel_x. ----
+constexpr uint32_t kDevLightEnv = 4u;  // the light table's type word of the map's light (3 is an emissive triangle there: capi.cpp gather_inputs)
+__device__ __forceinline__ envmap::Map env_map(const RenderParams &R) {
+  envmap::Map m;
+  m.texels = R.env_texels;
+  m.marginal = R.env_marginal;
+  m.conditional = R.env_conditional;
+  m.W = R.env_w;
+  m.H = R.env_h;
+  for (int k = 0; k < 9; k++) m.M[k] = R.env_m[k];
+  return m;
+}
+// Le(d) = c * texel of the direction; *pdf = its density over solid angle
+__device__ __forceinline__ V3 env_le(const RenderParams &R, V3 d, float *pdf) {
+  const envmap::Map m = env_map(R);
+  float st;
+  const float4 tx = m.texels[envmap::lookup(m, d.x, d.y, d.z, &st)];
+  *pdf = envmap::pdf_omega(tx.w, st);
+  return mk(R.env_c[0], R.env_c[1], R.env_c[2]) * xyz(tx);
+}
+// The map as the light of UniformSampleOneLight, from the (u1, u2) every light gets: Ld = (f Le) ((cos / pdf) nL), with MIS weighted by
+// pl^2 / (pl^2 + pb^2), pl = pdf / nL, pb = cos / pi, in the operation order of sample_light's triangle branch; the shadow ray of a distant light
+__device__ __forceinline__ bool sample_env_light(const RenderParams &R, V3 nf, V3 kd, float u1, float u2, float nLf, V3 &Ld, V3 &wi, float &tmax, const bool mis) {
+  const envmap::Map m = env_map(R);
+  float st;
+  const float4 tx = m.texels[envmap::sample(m, u1, u2, &wi.x, &wi.y, &wi.z, &st)];
+  const float pdf = envmap::pdf_omega(tx.w, st);
+  const float cs = dot(wi, nf);
+  if (!(cs > 0.f) || !(pdf > 0.f)) return false;
+  const V3 f = kd * kInvPi;
+  float scale = (cs / pdf) * nLf;
+  if (mis) {
+    const float pl = pdf / nLf, pbl = cs * kInvPi;
+    scale = scale * ((pl * pl) / (pl * pl + pbl * pbl));
+  }
+  Ld = (f * (mk(R.env_c[0], R.env_c[1], R.env_c[2]) * xyz(tx))) * scale;
+  tmax = kInf;
+  return true;
 }
 
 enum : uint32_t { ST_NEW = 0, ST_CLOSEST = 1, ST_SHADOW = 2, ST_DONE = 3, ST_FETCH = 4 };
@@ -948,8 +992,10 @@ template <bool SPH, bool COUNT, bool EXACT, int STACK, int STEPS = PBRT_STEPS_PE
 // of 3 waves per SIMD: the f64 quadratic of lib.rs:181-203 does not fit 128 VGPRs beside the path state)
 __global__ void __launch_bounds__(64, (COUNT ? 1 : (SPH ? 3 : PBRT_RENDER_WAVES_PER_SIMD))) render_kernel(const DevScene S, const RenderParams R) {
   constexpr bool MIS = false, TEX = false, GLS = false;  // (the variants: render_kernel_x below)
+  constexpr bool ENV = false;                            // (an environment map: kernels_env.hip render_kernel_env)
   (void)MIS;
   (void)GLS;
+  (void)ENV;
 #include "render_body.inc"
 }
 // The variants of the path that BASELINE's configs do not use, in a kernel of their own name so that the instantiations above keep
@@ -961,7 +1007,9 @@ __global__ void __launch_bounds__(64, (COUNT ? 1 : (SPH ? 3 : PBRT_RENDER_WAVES_
 template <bool SPH, int STACK, bool MIS, bool TEX, bool SND, bool WIDE, bool GLS = false>
 __global__ void __launch_bounds__(64, ((SPH || GLS) ? 3 : PBRT_RENDER_WAVES_PER_SIMD)) render_kernel_x(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false;
+  constexpr bool ENV = false;  // (an environment map: kernels_env.hip render_kernel_env)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
+  (void)ENV;
 #include "render_body.inc"
 }
 
@@ -1125,6 +1173,7 @@ __global__ void film_from_acc_kernel(const unsigned long long *acc, float4 *film
 
 }  // namespace
 
+#ifndef PBRT_KERNELS_ENV_TU  // (kernels_env.hip includes this file for the kernels' building blocks and defines its own launchers)
 // the fixed-point accumulators of two ranks on one device added (multi_gpu.cpp's loopback exchange; with one rank per device ncclReduce adds them)
 __global__ void acc_add_kernel(unsigned long long *dst, const unsigned long long *src, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1157,6 +1206,7 @@ static hipError_t with_bools(F &&f, bool b, Bs... rest) {
 // stack in LDS; the exact walk's is its stack rows.
 hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
   if (R.n_items == 0) return hipSuccess;
+  if (L.env) return launch_render_env(S, R, L, st);  // a scene with an environment map: kernels_env.hip
   auto go = [&](void (*kernel)(DevScene, RenderParams)) {
     hipLaunchKernelGGL(kernel, dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
     return hipGetLastError();
@@ -1238,5 +1288,6 @@ hipError_t launch_assemble(const float4 *slab, float4 *film, int32_t w, int32_t 
                      n_local_super);
   return hipGetLastError();
 }
+#endif  // PBRT_KERNELS_ENV_TU
 
 }  // namespace pbrt_hip

@@ -1,0 +1,78 @@
+// kernels_env.hip -- the render kernel of scenes with an environment-map infinite light, in a translation unit of its
+// own so that it compiles BESIDE kernels.hip (pbrt_amd/build.py runs the units in parallel; kernels.hip is the longest) and so that
+// kernels.hip's instantiations keep their names and their machine code.  It includes kernels.hip for the building blocks -- the walk, the
+// samplers, the path records, render_body.inc --, all of which sit in that file's anonymous namespace; the launchers of that file are
+// compiled out here (PBRT_KERNELS_ENV_TU).
+//
+//   render_kernel_env   render_body.inc with ENV = true: a ray that escapes collects the map (envmap_core.hpp lookup), the map is a light
+//                       of the one-light direct estimate (Distribution2D sampling, MIS against the cosine-sampled bounce ray).  GLS = true
+//                       always (a glass table that is never read costs nothing, and the instantiations halve); a register budget of
+//                       4 waves per SIMD.
+//   envmap_eval_kernel  envmap_core.hpp over arrays: pbrt_hip_envmap_eval_device, the hook that shows the device computes the host's bits.
+//
+// Combinations that do NOT exist (capi.cpp check_render_desc refuses them with PBRT_HIP_ERR_LIMIT): a box filter radius other than
+// 0.5 (WIDE) and the counter flags.
+#define PBRT_KERNELS_ENV_TU 1
+#include "kernels.hip"
+
+namespace pbrt_hip {
+namespace {
+
+// waves per SIMD the register allocator leaves room for: the body needs 101 .. 109 VGPRs (more than the 96 of 5 waves), which
+// the 128 of 4 waves hold without a spill -- one wave per SIMD more than the GLS instantiations' budget (capi.cpp kRenderWavesPerCuEnv)
+#ifndef PBRT_ENV_WAVES_PER_SIMD
+#define PBRT_ENV_WAVES_PER_SIMD 4
+#endif
+template <bool SPH, int STACK, bool MIS, bool TEX, bool SND>
+__global__ void __launch_bounds__(64, PBRT_ENV_WAVES_PER_SIMD) render_kernel_env(const DevScene S, const RenderParams R) {
+  constexpr bool COUNT = false, EXACT = false, WIDE = false, GLS = true, ENV = true;
+  constexpr int STEPS = PBRT_STEPS_PER_CHECK;
+#include "render_body.inc"
+}
+
+__global__ void envmap_eval_kernel(const RenderParams R, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const envmap::Map m = env_map(R);
+  float st;
+  uint32_t t;
+  if (u12) {
+    float x, y, z;
+    t = envmap::sample(m, u12[2 * i], u12[2 * i + 1], &x, &y, &z, &st);
+    d[3 * i] = x; d[3 * i + 1] = y; d[3 * i + 2] = z;
+  } else {
+    t = envmap::lookup(m, d[3 * i], d[3 * i + 1], d[3 * i + 2], &st);
+  }
+  const float4 tx = m.texels[t];
+  if (texel) texel[i] = t;
+  if (le) { le[3 * i] = tx.x; le[3 * i + 1] = tx.y; le[3 * i + 2] = tx.z; }
+  if (pdf) pdf[i] = envmap::pdf_omega(tx.w, st);
+}
+
+template <class F>
+hipError_t env_with_bools(F &&f) { return f(); }
+template <class F, class... Bs>
+hipError_t env_with_bools(F &&f, bool b, Bs... rest) {
+  if (b) return env_with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+  return env_with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+}  // namespace
+
+hipError_t launch_render_env(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
+  if (R.n_items == 0) return hipSuccess;
+  if (L.wide || L.counters != kCountNone || !R.env_texels) return hipErrorInvalidValue;  // (refused with a message by capi.cpp check_render_desc)
+  return env_with_bools([&](auto SPH, auto OVF, auto MIS, auto TEX, auto SND) {
+    constexpr int STACK = OVF ? (int)kQuadLdsStackOvf : 0;
+    hipLaunchKernelGGL((render_kernel_env<SPH, STACK, MIS, TEX, SND>), dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
+    return hipGetLastError();
+  }, L.spheres, L.plan.overflow, L.mis, L.textured, L.table_sampler);
+}
+
+hipError_t launch_envmap_eval(const RenderParams &R, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(envmap_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, R, n, u12, d, texel, le, pdf);
+  return hipGetLastError();
+}
+
+}  // namespace pbrt_hip

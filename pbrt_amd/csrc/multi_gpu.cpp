@@ -164,6 +164,7 @@ int clone_scene(const pbrt_hip_scene *src, int device, pbrt_hip_scene **out) {
   } while (0)
   CLONE(d_P); CLONE(d_idx); CLONE(d_order); CLONE(d_mat_id); CLONE(d_nodes); CLONE(d_quads);
   CLONE(d_tris); CLONE(d_mats); CLONE(d_lights); CLONE(d_spheres); CLONE(d_tri_uv); CLONE(d_textures); CLONE(d_glass);
+  CLONE(d_env_texels); CLONE(d_env_marginal); CLONE(d_env_conditional);
 #undef CLONE
   HIP_TRY(hipStreamSynchronize(s->stream));
   s->dev = src->dev;
@@ -175,6 +176,10 @@ int clone_scene(const pbrt_hip_scene *src, int device, pbrt_hip_scene **out) {
   s->dev.spheres = s->d_spheres.p;
   s->textured = src->textured;
   s->glass = src->glass;
+  s->env = src->env;
+  s->env_w = src->env_w; s->env_h = src->env_h;
+  for (int k = 0; k < 9; k++) s->env_m[k] = src->env_m[k];
+  for (int k = 0; k < 3; k++) s->env_c[k] = src->env_c[k];
   *out = s.release();
   return PBRT_HIP_OK;
 }

@@ -1,5 +1,6 @@
 // render_body.inc -- the body of render_kernel and of render_kernel_x (kernels.hip), included once in each: the two are the same
-// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS in scope.  (A shared __device__
+// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV in scope (kernels_env.hip
+// includes it a third time, for render_kernel_env, the one kernel with ENV = true).  (A shared __device__
 // function would be the tidy way to say this; the text is included instead because wrapping the body in a function -- forceinline or
 // not -- perturbs the register allocation of the production instantiation, whose machine code the committed counter profiles are
 // keyed by: pbrt_amd/isa_id.py; measured in round 5.)  In scope as well: `S` (DevScene) and `R` (RenderParams), the kernel's arguments.
@@ -119,6 +120,12 @@
             if (hit) {
               const V3 le = xyz(m1);
               if ((le.x > 0.f || le.y > 0.f || le.z > 0.f) && dot(ng, wo) > 0.f) P.L = P.L + P.beta * le;
+            } else if (ENV) {
+              // the ray escapes into the environment map (DESIGN.md 3.17): L += beta (le_inf + Le(d)), in full -- no light sample stood for it
+              float pdf_l;
+              V3 le = env_le(R, T.d, &pdf_l);
+              if (S.has_inf) le = mk(S.le_inf[0], S.le_inf[1], S.le_inf[2]) + le;
+              P.L = P.L + P.beta * le;
             } else if (S.has_inf) {
               P.L = P.L + P.beta * mk(S.le_inf[0], S.le_inf[1], S.le_inf[2]);
             }
@@ -137,6 +144,16 @@
             } else if (!hit && S.has_inf) {
               const float w = (nLf * nLf) / (nLf * nLf + 1.0f);
               P.L = P.L + (P.beta * mk(S.le_inf[0], S.le_inf[1], S.le_inf[2])) * w;
+            }
+            if (ENV && !hit) {
+              // 3.17: the BSDF-sampled ray found the map; light sampling would have drawn this direction with pl = pdf_omega(d) / nL
+              // (the constant part above keeps its own weight)
+              float pdf_l;
+              const V3 le = env_le(R, T.d, &pdf_l);
+              const float pb = rec_load(rec, kRecLpend).w;
+              const float pl = pdf_l / nLf;
+              const float w = (pb * pb) / (pb * pb + pl * pl);
+              P.L = P.L + (P.beta * le) * w;
             }
           }
           PROBE_SEC(2);
@@ -198,6 +215,13 @@
                 uint32_t li = (uint32_t)(xi * nLf);
                 li = min(li, nL - 1u);
                 V3 Ld;
+                if (ENV && __float_as_uint(S.lights[5 * li].x) == kDevLightEnv) {  // the environment map's light (3.17): the same (u1, u2)
+                  if (sample_env_light(R, nf, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS)) {
+                    need_shadow = true;
+                    lpend = P.beta * Ld;
+                    if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
+                  }
+                } else
                 if (sample_light(S, li, po, nf, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS)) {
                   need_shadow = true;
                   lpend = P.beta * Ld;

@@ -11,6 +11,7 @@
 #include <memory>
 #include <tuple>
 
+#include "envmap.hpp"
 #include "host_math.hpp"
 #include "ply_reader.hpp"
 
@@ -595,6 +596,53 @@ struct Api {
     return true;
   }
 
+  // turns the constant infinite light *l into the environment-map light of image `map` (type 3, its record in a slot of out->textures)
+  void environment_map(const std::string &map, pbrt_hip_light *l) {
+    if (!out->env_rgb.empty()) { warn("infinite light \"" + map + "\": one environment map per scene, constant L used for this one"); return; }
+    const std::string path = (map[0] == '/' || cur_dir.empty()) ? map : cur_dir + "/" + map;
+    int32_t w = 0, h = 0;
+    std::vector<float> rgb;
+    bool ok = pbrt_hip_read_image(path.c_str(), nullptr, &w, &h) == PBRT_HIP_OK && w > 0 && h > 0 && (uint64_t)w * (uint64_t)h <= (1ull << 24);
+    if (ok) {
+      rgb.resize(3 * (size_t)w * (size_t)h);
+      ok = pbrt_hip_read_image(path.c_str(), rgb.data(), &w, &h) == PBRT_HIP_OK;
+    }
+    for (size_t i = 0; ok && i < rgb.size(); i++) ok = std::isfinite(rgb[i]) && rgb[i] >= 0.f;
+    if (!ok) { warn("infinite light: environment map \"" + map + "\" cannot be read (missing, too large, or texels that are negative / not finite): constant L used"); return; }
+    // world_to_light = the rotation of the CTM, inverted.  A CTM that is a rotation gives its inverse's 3 x 3 as it stands; one that scales
+    // or shears: a warning, and the rotation that Gram-Schmidt leaves of the light's axes (x kept, y made orthogonal to it, z completing them)
+    pbrt_hip_envmap e{};
+    e.type = 1u; e.width = (uint32_t)w; e.height = (uint32_t)h;
+    const float *m = ctm[0].m, *mi = ctm[0].inv;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) e.world_to_light[3 * i + j] = mi[4 * i + j];
+    // (the library's own test and bound, envmap_check: what passes here is not refused there, and a chain of Rotate directives has
+    // fp32 rounding's room)
+    if (envmap_orthonormal_error(e.world_to_light) <= kEnvOrthonormalTolerance) {
+    } else {
+      warn("infinite light: the transformation of an environment map scales or shears; its rotation part is used");
+      double x[3] = {m[0], m[4], m[8]}, y[3] = {m[1], m[5], m[9]}, c2[3] = {m[2], m[6], m[10]};
+      auto norm = [](double *v) { const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); for (int k = 0; k < 3; k++) v[k] = n > 0.0 ? v[k] / n : 0.0; return n; };
+      bool good = norm(x) > 0.0;
+      const double xy = x[0] * y[0] + x[1] * y[1] + x[2] * y[2];
+      for (int k = 0; k < 3; k++) y[k] -= xy * x[k];
+      good = norm(y) > 0.0 && good;
+      double z[3] = {x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]};
+      if (z[0] * c2[0] + z[1] * c2[1] + z[2] * c2[2] < 0.0) for (int k = 0; k < 3; k++) z[k] = -z[k];  // (a mirroring CTM keeps its handedness)
+      if (!good) { warn("infinite light: the transformation of an environment map is singular: constant L used"); return; }
+      for (int k = 0; k < 3; k++) { e.world_to_light[k] = (float)x[k]; e.world_to_light[3 + k] = (float)y[k]; e.world_to_light[6 + k] = (float)z[k]; }
+    }
+    out->env_rgb.swap(rgb);
+    e.rgb = out->env_rgb.data();  // (filled once: the vector is not touched again)
+    pbrt_hip_texture slot{};
+    static_assert(sizeof slot == sizeof e, "an environment map takes one slot of the texture table");
+    std::memcpy(&slot, &e, sizeof slot);
+    out->textures.push_back(slot);
+    const uint32_t number = (uint32_t)out->textures.size();  // 1-based
+    l->type = PBRT_HIP_LIGHT_ENVMAP;
+    std::memcpy(&l->pad, &number, 4);
+  }
+
   void light_source(const std::string &name, const ParamSet &ps) {  // replaces make_light's todo!()s, api.rs:334-351
     warn_if_animated_transform("pbrt.light_source");  // api.rs:687
     float scale[3] = {1, 1, 1};
@@ -621,10 +669,14 @@ struct Api {
     } else if (name == "infinite" || name == "exinfinite") {
       float L[3] = {1, 1, 1};
       spectrum(ps, "L", L);
-      if (ps.find("mapname", "string")) warn("infinite light: environment maps are out of scope, constant L used");
       ps.find("samples", "integer"); ps.find("nsamples", "integer");
       l.type = 2;
       for (int i = 0; i < 3; i++) l.c[i] = L[i] * scale[i];
+      // "string mapname" (infinite.rs:52-66): the image through the library's own reader, relative names against the
+      // scene file's directory like "plymesh"; the texels are multiplied by L x scale (infinite.rs:54); a file that cannot be read is a
+      // warning and the constant L x scale (infinite.rs:56-58)
+      const std::string map = ps.one_string("mapname", "");
+      if (!map.empty()) environment_map(map, &l);
     } else {
       warn("light_source: light type '" + name + "' unknown.");  // api.rs:692 (spot, goniometric, projection: not on this path either)
       return;

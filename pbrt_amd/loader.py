@@ -6,7 +6,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import RenderDesc, SceneDesc, check, lib
+from ._lib import EnvMap, RenderDesc, SceneDesc, check, lib
 from .api import GLASS, SceneData
 
 
@@ -40,7 +40,19 @@ def _collect(h):
         def arr(ptr, n, dt):
             return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt).copy() if n else np.zeros(0, dt)
 
+        # an environment map's record sits in a slot of the texture table whose first word is 1: it becomes SceneData's
+        # `envmap`, the other slots stay the checkerboards -- numbered as they are while the map's slot is the last one, as the parser leaves
+        # it unless a texture is declared after the light (such a scene's texture numbers are remapped here)
+        env_slots = [i for i in range(d.n_textures) if d.textures[i].type == 1]
+        tex_slots = [i for i in range(d.n_textures) if d.textures[i].type != 1]
+        renum = {0: 0, **{i + 1: k + 1 for k, i in enumerate(tex_slots)}}
+        envmap, env_m = np.zeros((0, 0, 3), np.float32), np.eye(3, dtype=np.float32)
+        if env_slots:
+            e = EnvMap.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[env_slots[0]]), C.sizeof(EnvMap))))
+            envmap = arr(e.rgb, 3 * e.width * e.height, np.float32).reshape(e.height, e.width, 3)
+            env_m = np.array(list(e.world_to_light), np.float32).reshape(3, 3)
         sd = SceneData(
+            envmap=envmap, envmap_world_to_light=env_m,
             P=arr(d.P, 3 * d.n_verts, np.float32).reshape(-1, 3), idx=arr(d.idx, 3 * d.n_tris, np.uint32).reshape(-1, 3),
             mat_id=arr(d.mat_id, d.n_tris, np.uint16),
             materials=np.array([[d.mats[i].type, *d.mats[i].k, *d.mats[i].le] for i in range(d.n_mats)], np.float32).reshape(-1, 7),
@@ -48,11 +60,11 @@ def _collect(h):
             spheres=np.array([[*d.spheres[i].c, d.spheres[i].r, d.spheres[i].mat] for i in range(d.n_spheres)], np.float32).reshape(-1, 5),
             cam_to_world=np.array(list(d.cam_to_world), np.float32).reshape(4, 4), fov=d.fov, xres=d.xres, yres=d.yres,
             crop=tuple(d.crop),
-            mat_tex=np.array([0 if d.mats[i].type == GLASS else d.mats[i].kd_tex for i in range(d.n_mats)], np.uint32),
+            mat_tex=np.array([0 if d.mats[i].type == GLASS else renum[d.mats[i].kd_tex] for i in range(d.n_mats)], np.uint32),
             mat_eta=(np.array([d.mats[i].kd_tex if d.mats[i].type == GLASS else 0x3FC00000 for i in range(d.n_mats)], np.uint32).view(np.float32)
                      if any(d.mats[i].type == GLASS for i in range(d.n_mats)) else np.zeros(0, np.float32)),
             textures=np.array([[d.textures[i].type, *d.textures[i].tex1, *d.textures[i].tex2, d.textures[i].su, d.textures[i].sv, d.textures[i].du,
-                                d.textures[i].dv] for i in range(d.n_textures)], np.float32).reshape(-1, 11),
+                                d.textures[i].dv] for i in tex_slots], np.float32).reshape(-1, 11),
             tri_uv=(arr(d.tri_uv, 6 * d.n_tris, np.float32).reshape(-1, 6) if d.tri_uv else np.zeros((0, 6), np.float32))).normalized()
         wbuf = C.create_string_buffer(1 << 16)
         nw = l.pbrt_hip_loaded_warnings(h, wbuf, len(wbuf))

@@ -6,10 +6,11 @@
   random_mesh_scene   C2 / C3: N random triangles in a box with a ceiling area light
   cornell_scene       C4: Cornell-style box
   glass_sphere_scene  a glass sphere and a glass cube in a Cornell-style box (= scenes/glass_sphere.pbrt)
+  envmap_scene        a matte ground, a glass and a mirror sphere under an environment map (= scenes/envmap_spheres.pbrt)
 """
 import numpy as np
 
-from .api import GLASS, LIGHT_DISTANT, LIGHT_INFINITE, LIGHT_POINT, MATTE, MIRROR, SceneData, look_at
+from .api import GLASS, LIGHT_DISTANT, LIGHT_ENVMAP, LIGHT_INFINITE, LIGHT_POINT, MATTE, MIRROR, SceneData, look_at
 
 MESH_SEED = 0x5EED0001
 
@@ -206,6 +207,49 @@ def glass_sphere_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), glass=True
         materials=np.array(mats, np.float32), mat_eta=np.array(eta, np.float32),
         spheres=np.array([[0.4, -0.2, -0.45, 0.35, BALL]], np.float32),
         cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
+    ).normalized()
+
+
+def procedural_sky(width=64, height=32):
+    """A latitude-longitude sky, (height, width, 3) float32 with row 0 at the zenith (+z of the light): a gradient from a blue zenith to a
+    pale horizon, a dark ground below it, and a small sun -- radiance (600, 540, 420) in the texels whose centre lies within
+    max(2 degrees, 0.75 texel heights) of the direction theta 50, phi 120 degrees.  tools/make_sky_pfm.py writes the 64 x 32 one as
+    scenes/sky_small.pfm."""
+    theta = (np.arange(height, dtype=np.float64)[:, None] + 0.5) * np.pi / height
+    phi = (np.arange(width, dtype=np.float64)[None, :] + 0.5) * 2.0 * np.pi / width
+    ct = np.cos(theta) + 0.0 * phi
+    up = np.clip(ct, 0.0, 1.0)[..., None] ** 0.6
+    sky = (1.0 - up) * np.array([0.85, 0.88, 0.95]) + up * np.array([0.22, 0.42, 0.90])
+    sky = np.where(ct[..., None] >= 0.0, sky, np.array([0.16, 0.13, 0.10]))
+    ts, ps = np.radians(50.0), np.radians(120.0)
+    cos_sun = np.sin(theta) * np.sin(ts) * np.cos(phi - ps) + ct * np.cos(ts)
+    radius = max(np.radians(2.0), 0.75 * np.pi / height)
+    sky = np.where((cos_sun >= np.cos(radius))[..., None], np.array([600.0, 540.0, 420.0]), sky)
+    return np.ascontiguousarray(sky, np.float32)
+
+
+def envmap_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), sky=None, world_to_light=None, factor=(1.0, 1.0, 1.0), constant=False):
+    """The environment map's scene, with the defaults array for array what scenes/envmap_spheres.pbrt loads to: a matte
+    ground z = 0 (Kd .5 .48 .45), a glass sphere (eta 1.5) and a mirror sphere (Kr .9) of radius 1 standing on it, under the sky `sky`
+    ((H, W, 3), default procedural_sky(64, 32)) rotated by `world_to_light` and scaled by `factor`.  `constant=True`: the same scene under
+    a constant infinite light of the map's solid-angle mean radiance x factor (tools/envmap_cost.py's comparison)."""
+    GROUND, GLASS_M, MIRROR_M = range(3)
+    mats = [_mat(MATTE, (0.5, 0.48, 0.45)), _mat(GLASS, (1, 1, 1), (1, 1, 1)), _mat(MIRROR, (0.9, 0.9, 0.9))]
+    verts, tris = _quad((-20, -20, 0), (20, -20, 0), (20, 20, 0), (-20, 20, 0))
+    sky = procedural_sky() if sky is None else np.ascontiguousarray(sky, np.float32)
+    kw = {}
+    if constant:
+        w = np.sin((np.arange(sky.shape[0]) + 0.5) * np.pi / sky.shape[0])[:, None, None]
+        mean = (sky.astype(np.float64) * w).sum(axis=(0, 1)) / (w.sum() * sky.shape[1])
+        lights = [[LIGHT_INFINITE, 0, 0, 0, *(mean * np.asarray(factor, np.float64))]]
+    else:
+        lights = [[LIGHT_ENVMAP, 0, 0, 0, *factor]]
+        kw = dict(envmap=sky, envmap_world_to_light=np.eye(3, dtype=np.float32) if world_to_light is None else world_to_light)
+    return SceneData(
+        P=np.array(verts, np.float32), idx=np.array(tris, np.uint32), mat_id=np.array([GROUND, GROUND], np.uint16),
+        materials=np.array(mats, np.float32), mat_eta=np.array([1.5, 1.5, 1.5], np.float32), lights=np.array(lights, np.float32),
+        spheres=np.array([[-1.15, 0, 1, 1, GLASS_M], [1.15, 0, 1, 1, MIRROR_M]], np.float32),
+        cam_to_world=_camera((0, -7, 2.6), (0, 0, 0.9), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop, **kw,
     ).normalized()
 
 

@@ -18,6 +18,12 @@ pub const MATERIAL_MATTE: u32 = 0; pub const MATERIAL_MIRROR: u32 = 1; pub const
 // kind == MATERIAL_GLASS (smooth dielectric): k = Kr, le = Kt (glass does not emit), kd_tex = eta.to_bits() (eta in [1, 16])
 #[repr(C)] pub struct HipTexture  { pub kind: u32, pub tex1: [f32; 3], pub tex2: [f32; 3], pub su: f32, pub sv: f32, pub du: f32, pub dv: f32, pub pad: [u32; 5] }  // Texture "..." "spectrum" "checkerboard" (check-sphere.pbrt:24-25)
 #[repr(C)] pub struct HipLight    { pub kind: u32, pub p: [f32; 3], pub c: [f32; 3], pub pad: f32 }
+// kind == LIGHT_ENVMAP (3): c = L * scale, the factor on the texels (lights/infinite.rs:54); pad = f32::from_bits(n), n = the 1-based number of the
+// slot of `textures` that holds the map's record; p is ignored
+pub const LIGHT_ENVMAP: u32 = 3;
+// pbrt_hip_envmap: what a slot of `textures` IS when its first word is 1 -- 64 bytes like HipTexture; copy it into the slot with ptr::copy_nonoverlapping
+// (HipTexture is 4-aligned, this record holds a pointer).  rgb: 3 * width * height floats, row 0 = the light's +z, copied during scene_create
+#[repr(C)] pub struct HipEnvMap   { pub kind: u32 /* = 1 */, pub width: u32, pub height: u32, pub reserved: u32, pub rgb: *const f32, pub world_to_light: [f32; 9], pub pad: u32 }
 #[repr(C)] pub struct HipSphere   { pub c: [f32; 3], pub r: f32, pub mat: u32, pub pad: [u32; 3] }
 #[repr(C)] pub struct HipSceneDesc {
     pub p: *const f32, pub idx: *const u32, pub mat_id: *const u16,

@@ -117,6 +117,10 @@ def lib(native=False):
         l.orc_sobol_points.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
         l.orc_halton_points.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         l.orc_halton_points.restype = C.c_uint32
+        l.orc_envmap_tables.restype = C.c_int
+        l.orc_envmap_tables.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.orc_envmap_eval.restype = C.c_int
+        l.orc_envmap_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int64] + [C.c_void_p] * 5
         l.orc_quad_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
         _libs[native] = l
     return _libs[native]
@@ -321,6 +325,8 @@ class OracleScene:
         keep = fill_desc(desc, self.sd, Material, Light, Sphere, Texture)
         self.h = self.l.orc_scene_create(C.byref(desc))
         del keep
+        if not self.h:
+            raise ValueError("orc_scene_create: a scene the oracle does not know (material type > 2, light type > 3, a map light without its map slot, a matte Kd from a map slot)")
 
     def close(self):
         if getattr(self, "h", None):
@@ -402,6 +408,33 @@ class OracleScene:
         if rc != 0:
             raise ValueError("orc_render_acc: bad render description")
         return acc, {k: getattr(st, k) for k, _ in Stats._fields_}
+
+
+def envmap_tables(rgb):
+    """orc_envmap_tables: (marginal[H + 1], conditional[H, W + 1], p_uv[H, W]) of an (H, W, 3) map, DESIGN.md 3.17"""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    h, w = rgb.shape[:2]
+    marg, cond, puv = np.zeros(h + 1, np.float32), np.zeros((h, w + 1), np.float32), np.zeros((h, w), np.float32)
+    if lib().orc_envmap_tables(_p(rgb), w, h, _p(marg), _p(cond), _p(puv)) != 0:
+        raise ValueError("orc_envmap_tables: bad argument")
+    return marg, cond, puv
+
+
+def envmap_eval(rgb, world_to_light=None, u12=None, d=None):
+    """orc_envmap_eval: u12 (n, 2): SAMPLE -> (d[n, 3], texel[n] = row * W + col, le[n, 3], pdf[n]); else d (n, 3): LOOKUP -> the same four"""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    h, w = rgb.shape[:2]
+    m = np.ascontiguousarray(np.eye(3) if world_to_light is None else world_to_light, np.float32).reshape(9)
+    if u12 is not None:
+        u12 = np.ascontiguousarray(u12, np.float32).reshape(-1, 2)
+        d = np.zeros((len(u12), 3), np.float32)
+    else:
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3).copy()
+    n = len(d)
+    texel, le, pdf = np.zeros(n, np.uint32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+    if lib().orc_envmap_eval(_p(rgb), w, h, _p(m), n, _p(u12) if u12 is not None else None, _p(d), _p(texel), _p(le), _p(pdf)) != 0:
+        raise ValueError("orc_envmap_eval: bad argument")
+    return d, texel, le, pdf
 
 
 def film_from_acc(acc):

@@ -359,8 +359,14 @@ class PathIntegrator {
       }
       if (bounces == 0 || specular) {
         if (hit) {
-          Vec3 le = v3(m->le[0], m->le[1], m->le[2]);
+          Vec3 le = emitted(*m);
           if ((le.x > 0.f || le.y > 0.f || le.z > 0.f) && dot(ng, wo) > 0.f) L = L + beta * le;
+        } else if (scene.has_env) {
+          // the ray escapes into the map -- beta (le_inf + Le(d)), in full: no light sample stood for this direction
+          float pdf;
+          Vec3 le = env_radiance(ray.d, &pdf);
+          if (scene.has_infinite) le = scene.le_infinite + le;
+          L = L + beta * le;
         } else if (scene.has_infinite) {
           L = L + beta * scene.le_infinite;
         }
@@ -369,7 +375,7 @@ class PathIntegrator {
         // with pl -- an emissive triangle (picked with 1 / nL, a uniform point of it): (t^2 / (cos_l A)) / nL; the constant
         // environment (picked with 1 / nL, cosine-sampled): pb / nL.  Power heuristic: w = pb^2 / (pb^2 + pl^2).
         if (hit && h.prim < scene.n_tris()) {
-          Vec3 le = v3(m->le[0], m->le[1], m->le[2]);
+          Vec3 le = emitted(*m);
           const float cl = dot(ng, wo);
           if ((le.x > 0.f || le.y > 0.f || le.z > 0.f) && cl > 0.f) {
             Vec3 p0, p1, p2;
@@ -382,6 +388,16 @@ class PathIntegrator {
         } else if (!hit && scene.has_infinite) {
           const float w = (nLf * nLf) / (nLf * nLf + 1.0f);
           L = L + (beta * scene.le_infinite) * w;
+        }
+        if (!hit && scene.has_env) {
+          // 3.17: the BSDF-sampled ray found the map, whose light sample would have drawn this direction with pl = pdf_omega(d) / nL; the
+          // constant sky above keeps its own weight beside it
+          float pdf;
+          const Vec3 le = env_radiance(ray.d, &pdf);
+          const float pl = pdf / nLf;
+          const float w = (pb * pb) / (pb * pb + pl * pl);
+          if (g_debug_li) std::fprintf(stderr, "ORC   map escape pb %a pl %a w %a\n", pb, pl, w);
+          L = L + (beta * le) * w;
         }
       }
       if (!hit || bounces >= max_depth_) break;
@@ -408,7 +424,43 @@ class PathIntegrator {
         k = (cf - 2.0f * std::floor(0.5f * cf)) == 0.f ? v3(tx.tex1[0], tx.tex1[1], tx.tex1[2]) : v3(tx.tex2[0], tx.tex2[1], tx.tex2[2]);
       }
       Vec3 wi;
-      if (m->type == 0) {  // matte
+      Vec3 leave = po;  // where the next ray starts
+      if (m->type == 2) {
+        // glass: one Fresnel-specular lobe between index 1 (the side ng points to) and eta.  k = Kr, le = Kt, kd_tex =
+        // the bits of eta.  ONE 1-D request where a matte vertex picks its light; no light sample, no shadow ray.
+        float eta;
+        std::memcpy(&eta, &m->kd_tex, 4);
+        const float cos_o = dot(ng, wo);
+        const float abs_o = std::fabs(cos_o);
+        const float ci = abs_o < 1.0f ? abs_o : 1.0f;
+        const float r = cos_o > 0.f ? 1.0f / eta : eta;  // eta_i / eta_t: entering where wo is on ng's side
+        const float one_minus = 1.0f - ci * ci;
+        const float s2i = one_minus > 0.f ? one_minus : 0.f;
+        const float s2t = (r * r) * s2i;
+        float F, ct;
+        if (s2t >= 1.0f) {  // total internal reflection
+          F = 1.0f;
+          ct = 0.f;
+        } else {
+          ct = std::sqrt(1.0f - s2t);
+          const float e = 1.0f / r;
+          const float rpar = (e * ci - ct) / (e * ci + ct);
+          const float rper = (ci - e * ct) / (ci + e * ct);
+          F = 0.5f * (rpar * rpar + rper * rper);
+        }
+        const float u = sampler.Get1D();
+        const bool reflect = u < F;
+        if (reflect) {
+          wi = -wo + nf * (2.0f * ci);
+          beta = beta * k;
+        } else {
+          wi = (-wo) * r + nf * (r * ci - ct);
+          beta = beta * (v3(m->le[0], m->le[1], m->le[2]) * (r * r));
+          leave = p - nf * kSpawnEps;
+        }
+        if (g_debug_li) std::fprintf(stderr, "ORC   glass eta %a ci %a r %a ct %a F %a u %a %s wi %a %a %a\n", eta, ci, r, ct, F, u, reflect ? "reflect" : "refract", wi.x, wi.y, wi.z);
+        specular = true;
+      } else if (m->type == 0) {  // matte
         if (nL > 0) {
           float xi = sampler.Get1D();
           float u1, u2;
@@ -417,7 +469,8 @@ class PathIntegrator {
           if (li > nL - 1) li = nL - 1;
           Vec3 Ld;
           Ray sh;
-          if (sample_light(scene.lights[li], po, nf, k, u1, u2, nLf, &Ld, &sh, mis_)) {
+          const LightRec &lt = scene.lights[li];
+          if (lt.type == 4 ? sample_env_light(po, nf, k, u1, u2, nLf, &Ld, &sh) : sample_light(lt, po, nf, k, u1, u2, nLf, &Ld, &sh, mis_)) {
             st.shadow++;
             const bool occ = scene.IntersectP(sh, &st.c);
             if (g_debug_li) { uint32_t a; std::memcpy(&a, &Ld.x, 4); std::fprintf(stderr, "ORC   light %u Ld %08x occluded %d tmax %a\n", li, a, (int)occ, sh.tmax); }
@@ -443,7 +496,7 @@ class PathIntegrator {
         specular = true;
       }
       if (beta.x == 0.f && beta.y == 0.f && beta.z == 0.f) break;
-      ray.o = po;
+      ray.o = leave;
       ray.d = wi;
       ray.tmax = kInf;
       if (bounces > 3) {
@@ -454,6 +507,42 @@ class PathIntegrator {
       }
     }
     return L;
+  }
+
+  // what a surface emits: a glass material's `le` words hold Kt -- glass does not emit
+  static Vec3 emitted(const orc_material &m) { return m.type == 2 ? v3(0.f, 0.f, 0.f) : v3(m.le[0], m.le[1], m.le[2]); }
+
+  // Le(d) = c * the texel direction d looks at (point-sampled); *pdf = the density over solid angle with which the map's
+  // light sample draws d
+  Vec3 env_radiance(Vec3 d, float *pdf) const {
+    float st;
+    const uint32_t k = scene.env.lookup(d, &st);
+    *pdf = env_pdf_omega(scene.env.p_uv[k], st);
+    if (g_debug_li) std::fprintf(stderr, "ORC   map lookup texel %u sin %a pdf %a\n", k, st, *pdf);
+    return scene.env_c * scene.env.texel(k);
+  }
+
+  // The map as the light UniformSampleOneLight picked (3.17), from the (u1, u2) every light gets: Ld = (f Le) ((cos / pdf) nL), under MIS
+  // times pl^2 / (pl^2 + pb^2) with pl = pdf / nL and pb = cos / pi, in the order of the triangle branch below; a distant light's shadow ray
+  bool sample_env_light(Vec3 po, Vec3 nf, Vec3 kd, float u1, float u2, float nLf, Vec3 *Ld, Ray *sh) const {
+    Vec3 wi;
+    float st;
+    const uint32_t k = scene.env.sample(u1, u2, &wi, &st);
+    const float pdf = env_pdf_omega(scene.env.p_uv[k], st);
+    const float cs = dot(wi, nf);
+    if (g_debug_li) std::fprintf(stderr, "ORC   map sample u1 %a u2 %a texel %u wi %a %a %a pdf %a cs %a\n", u1, u2, k, wi.x, wi.y, wi.z, pdf, cs);
+    if (!(cs > 0.f) || !(pdf > 0.f)) return false;
+    const Vec3 f = kd * kInvPi;
+    float scale = (cs / pdf) * nLf;
+    if (mis_) {
+      const float pl = pdf / nLf, pbl = cs * kInvPi;
+      scale = scale * ((pl * pl) / (pl * pl + pbl * pbl));
+    }
+    *Ld = (f * (scene.env_c * scene.env.texel(k))) * scale;
+    sh->o = po;
+    sh->d = wi;
+    sh->tmax = kInf;
+    return true;
   }
 
   // UniformSampleOneLight's per-light part.  Returns false when geometry rules the
@@ -764,7 +853,45 @@ int orc_solve_2x2(const float a[4], const float b[2], float x[2]) {
 float orc_gamma_correct(float v) { return gamma_correct(v); }
 uint8_t orc_to_byte(float v) { return to_byte(v); }
 
+// An environment-map record as it lies in a slot of `textures`: the oracle's own declaration of the 64 bytes
+struct orc_envmap {
+  uint32_t type;  // 1
+  uint32_t width, height, reserved;
+  const float *rgb;  // 3 * width * height, row 0 = theta 0
+  float world_to_light[9];
+  uint32_t pad;
+};
+static_assert(sizeof(orc_envmap) == sizeof(orc_texture) && sizeof(orc_envmap) == 64, "a map record takes one slot of the texture table");
+static uint32_t slot_type(const orc_scene_desc *d, uint32_t slot) {  // slot: 0-based, < n_textures
+  uint32_t t;
+  std::memcpy(&t, (const char *)d->textures + 64 * (size_t)slot, 4);
+  return t;
+}
+// what the oracle does not know it refuses (NULL from orc_scene_create), so that no test gets a film of something else
+static bool scene_is_known(const orc_scene_desc *d) {
+  for (uint32_t i = 0; i < d->n_mats; i++) {
+    const orc_material &m = d->mats[i];
+    if (m.type > 2u) return false;
+    if (m.type == 0u && m.kd_tex != 0u && m.kd_tex <= d->n_textures && slot_type(d, m.kd_tex - 1u) == 1u) return false;  // Kd from a map slot
+  }
+  uint32_t n_maps = 0;
+  for (uint32_t i = 0; i < d->n_lights; i++) {
+    const orc_light &l = d->lights[i];
+    if (l.type > 3u) return false;
+    if (l.type != 3u) continue;
+    uint32_t slot;
+    std::memcpy(&slot, &l.pad, 4);
+    if (slot == 0u || slot > d->n_textures || slot_type(d, slot - 1u) != 1u) return false;
+    orc_envmap e;
+    std::memcpy(&e, (const char *)d->textures + 64 * (size_t)(slot - 1u), sizeof e);
+    if (e.width == 0u || e.height == 0u || !e.rgb) return false;
+    if (++n_maps > 1u) return false;  // one map per scene (3.17)
+  }
+  return true;
+}
+
 orc_scene *orc_scene_create(const orc_scene_desc *d) {
+  if (!scene_is_known(d)) return nullptr;
   orc_scene *h = new orc_scene();
   Scene &s = h->s;
   s.P.resize(d->n_verts);
@@ -781,12 +908,25 @@ orc_scene *orc_scene_create(const orc_scene_desc *d) {
     l.type = d->lights[i].type;
     l.p0 = v3(d->lights[i].p[0], d->lights[i].p[1], d->lights[i].p[2]);
     l.c = v3(d->lights[i].c[0], d->lights[i].c[1], d->lights[i].c[2]);
+    if (l.type == 3) {  // the ABI's environment map (LightRec's 3 is an emissive triangle): its record sits in the slot `pad` names
+      l.type = 4;
+      uint32_t slot;
+      std::memcpy(&slot, &d->lights[i].pad, 4);
+      orc_envmap e;
+      std::memcpy(&e, (const char *)d->textures + 64 * (size_t)(slot - 1u), sizeof e);
+      s.env.W = e.width; s.env.H = e.height;
+      std::memcpy(s.env.M, e.world_to_light, sizeof s.env.M);
+      s.env.rgb.assign(e.rgb, e.rgb + 3 * (size_t)e.width * e.height);
+      s.env.build_tables();
+      s.env_c = l.c;
+      s.has_env = true;
+    }
     s.lights.push_back(l);
     if (l.type == 2) { s.le_infinite = s.le_infinite + l.c; s.has_infinite = true; }
   }
   for (uint32_t t = 0; t < d->n_tris; t++) {
     const orc_material &m = s.mats[s.mat_id[t]];
-    if (m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f) {
+    if (m.type != 2 && (m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) {  // (a glass material's le words are Kt: not a light)
       LightRec l{};
       l.type = 3;
       s.tri_verts(t, &l.p0, &l.p1, &l.p2);
@@ -803,6 +943,45 @@ orc_scene *orc_scene_create(const orc_scene_desc *d) {
   return h;
 }
 void orc_scene_destroy(orc_scene *s) { delete s; }
+
+// The map's arithmetic over arrays (tests): the tables of an (H, W) map -- any output may be NULL -- ...
+int orc_envmap_tables(const float *rgb, uint32_t W, uint32_t H, float *marginal, float *conditional, float *p_uv) {
+  if (!rgb || W == 0u || H == 0u) return -1;
+  EnvMap e;
+  e.W = W; e.H = H;
+  e.rgb.assign(rgb, rgb + 3 * (size_t)W * H);
+  e.build_tables();
+  if (marginal) std::memcpy(marginal, e.marginal.data(), e.marginal.size() * 4);
+  if (conditional) std::memcpy(conditional, e.conditional.data(), e.conditional.size() * 4);
+  if (p_uv) std::memcpy(p_uv, e.p_uv.data(), e.p_uv.size() * 4);
+  return 0;
+}
+// ... and n samples (u12 != NULL: d is written) or n lookups (u12 == NULL: d is read) under world_to_light M: the texel (row * W + col),
+// its rgb and the density over solid angle
+int orc_envmap_eval(const float *rgb, uint32_t W, uint32_t H, const float M[9], int64_t n, const float *u12, float *d, uint32_t *texel,
+                    float *le, float *pdf) {
+  if (!rgb || W == 0u || H == 0u || !M || n < 0 || (n && !d)) return -1;
+  EnvMap e;
+  e.W = W; e.H = H;
+  std::memcpy(e.M, M, sizeof e.M);
+  e.rgb.assign(rgb, rgb + 3 * (size_t)W * H);
+  e.build_tables();
+  for (int64_t i = 0; i < n; i++) {
+    float st;
+    uint32_t k;
+    if (u12) {
+      Vec3 w;
+      k = e.sample(u12[2 * i], u12[2 * i + 1], &w, &st);
+      d[3 * i] = w.x; d[3 * i + 1] = w.y; d[3 * i + 2] = w.z;
+    } else {
+      k = e.lookup(v3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), &st);
+    }
+    if (texel) texel[i] = k;
+    if (le) { const Vec3 t = e.texel(k); le[3 * i] = t.x; le[3 * i + 1] = t.y; le[3 * i + 2] = t.z; }
+    if (pdf) pdf[i] = env_pdf_omega(e.p_uv[k], st);
+  }
+  return 0;
+}
 uint32_t orc_bvh_node_count(const orc_scene *s) { return (uint32_t)s->s.nodes.size(); }
 uint32_t orc_bvh_depth(const orc_scene *s) { return s->s.depth; }
 void orc_bvh_export(const orc_scene *s, uint32_t *nodes, uint32_t *order) {

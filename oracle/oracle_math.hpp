@@ -270,4 +270,66 @@ static inline void sphere_uv(float nx, float ny, float nz, float *u, float *v) {
   *v = (theta - 3.14159265358979323846f) / (0.f - 3.14159265358979323846f);
 }
 
+// ---- the environment map's arithmetic, restated from the spec's text: the oracle's own declarations, nothing shared with
+// the product.  fp32, one order of operations, no libm on the path: atan / acos are the polynomials above, sin / cos those of 3.6 carried
+// over [0, 2 pi] by Cephes' octant reduction. ----
+static const float kTwoPi = 6.28318530717958647692f;
+static const float kInvTwoPi = 0.15915494309189533577f;
+static const float kTwoPiSquared = 19.739208802178716f;  // the Jacobian of (u, v) -> direction is 2 pi^2 sin theta
+
+// sin and cos of x in [0, 2 pi]: the octant of x 4 / pi made even (an odd one goes up), y = x minus that many pi / 4 taken off in the three
+// parts Cephes splits pi / 4 into, the two polynomials on |y| <= pi / 4 handed out by the quadrant
+static inline void sincos_octants(float x, float *sn, float *cs) {
+  uint32_t oct = (uint32_t)(x * 1.27323954473516f);
+  if (oct & 1u) oct += 1u;
+  const float n = (float)oct;
+  float y = x - n * 0.78515625f;
+  y = y - n * 2.4187564849853515625e-4f;
+  y = y - n * 3.77489497744594108e-8f;
+  const float a = poly_sin(y), b = poly_cos(y);
+  switch ((oct / 2u) % 4u) {
+    case 0: *sn = a; *cs = b; break;
+    case 1: *sn = b; *cs = -a; break;
+    case 2: *sn = -a; *cs = -b; break;
+    default: *sn = -b; *cs = a; break;
+  }
+}
+// min((int)x, n - 1) for x >= 0; negative and NaN: 0
+static inline uint32_t env_cell(float x, uint32_t n) {
+  if (!(x > 0.f)) return 0u;
+  return x < (float)n ? (uint32_t)x : n - 1u;
+}
+// the sine of the polar angle as lookup and sample both take it: from cos theta, clamped to [-1, 1]
+static inline float env_sin_theta(float cos_theta, float *clamped) {
+  const float z = cos_theta < -1.0f ? -1.0f : (cos_theta > 1.0f ? 1.0f : cos_theta);
+  if (clamped) *clamped = z;
+  const float s2 = 1.0f - z * z;
+  return std::sqrt(s2 > 0.f ? s2 : 0.f);
+}
+// pdf over solid angle of a direction whose texel has density p_uv over (u, v); sin theta == 0: 0
+static inline float env_pdf_omega(float p_uv, float sin_theta) {
+  if (sin_theta == 0.f) return 0.f;
+  return p_uv / (kTwoPiSquared * sin_theta);
+}
+// pbrt-v3 FindInterval: the largest k in [0, n - 1] with cdf[k] <= u, by bisection over the n + 1 entries
+static inline uint32_t env_find_interval(const float *cdf, uint32_t n, float u) {
+  uint32_t first = 0u, last = n;
+  while (last - first > 1u) {
+    const uint32_t half = (first + last) / 2u;
+    if (cdf[half] <= u) first = half; else last = half;
+  }
+  return first;
+}
+// Distribution1D::SampleContinuous: -> (k + place inside interval k) / n, the place capped at 1 - 2^-23
+static inline float env_sample_continuous(const float *cdf, uint32_t n, float u, uint32_t *k_out) {
+  const uint32_t k = env_find_interval(cdf, n, u);
+  const float width = cdf[k + 1u] - cdf[k];
+  float place = u - cdf[k];
+  if (width > 0.f) place = place / width;
+  const float cap = 1.0f - std::numeric_limits<float>::epsilon();
+  if (!(place < cap)) place = cap;
+  *k_out = k;
+  return ((float)k + place) / (float)n;
+}
+
 }  // namespace orc

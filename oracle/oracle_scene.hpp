@@ -63,8 +63,91 @@ struct LinearBVHNode {
 };
 static_assert(sizeof(LinearBVHNode) == 32, "node must be 32 bytes");
 
+// The environment map of a type-3 light: texels, the density p_uv = f / mean(f) of each, and pbrt-v3's Distribution2D as
+// two tables of floats.  Written from the spec's text; nothing here comes from the product's sources.
+struct EnvMap {
+  uint32_t W = 0, H = 0;
+  float M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // world_to_light, row-major
+  std::vector<float> rgb;          // 3 per texel, row-major, row 0 = theta 0
+  std::vector<float> p_uv;         // W * H
+  std::vector<float> marginal;     // H + 1
+  std::vector<float> conditional;  // H rows of W + 1
+
+  // f[row][col] = y(texel) sin(pi (row + 1/2) / H) in float64 (a map whose f sums to nothing: f = the sine alone).  The ORDER of the
+  // float64 sums is part of the spec: the grand total is the running sum over the texels in row-major order; a row's total is the running
+  // sum over its columns; conditional[row][col] = (the running sum of the row's f before col) / (the row's total), taken after the row's
+  // total is known (a row of zeros: col / W); marginal[row] = (the running sum of the ROW TOTALS before row) / (the grand total);
+  // p_uv = f / (grand total / (W H)).  Each quotient is rounded to float once; the last entry of every CDF is exactly 1.
+  void build_tables() {
+    const size_t n = (size_t)W * H;
+    std::vector<double> f(n), s(H);
+    for (uint32_t r = 0; r < H; r++) s[r] = std::sin(3.14159265358979323846 * ((double)r + 0.5) / (double)H);
+    double grand = 0.0;
+    for (size_t i = 0; i < n; i++) {
+      const double y = 0.212671 * (double)rgb[3 * i] + 0.715160 * (double)rgb[3 * i + 1] + 0.072169 * (double)rgb[3 * i + 2];
+      f[i] = y * s[i / W];
+      grand += f[i];
+    }
+    if (!(grand > 0.0)) {
+      grand = 0.0;
+      for (size_t i = 0; i < n; i++) { f[i] = s[i / W]; grand += f[i]; }
+    }
+    const double mean = grand / (double)n;
+    p_uv.resize(n);
+    for (size_t i = 0; i < n; i++) p_uv[i] = (float)(f[i] / mean);
+    marginal.assign((size_t)H + 1, 0.f);
+    conditional.assign((size_t)H * (W + 1), 0.f);
+    double rows_done = 0.0;
+    for (uint32_t r = 0; r < H; r++) {
+      const double *fr = &f[(size_t)r * W];
+      double row_total = 0.0;
+      for (uint32_t c = 0; c < W; c++) row_total += fr[c];
+      float *cdf = &conditional[(size_t)r * (W + 1)];
+      double run = 0.0;
+      for (uint32_t c = 0; c < W; c++) {
+        cdf[c] = row_total > 0.0 ? (float)(run / row_total) : (float)((double)c / (double)W);
+        run += fr[c];
+      }
+      cdf[W] = 1.0f;
+      marginal[r] = (float)(rows_done / grand);
+      rows_done += row_total;
+    }
+    marginal[H] = 1.0f;
+  }
+
+  // the texel (row * W + col) a world direction looks at, and the sine of its polar angle
+  uint32_t lookup(Vec3 d, float *sin_theta) const {
+    const Vec3 w = {dot(v3(M[0], M[1], M[2]), d), dot(v3(M[3], M[4], M[5]), d), dot(v3(M[6], M[7], M[8]), d)};
+    const float ax = std::fabs(w.x), ay = std::fabs(w.y);
+    float phi = (ax == 0.f && ay == 0.f) ? 0.f : poly_atan_pos(ay / ax);
+    if (w.x < 0.f) phi = kPi - phi;
+    if (w.y < 0.f) phi = kTwoPi - phi;
+    float z;
+    *sin_theta = env_sin_theta(w.z, &z);
+    const float theta = poly_acos(z);
+    const float u = phi * kInvTwoPi, v = theta * kInvPi;
+    return env_cell(v * (float)H, H) * W + env_cell(u * (float)W, W);
+  }
+
+  // SampleContinuous on (u1, u2): the row from the marginal at u2, the column from that row's conditional at u1
+  uint32_t sample(float u1, float u2, Vec3 *d, float *sin_theta) const {
+    uint32_t row, col;
+    const float v = env_sample_continuous(marginal.data(), H, u2, &row);
+    const float u = env_sample_continuous(&conditional[(size_t)row * (W + 1)], W, u1, &col);
+    float sin_t, cos_t, sin_p, cos_p;
+    sincos_octants(v * kPi, &sin_t, &cos_t);
+    sincos_octants(u * kTwoPi, &sin_p, &cos_p);
+    const Vec3 w = {sin_t * cos_p, sin_t * sin_p, cos_t};
+    // d = M^T w
+    *d = {dot(v3(M[0], M[3], M[6]), w), dot(v3(M[1], M[4], M[7]), w), dot(v3(M[2], M[5], M[8]), w)};
+    *sin_theta = env_sin_theta(w.z, nullptr);
+    return row * W + col;
+  }
+  Vec3 texel(uint32_t k) const { return v3(rgb[3 * (size_t)k], rgb[3 * (size_t)k + 1], rgb[3 * (size_t)k + 2]); }
+};
+
 struct LightRec {
-  uint32_t type;  // 0 point, 1 distant, 2 infinite, 3 triangle
+  uint32_t type;  // 0 point, 1 distant, 2 infinite, 3 triangle, 4 the environment map (type 3 of the ABI)
   Vec3 p0, p1, p2;  // point: p0 = position; distant: p0 = direction to light; triangle: vertices
   Vec3 c;           // I / L / Le
   Vec3 n;           // triangle: geometric normal
@@ -83,6 +166,9 @@ class Scene {
   std::vector<LightRec> lights;
   Vec3 le_infinite{0, 0, 0};
   bool has_infinite = false;
+  EnvMap env;              // the map of the type-3 light, if has_env
+  Vec3 env_c{0, 0, 0};     // that light's factor on the texels
+  bool has_env = false;
   // camera
   Mat4 c2w;
   float cam_ax, cam_bx, cam_ay, cam_by;

@@ -29,24 +29,28 @@ extern "C" {
  * include/pbrt_hip.h's pbrt_hip_scene_desc so a test can hand both the same bytes,
  * but declared independently. */
 typedef struct {
-  uint32_t type;  /* 0 = matte, 1 = mirror */
-  float k[3];     /* Kd (matte) or Kr (mirror) */
-  float le[3];    /* emitted radiance (one-sided, along the geometric normal) */
-  uint32_t kd_tex; /* matte: 0 = Kd is k, t > 0 = textures[t - 1] at the hit's (u, v) on triangles */
+  uint32_t type;  /* 0 = matte, 1 = mirror, 2 = glass; anything else: orc_scene_create returns NULL */
+  float k[3];     /* Kd (matte) or Kr (mirror, glass) */
+  float le[3];    /* emitted radiance (one-sided, along the geometric normal); glass: Kt -- a glass surface does not emit */
+  uint32_t kd_tex; /* matte: 0 = Kd is k, t > 0 = textures[t - 1] at the hit's (u, v) on triangles (the slot must be a
+                      checkerboard, not a map: NULL).  glass: the IEEE-754 bits of the float eta */
 } orc_material;
 
 typedef struct {
-  uint32_t type;  /* 0 = checkerboard 2D over (u, v): pbrt-v3 Checkerboard2DTexture, aamode none */
+  uint32_t type;  /* 0 = checkerboard 2D over (u, v): pbrt-v3 Checkerboard2DTexture, aamode none.  A slot whose first word is 1 is not
+                     this struct but the 64-byte record of an environment map (type = 1, width, height, reserved,
+                     const float *rgb, float world_to_light[9], pad), which the oracle reads with memcpy into a struct of its own */
   float tex1[3], tex2[3];
   float su, sv, du, dv;
   uint32_t pad[5];
 } orc_texture;
 
 typedef struct {
-  uint32_t type;  /* 0 point, 1 distant, 2 infinite(constant) */
+  uint32_t type;  /* 0 point, 1 distant, 2 infinite(constant), 3 infinite with an environment map; above: NULL */
   float p[3];     /* point: position; distant: direction TOWARDS the light (normalised by caller) */
-  float c[3];     /* point: intensity I; distant/infinite: radiance L */
-  float pad;
+  float c[3];     /* point: intensity I; distant/infinite: radiance L; map: the factor on the texels */
+  float pad;      /* map: the BITS of the 1-based number of the textures slot that holds its record (no such slot, a slot that is no
+                     map, a second map light: NULL) */
 } orc_light;
 
 typedef struct {
@@ -74,13 +78,14 @@ typedef struct {
 } orc_scene_desc;
 
 typedef struct {
-  uint32_t integrator; /* 0 = path, 1 = directlighting */
+  uint32_t integrator; /* 0 = path, 1 = directlighting, 2 = path with the one-sample MIS of DESIGN.md 3.14 */
   uint32_t max_depth;
   uint32_t spp_x, spp_y;
   uint64_t seed;
   uint32_t rank, world_size; /* which 64x64 super-tiles to render (t % world == rank) */
   uint32_t flags;
-  uint32_t sampler;    /* 0 = stratified, 1 = padded (0,2)-sequence (3.10), 2 = Sobol' with its own dimensions per request (3.12) */
+  uint32_t sampler;    /* 0 = stratified, 1 = padded (0,2)-sequence (3.10), 2 = Sobol' with its own dimensions per request (3.12),
+                          3 = Halton (3.13) */
   float filter_xwidth, filter_ywidth; /* box filter radii (box.rs:57-61); 0 = the default 0.5.  Other radii: DESIGN.md 3.11 */
   float max_sample_luminance;         /* Film "maxsampleluminance" (film.rs:75,279); 0 = infinity */
 } orc_render_desc;
@@ -131,6 +136,8 @@ float orc_gamma_correct(float v);
 uint8_t orc_to_byte(float v);
 
 /* ---- scene / BVH / rays ---- */
+/* NULL for what the oracle does not know: a material type above 2, a light type above 3, a type-3 light that names no map slot (or a
+ * second one), a matte kd_tex that names a map slot */
 orc_scene *orc_scene_create(const orc_scene_desc *desc);
 void orc_scene_destroy(orc_scene *s);
 uint32_t orc_bvh_node_count(const orc_scene *s);
@@ -143,6 +150,13 @@ void orc_intersect(const orc_scene *s, int64_t n, const float *o, const float *d
                    float *t, uint32_t *prim, float *b1, float *b2, uint64_t *counters, int brute_force);
 void orc_occluded(const orc_scene *s, int64_t n, const float *o, const float *d, const float *tmax,
                   uint8_t *hit, int brute_force);
+/* ---- the environment map's arithmetic over arrays (tests compare it with the product's host hooks) ---- */
+/* the tables of an H x W map: marginal[H + 1], conditional[H * (W + 1)], p_uv[H * W]; any may be NULL.  0, or -1 for a bad argument */
+int orc_envmap_tables(const float *rgb, uint32_t W, uint32_t H, float *marginal, float *conditional, float *p_uv);
+/* u12 != NULL: n SAMPLES from (u1, u2) pairs, d[3n] written; u12 == NULL: n LOOKUPS of the directions d[3n].  M = world_to_light.
+ * texel[n] = row * W + col, le[3n] = the texel's rgb, pdf[n] = the density over solid angle; any of the three may be NULL */
+int orc_envmap_eval(const float *rgb, uint32_t W, uint32_t H, const float M[9], int64_t n, const float *u12, float *d, uint32_t *texel,
+                    float *le, float *pdf);
 /* camera ray for film point (fx, fy) */
 void orc_camera_ray(const orc_scene *s, float fx, float fy, float o[3], float d[3]);
 /* radiance of ONE pixel's samples (debug / fixtures): out = spp*3 floats */

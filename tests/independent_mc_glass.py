@@ -1,6 +1,6 @@
 """An independent Monte Carlo reference for the glass material, in float64 numpy: test infrastructure modelled on
 tests/independent_mc.py -- analytic intersections (box planes, one sphere or one axis-aligned cube), its own random numbers, no light
-sampling, nothing shared with the library or the oracle (which cannot render glass).
+sampling, nothing shared with the library or the oracle.
 
 It does NOT use the library's strategy at a glass surface.  The library draws reflection with probability F (the Fresnel reflectance) and
 weights by Kr, refraction with 1 - F and weights by Kt eta_i^2 / eta_t^2.  Here reflection and refraction are drawn with probability 1/2 each

@@ -10,7 +10,9 @@ a wrong term (a pdf, a cosine, the n_lights factor, the order of the draws, the 
 Every sampler, integrator and film path of the spec has its second implementation here.  What differs legitimately: float64 against fp32 arithmetic (1e-6 relative), and a handful of paths per image whose discrete decisions (which
 triangle at an edge, roulette at the threshold, the picked light) fall the other way.
 
-Supported: triangles and spheres (matte / mirror; emissive triangles = area lights), point / distant / constant-infinite lights, integrators 0
+Supported: triangles and spheres (matte / mirror / glass -- 3.16, numpy's sqrt --; emissive triangles = area lights), point / distant /
+constant-infinite lights and the environment map of 3.17 (numpy's arctan2 / arccos / sin / cos, np.searchsorted on float64 CDFs of this file's
+own that are never rounded to float), integrators 0
 (path), 1 (direct) and 2 (path with the one-sample MIS of 3.14), the stratified sampler, the padded (0,2)-sequence of 3.10 ("sobol") and the
 Halton sampler of 3.13 ("halton"), the Sobol' sampler of 3.12 ("sobol_nd": the generator matrices are a table, handed in), checkerboard textures
 (3.15; numpy's arctan2 / arccos for a sphere's (u, v)), box filters of any radius (3.11: the fixed-point film) and "maxsampleluminance"."""
@@ -253,6 +255,70 @@ def _cosine_about(n, u1, u2):
     return v2 * dx[:, None] + v3 * dy[:, None] + n * z[:, None], z
 
 
+class _Sky:
+    """The environment map of DESIGN.md 3.17 from its text, in float64: a point-sampled latitude-longitude image (row 0 = theta 0 of the
+    light's frame, w = M d), its density over (u, v) proportional to luminance x sin(row centre) -- the sine alone for a map that is black
+    everywhere --, and pbrt-v3's Distribution2D::SampleContinuous by np.searchsorted on the marginal and conditional CDFs."""
+
+    def __init__(self, texels, world_to_light, factor):
+        self.tex = np.asarray(texels, np.float64)
+        self.H, self.W = self.tex.shape[:2]
+        self.M = np.asarray(world_to_light, np.float64).reshape(3, 3)
+        self.c = np.asarray(factor, np.float64)
+        sine = np.sin(np.pi * (np.arange(self.H) + 0.5) / self.H)
+        f = (0.212671 * self.tex[..., 0] + 0.715160 * self.tex[..., 1] + 0.072169 * self.tex[..., 2]) * sine[:, None]
+        if not f.sum() > 0:
+            f = np.tile(sine[:, None], (1, self.W))
+        self.p_uv = f / f.mean()
+        rows = f.sum(1)
+        self.marg = np.concatenate([[0.0], np.cumsum(rows) / rows.sum()])
+        self.marg[-1] = 1.0
+        with np.errstate(all="ignore"):
+            cond = np.where(rows[:, None] > 0, np.cumsum(f, 1) / rows[:, None], (np.arange(self.W) + 1.0)[None] / self.W)
+        self.cond = np.concatenate([np.zeros((self.H, 1)), cond], 1)
+        self.cond[:, -1] = 1.0
+
+    @staticmethod
+    def _pdf(p_uv, wz):
+        st = np.sqrt(np.maximum(0.0, 1.0 - np.clip(wz, -1.0, 1.0) ** 2))
+        with np.errstate(all="ignore"):
+            return np.where(st == 0, 0.0, p_uv / (2.0 * np.pi * np.pi * st))
+
+    def look(self, d):
+        """-> (Le = c x texel, pdf over solid angle) of world directions d"""
+        w = d @ self.M.T
+        phi = np.arctan2(w[:, 1], w[:, 0])
+        phi = np.where(phi < 0, phi + 2 * np.pi, phi)
+        theta = np.arccos(np.clip(w[:, 2], -1.0, 1.0))
+        col = np.minimum((phi / (2 * np.pi) * self.W).astype(np.int64), self.W - 1)
+        row = np.minimum((theta / np.pi * self.H).astype(np.int64), self.H - 1)
+        return self.c * self.tex[row, col], self._pdf(self.p_uv[row, col], w[:, 2])
+
+    @staticmethod
+    def _invert(cdf, u):
+        """cdf [m + 1], or [n, m + 1] with one row per u: the largest k <= m - 1 with cdf[k] <= u, and (k + the place inside interval k) / m"""
+        m = cdf.shape[-1] - 1
+        if cdf.ndim == 1:
+            k = np.clip(np.searchsorted(cdf, u, side="right") - 1, 0, m - 1)
+            lo, width = cdf[k], cdf[k + 1] - cdf[k]
+        else:
+            k = np.array([np.searchsorted(c, x, side="right") - 1 for c, x in zip(cdf, u)], np.int64).reshape(-1)
+            k = np.clip(k, 0, m - 1)
+            r = np.arange(len(u))
+            lo, width = cdf[r, k], cdf[r, k + 1] - cdf[r, k]
+        with np.errstate(all="ignore"):
+            place = np.where(width > 0, (u - lo) / width, u - lo)
+        return k, (k + np.minimum(place, 1.0 - 2.0 ** -23)) / m
+
+    def draw(self, u1, u2):
+        """-> (wi, Le, pdf) of the light samples (u1, u2): the row from the marginal at u2, the column from its conditional at u1"""
+        row, v = self._invert(self.marg, u2)
+        col, u = self._invert(self.cond[row], u1)
+        theta, phi = v * np.pi, u * 2 * np.pi
+        w = np.stack([np.sin(theta) * np.cos(phi), np.sin(theta) * np.sin(phi), np.cos(theta)], 1)
+        return w @ self.M, self.c * self.tex[row, col], self._pdf(self.p_uv[row, col], w[:, 2])
+
+
 def render(sd, integrator=0, max_depth=5, spp=(1, 1), seed=0, sampler="stratified", filter_width=None, max_sample_luminance=0.0, sobol_matrices=None,
            window=None, trace=None):
     """-> film [h, w, 4] float64 {X, Y, Z, weight} of SceneData `sd` (whole image; `window` = (x0, y0, w, h): those pixels of it only -- the
@@ -294,12 +360,19 @@ def render(sd, integrator=0, max_depth=5, spp=(1, 1), seed=0, sampler="stratifie
     mat_tex = sd.mat_tex.astype(np.int64)
     have_uv = sd.tri_uv.shape[0] == T and T > 0
     tri_uv = sd.tri_uv.astype(np.float64) if have_uv else np.zeros((max(T, 1), 6))
-    is_mirror = mats[:, 0] == 1
-    kcol, le = mats[:, 1:4], mats[:, 4:7]
+    is_matte, is_glass = mats[:, 0] == 0, mats[:, 0] == 2
+    # (3.16: a glass row is (type, Kr, Kt) with the index of refraction beside it; glass does not emit)
+    kcol, le = mats[:, 1:4], np.where(is_glass[:, None], 0.0, mats[:, 4:7])
+    k_trans = mats[:, 4:7]
+    eta_of = sd.mat_eta.astype(np.float64) if len(sd.mat_eta) else np.full(len(mats), 1.5)
     # the light list (3.8): explicit lights in order, then every emissive triangle in index order
     L = []
+    sky = None
     for row in sd.lights.astype(np.float64):
-        L.append(dict(type=int(row[0]), p=row[1:4], c=row[4:7]))
+        L.append(dict(type=4 if int(row[0]) == 3 else int(row[0]), p=row[1:4], c=row[4:7]))  # (the ABI's 3 is the map; 3 below: an emissive triangle)
+        if int(row[0]) == 3:
+            assert sky is None and sd.envmap.size  # one map per scene
+            sky = _Sky(sd.envmap, sd.envmap_world_to_light, row[4:7])
     le_inf = sum((l["c"] for l in L if l["type"] == 2), np.zeros(3))
     has_inf = any(l["type"] == 2 for l in L)
     for t in range(len(P)):
@@ -378,6 +451,13 @@ def render(sd, integrator=0, max_depth=5, spp=(1, 1), seed=0, sampler="stratifie
                 Lsum[a] += np.where((emits & collect)[:, None], beta[a] * le[m], 0.0)
                 if has_inf:
                     Lsum[a] += np.where((~hit & collect)[:, None], beta[a] * le_inf, 0.0)
+                if sky is not None and (~hit).any():  # 3.17: a ray that escapes sees the map -- in full here, MIS-weighted below
+                    sky_le, sky_pdf = sky.look(d[a])
+                    Lsum[a] += np.where((~hit & collect)[:, None], beta[a] * sky_le, 0.0)
+                    if mis:
+                        with np.errstate(all="ignore"):
+                            wsky = pb_prev[a] ** 2 / (pb_prev[a] ** 2 + (sky_pdf / nL) ** 2)
+                        Lsum[a] += np.where((~hit & ~collect)[:, None], beta[a] * sky_le * wsky[:, None], 0.0)
                 if mis:  # 3.14: the BSDF-sampled half of the previous vertex's estimate, where the bounce ray lands on a light
                     with np.errstate(all="ignore"):
                         cl = (ng * wo).sum(1)
@@ -401,7 +481,7 @@ def render(sd, integrator=0, max_depth=5, spp=(1, 1), seed=0, sampler="stratifie
                     p = np.where(on_tri[:, None], p, sph[si, :3] + ((o[a] - sph[si, :3]) + d[a] * t[:, None]))
                 nf = np.where(((ng * wo).sum(1) < 0)[:, None], -ng, ng)
                 po = p + nf * 1e-4
-                matte = ~is_mirror[m]
+                matte, glass = is_matte[m], is_glass[m]
                 k = kcol[m]
                 if n_tex and (mat_tex[m] > 0).any():
                     # 3.15: a matte Kd from a checkerboard over the primitive's (u, v), point-sampled
@@ -426,10 +506,12 @@ def render(sd, integrator=0, max_depth=5, spp=(1, 1), seed=0, sampler="stratifie
                 lpend = np.zeros((len(a), 3))
                 need_shadow = np.zeros(len(a), bool)
                 sh_d, sh_t = np.zeros((len(a), 3)), np.full(len(a), np.inf)
+                # (a glass vertex makes ONE 1-D request where a matte vertex picks its light, 3.16)
+                full[a[(matte & (nL > 0)) | glass]] = True
+                xi = rng.get1(full)[a] if full.any() else np.zeros(len(a), np.float32)
                 if nL > 0:
                     full[:] = False
                     full[a[matte]] = True
-                    xi = rng.get1(full)[a]
                     l1, l2 = (v[a] for v in rng.get2(full))
                     li = np.minimum((xi * nLf).astype(np.int64), nL - 1)  # (fp32 product, truncated: the spec's pick)
                     f = k / np.pi
@@ -471,7 +553,20 @@ def render(sd, integrator=0, max_depth=5, spp=(1, 1), seed=0, sampler="stratifie
                     if mis:
                         ld_i = ld_i * (1.0 / (1.0 + nL * nL))
                     ok_t = (ty == 3) & (d2t > 0) & (cs_t > 0) & (cl_t > 0)
-                    need_shadow = matte & (ok_p | ok_d | ok_i | ok_t)
+                    # the environment map (3.17): the direction from the same pair, the shadow ray of a distant light
+                    ok_e = np.zeros(len(a), bool)
+                    if sky is not None:
+                        wi_e, le_e, pdf_e = sky.draw(l1.astype(np.float64), l2.astype(np.float64))
+                        cs_e = (wi_e * nf).sum(1)
+                        ok_e = (ty == 4) & (cs_e > 0) & (pdf_e > 0)
+                        with np.errstate(all="ignore"):
+                            ld_e = f * le_e * ((cs_e / pdf_e) * nL)[:, None]
+                            if mis:
+                                pl_e, pb_e = pdf_e / nL, cs_e / np.pi
+                                ld_e = ld_e * (pl_e ** 2 / (pl_e ** 2 + pb_e ** 2))[:, None]
+                        ld_t = np.where(ok_e[:, None], ld_e, ld_t)
+                        wi_t = np.where(ok_e[:, None], wi_e, wi_t)
+                    need_shadow = matte & (ok_p | ok_d | ok_i | ok_t | ok_e)
                     with np.errstate(all="ignore"):
                         ld = np.where(ok_p[:, None], ld_p, np.where(ok_d[:, None], ld_d, np.where(ok_i[:, None], ld_i, ld_t)))
                         sh_d = np.where(ok_p[:, None], wi_p, np.where(ok_d[:, None], lp[li], np.where(ok_i[:, None], wi_i, wi_t)))
@@ -491,6 +586,26 @@ def render(sd, integrator=0, max_depth=5, spp=(1, 1), seed=0, sampler="stratifie
                     go &= ~(matte & (z_c == 0))
                     pb_prev[a] = z_c / np.pi
                 new_beta = np.where(go[:, None], beta[a] * k, beta[a])
+                leave = po
+                if glass.any():
+                    # 3.16: the Fresnel reflectance of the interface between 1 (the side ng points to) and eta; reflection with probability F
+                    # (weight Kr), else refraction (weight Kt r^2, the ray leaves from BELOW the surface)
+                    cos_o = (ng * wo).sum(1)
+                    ci = np.minimum(np.abs(cos_o), 1.0)
+                    r = np.where(cos_o > 0, 1.0 / eta_of[m], eta_of[m])
+                    s2t = r * r * np.maximum(0.0, 1.0 - ci * ci)
+                    tir = s2t >= 1.0
+                    ct = np.sqrt(np.maximum(0.0, 1.0 - s2t))
+                    with np.errstate(all="ignore"):
+                        e = 1.0 / r
+                        rpar, rper = (e * ci - ct) / (e * ci + ct), (ci - e * ct) / (ci + e * ct)
+                        F = np.where(tir, 1.0, 0.5 * (rpar * rpar + rper * rper))
+                    refl = xi.astype(np.float64) < F
+                    wi_g = np.where(refl[:, None], -wo + nf * (2.0 * ci)[:, None], -wo * r[:, None] + nf * (r * ci - ct)[:, None])
+                    beta_g = np.where(refl[:, None], beta[a] * k, beta[a] * k_trans[m] * (r * r)[:, None])
+                    wi_next = np.where(glass[:, None], wi_g, wi_next)
+                    new_beta = np.where(glass[:, None], beta_g, new_beta)
+                    leave = np.where((glass & ~refl)[:, None], p - nf * 1e-4, po)
                 spec_next = ~matte
                 go &= ~(new_beta == 0).all(1)
                 if bounces > 3:  # Russian roulette (3.9)
@@ -515,7 +630,7 @@ def render(sd, integrator=0, max_depth=5, spp=(1, 1), seed=0, sampler="stratifie
                 if not mis:  # (with MIS the ray at the limit IS traced: the BSDF half of the last vertex's estimate)
                     go &= ~((bounces + 1 >= max_depth) & ~spec_next)
                 alive[a] = go
-                o[a], d[a] = po, wi_next
+                o[a], d[a] = leave, wi_next
                 bounces += 1
             y = 0.212671 * Lsum[:, 0] + 0.715160 * Lsum[:, 1] + 0.072169 * Lsum[:, 2]
             bad = np.isnan(Lsum).any(1) | (y < -1e-5) | np.isinf(y)

@@ -1,4 +1,4 @@
-"""Environment-map infinite lights on the GPU.  The oracle cannot render a map, so nothing here asks it: the device against
+"""Environment-map infinite lights on the GPU.  The oracle's own rendering of a map is compared bit for bit in tests/test_glass_env_parity_gpu.py; nothing here asks it: the device against
 the host bit for bit (pbrt_amd/csrc/envmap_core.hpp is one piece of arithmetic), closed forms (the camera sees the texels, a uniform map is
 the constant sky, a one-texel sun), the independent float64 program of tests/independent_envmap.py, the furnace, and the library against
 itself (runs, builders, scene file = arrays, shards, render_multi)."""
@@ -31,7 +31,7 @@ def _bits(a):
 
 def test_device_hook_equals_host_hook(gpu):
     """Sample, lookup and pdf over 2^20 inputs: the kernel that calls envmap_core.hpp on the device returns the bits the host returns --
-    the project's fp32 contract, for the one piece the oracle does not cover."""
+    the project's fp32 contract for the piece written once for host and device (the oracle's restatement of it: tests/test_oracle_glass_env.py)."""
     n = 1 << 20
     rgb, m = random_map(16, 32, 31), random_rotation(8).astype(np.float32)
     rng = np.random.default_rng(77)

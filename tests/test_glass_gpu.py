@@ -1,4 +1,4 @@
-"""The glass material on the GPU.  The oracle cannot render glass, so nothing here asks it: closed forms (the Fresnel curve,
+"""The glass material on the GPU.  The oracle's own rendering of glass is compared bit for bit in tests/test_glass_env_parity_gpu.py; nothing here asks it: closed forms (the Fresnel curve,
 index-matched glass, the furnace), the independent float64 reference of tests/independent_mc_glass.py, and the library against itself
 (scene file = arrays, builders, shards, runs)."""
 import dataclasses

@@ -559,8 +559,13 @@ def random_twin_case(seed):
     triangles and a few spheres: the twin tests every ray against every primitive) under integrator seed % 3, sampler (seed // 3) % 4 --
     stratified, the padded (0,2)-sequence, Halton, Sobol' -- and random depth, strata and seed, three in ten of the whole images under a wide box
     filter, a quarter with the luminance clamp, a third with checkerboard textures; None where the soak drew a scene too big for that"""
+    return _twin_case(seed, True)
+
+
+def _twin_case(seed, cap):
+    """random_twin_case(seed); cap=False: also for the scenes too big for the twin (the oracle has a BVH)"""
     sd, rng = random_scene(seed)
-    if sd.idx.shape[0] > 300 or sd.spheres.shape[0] > 4:
+    if cap and (sd.idx.shape[0] > 300 or sd.spheres.shape[0] > 4):
         return None
     depth, spp, rseed = int(rng.integers(0, 12)), (int(rng.integers(1, 4)), int(rng.integers(1, 4))), int(rng.integers(0, 1 << 20))
     kw = dict(integrator=(0, 1, 2)[seed % 3], max_depth=depth, spp=spp, seed=rseed, sampler=("stratified", "sobol", "halton", "sobol_nd")[(seed // 3) % 4])
@@ -616,3 +621,114 @@ def meets_random_scene_bar(twin, film, kw):
     off4, off3 = int((rel >= 1e-4).sum()), int((rel >= 1e-3).sum())
     ok = np.array_equal(twin[..., 3], film[..., 3]) and (ps >= 120.0 or (off4 <= max(0.03 * n, 2 * fp) and off3 <= max(0.01 * n, fp)))
     return bool(ok), float(ps), off4
+
+
+def random_glass_env_case(seed, cap=True):
+    """(scene, render arguments) number `seed` for glass and the environment map (3.17): random_twin_case(seed) -- None where
+    that is None -- changed by a generator of its own, np.random.default_rng(91_000 + seed), so that random_scene and random_twin_case keep
+    drawing what they draw: materials that do not emit become glass with probability 0.45 each (eta of 1, 1.33, 1.5, 2.4 or 16, random Kr and
+    Kt, one in ten with Kt = 0 or Kr = 0), and where nothing was turned the material most primitives use is, on half the seeds; two seeds in
+    three (drawn) get a type-3 light with a random map appended (H of 1, 2, 5, 8, 16; W of 1, 3, 16, 32; HDR on half; one in eight a
+    one-texel sun, one in sixteen all black; a random rotation and factor) and lose their wide filter, a combination the product refuses.
+    cap=False (the parity tests against the oracle, which has a BVH): never None."""
+    import dataclasses
+    from pbrt_amd import GLASS, LIGHT_ENVMAP
+    case = _twin_case(seed, cap)
+    if case is None:
+        return None
+    sd, kw = case
+    g = np.random.default_rng(91_000 + seed)
+    mats = sd.materials.copy()
+    n = len(mats)
+    eta = np.full(n, 1.5, np.float32)
+    emits = (mats[:, 4:7] > 0).any(1)
+    draws = [(g.random(), float(g.choice([1.0, 1.33, 1.5, 2.4, 16.0])), g.uniform(0.05, 1.0, 3), g.uniform(0.05, 1.0, 3), g.random()) for _ in range(n)]
+    used = np.bincount(np.concatenate([sd.mat_id.astype(np.int64), sd.spheres[:, 4].astype(np.int64)]), minlength=n)[:n]
+    turn = np.array([d[0] < 0.45 for d in draws]) & ~emits
+    force = g.random() < 0.5
+    if not (turn & (used > 0)).any() and force and (used * ~emits).max(initial=0) > 0:
+        turn[int(np.argmax(used * ~emits))] = True
+    for i in np.flatnonzero(turn):
+        _, e, kr, kt, z = draws[i]
+        if z < 0.05:
+            kt = np.zeros(3)
+        elif z < 0.1:
+            kr = np.zeros(3)
+        mats[i] = [GLASS, *kr, *kt]
+        eta[i] = e
+    mat_tex = np.where(turn, 0, sd.mat_tex).astype(np.uint32)
+    rep = dict(materials=mats, mat_eta=eta, mat_tex=mat_tex)
+    kw = dict(kw)
+    # (the map's draws are taken on every seed, so that a scene's glass does not depend on whether it has a map)
+    H, W = int(g.choice([1, 2, 5, 8, 16])), int(g.choice([1, 3, 16, 32]))
+    x = g.random((H, W, 3))
+    texels = 0.1 + 20.0 * x ** 4 if g.random() < 0.5 else 0.5 + x
+    kind = g.random()
+    sun_at, sun = (int(g.integers(0, H)), int(g.integers(0, W))), g.uniform(50.0, 500.0, 3)
+    if kind < 1 / 8:
+        texels = np.zeros((H, W, 3))
+        texels[sun_at] = sun
+    elif kind < 1 / 8 + 1 / 16:
+        texels = np.zeros((H, W, 3))
+    q, r = np.linalg.qr(g.normal(size=(3, 3)))
+    q = q * np.sign(np.diag(r))
+    if np.linalg.det(q) < 0:
+        q[:, 2] = -q[:, 2]
+    factor = g.uniform(0.2, 2.0, 3)
+    if g.random() < 2 / 3:
+        rep.update(lights=np.concatenate([sd.lights, np.array([[LIGHT_ENVMAP, 0, 0, 0, *factor]], np.float32)]), envmap=texels.astype(np.float32),
+                   envmap_world_to_light=q.astype(np.float32))
+        kw.pop("filter_width", None)
+    return dataclasses.replace(sd, **rep).normalized(), kw
+
+
+def case_holds_glass(sd):
+    """a primitive of the scene is glass"""
+    m = np.concatenate([sd.mat_id.astype(np.int64), sd.spheres[:, 4].astype(np.int64)])
+    return bool(len(m)) and bool((sd.materials[m, 0] == 2).any())
+
+
+def case_holds_map(sd):
+    return bool((sd.lights[:, 0] == 3).any())
+
+
+# ---- small scenes of the glass / environment-map tests (tests/test_oracle_glass_env.py on the oracle, tests/test_glass_env_parity_gpu.py on
+# the HIP path): a material table that holds a matte, a glass, a mirror and an emitter, and a closed room to put glass into ----
+M_MATTE, M_GLASS, M_MIRROR, M_LAMP = range(4)
+GRID_MATS = np.array([[0, .6, .5, .4, 0, 0, 0], [2, .9, .95, .85, .9, .8, .95], [1, .85, .85, .9, 0, 0, 0], [0, 0, 0, 0, 6, 5, 4]], np.float32)  # (type, k, le / Kt)
+
+
+def quad_corners(p0, p1, p2, p3):
+    return [p0, p1, p2, p3], [[0, 1, 2], [0, 2, 3]]
+
+
+def quad_mesh(parts):
+    """[(four corners, material)] -> P, idx, mat_id"""
+    V, I, M = [], [], []
+    for q, m in parts:
+        base = len(V)
+        v, t = quad_corners(*q)
+        V += v
+        I += [[base + a for a in tri] for tri in t]
+        M += [m, m]
+    return np.array(V, np.float32).reshape(-1, 3), np.array(I, np.uint32).reshape(-1, 3), np.array(M, np.uint16)
+
+
+def cube_faces(lo, hi, m, inward=False):
+    """the six faces of the box [lo, hi], wound so that the normals point outwards (inward=True: inwards)"""
+    (x0, y0, z0), (x1, y1, z1) = lo, hi
+    c = [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)]
+    faces = ((0, 3, 2, 1), (4, 5, 6, 7), (0, 1, 5, 4), (3, 7, 6, 2), (0, 4, 7, 3), (1, 2, 6, 5))
+    return [(tuple(c[i] for i in (f[::-1] if inward else f)), m) for f in faces]
+
+
+def glass_room_scene(extra_parts=(), spheres=(), eye=(0.0, -0.2, 0.1), look=(0.3, 1.0, 0.2), res=32, lights=None, mats=None, eta=1.5):
+    """a closed matte room [-2, 2]^3 with a ceiling emitter, the camera inside"""
+    from pbrt_amd import SceneData, look_at
+    mats = GRID_MATS if mats is None else mats
+    parts = cube_faces((-2, -2, -2), (2, 2, 2), M_MATTE, inward=True) + [(((-0.5, -0.5, 1.99), (-0.5, 0.5, 1.99), (0.5, 0.5, 1.99), (0.5, -0.5, 1.99)), M_LAMP)]
+    P, idx, mat_id = quad_mesh(parts + list(extra_parts))
+    return SceneData(P=P, idx=idx, mat_id=mat_id, materials=mats, mat_eta=np.full(len(mats), eta, np.float32),
+                     lights=np.zeros((0, 7), np.float32) if lights is None else np.array(lights, np.float32),
+                     spheres=np.array(spheres, np.float32).reshape(-1, 5), cam_to_world=look_at(eye, look, (0, 0, 1))[1], fov=70.0, xres=res,
+                     yres=res).normalized()

@@ -171,7 +171,7 @@ int orc_render(const orc_scene *s, const orc_render_desc *r, float *film_xyzw, o
 int orc_render_acc(const orc_scene *s, const orc_render_desc *r, int64_t *acc, orc_stats *st, int n_threads);
 void orc_film_from_acc(const int64_t *acc, int64_t n_px, float *film_xyzw);
 
-/* ---- the production walk of the render kernel (pbrt_amd/csrc/kernels.hip, quantised 4-wide nodes of DESIGN.md section
+/* ---- the production walk of the render kernel (pbrt_amd/csrc/kernel_walk.hpp, quantised 4-wide nodes of DESIGN.md section
  * 4) restated one ray at a time (quad_walk.cpp): checks the trees the product's builders emit without a GPU, and counts
  * node steps / triangle tests per ray.  quads: 16 words per node; root_ref: 0 = quad 0, a leaf ref for a tree that is one
  * leaf, 0xffffffff = no tree; order: leaf slot -> triangle id.  Every output may be NULL. ---- */

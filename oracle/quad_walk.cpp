@@ -1,4 +1,4 @@
-// quad_walk.cpp -- CPU restatement of the PRODUCTION walk of the render kernel (pbrt_amd/csrc/kernels.hip trav_run,
+// quad_walk.cpp -- CPU restatement of the PRODUCTION walk of the render kernel (pbrt_amd/csrc/kernel_walk.hpp trav_run,
 // production instantiation) over the quantised 4-wide nodes of DESIGN.md section 4, one ray at a time.
 //
 // TEST INFRASTRUCTURE ONLY (see pbrt_oracle.h): tests/ and tools/ use it to check, without a GPU, that a tree a product
@@ -76,7 +76,7 @@ void walk(const Tree &T, V3 o, V3 d, float tmax, bool any, Out *out) {
     const bool inside = o.x >= b[0] && o.x <= b[3] && o.y >= b[1] && o.y <= b[4] && o.z >= b[2] && o.z <= b[5];
     if (inside || box_test(b, o, inv1, tmax)) cur = (T.root_ref & kLeafRef) ? T.root_ref : 0u;
   }
-  // the kernel's stand-in for 1 / 0 (kernels.hip trav_run; pbrt_amd/csrc/host_math.hpp inv_parallel_for_extent, restated)
+  // the kernel's stand-in for 1 / 0 (kernel_walk.hpp trav_run; pbrt_amd/csrc/host_math.hpp inv_parallel_for_extent, restated)
   float big;
   {
     const float *b = T.root_box;

@@ -99,7 +99,7 @@ FilmGeom film_geom(const pbrt_hip_scene_desc &d, const pbrt_hip_render_desc &r) 
   return g;
 }
 
-// Scheduling thresholds of the traversal loop (kernels.hip trav_run).  They change only how lanes
+// Scheduling thresholds of the traversal loop (kernel_walk.hpp trav_run).  They change only how lanes
 // are interleaved, never a result; PBRT_HIP_MIN_WALKERS / PBRT_HIP_MIN_PARKED override them for
 // tuning runs.
 uint32_t tuning(const char *name, uint32_t dflt, long cap = 64) {
@@ -342,7 +342,7 @@ struct SceneInputs {
   float le_inf[3] = {0.f, 0.f, 0.f};
   bool has_inf = false;
   bool textured_tris = false;  // a triangle whose material's Kd is a texture: its corner (u, v) go up too
-  bool textured_sph = false;   // a sphere whose material's Kd is one: (u, v) from its own parametrisation (kernels.hip sphere_uv)
+  bool textured_sph = false;   // a sphere whose material's Kd is one: (u, v) from its own parametrisation (kernel_math.hpp sphere_uv)
 };
 void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
   auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
@@ -368,7 +368,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
   // light table: explicit lights, then every emissive triangle in index order
   for (uint32_t i = 0; i < d.n_lights; i++) {
     const pbrt_hip_light &l = d.lights[i];
-    // (type 3 of the boundary, the environment map, is 4 in this table: 3 is an emissive triangle here -- kernels.hip kDevLightEnv)
+    // (type 3 of the boundary, the environment map, is 4 in this table: 3 is an emissive triangle here -- kernel_path.hpp kDevLightEnv)
     in->lights.push_back(make_float4(as_f(l.type == PBRT_HIP_LIGHT_ENVMAP ? 4u : l.type), l.p[0], l.p[1], l.p[2]));
     in->lights.push_back(make_float4(0, 0, 0, 0));
     in->lights.push_back(make_float4(0, 0, 0, 0));
@@ -747,7 +747,7 @@ static int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc
   const bool table_sampler = r->sampler == PBRT_HIP_SAMPLER_SOBOL_ND || r->sampler == PBRT_HIP_SAMPLER_HALTON;
   if (table_sampler && (r->flags & (PBRT_HIP_FLAG_COUNTERS | PBRT_HIP_FLAG_WALK_COUNTERS)))
     return fail(PBRT_HIP_ERR_INVALID, "render: the counter flags are not available with the Sobol' / Halton samplers (samplers 2, 3)");
-  // the kernels pack the sample index into 20 bits and the bounce count into 10 (kernels.hip path_store): beyond that a
+  // the kernels pack the sample index into 20 bits and the bounce count into 10 (kernel_path.hpp path_store): beyond that a
   // persistent wave would never see its pixel finish
   if ((uint64_t)r->spp_x * (uint64_t)r->spp_y > PBRT_HIP_MAX_SPP)
     return fail(PBRT_HIP_ERR_LIMIT, "render: more than 2^20 samples per pixel");
@@ -823,7 +823,7 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
     L.lds_bytes = L.exact_rows * 512u;
   }
   // (the instantiations for another filter radius and for the table samplers fit the 96 VGPRs of 5 waves per SIMD like the default one)
-  L.waves_per_cu = (L.spheres || L.glass) ? std::min(kRenderWavesPerCuSpheres, L.plan.waves_per_cu) : L.plan.waves_per_cu;  // (glass: the spheres' budget, kernels.hip)
+  L.waves_per_cu = (L.spheres || L.glass) ? std::min(kRenderWavesPerCuSpheres, L.plan.waves_per_cu) : L.plan.waves_per_cu;  // (glass: the spheres' budget, kernels_x.hip)
   if (L.env) L.waves_per_cu = std::min(kRenderWavesPerCuEnv, L.plan.waves_per_cu);  // (whatever else the scene holds: render_kernel_env's own budget)
   L.chunk_shift = sample_chunk_shift(r->spp_x * r->spp_y);
   const uint32_t n_chunks = 1u << L.chunk_shift;  // K: DESIGN.md 3.1
@@ -856,7 +856,7 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
     HIP_TRY(s->d_halton.alloc(kHaltonDims * 4));
     HIP_TRY(hipMemcpy(s->d_halton.p, tab, sizeof(tab), hipMemcpyHostToDevice));
   }
-  // float4 records: 5 x 64 per one-wave workgroup (kernels.hip LaneRecords); with another box filter radius 16 x 2 x 64 more
+  // float4 records: 5 x 64 per one-wave workgroup (kernel_path.hpp LaneRecords); with another box filter radius 16 x 2 x 64 more
   // behind them (kWideSlotFloat4: a chunk's sums per footprint)
   HIP_TRY(s->d_lane_state.grow((size_t)L.n_workgroups * (L.wide ? 320 + 2048 : 320)));
   if (!L.wide) {
@@ -972,7 +972,7 @@ int pbrt_hip_render_device(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, voi
     const uint32_t spp = r->spp_x * r->spp_y;
     R.spp_mask = 0;
     while (R.spp_mask + 1u < spp) R.spp_mask = 2u * R.spp_mask + 1u;
-    // reciprocals for the kernel's two divisions by run-time values (kernels.hip pixel_xy, stratified sample): ceil(2^32 / d);
+    // reciprocals for the kernel's two divisions by run-time values (render_body.inc pixel_xy, stratified sample): ceil(2^32 / d);
     // tsup / stx is exact while tsup * stx < 2^32
     auto recip32 = [](uint32_t d) { return d <= 1u ? 0u : (uint32_t)(((1ull << 32) + d - 1u) / d); };
     R.stx_recip = recip32(sh.stx);

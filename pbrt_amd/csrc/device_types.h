@@ -54,12 +54,12 @@ constexpr uint32_t kLdsBytesPerCu = 160u * 1024u;
 #define PBRT_TRI_STRIDE 4
 #endif
 constexpr uint32_t kTriStride = PBRT_TRI_STRIDE;
-// node steps of the production walk between two scheduling checks (kernels.hip trav_run): 3 for deep trees (C3 +1 %, C2 +2 % over
+// node steps of the production walk between two scheduling checks (kernel_walk.hpp trav_run): 3 for deep trees (C3 +1 %, C2 +2 % over
 // 2); the default path takes 2 in shallow trees, whose walks are a few steps long (capi.cpp render_launch; C4: 3 would cost 5 %)
 #ifndef PBRT_STEPS_PER_CHECK
 #define PBRT_STEPS_PER_CHECK 3
 #endif
-#ifndef PBRT_RENDER_MAX_WAVES_PER_CU  // 4 SIMDs x the waves per SIMD the render kernel's register budget allows (kernels.hip)
+#ifndef PBRT_RENDER_MAX_WAVES_PER_CU  // 4 SIMDs x the waves per SIMD the render kernel's register budget allows (kernel_path.hpp)
 #define PBRT_RENDER_MAX_WAVES_PER_CU 20
 #endif
 constexpr uint32_t kRenderMaxWavesPerCu = PBRT_RENDER_MAX_WAVES_PER_CU;
@@ -141,7 +141,7 @@ struct DevScene {
   float cam_ax, cam_bx, cam_ay, cam_by;
   int32_t xres, yres;
   int32_t cx0, cy0, cx1, cy1;  // cropped pixel bounds
-  // The production walk's stand-in for 1 / 0 (a ray PARALLEL to a slab; kernels.hip trav_run): a power of two so large that every t it
+  // The production walk's stand-in for 1 / 0 (a ray PARALLEL to a slab; kernel_walk.hpp trav_run): a power of two so large that every t it
   // makes lies outside any ray interval, yet small enough that (o - origin) x it stays finite for every origin inside the root box
   // (host_math.hpp inv_parallel_for_extent).
   float inv_parallel;
@@ -153,14 +153,14 @@ struct RenderParams {
   uint32_t rank, world;
   float inv_nx, inv_ny;
   unsigned long long *counters;  // 5: camera, bounce, shadow rays, nodes visited, triangles tested
-  uint32_t min_walkers, min_parked;  // traversal scheduling thresholds (kernels.hip trav_run)
-  float4 *lane_state;                // 5 x 64 float4 per workgroup: path state parked in HBM (kernels.hip PathState)
-  float4 *wide_slots;                // wide box filter: 16 x 2 x 64 float4 per workgroup, a chunk's sums per footprint (kernels.hip)
+  uint32_t min_walkers, min_parked;  // traversal scheduling thresholds (kernel_walk.hpp trav_run)
+  float4 *lane_state;                // 5 x 64 float4 per workgroup: path state parked in HBM (kernel_path.hpp PathState)
+  float4 *wide_slots;                // wide box filter: 16 x 2 x 64 float4 per workgroup, a chunk's sums per footprint (kernel_path.hpp)
   uint32_t *stack_overflow;          // [workgroup][entry][lane]: stack entries beyond the LDS part
   uint32_t stack_overflow_entries;
   uint32_t *next_item;    // hand-out counters of the render kernel's item list, one per region, 16 words apart (zeroed before the launch)
-  uint32_t n_regions;     // contiguous parts of the list, one per XCD (kernels.hip fetch step)
-  uint32_t n_items;       // n_local_super * 4096 pixels * K chunks (kernels.hip: item = block, chunk, pixel in block)
+  uint32_t n_regions;     // contiguous parts of the list, one per XCD (render_body.inc fetch step)
+  uint32_t n_items;       // n_local_super * 4096 pixels * K chunks (render_body.inc: item = block, chunk, pixel in block)
   uint32_t chunk_shift;   // log2 K, K = sample_chunks(spp)
   uint32_t n_workgroups;  // one-wave workgroups launched: what the device holds at once, not one per tile
   float4 *partials;       // [slab position][K]: the partial film sums of the chunks (merge_kernel adds them in order)
@@ -243,6 +243,8 @@ struct RenderLaunch {
 
 // launchers (kernels.hip)
 hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t stream);
+// kernels_x.hip: the launch of render_kernel_x, the MIS / texture / glass variants (launch_render hands it over)
+hipError_t launch_render_x(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t stream);
 // kernels_env.hip: the launch of a scene with an environment map (launch_render hands it over), and envmap_core.hpp over device arrays
 // (pbrt_hip_envmap_eval_device: u12 != nullptr samples into d, else d is looked up; R's env_* fields are the map)
 hipError_t launch_render_env(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t stream);

@@ -1,9 +1,8 @@
 // envmap_core.hpp -- the arithmetic of an environment-map infinite light, written once for the device (kernels_env.hip:
 // render_kernel_env and the debug hook's kernel) and for the host (capi.cpp: pbrt_hip_envmap_eval_host, what the CPU tests run), in
 // the manner of reinsert_core.hpp and quad_encode.hpp: fp32, one fixed order of operations, built with -ffp-contract=off, and no call
-// into libm / ocml -- atan, acos, sin and cos are the Cephes single-precision polynomials kernels.hip already uses for a sphere's
-// (u, v) and for cosine sampling (the same coefficients, restated here as host + device functions: kernels.hip's own are device-only
-// and stay untouched, so that the production kernels keep their machine code), sin / cos over the full range by an octant reduction.
+// into libm / ocml -- atan, acos, sin and cos are the Cephes single-precision polynomials of cephes_poly.hpp, the ones the kernels use
+// for a sphere's (u, v) and for cosine sampling (kernel_math.hpp), sin / cos over the full range by an octant reduction.
 // The same bits on the CPU and on the GPU: tests/test_envmap_gpu.py compares the two over 2^20 inputs.
 //
 // The reference names the light and stops at todo!() before its MIPMap and Distribution2D (src/lights/infinite.rs:52-66); this is
@@ -24,9 +23,10 @@
 #pragma once
 #include <stdint.h>
 
-// (every unit of the library is compiled by hipcc as HIP, the host-only ones included: float4 and the qualifiers come from here)
+// (every unit of the library is compiled by hipcc as HIP, the host-only ones included: float4 comes from here)
 #include <hip/hip_runtime.h>
-#define ENV_HD __host__ __device__ inline __attribute__((always_inline))
+
+#include "cephes_poly.hpp"  // poly_sin .. poly_acos, PBRT_HD
 
 namespace pbrt_hip {
 namespace envmap {
@@ -34,7 +34,7 @@ namespace envmap {
 constexpr float kPi = 3.14159265358979323846f, kTwoPi = 6.28318530717958647692f, kHalfPi = 1.5707963267948966f;
 constexpr float kInvPi = 0.31830988618379067154f, kInvTwoPi = 0.15915494309189533577f;
 constexpr float kTwoPiSquared = 19.739208802178716f;  // 2 pi^2: the Jacobian of (u, v) -> direction is 2 pi^2 sin theta
-constexpr float kOneMinusEps = 0x1.fffffcp-1f;        // the samplers' largest value (kernels.hip)
+constexpr float kOneMinusEps = 0x1.fffffcp-1f;        // the samplers' largest value (kernel_math.hpp)
 
 // The texels {r, g, b, p_uv} (row-major, row 0 = theta 0), the marginal CDF over rows and the conditional CDFs of the rows, in the
 // memory of whoever runs the functions below; M = world_to_light, row-major 3 x 3.
@@ -46,51 +46,10 @@ struct Map {
   float M[9];
 };
 
-// ---- the polynomials (Cephes sinf / cosf / atanf / asinf; kernels.hip poly_sin .. poly_acos) ----
-ENV_HD float poly_sin(float x) {  // |x| <= pi / 4
-  const float z = x * x;
-  float p = -1.9515295891e-4f * z + 8.3321608736e-3f;
-  p = p * z - 1.6666654611e-1f;
-  return (p * z) * x + x;
-}
-ENV_HD float poly_cos(float x) {  // |x| <= pi / 4
-  const float z = x * x;
-  float p = 2.443315711809948e-5f * z - 1.388731625493765e-3f;
-  p = p * z + 4.166664568298827e-2f;
-  return ((p * z) * z - 0.5f * z) + 1.0f;
-}
-ENV_HD float poly_atan_pos(float x) {  // x >= 0 (+inf included): atan(x) in [0, pi / 2]
-  float y0 = 0.f;
-  if (x > 2.414213562373095f) {
-    y0 = kHalfPi;
-    x = -(1.0f / x);
-  } else if (x > 0.4142135623730950f) {
-    y0 = 0.7853981633974483f;
-    x = (x - 1.0f) / (x + 1.0f);
-  }
-  const float z = x * x;
-  float p = 8.05374449538e-2f * z - 1.38776856032e-1f;
-  p = p * z + 1.99777106478e-1f;
-  p = p * z - 3.33329491539e-1f;
-  return y0 + ((p * z) * x + x);
-}
-ENV_HD float poly_asin_small(float a) {  // |a| <= 0.5
-  const float z = a * a;
-  float p = 4.2163199048e-2f * z + 2.4181311049e-2f;
-  p = p * z + 4.5470025998e-2f;
-  p = p * z + 7.4953002686e-2f;
-  p = p * z + 1.6666752422e-1f;
-  return (p * z) * a + a;
-}
-ENV_HD float poly_acos(float x) {  // x in [-1, 1]
-  if (x < -0.5f) return kPi - 2.0f * poly_asin_small(sqrtf(0.5f * (1.0f + x)));
-  if (x > 0.5f) return 2.0f * poly_asin_small(sqrtf(0.5f * (1.0f - x)));
-  return kHalfPi - poly_asin_small(x);
-}
 // sin and cos of x in [0, 2 pi]: j = the nearest even multiple of pi / 4 (Cephes: the octant made even), y = x - j pi / 4 in three
 // steps (pi / 4 split into DP1 + DP2 + DP3, the first two with few mantissa bits: j DP1 and j DP2 are exact), then the polynomials
 // on |y| <= pi / 4 swapped and negated by the quadrant
-ENV_HD void sincos_0_2pi(float x, float *s, float *c) {
+PBRT_HD void sincos_0_2pi(float x, float *s, float *c) {
   uint32_t j = (uint32_t)(x * 1.27323954473516f);  // 4 / pi; x >= 0
   j = (j + 1u) & ~1u;
   const float jf = (float)j;
@@ -102,13 +61,13 @@ ENV_HD void sincos_0_2pi(float x, float *s, float *c) {
 }
 
 // (int)(x) clamped to [0, n - 1]; a NaN goes to 0 (a cast of one is undefined on the host and saturates on the device)
-ENV_HD uint32_t cell(float x, uint32_t n) {
+PBRT_HD uint32_t cell(float x, uint32_t n) {
   const float xp = x > 0.f ? x : 0.f;
   return xp < (float)n ? (uint32_t)xp : n - 1u;
 }
 
 // w = M d and its texel: *sin_theta for the density
-ENV_HD uint32_t lookup(const Map &m, float dx, float dy, float dz, float *sin_theta) {
+PBRT_HD uint32_t lookup(const Map &m, float dx, float dy, float dz, float *sin_theta) {
   const float wx = (m.M[0] * dx + m.M[1] * dy) + m.M[2] * dz;
   const float wy = (m.M[3] * dx + m.M[4] * dy) + m.M[5] * dz;
   const float wz = (m.M[6] * dx + m.M[7] * dy) + m.M[8] * dz;
@@ -125,10 +84,10 @@ ENV_HD uint32_t lookup(const Map &m, float dx, float dy, float dz, float *sin_th
 }
 
 // the density over solid angle of a direction whose texel has p_uv and whose polar angle has this sine
-ENV_HD float pdf_omega(float p_uv, float sin_theta) { return sin_theta == 0.f ? 0.f : p_uv / (kTwoPiSquared * sin_theta); }
+PBRT_HD float pdf_omega(float p_uv, float sin_theta) { return sin_theta == 0.f ? 0.f : p_uv / (kTwoPiSquared * sin_theta); }
 
 // pbrt-v3 FindInterval on a CDF of n + 1 entries (cdf[0] = 0, cdf[n] = 1): the largest k in [0, n - 1] with cdf[k] <= u
-ENV_HD uint32_t find_interval(const float *cdf, uint32_t n, float u) {
+PBRT_HD uint32_t find_interval(const float *cdf, uint32_t n, float u) {
   uint32_t lo = 0u, hi = n;
   while (hi - lo > 1u) {
     const uint32_t mid = (lo + hi) >> 1;
@@ -137,7 +96,7 @@ ENV_HD uint32_t find_interval(const float *cdf, uint32_t n, float u) {
   return lo;
 }
 // Distribution1D::SampleContinuous: the interval k and (k + the place inside it) / n
-ENV_HD float sample_1d(const float *cdf, uint32_t n, float u, uint32_t *k) {
+PBRT_HD float sample_1d(const float *cdf, uint32_t n, float u, uint32_t *k) {
   const uint32_t i = find_interval(cdf, n, u);
   const float c0 = cdf[i], c1 = cdf[i + 1u];
   float du = u - c0;
@@ -149,7 +108,7 @@ ENV_HD float sample_1d(const float *cdf, uint32_t n, float u, uint32_t *k) {
 
 // One light sample from (u1, u2), both in [0, 1): the direction d (world space), the texel drawn (row * W + col: radiance and p_uv
 // are read from it, no second lookup) and the sine of its polar angle for pdf_omega -- taken from w.z exactly as lookup() takes it.
-ENV_HD uint32_t sample(const Map &m, float u1, float u2, float *dx, float *dy, float *dz, float *sin_theta) {
+PBRT_HD uint32_t sample(const Map &m, float u1, float u2, float *dx, float *dy, float *dz, float *sin_theta) {
   uint32_t row, col;
   const float v = sample_1d(m.marginal, m.H, u2, &row);
   const float u = sample_1d(m.conditional + (size_t)row * (m.W + 1u), m.W, u1, &col);

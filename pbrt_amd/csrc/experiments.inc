@@ -1,5 +1,5 @@
-// experiments.inc -- measurement aids and measured-negative variants of kernels.hip, included INSIDE its anonymous
-// namespace.  Nothing here exists in the product build: every hook the kernels call expands to nothing unless the library
+// experiments.inc -- measurement aids and measured-negative variants of the kernels, included by kernel_walk.hpp INSIDE the
+// kernels' anonymous namespace.  Nothing here exists in the product build: every hook the kernels call expands to nothing unless the library
 // is built with the switch named beside it (pbrt_amd/build.py PBRT_HIP_EXTRA_FLAGS="-D..."; tools/README.md):
 //   PBRT_PHASE_PROBE     wave passes / active lanes per phase and a wave's s_memtime per section of render_kernel's loop
 //   PBRT_RAY_LOG         every ray a frame traces, in launch order, to /tmp/raylog.bin (tools/raylog_probe.py)

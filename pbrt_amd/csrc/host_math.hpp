@@ -137,7 +137,7 @@ inline void sobol_nd_matrices(uint32_t out[kSobolNdDims * 32]) {
 
 // The Halton sampler's table, four words per dimension d < 128: {base b = the d-th prime, K = the largest K with
 // b^K < 2^32 (32 for b = 2), ceil(2^32 / b), the bits of the float 1 / (float)b^K}.  The kernel's digit loop divides by b with the
-// reciprocal (kernels.hip halton_dim); the oracle divides (oracle.cpp HaltonSampler).
+// reciprocal (kernel_path.hpp halton_dim); the oracle divides (oracle.cpp HaltonSampler).
 constexpr int kHaltonDims = 128;
 // The production walk computes a quantised plane's t as fma(q, cell * inv, -(o - origin) * inv).  With inv = 1 / 0 = inf both terms are
 // infinite and every t of that axis is NaN: the slab test ignores the axis, and a ray parallel to two axes (a shadow ray towards a sun

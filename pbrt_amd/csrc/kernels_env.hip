@@ -1,8 +1,7 @@
 // kernels_env.hip -- the render kernel of scenes with an environment-map infinite light, in a translation unit of its
-// own so that it compiles BESIDE kernels.hip (pbrt_amd/build.py runs the units in parallel; kernels.hip is the longest) and so that
-// kernels.hip's instantiations keep their names and their machine code.  It includes kernels.hip for the building blocks -- the walk, the
-// samplers, the path records, render_body.inc --, all of which sit in that file's anonymous namespace; the launchers of that file are
-// compiled out here (PBRT_KERNELS_ENV_TU).
+// own so that it compiles BESIDE kernels.hip and kernels_x.hip (pbrt_amd/build.py runs the units in parallel) and so that their
+// instantiations keep their names and their machine code.  The building blocks -- the walk, the samplers, the path records -- come from
+// kernel_path.hpp, the body is render_body.inc.
 //
 //   render_kernel_env   render_body.inc with ENV = true: a ray that escapes collects the map (envmap_core.hpp lookup), the map is a light
 //                       of the one-light direct estimate (Distribution2D sampling, MIS against the cosine-sampled bounce ray).  GLS = true
@@ -12,8 +11,8 @@
 //
 // Combinations that do NOT exist (capi.cpp check_render_desc refuses them with PBRT_HIP_ERR_LIMIT): a box filter radius other than
 // 0.5 (WIDE) and the counter flags.
-#define PBRT_KERNELS_ENV_TU 1
-#include "kernels.hip"
+#include "kernel_path.hpp"
+#include "with_bools.hpp"
 
 namespace pbrt_hip {
 namespace {
@@ -49,20 +48,12 @@ __global__ void envmap_eval_kernel(const RenderParams R, int64_t n, const float 
   if (pdf) pdf[i] = envmap::pdf_omega(tx.w, st);
 }
 
-template <class F>
-hipError_t env_with_bools(F &&f) { return f(); }
-template <class F, class... Bs>
-hipError_t env_with_bools(F &&f, bool b, Bs... rest) {
-  if (b) return env_with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
-  return env_with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
-}
-
 }  // namespace
 
 hipError_t launch_render_env(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
   if (R.n_items == 0) return hipSuccess;
   if (L.wide || L.counters != kCountNone || !R.env_texels) return hipErrorInvalidValue;  // (refused with a message by capi.cpp check_render_desc)
-  return env_with_bools([&](auto SPH, auto OVF, auto MIS, auto TEX, auto SND) {
+  return with_bools([&](auto SPH, auto OVF, auto MIS, auto TEX, auto SND) {
     constexpr int STACK = OVF ? (int)kQuadLdsStackOvf : 0;
     hipLaunchKernelGGL((render_kernel_env<SPH, STACK, MIS, TEX, SND>), dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
     return hipGetLastError();

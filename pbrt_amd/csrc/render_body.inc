@@ -1,4 +1,4 @@
-// render_body.inc -- the body of render_kernel and of render_kernel_x (kernels.hip), included once in each: the two are the same
+// render_body.inc -- the body of render_kernel (kernels.hip) and of render_kernel_x (kernels_x.hip), included once in each: the two are the same
 // program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV in scope (kernels_env.hip
 // includes it a third time, for render_kernel_env, the one kernel with ENV = true).  (A shared __device__
 // function would be the tidy way to say this; the text is included instead because wrapping the body in a function -- forceinline or

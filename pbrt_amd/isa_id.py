@@ -104,6 +104,19 @@ def kernel_ids_by_symbol(lib_path, arch="gfx950"):
     return found
 
 
+def kernel_definition_counts(lib_path, arch="gfx950"):
+    """{MANGLED kernel symbol: the number of code objects that define it}.  kernel_ids_by_symbol merges the code objects (one per
+    translation unit) into one dict, so a kernel compiled into two units shows there once: here it counts 2.  Pure file parsing."""
+    blob = open(lib_path, "rb").read()
+    counts = {}
+    for elf in _code_objects(blob, arch):
+        _, secs, syms = _elf_symbols(elf)
+        kd = {n[:-3] for n, t, shndx, value, size in syms if n.endswith(".kd") and size}
+        for n in {n for n, t, shndx, value, size in syms if t == 2 and n in kd and size and shndx < len(secs)}:  # as kernel_ids_by_symbol
+            counts[n] = counts.get(n, 0) + 1
+    return counts
+
+
 def kernel_resources(lib_path, symbol, arch="gfx950"):
     """{vgpr_count, sgpr_count, agpr_count, vgpr_spill_count, private_segment_fixed_size, group_segment_fixed_size (STATIC LDS; the render
     kernels' stack is dynamic), wavefront_size, max_flat_workgroup_size} of the kernel with mangled symbol `symbol`, from the code object's

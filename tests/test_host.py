@@ -108,6 +108,17 @@ def test_kernel_isa_ids():
     assert any(k.startswith("intersect_kernel<") for k in ids) and "merge_kernel" in " ".join(ids)
 
 
+def test_every_kernel_is_defined_in_one_code_object():
+    """A kernel belongs to ONE translation unit: every kernel symbol of the library is defined in exactly one gfx950 code object.  (A unit
+    that includes another's kernels carries copies nobody launches; isa_id.kernel_ids_by_symbol merges the code objects and would hide them.)"""
+    from pbrt_amd import isa_id
+    counts = isa_id.kernel_definition_counts(_lib.LIB_PATH)
+    assert set(counts) == set(isa_id.kernel_ids_by_symbol(_lib.LIB_PATH)) and len(counts) >= 100
+    for family in ("render_kernelI", "render_kernel_xI", "render_kernel_envI", "intersect_kernelI", "merge_kernel", "pack_tris_kernel"):
+        assert any(family in n for n in counts), family
+    assert {n: c for n, c in counts.items() if c != 1} == {}
+
+
 def test_committed_profiles_price_the_built_kernel():
     """profiles/pmc_<workload>.json carry the id of the kernel their counters were taken on; bench.py withholds roofline.frac when the
     loaded library's kernel of that name has another one.  The tree as committed must not be in that state: the production instantiation

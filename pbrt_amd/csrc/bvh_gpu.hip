@@ -13,7 +13,7 @@
 // by the tie rule of DESIGN.md 3.4 a ray's hit does not depend on the shape of the tree, so a scene built here renders
 // the same film, bit for bit, as one built by the host's SAH builder (tests/test_gpu_parity.py::test_gpu_built_scene_*).
 // The canonical counters (the oracle's walk of ITS tree) of such a scene come from the oracle's tree, built on the host
-// the first time they are asked for (capi.cpp ensure_canonical).
+// the first time they are asked for (capi_scene.cpp ensure_canonical).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

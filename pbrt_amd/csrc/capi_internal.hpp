@@ -1,8 +1,10 @@
-// capi_internal.hpp -- what the translation units behind the C ABI share: error reporting, device buffers and the scene
-// object (capi.cpp owns single-GPU scenes, multi_gpu.cpp replicates them across the devices of a node).
+// capi_internal.hpp -- what the translation units behind the C ABI share: error reporting, device buffers, the scene object with the
+// table of its arrays, and the film geometry (capi_scene.cpp makes single-GPU scenes, capi_render.cpp renders them, multi_gpu.cpp
+// replicates them across the devices of a node).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <exception>
 #include <string>
 #include <utility>
 
@@ -15,6 +17,11 @@ namespace pbrt_hip {
 // sets the thread-local message behind pbrt_hip_last_error() and returns `code`
 int fail(int code, const std::string &msg);
 const char *last_error_message();
+// runs the body of an extern "C" function: an exception that reaches the boundary becomes PBRT_HIP_ERR_INTERNAL with its text
+template <class F>
+int guarded(F &&body) {
+  try { return body(); } catch (const std::exception &e) { return fail(PBRT_HIP_ERR_INTERNAL, e.what()); }
+}
 
 // A device allocation that the buffer owns: freed by its destructor, on whichever device is current then.  n and p change only
 // when hipMalloc succeeds; after a failure the buffer is empty (n == 0, p == nullptr), so a later grow() tries again.
@@ -65,6 +72,57 @@ struct SceneStream {
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
+// The device arrays that ARE a scene: what scene creation uploads and builds, what device_bytes counts and what a clone on another device
+// carries.  Per-render scratch (slab, film, lane state, partial sums, counters, stack overflow, sampler tables) is not part of it.
+struct SceneArrays {
+  DevBuf<float> d_P;  // vertices and indices of the tree's primitives: the triangles, then the spheres' proxy triangles (capi_scene.cpp SceneInputs)
+  DevBuf<uint32_t> d_idx, d_order;
+  DevBuf<uint16_t> d_mat_id;
+  DevBuf<uint4> d_nodes, d_quads;
+  DevBuf<float4> d_tris, d_mats, d_lights, d_spheres;
+  DevBuf<float> d_tri_uv_in;  // textured scenes: corner (u, v) as uploaded (triangle order) ...
+  DevBuf<float2> d_tri_uv;    // ... and in leaf-slot order (3 per slot)
+  DevBuf<float4> d_textures;
+  DevBuf<float4> d_glass;  // {Kt, eta} per material of a scene with glass; empty otherwise
+  // an environment-map infinite light: texels {r, g, b, p_uv}, the marginal and conditional CDFs (envmap.hpp EnvTables)
+  DevBuf<float4> d_env_texels;
+  DevBuf<float> d_env_marginal, d_env_conditional;
+  // the canonical walk's triangle records and leaf order of a device-built scene (ensure_canonical)
+  DevBuf<float4> d_tris_exact;
+  DevBuf<uint32_t> d_order_exact;
+
+  // THE list of the arrays: f(pointer to member, whether a clone of the scene carries the array)
+  template <class F>
+  static void for_each(F &&f) {
+    f(&SceneArrays::d_P, true); f(&SceneArrays::d_idx, true); f(&SceneArrays::d_order, true); f(&SceneArrays::d_mat_id, true);
+    f(&SceneArrays::d_nodes, true); f(&SceneArrays::d_quads, true);
+    f(&SceneArrays::d_tris, true); f(&SceneArrays::d_mats, true); f(&SceneArrays::d_lights, true); f(&SceneArrays::d_spheres, true);
+    f(&SceneArrays::d_tri_uv_in, false);  // (read by pack_uv during scene creation and by nothing after it)
+    f(&SceneArrays::d_tri_uv, true); f(&SceneArrays::d_textures, true); f(&SceneArrays::d_glass, true);
+    f(&SceneArrays::d_env_texels, true); f(&SceneArrays::d_env_marginal, true); f(&SceneArrays::d_env_conditional, true);
+    f(&SceneArrays::d_tris_exact, false); f(&SceneArrays::d_order_exact, false);  // (canonical_ready is not copied: a clone makes its own on first use)
+  }
+  // bytes on the device: pbrt_hip_scene_info's device_bytes
+  uint64_t bytes() const {
+    uint64_t total = 0;
+    for_each([&](auto m, bool) { total += (uint64_t)(this->*m).n * sizeof(*(this->*m).p); });
+    return total;
+  }
+};
+static_assert(sizeof(SceneArrays) == 19 * sizeof(DevBuf<float>), "an array of SceneArrays is missing from SceneArrays::for_each");
+
+// What a scene is beside its arrays, its host tree and its description: plain values, which a clone takes in one assignment
+struct SceneTraits {
+  uint32_t n_prims = 0;  // primitives of the tree: dev.n_tris triangles + the spheres
+  bool gpu_built = false;  // accelerator built on the device: the canonical tree (counter flags) is made on first use
+  uint32_t n_quads_gpu = 0;
+  bool textured = false;  // some primitive's material has kd_tex != 0: the TEX instantiations render the scene
+  bool glass = false;     // some material is glass: the GLS instantiations render the scene
+  bool env = false;       // an environment-map light: render_kernel_env renders the scene; the map's size, world_to_light and the light's factor
+  uint32_t env_w = 0, env_h = 0;
+  float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
+  BuildStats build;
+};
 }  // namespace pbrt_hip
 
 #define HIP_TRY(expr)                                                                                     \
@@ -74,55 +132,55 @@ struct SceneStream {
       return pbrt_hip::fail(PBRT_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
   } while (0)
 
-struct pbrt_hip_scene : pbrt_hip::SceneStream {
+// (base classes are destroyed in reverse order, after the members: every buffer is freed before the stream and the events)
+struct pbrt_hip_scene : pbrt_hip::SceneStream, pbrt_hip::SceneArrays, pbrt_hip::SceneTraits {
   int device = 0;
   uint32_t n_cu = 256;  // hipDeviceProp_t::multiProcessorCount of `device`
   pbrt_hip_scene_desc desc{};  // scalar fields only; pointers are cleared
   pbrt_hip::Bvh bvh;
   pbrt_hip::DevScene dev{};
-  // device allocations
-  pbrt_hip::DevBuf<float> d_P;
-  pbrt_hip::DevBuf<uint32_t> d_idx, d_order;
-  pbrt_hip::DevBuf<uint16_t> d_mat_id;
-  pbrt_hip::DevBuf<uint4> d_nodes, d_quads;
+  // per-render scratch
   pbrt_hip::DevBuf<uint32_t> d_stack_overflow;  // per-lane spill area of the quad walk's stack beyond its LDS part
-  pbrt_hip::DevBuf<float4> d_tris, d_mats, d_lights, d_spheres;
   pbrt_hip::DevBuf<float4> d_slab, d_film;          // scratch of pbrt_hip_render()
   pbrt_hip::DevBuf<float4> d_lane_state;            // per-lane path state records of the render kernel
   pbrt_hip::DevBuf<float4> d_partials;              // partial film sums of the work items (8 chunks per slab pixel)
   pbrt_hip::DevBuf<unsigned long long> d_counters;  // 80: see open()
+  pbrt_hip::DevBuf<uint32_t> d_sobol;  // generator matrices of sampler 2 (uploaded at its first use)
+  pbrt_hip::DevBuf<uint32_t> d_halton; // per-dimension table of sampler 3 (likewise)
   bool pending = false;
   bool pending_counters = false;
-  uint32_t n_quads_gpu = 0;
-  uint32_t n_prims = 0;  // primitives of the tree: dev.n_tris triangles + the spheres (whose places in d_P / d_idx are proxy triangles: capi.cpp)
-  bool gpu_built = false;  // accelerator built on the device: the canonical tree (counter flags) is made on first use
+  uint64_t pending_samples = 0;
   // The canonical walk's view of a device-built scene (pbrt_hip::ensure_canonical): the oracle's binary tree, built on the
   // host from the vertex / index buffers read back from the device, and triangle records in ITS leaf order.  For a
   // host-built scene the production arrays serve both walks and dev_exact == dev.
   pbrt_hip::DevScene dev_exact{};
   bool canonical_ready = false;
-  pbrt_hip::DevBuf<uint32_t> d_sobol;  // generator matrices of sampler 2 (uploaded at its first use)
-  pbrt_hip::DevBuf<uint32_t> d_halton; // per-dimension table of sampler 3 (likewise)
-  pbrt_hip::DevBuf<float> d_tri_uv_in;  // textured scenes: corner (u, v) as uploaded (triangle order) ...
-  pbrt_hip::DevBuf<float2> d_tri_uv;    // ... and in leaf-slot order (3 per slot)
-  pbrt_hip::DevBuf<float4> d_textures;
-  bool textured = false;                // some triangle's material has kd_tex != 0: the TEX instantiations render it
-  pbrt_hip::DevBuf<float4> d_glass;     // {Kt, eta} per material of a scene with glass; empty otherwise
-  bool glass = false;                   // some material is glass: the GLS instantiations render the scene
-  // an environment-map infinite light: texels {r, g, b, p_uv}, the marginal and conditional CDFs (envmap.hpp EnvTables),
-  // world_to_light and the light's factor; env: the scene has one and render_kernel_env renders it
-  pbrt_hip::DevBuf<float4> d_env_texels;
-  pbrt_hip::DevBuf<float> d_env_marginal, d_env_conditional;
-  bool env = false;
-  uint32_t env_w = 0, env_h = 0;
-  float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
-  pbrt_hip::DevBuf<float4> d_tris_exact;
-  pbrt_hip::DevBuf<uint32_t> d_order_exact;
   double canonical_build_ms = 0.0;
-  pbrt_hip::BuildStats build;
-  uint64_t pending_samples = 0;
-  uint64_t device_bytes = 0;
+  uint64_t device_bytes = 0;  // SceneArrays::bytes() when the scene was finished, and again with its canonical tree
 
   // what every scene has on `device` beside its arrays (scene_create, clone_scene): the CU count, the stream, the events, the counters
   int open(int device);
 };
+
+namespace pbrt_hip {
+// the canonical tree of a device-built scene, made on first use (capi_scene.cpp)
+int ensure_canonical(pbrt_hip_scene *s);
+// the array pointers of s->dev from the scene's buffers: the one place that sets them (scene creation, ensure_canonical, clone_scene)
+void bind_scene_arrays(pbrt_hip_scene *s);
+
+// ---- film geometry (capi_render.cpp) ----
+// Film geometry of one render: the cropped window (film.rs:92-101), the sample bounds (film.rs:166-175) and whether the
+// box filter has the default radius 0.5 -- then a sample lands in its own pixel and the two rectangles coincide -- or
+// another one (samples reach pad = ceil(radius - 0.5) pixels beyond the window, fixed-point film).
+struct FilmGeom {
+  bool wide;
+  float rx, ry;
+  int32_t pad_x, pad_y;
+  int32_t crop[4], sb[4];
+  int32_t crop_w() const { return crop[2] > crop[0] ? crop[2] - crop[0] : 0; }
+  int32_t crop_h() const { return crop[3] > crop[1] ? crop[3] - crop[1] : 0; }
+  size_t crop_px() const { return (size_t)crop_w() * (size_t)crop_h(); }
+};
+// (a filter width of 0 is the default radius 0.5, as in pbrt_hip_render_desc)
+FilmGeom film_geom(const pbrt_hip_scene_desc &d, float filter_xwidth = 0.f, float filter_ywidth = 0.f);
+}  // namespace pbrt_hip

@@ -1,0 +1,648 @@
+// capi_scene.cpp -- everything up to a finished scene behind the C ABI of include/pbrt_hip.h: checking a description, flattening it,
+// the upload, the tree (and the canonical tree a device-built scene gets on first use), the scene's getters, the host tree builders'
+// entry points and the library's error text.  capi_render.cpp uses what is made here.  (Together they replace the empty body of
+// PbrtAPI::world_end, /root/reference/src/core/api.rs:432-473.)
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <algorithm>
+#include <chrono>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/pbrt_hip.h"
+#include "bvh_build.hpp"
+#include "capi_internal.hpp"
+#include "device_types.h"
+#include "envmap.hpp"
+#include "host_math.hpp"
+#include "quad_nodes.hpp"
+
+using namespace pbrt_hip;
+
+namespace {
+
+thread_local std::string g_err;
+
+}  // namespace
+
+namespace pbrt_hip {
+int fail(int code, const std::string &msg) {
+  g_err = msg;
+  return code;
+}
+const char *last_error_message() { return g_err.c_str(); }
+}  // namespace pbrt_hip
+
+namespace {
+
+// A vertex that a triangle uses and that is NaN or infinite would send the builders' bucket index out of range:
+// such input is refused at the boundary.  Returns the first offending vertex, or -1.
+long long first_non_finite_vertex(const float *P, const uint32_t *idx, uint32_t n_tris) {
+  for (size_t i = 0; i < 3 * (size_t)n_tris; i++) {
+    const float *v = P + 3 * (size_t)idx[i];
+    if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2])) return (long long)idx[i];
+  }
+  return -1;
+}
+
+// `count` elements from `src` into `buf`, allocated anew, asynchronously on `stream` (src must live until the stream has caught up)
+template <class T>
+hipError_t upload(DevBuf<T> *buf, const T *src, size_t count, hipStream_t stream) {
+  const hipError_t e = buf->alloc(count);
+  if (e != hipSuccess || count == 0) return e;
+  return hipMemcpyAsync(buf->p, src, count * sizeof(T), hipMemcpyHostToDevice, stream);
+}
+
+// The canonical tree (the oracle's binary tree) of the n primitives P / idx: the tree itself in s->bvh, its child-pair
+// records in s->d_nodes, its leaf order in `order`, the scene's triangle records packed in that order into `tris`, and the tree's fields
+// of *D (its array pointers are the caller's).  A host-built scene's tree (build_tree) and a device-built scene's counting walk (ensure_canonical) both come from here;
+// `what` prefixes the refusals.  *host_ms (if asked for): the time of the tree and the pair records.
+int build_canonical(pbrt_hip_scene *s, const float *P, const uint32_t *idx, uint32_t n, const std::string &what, DevBuf<uint32_t> *order,
+                    DevBuf<float4> *tris, DevScene *D, double *host_ms = nullptr) {
+  const auto t0 = std::chrono::steady_clock::now();
+  build_bvh(P, idx, n, &s->bvh);
+  if (s->bvh.depth > 64) return fail(PBRT_HIP_ERR_LIMIT, what + "BVH deeper than the 64-entry traversal stack");
+  PairNodes pairs;
+  std::string why;
+  if (!make_pair_nodes(s->bvh, &pairs, &why)) return fail(PBRT_HIP_ERR_LIMIT, what + why);
+  if (host_ms) *host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  HIP_TRY(upload(&s->d_nodes, pairs.q.data(), pairs.q.size(), s->stream));
+  HIP_TRY(upload(order, s->bvh.order.data(), n, s->stream));
+  HIP_TRY(tris->alloc(kTriStride * (size_t)n));
+  HIP_TRY(launch_pack_tris(s->d_P.p, s->d_idx.p, s->d_mat_id.p, order->p, n, D->n_tris, s->d_spheres.p, tris->p, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));  // (pairs is a local)
+  D->n_nodes = (uint32_t)s->bvh.nodes.size();
+  D->root_ref = pairs.root_ref;
+  for (int k = 0; k < 3; k++) { D->root_lo[k] = pairs.root_lo[k]; D->root_hi[k] = pairs.root_hi[k]; }
+  return PBRT_HIP_OK;
+}
+
+// ---- scene creation in stages (pbrt_hip_scene_create_ex): check_scene_desc, open, gather_inputs, upload_inputs, build_tree, set_view ----
+
+// The accelerator's builder.  ONE default -- the device builder (binned SAH + parallel re-insertion + collapse), whoever asks and
+// however (pbrt_hip_scene_create, flags 0, pbrt_hip_render_multi, the command line, bench.py); the host's binned-SAH builder only on
+// request (PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE, or PBRT_HIP_BUILDER=host in the environment when the caller left the choice open).
+enum class Builder { kHost, kHostOptimized, kGpu, kGpuPlain };
+
+// a material whose Kd is a texture
+bool kd_textured(const pbrt_hip_material &m) { return m.kd_tex != 0u && m.type == 0u; }
+// the 1-based texture-table number an environment-map light carries as the bits of its `pad`
+uint32_t light_env_slot(const pbrt_hip_light &l) { uint32_t u; std::memcpy(&u, &l.pad, 4); return u; }
+// a glass material's index of refraction: the float whose bits ride in kd_tex
+float glass_eta(const pbrt_hip_material &m) { float e; std::memcpy(&e, &m.kd_tex, 4); return e; }
+// glass is an interface between index 1 and eta: eta = 1 (index-matched: nothing reflects, nothing bends) is legal; 16 is four times
+// the densest real dielectric and keeps eta^2 and 1 / eta^2 -- the radiance scale of a refraction -- far from fp32's ends
+constexpr float kGlassEtaMin = 1.0f, kGlassEtaMax = 16.0f;
+
+// Every refusal that depends on the description alone, before any HIP call, and the builder that `flags` (and PBRT_HIP_BUILDER) ask for.
+int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *builder) {
+  if (d->xres <= 0 || d->yres <= 0) return fail(PBRT_HIP_ERR_INVALID, "scene_create: resolution must be positive");
+  if (d->n_tris && (!d->P || !d->idx || !d->mat_id)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: missing mesh arrays");
+  if ((d->n_tris || d->n_spheres) && (!d->mats || d->n_mats == 0)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: no materials");
+  if (d->n_mats > 65536) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 65536 materials");
+  if (d->n_tris > (1u << 24)) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 2^24 triangles (leaf references hold a 24-bit slot)");
+  if ((uint64_t)d->n_tris + d->n_spheres > (1u << 24)) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than 2^24 primitives (triangles + spheres; leaf references hold a 24-bit slot)");
+  if (d->n_spheres && !d->spheres) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_spheres > 0 but no sphere table");
+  for (size_t i = 0; i < 3 * (size_t)d->n_tris; i++)
+    if (d->idx[i] >= d->n_verts) return fail(PBRT_HIP_ERR_INVALID, "scene_create: vertex index out of range");
+  for (uint32_t t = 0; t < d->n_tris; t++)
+    if (d->mat_id[t] >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material id out of range");
+  {
+    const long long bad = first_non_finite_vertex(d->P, d->idx, d->n_tris);
+    if (bad >= 0) return fail(PBRT_HIP_ERR_INVALID, "scene_create: vertex " + std::to_string(bad) + " is not finite");
+  }
+  for (uint32_t s = 0; s < d->n_spheres; s++) {
+    const pbrt_hip_sphere &sp = d->spheres[s];
+    if (!std::isfinite(sp.c[0]) || !std::isfinite(sp.c[1]) || !std::isfinite(sp.c[2]) || !std::isfinite(sp.r) || !(sp.r > 0.f))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere centre / radius must be finite and the radius positive");
+  }
+  // (a NaN in a light's position or in a colour travels into ray directions and throughputs: a ray that is not a number is pruned by
+  // nothing and walks the whole tree -- minutes per frame on a large scene -- before its sample is dropped as NaN)
+  if (d->n_lights && !d->lights) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_lights > 0 but no light table");
+  for (uint32_t i = 0; i < d->n_lights; i++)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(d->lights[i].p[k]) || !std::isfinite(d->lights[i].c[k]))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": position / direction / colour is not finite");
+  for (uint32_t i = 0; i < d->n_mats; i++)
+    for (int k = 0; k < 3; k++)
+      if (d->mats[i].type != PBRT_HIP_MATERIAL_GLASS && (!std::isfinite(d->mats[i].k[k]) || !std::isfinite(d->mats[i].le[k])))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": colour / emission is not finite");
+  for (uint32_t i = 0; i < d->n_mats; i++) {  // glass: k = Kr, le = Kt, kd_tex = the bits of eta
+    const pbrt_hip_material &m = d->mats[i];
+    if (m.type != PBRT_HIP_MATERIAL_GLASS) continue;
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(m.k[k]) || !std::isfinite(m.le[k]) || !(m.k[k] >= 0.f) || !(m.le[k] >= 0.f))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": glass Kr / Kt must be finite and >= 0");
+    const float eta = glass_eta(m);
+    if (!std::isfinite(eta) || !(eta >= kGlassEtaMin && eta <= kGlassEtaMax))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": glass eta (the float in kd_tex) must be finite and lie in [1, 16]");
+  }
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(d->cam_to_world[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: camera matrix is not finite");
+  if (!(d->fov > 0.f && d->fov < 180.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: fov must lie in (0, 180) degrees");
+  for (int k = 0; k < 4; k++)  // Film "cropwindow": fractions of the film (film.rs:92-101 multiplies and rounds them up: a NaN or 1e30 there is an int overflow)
+    if (!(d->crop[k] >= 0.f && d->crop[k] <= 1.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: crop window values must lie in [0, 1]");
+  for (uint32_t s = 0; s < d->n_spheres; s++)
+    if (d->spheres[s].mat >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere material id out of range");
+  if (d->n_textures && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_textures > 0 but no texture table");
+  for (uint32_t i = 0; i < d->n_mats; i++) {
+    if (d->mats[i].type == PBRT_HIP_MATERIAL_GLASS) continue;  // (kd_tex holds eta)
+    if (d->mats[i].kd_tex > d->n_textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
+    if (d->mats[i].kd_tex && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: textured material but no texture table");
+  }
+  for (uint32_t i = 0; i < d->n_mats; i++)  // (image textures for Kd do not exist: a type-1 slot is a light's map)
+    if (kd_textured(d->mats[i]) && is_envmap_slot(d->textures, d->mats[i].kd_tex - 1u))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names an environment map, which is not a texture for Kd");
+  for (uint32_t i = 0; i < d->n_textures; i++) {
+    const pbrt_hip_texture &tx = d->textures[i];
+    if (is_envmap_slot(d->textures, i)) {  // an environment map's record
+      const int rc = envmap_check(envmap_slot(d->textures, i), "scene_create: texture slot " + std::to_string(i + 1) + ": ");
+      if (rc) return rc;
+      continue;
+    }
+    if (tx.type != 0u) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown texture type");
+    if (!std::isfinite(tx.su) || !std::isfinite(tx.sv) || !std::isfinite(tx.du) || !std::isfinite(tx.dv))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture mapping is not finite");
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(tx.tex1[k]) || !std::isfinite(tx.tex2[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture colour is not finite");
+  }
+  bool textured = false;  // a triangle whose material's Kd is a texture: its corner (u, v) must be there
+  for (uint32_t t = 0; t < d->n_tris && !textured; t++) textured = kd_textured(d->mats[d->mat_id[t]]);
+  if (textured) {
+    if (!d->tri_uv) return fail(PBRT_HIP_ERR_INVALID, "scene_create: a triangle's material is textured but tri_uv is NULL");
+    for (size_t i = 0; i < 6 * (size_t)d->n_tris; i++)
+      if (!std::isfinite(d->tri_uv[i])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: tri_uv is not finite");
+  }
+  if (flags & ~(PBRT_HIP_SCENE_GPU_BUILD | PBRT_HIP_SCENE_OPTIMIZED_TREE | PBRT_HIP_SCENE_PLAIN_TREE | PBRT_HIP_SCENE_HOST_BUILD))
+    return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown flag");
+  const bool want_host = (flags & (PBRT_HIP_SCENE_HOST_BUILD | PBRT_HIP_SCENE_OPTIMIZED_TREE)) != 0u;
+  const bool want_gpu = (flags & (PBRT_HIP_SCENE_GPU_BUILD | PBRT_HIP_SCENE_PLAIN_TREE)) != 0u;
+  if (want_host && want_gpu)
+    return fail(PBRT_HIP_ERR_INVALID, "scene_create: PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE are host builds, not combined with PBRT_HIP_SCENE_GPU_BUILD / _PLAIN_TREE");
+  for (uint32_t s = 0; s < d->n_spheres; s++)  // (a finite centre and radius can still make an infinite box)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(d->spheres[s].c[k] - d->spheres[s].r) || !std::isfinite(d->spheres[s].c[k] + d->spheres[s].r))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: a sphere's bounding box is not finite");
+  for (uint32_t i = 0; i < d->n_lights; i++)
+    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+  uint32_t n_env = 0;
+  for (uint32_t i = 0; i < d->n_lights; i++) {  // an environment-map light names a type-1 slot of the texture table; one per scene
+    if (d->lights[i].type != PBRT_HIP_LIGHT_ENVMAP) continue;
+    const uint32_t t = light_env_slot(d->lights[i]);
+    if (t == 0u || t > d->n_textures || !d->textures || !is_envmap_slot(d->textures, t - 1u))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": an environment-map light (type 3) must name a type-1 slot of the texture table in `pad`");
+    if (++n_env > 1u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than one environment-map light (type 3)");
+  }
+  for (uint32_t i = 0; i < d->n_mats; i++)
+    if (d->mats[i].type > PBRT_HIP_MATERIAL_GLASS) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
+  const char *env = want_host || want_gpu ? nullptr : std::getenv("PBRT_HIP_BUILDER");
+  if (flags & PBRT_HIP_SCENE_OPTIMIZED_TREE) *builder = Builder::kHostOptimized;
+  else if ((flags & PBRT_HIP_SCENE_HOST_BUILD) || (env && std::strcmp(env, "host") == 0)) *builder = Builder::kHost;
+  else *builder = (flags & PBRT_HIP_SCENE_PLAIN_TREE) ? Builder::kGpuPlain : Builder::kGpu;  // (PBRT_HIP_SCENE_PLAIN_TREE alone qualifies the default)
+  return PBRT_HIP_OK;
+}
+
+// What a checked description puts on the device, assembled on the host.
+// Spheres are PRIMITIVES OF THE TREE (round 6; until round 5 every ray tested every sphere after the walk).  Every builder here --
+// the host's binned SAH, the device builder, the collapse, the lazily built canonical tree -- bounds a primitive by the box of its
+// three vertices, so sphere s enters the vertex / index buffers as a degenerate PROXY TRIANGLE (c - r, c + r, c - r): primitive
+// n_tris + s, bounded by exactly the sphere's box [c - r, c + r] (fp32 per component: the oracle's sphere_box), centroid its centre.
+// Its leaf record is a sphere's (pack_tris_kernel) and the leaf pass runs the sphere test on it (trav_run<..., SPH>).
+struct SceneInputs {
+  const float *P = nullptr;  // the primitives' vertices, indices and material ids: the caller's arrays, or *_aug with spheres
+  const uint32_t *idx = nullptr;
+  const uint16_t *mat = nullptr;
+  uint32_t n_verts = 0, n_prims = 0;  // primitives: the triangles + the spheres' proxies
+  std::vector<float> P_aug;
+  std::vector<uint32_t> idx_aug;
+  std::vector<uint16_t> mat_aug;
+  std::vector<float4> lights, mats, spheres, textures;  // the kernels' records: 5, 2, 2 and 3 per light / material / sphere / texture
+  std::vector<float4> glass;  // {Kt, eta} per material, when the scene has a glass one; else empty
+  // an environment-map light: its tables, world_to_light and factor
+  bool env = false;
+  EnvTables env_tables;
+  uint32_t env_w = 0, env_h = 0;
+  float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
+  float le_inf[3] = {0.f, 0.f, 0.f};
+  bool has_inf = false;
+  bool textured_tris = false;  // a triangle whose material's Kd is a texture: its corner (u, v) go up too
+  bool textured_sph = false;   // a sphere whose material's Kd is one: (u, v) from its own parametrisation (kernel_math.hpp sphere_uv)
+};
+void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
+  auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+  in->P = d.P; in->idx = d.idx; in->mat = d.mat_id;
+  in->n_verts = d.n_verts;
+  in->n_prims = d.n_tris + d.n_spheres;
+  if (d.n_spheres) {
+    in->P_aug.assign(d.P, d.P + (d.n_tris ? 3 * (size_t)d.n_verts : 0));
+    if (!d.n_tris) in->n_verts = 0;  // (a scene without triangles drops the caller's vertices)
+    in->idx_aug.assign(d.idx, d.idx + 3 * (size_t)d.n_tris);
+    in->mat_aug.assign(d.mat_id, d.mat_id + d.n_tris);
+    for (uint32_t i = 0; i < d.n_spheres; i++) {
+      const pbrt_hip_sphere &sp = d.spheres[i];
+      const uint32_t v0 = in->n_verts + 2 * i;
+      for (int k = 0; k < 3; k++) in->P_aug.push_back(sp.c[k] - sp.r);
+      for (int k = 0; k < 3; k++) in->P_aug.push_back(sp.c[k] + sp.r);
+      in->idx_aug.push_back(v0); in->idx_aug.push_back(v0 + 1); in->idx_aug.push_back(v0);
+      in->mat_aug.push_back((uint16_t)sp.mat);
+    }
+    in->n_verts += 2 * d.n_spheres;
+    in->P = in->P_aug.data(); in->idx = in->idx_aug.data(); in->mat = in->mat_aug.data();
+  }
+  // light table: explicit lights, then every emissive triangle in index order
+  for (uint32_t i = 0; i < d.n_lights; i++) {
+    const pbrt_hip_light &l = d.lights[i];
+    // (type 3 of the boundary, the environment map, is 4 in this table: 3 is an emissive triangle here -- kernel_path.hpp kDevLightEnv)
+    in->lights.push_back(make_float4(as_f(l.type == PBRT_HIP_LIGHT_ENVMAP ? 4u : l.type), l.p[0], l.p[1], l.p[2]));
+    in->lights.push_back(make_float4(0, 0, 0, 0));
+    in->lights.push_back(make_float4(0, 0, 0, 0));
+    in->lights.push_back(make_float4(l.c[0], l.c[1], l.c[2], 0));
+    in->lights.push_back(make_float4(0, 0, 0, 0));
+    if (l.type == 2) {
+      for (int k = 0; k < 3; k++) in->le_inf[k] = in->le_inf[k] + l.c[k];
+      in->has_inf = true;
+    }
+    if (l.type == PBRT_HIP_LIGHT_ENVMAP) {
+      const pbrt_hip_envmap e = envmap_slot(d.textures, light_env_slot(l) - 1u);
+      in->env = true;
+      in->env_w = e.width; in->env_h = e.height;
+      for (int k = 0; k < 9; k++) in->env_m[k] = e.world_to_light[k];
+      for (int k = 0; k < 3; k++) in->env_c[k] = l.c[k];
+      envmap_build_tables(e.rgb, e.width, e.height, &in->env_tables);
+    }
+  }
+  for (uint32_t t = 0; t < d.n_tris; t++) {
+    const pbrt_hip_material &m = d.mats[d.mat_id[t]];
+    if (m.type == PBRT_HIP_MATERIAL_GLASS) continue;  // (its le is Kt: glass does not emit)
+    if (!(m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) continue;
+    F3 p[3];
+    for (int v = 0; v < 3; v++) {
+      const float *q = d.P + 3 * (size_t)d.idx[3 * (size_t)t + v];
+      p[v] = {q[0], q[1], q[2]};
+    }
+    F3 cr = cross3(sub(p[1], p[0]), sub(p[2], p[0]));
+    float len = std::sqrt(dot3(cr, cr));
+    in->lights.push_back(make_float4(as_f(3u), p[0].x, p[0].y, p[0].z));
+    in->lights.push_back(make_float4(p[1].x, p[1].y, p[1].z, 0.5f * len));
+    in->lights.push_back(make_float4(p[2].x, p[2].y, p[2].z, 0));
+    in->lights.push_back(make_float4(m.le[0], m.le[1], m.le[2], 0));
+    in->lights.push_back(make_float4(cr.x / len, cr.y / len, cr.z / len, 0));
+  }
+  in->mats.resize(2 * (size_t)d.n_mats);
+  for (uint32_t i = 0; i < d.n_mats; i++) {
+    const pbrt_hip_material &m = d.mats[i];
+    in->mats[2 * i] = make_float4(as_f(m.type), m.k[0], m.k[1], m.k[2]);
+    in->mats[2 * i + 1] = make_float4(m.le[0], m.le[1], m.le[2], as_f(m.type == 0u ? m.kd_tex : 0u));
+    if (m.type == PBRT_HIP_MATERIAL_GLASS) {  // no emission on the device; {Kt, eta} in the table of the GLS instantiations
+      in->mats[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (in->glass.empty()) in->glass.assign(d.n_mats, make_float4(0.f, 0.f, 0.f, 1.f));
+      in->glass[i] = make_float4(m.le[0], m.le[1], m.le[2], glass_eta(m));
+    }
+  }
+  in->spheres.resize(2 * (size_t)d.n_spheres);
+  for (uint32_t i = 0; i < d.n_spheres; i++) {
+    const pbrt_hip_sphere &sp = d.spheres[i];
+    in->spheres[2 * i] = make_float4(sp.c[0], sp.c[1], sp.c[2], sp.r);
+    in->spheres[2 * i + 1] = make_float4(as_f(sp.mat), 0, 0, 0);
+    in->textured_sph = in->textured_sph || kd_textured(d.mats[sp.mat]);
+  }
+  for (uint32_t t = 0; t < d.n_tris && !in->textured_tris; t++) in->textured_tris = kd_textured(d.mats[d.mat_id[t]]);
+  if (in->textured_tris || in->textured_sph) {  // (the texture table goes up only when something is textured)
+    in->textures.resize(3 * (size_t)d.n_textures);
+    for (uint32_t i = 0; i < d.n_textures; i++) {
+      const pbrt_hip_texture &tx = d.textures[i];
+      if (is_envmap_slot(d.textures, i)) continue;  // (an environment map's slot: no material names it, its records stay zero)
+      in->textures[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
+      in->textures[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
+      in->textures[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
+    }
+  }
+}
+
+// The inputs into the scene's arrays (asynchronously: `in` outlives the stream's synchronisation) and the counts of s->dev they make
+int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const SceneInputs &in) {
+  HIP_TRY(upload(&s->d_P, in.P, 3 * (size_t)in.n_verts, s->stream));
+  HIP_TRY(upload(&s->d_idx, in.idx, 3 * (size_t)in.n_prims, s->stream));
+  HIP_TRY(upload(&s->d_mat_id, in.mat, in.n_prims, s->stream));
+  HIP_TRY(upload(&s->d_mats, in.mats.data(), in.mats.size(), s->stream));
+  HIP_TRY(upload(&s->d_lights, in.lights.data(), in.lights.size(), s->stream));
+  HIP_TRY(upload(&s->d_spheres, in.spheres.data(), in.spheres.size(), s->stream));
+  HIP_TRY(upload(&s->d_textures, in.textures.data(), in.textures.size(), s->stream));
+  HIP_TRY(upload(&s->d_glass, in.glass.data(), in.glass.size(), s->stream));
+  if (in.env) {
+    HIP_TRY(upload(&s->d_env_texels, in.env_tables.texels.data(), in.env_tables.texels.size(), s->stream));
+    HIP_TRY(upload(&s->d_env_marginal, in.env_tables.marginal.data(), in.env_tables.marginal.size(), s->stream));
+    HIP_TRY(upload(&s->d_env_conditional, in.env_tables.conditional.data(), in.env_tables.conditional.size(), s->stream));
+    s->env = true;
+    s->env_w = in.env_w; s->env_h = in.env_h;
+    for (int k = 0; k < 9; k++) s->env_m[k] = in.env_m[k];
+    for (int k = 0; k < 3; k++) s->env_c[k] = in.env_c[k];
+  }
+  if (in.textured_tris) HIP_TRY(upload(&s->d_tri_uv_in, d.tri_uv, 6 * (size_t)d.n_tris, s->stream));
+  DevScene &D = s->dev;
+  D.n_tris = d.n_tris;  // (the triangles: a hit's primitive id >= this is sphere id - n_tris)
+  D.n_spheres = d.n_spheres;
+  D.n_lights = (uint32_t)(in.lights.size() / 5);
+  D.n_lights_f = (float)D.n_lights;
+  for (int k = 0; k < 3; k++) D.le_inf[k] = in.le_inf[k];
+  D.has_inf = in.has_inf ? 1u : 0u;
+  return PBRT_HIP_OK;
+}
+
+// The tree over the uploaded primitives, on the host or on the device: d_nodes, d_quads and d_order, the triangle records packed in
+// leaf order into d_tris, s->build, and the tree's fields of s->dev (root ref and box, n_nodes, the walk's stack need).
+int build_tree(pbrt_hip_scene *s, const SceneInputs &in, Builder builder) {
+  DevScene &D = s->dev;
+  const uint32_t np = in.n_prims;
+  s->gpu_built = (builder == Builder::kGpu || builder == Builder::kGpuPlain) && np >= 2;
+  if (s->gpu_built) {  // the walk enters quad 0 through the root box; there is no canonical binary tree
+    HIP_TRY(s->d_order.alloc(np));
+    HIP_TRY(s->d_quads.alloc(4 * (size_t)np));
+    HIP_TRY(s->d_tris.alloc(kTriStride * (size_t)np));
+    GpuBuildInfo gb{};
+    HIP_TRY(gpu_build_quads(s->d_P.p, s->d_idx.p, np, s->d_order.p, s->d_quads.p, np, builder == Builder::kGpuPlain ? 0u : kGpuBuildReinsert, &gb,
+                            s->stream));
+    if (gb.stack_need + 1u > 4096u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: device-built tree too deep");
+    HIP_TRY(launch_pack_tris(s->d_P.p, s->d_idx.p, s->d_mat_id.p, s->d_order.p, np, D.n_tris, s->d_spheres.p, s->d_tris.p, s->stream));
+    s->build = {gb.build_ms, gb.reinsert_passes, gb.reinsert_moves, gb.reinsert_ms, gb.reinsert_cost_before, gb.reinsert_cost_after, gb.reinsert_undone};
+    s->n_quads_gpu = gb.n_quads;
+    D.n_nodes = 2u * np - 1u;
+    D.root_ref = 0u;
+    for (int k = 0; k < 3; k++) { D.root_lo[k] = gb.root_lo[k]; D.root_hi[k] = gb.root_hi[k]; }
+    D.quad_stack_need = gb.stack_need;
+  } else {
+    double canon_ms = 0.0;
+    const int rc = build_canonical(s, in.P, in.idx, np, "scene_create: ", &s->d_order, &s->d_tris, &D, &canon_ms);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const char *sl = debug_knob("PBRT_HIP_SPLIT_LEAVES");
+    QuadNodes quads;
+    build_production_quads(s->bvh, in.P, in.idx, np, builder == Builder::kHostOptimized ? kTreeReinsert : production_tree_default(),
+                           !(sl && sl[0] == '0'), &quads);
+    s->build.build_ms = canon_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HIP_TRY(upload(&s->d_quads, quads.q.data(), quads.q.size(), s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));  // (quads is a local)
+    D.quad_stack_need = quads.stack_need;
+  }
+  D.inv_parallel = inv_parallel_for_extent(std::max(D.root_hi[0] - D.root_lo[0], std::max(D.root_hi[1] - D.root_lo[1], D.root_hi[2] - D.root_lo[2])));
+  return PBRT_HIP_OK;
+}
+
+// The perspective camera and the crop window of `d` into D: screen window from the aspect ratio, fov on the shorter axis
+void set_view(DevScene *D, const pbrt_hip_scene_desc &d) {
+  for (int k = 0; k < 12; k++) D->c2w[k] = d.cam_to_world[k];
+  const float aspect = (float)d.xres / (float)d.yres;
+  float sx0, sx1, sy0, sy1;
+  if (aspect > 1.f) { sx0 = -aspect; sx1 = aspect; sy0 = -1.f; sy1 = 1.f; }
+  else { sx0 = -1.f; sx1 = 1.f; sy0 = -1.f / aspect; sy1 = 1.f / aspect; }
+  const float tan_half = (float)std::tan((double)d.fov * (3.14159265358979323846 / 180.0) * 0.5);
+  D->cam_ax = ((sx1 - sx0) / (float)d.xres) * tan_half;
+  D->cam_bx = sx0 * tan_half;
+  D->cam_ay = -((sy1 - sy0) / (float)d.yres) * tan_half;
+  D->cam_by = sy1 * tan_half;
+  D->xres = d.xres;
+  D->yres = d.yres;
+  int32_t cb[4];
+  film_cropped_bounds(d.xres, d.yres, d.crop, cb);
+  D->cx0 = cb[0]; D->cy0 = cb[1]; D->cx1 = cb[2]; D->cy1 = cb[3];
+}
+
+}  // namespace
+
+namespace pbrt_hip {
+void bind_scene_arrays(pbrt_hip_scene *s) {
+  DevScene &D = s->dev;
+  D.nodes = s->d_nodes.p;
+  D.quads = s->d_quads.p;
+  D.tris = s->d_tris.p;
+  D.mats = s->d_mats.p;
+  D.lights = s->d_lights.p;
+  D.spheres = s->d_spheres.p;
+}
+
+// The counter flags (PBRT_HIP_FLAG_COUNTERS, counters of pbrt_hip_intersect) count the CANONICAL walk: the oracle's binary
+// tree of DESIGN.md 3.3.  A host-built scene has it; a device-built one gets it here on first use -- vertex / index buffers
+// read back from the device, the host builder (one core, about a second for 1M triangles: a measurement aid, off the
+// product's path), child-pair records and triangle records in the canonical leaf order uploaded beside the production arrays.
+int ensure_canonical(pbrt_hip_scene *s) {
+  if (s->canonical_ready) return PBRT_HIP_OK;
+  if (!s->gpu_built) { s->dev_exact = s->dev; s->canonical_ready = true; return PBRT_HIP_OK; }
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<float> P(s->d_P.n);
+  std::vector<uint32_t> idx(s->d_idx.n);
+  HIP_TRY(hipSetDevice(s->device));
+  if (!P.empty()) HIP_TRY(hipMemcpy(P.data(), s->d_P.p, P.size() * 4, hipMemcpyDeviceToHost));
+  if (!idx.empty()) HIP_TRY(hipMemcpy(idx.data(), s->d_idx.p, idx.size() * 4, hipMemcpyDeviceToHost));
+  s->dev_exact = s->dev;
+  const int rc = build_canonical(s, P.data(), idx.data(), s->n_prims, "counters: canonical ", &s->d_order_exact, &s->d_tris_exact, &s->dev_exact);
+  if (rc) return rc;
+  bind_scene_arrays(s);  // (d_nodes: the pre-canonical allocation was empty and has just been released, no stale pointer is kept)
+  s->dev_exact.nodes = s->d_nodes.p;
+  s->dev_exact.tris = s->d_tris_exact.p;
+  s->device_bytes = s->bytes();
+  s->canonical_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  s->canonical_ready = true;
+  return PBRT_HIP_OK;
+}
+}  // namespace pbrt_hip
+
+int pbrt_hip_scene::open(int on_device) {
+  device = on_device;
+  HIP_TRY(hipSetDevice(device));
+  int cus = 0;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  n_cu = cus > 0 ? (uint32_t)cus : 1u;
+  HIP_TRY(hipStreamCreate(&stream));
+  HIP_TRY(hipEventCreate(&ev0));
+  HIP_TRY(hipEventCreate(&ev1));
+  HIP_TRY(d_counters.alloc(80));  // [0..4] ray / visit counters, [6..7] pixel-order scratch, [8..71] the pixel hand-out counters
+  return PBRT_HIP_OK;
+}
+
+extern "C" {
+
+int pbrt_hip_device_count(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+  return n;
+}
+
+const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.7 (gfx950; struct sizes of 0.6)"; }
+#ifndef PBRT_HIP_BUILD_ID
+#define PBRT_HIP_BUILD_ID "unknown"
+#endif
+const char *pbrt_hip_build_id(void) { return PBRT_HIP_BUILD_ID; }
+
+int pbrt_hip_bvh_build_host(const float *P, uint32_t n_verts, const uint32_t *idx, uint32_t n_tris, uint32_t *nodes,
+                            uint32_t *order, uint32_t *n_nodes, uint32_t *depth) {
+  return guarded([&]() -> int {
+    if ((n_tris && (!P || !idx)) || !n_nodes || !depth) return fail(PBRT_HIP_ERR_INVALID, "bvh_build_host: null argument");
+    for (size_t i = 0; i < 3 * (size_t)n_tris; i++)
+      if (idx[i] >= n_verts) return fail(PBRT_HIP_ERR_INVALID, "bvh_build_host: vertex index out of range");
+    if (first_non_finite_vertex(P, idx, n_tris) >= 0) return fail(PBRT_HIP_ERR_INVALID, "bvh_build_host: a vertex is not finite");
+    Bvh b;
+    build_bvh(P, idx, n_tris, &b);
+    *n_nodes = (uint32_t)b.nodes.size();
+    *depth = b.depth;
+    if (nodes && !b.nodes.empty()) std::memcpy(nodes, b.nodes.data(), b.nodes.size() * sizeof(BvhNode));
+    if (order && !b.order.empty()) std::memcpy(order, b.order.data(), b.order.size() * 4);
+    return PBRT_HIP_OK;
+  });
+}
+
+int pbrt_hip_quad_build_host(const float *P, uint32_t n_verts, const uint32_t *idx, uint32_t n_tris, int split_leaves,
+                             uint32_t *quads, uint32_t cap_nodes, uint32_t *n_quads, uint32_t *stack_need) {
+  return pbrt_hip_quad_build_host_ex(P, n_verts, idx, n_tris, split_leaves, PBRT_HIP_TREE_DEFAULT, quads, cap_nodes, n_quads, stack_need,
+                                     nullptr, nullptr, nullptr, nullptr);
+}
+
+int pbrt_hip_quad_build_host_ex(const float *P, uint32_t n_verts, const uint32_t *idx, uint32_t n_tris, int split_leaves, uint32_t tree,
+                                uint32_t *quads, uint32_t cap_nodes, uint32_t *n_quads, uint32_t *stack_need, uint32_t *order,
+                                float *root_box, uint32_t *n_refs, float *exact_boxes) {
+  return guarded([&]() -> int {
+    if ((n_tris && (!P || !idx)) || !n_quads || !stack_need) return fail(PBRT_HIP_ERR_INVALID, "quad_build_host: null argument");
+    if (tree != PBRT_HIP_TREE_SAH && tree != PBRT_HIP_TREE_REINSERT && tree != PBRT_HIP_TREE_DEFAULT) return fail(PBRT_HIP_ERR_INVALID, "quad_build_host: unknown tree");
+    for (size_t i = 0; i < 3 * (size_t)n_tris; i++)
+      if (idx[i] >= n_verts) return fail(PBRT_HIP_ERR_INVALID, "quad_build_host: vertex index out of range");
+    if (first_non_finite_vertex(P, idx, n_tris) >= 0) return fail(PBRT_HIP_ERR_INVALID, "quad_build_host: a vertex is not finite");
+    Bvh b;
+    build_bvh(P, idx, n_tris, &b);
+    QuadNodes q;
+    const ProductionTree pt = tree == PBRT_HIP_TREE_DEFAULT ? production_tree_default() : (ProductionTree)tree;
+    build_production_quads(b, P, idx, n_tris, pt, split_leaves != 0, &q, n_refs);
+    *n_quads = (uint32_t)(q.q.size() / 4);
+    *stack_need = q.stack_need;
+    if (order && !b.order.empty()) std::memcpy(order, b.order.data(), b.order.size() * 4);
+    if (root_box && !b.nodes.empty())
+      for (int a = 0; a < 3; a++) { root_box[a] = b.nodes[0].lo[a]; root_box[3 + a] = b.nodes[0].hi[a]; }
+    if (quads) {
+      if (*n_quads > cap_nodes) return fail(PBRT_HIP_ERR_LIMIT, "quad_build_host: output too small");
+      if (!q.q.empty()) std::memcpy(quads, q.q.data(), q.q.size() * 16);
+      if (exact_boxes && !q.exact.empty()) std::memcpy(exact_boxes, q.exact.data(), q.exact.size() * 4);
+    }
+    return PBRT_HIP_OK;
+  });
+}
+
+int pbrt_hip_scene_create(const pbrt_hip_scene_desc *d, int device, pbrt_hip_scene **out) {
+  return pbrt_hip_scene_create_ex(d, device, 0u, out);  // the default: built and optimised on the device
+}
+
+int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t flags, pbrt_hip_scene **out) {
+  if (!d || !out) return fail(PBRT_HIP_ERR_INVALID, "scene_create: null argument");
+  *out = nullptr;
+  return guarded([&]() -> int {
+    Builder builder;
+    int rc = check_scene_desc(d, flags, &builder);
+    if (rc) return rc;
+    int ndev = pbrt_hip_device_count();
+    if (ndev <= 0) return fail(PBRT_HIP_ERR_NO_DEVICE, "scene_create: no HIP device (there is no CPU fallback)");
+    if (device < 0) HIP_TRY(hipGetDevice(&device));
+    if (device >= ndev) return fail(PBRT_HIP_ERR_INVALID, "scene_create: device index out of range");
+
+    SceneInputs in;  // (declared before the scene: freed after it, on every exit)
+    std::unique_ptr<pbrt_hip_scene> s(new pbrt_hip_scene());
+    if ((rc = s->open(device))) return rc;
+    s->desc = *d;
+    s->desc.P = nullptr; s->desc.idx = nullptr; s->desc.mat_id = nullptr;
+    s->desc.mats = nullptr; s->desc.lights = nullptr; s->desc.spheres = nullptr;
+    s->desc.tri_uv = nullptr; s->desc.textures = nullptr;
+    gather_inputs(*d, &in);
+    s->n_prims = in.n_prims;
+    s->textured = in.textured_tris || in.textured_sph;
+    s->glass = !in.glass.empty();
+    if ((rc = upload_inputs(s.get(), *d, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
+    if (in.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
+      HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));
+      HIP_TRY(launch_pack_uv(s->d_tri_uv_in.p, s->d_order.p, in.n_prims, d->n_tris, s->d_tri_uv.p, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    bind_scene_arrays(s.get());
+    s->device_bytes = s->bytes();
+    set_view(&s->dev, *d);
+    *out = s.release();
+    return PBRT_HIP_OK;
+  });
+}
+
+void pbrt_hip_scene_destroy(pbrt_hip_scene *scene) {
+  if (!scene) return;
+  (void)hipSetDevice(scene->device);
+  delete scene;
+}
+
+int pbrt_hip_scene_info(const pbrt_hip_scene *s, uint32_t *n_nodes, uint32_t *depth, uint32_t *n_lights,
+                        uint64_t *device_bytes) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "scene_info: null scene");
+  if (n_nodes) *n_nodes = (uint32_t)s->bvh.nodes.size();
+  if (depth) *depth = s->bvh.depth;
+  if (n_lights) *n_lights = s->dev.n_lights;
+  if (device_bytes) *device_bytes = s->device_bytes;
+  return PBRT_HIP_OK;
+}
+
+int pbrt_hip_scene_walk_info(const pbrt_hip_scene *s, uint32_t *quad_nodes, uint32_t *stack_need) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "walk_info: null scene");
+  if (quad_nodes) *quad_nodes = s->gpu_built ? s->n_quads_gpu : (uint32_t)(s->d_quads.n / 4);
+  if (stack_need) *stack_need = s->dev.quad_stack_need;
+  return PBRT_HIP_OK;
+}
+
+int pbrt_hip_scene_build_info(const pbrt_hip_scene *s, uint32_t *gpu_built, double *build_ms) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "build_info: null scene");
+  if (gpu_built) *gpu_built = s->gpu_built ? 1u : 0u;
+  if (build_ms) *build_ms = s->build.build_ms;
+  return PBRT_HIP_OK;
+}
+
+int pbrt_hip_scene_optimize_info(const pbrt_hip_scene *s, uint32_t *passes, uint32_t *moves, double *ms) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "optimize_info: null scene");
+  if (passes) *passes = s->build.reinsert_passes;
+  if (moves) *moves = s->build.reinsert_moves;
+  if (ms) *ms = s->build.reinsert_ms;
+  return PBRT_HIP_OK;
+}
+
+int pbrt_hip_scene_optimize_cost(const pbrt_hip_scene *s, double *before, double *after, uint32_t *undone) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "optimize_cost: null scene");
+  if (before) *before = s->build.reinsert_cost_before;
+  if (after) *after = s->build.reinsert_cost_after;
+  if (undone) *undone = s->build.reinsert_undone;
+  return PBRT_HIP_OK;
+}
+
+int pbrt_hip_scene_canonical_info(const pbrt_hip_scene *s, uint32_t *ready, double *build_ms) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "canonical_info: null scene");
+  if (ready) *ready = (s->canonical_ready || !s->gpu_built) ? 1u : 0u;
+  if (build_ms) *build_ms = s->gpu_built ? s->canonical_build_ms : s->build.build_ms;
+  return PBRT_HIP_OK;
+}
+
+
+int pbrt_hip_scene_export_quads(const pbrt_hip_scene *s, uint32_t *quads, uint32_t cap_nodes, uint32_t *n_quads, uint32_t *order) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "export_quads: null scene");
+  const uint32_t n = s->gpu_built ? s->n_quads_gpu : (uint32_t)(s->d_quads.n / 4);
+  if (n_quads) *n_quads = n;
+  HIP_TRY(hipSetDevice(s->device));
+  if (quads) {
+    if (cap_nodes < n) return fail(PBRT_HIP_ERR_LIMIT, "export_quads: output too small");
+    if (n) HIP_TRY(hipMemcpy(quads, s->d_quads.p, 64 * (size_t)n, hipMemcpyDeviceToHost));
+  }
+  if (order && s->d_order.n) HIP_TRY(hipMemcpy(order, s->d_order.p, 4 * s->d_order.n, hipMemcpyDeviceToHost));
+  return PBRT_HIP_OK;
+}
+
+int pbrt_hip_scene_export_bvh(const pbrt_hip_scene *s, uint32_t *nodes, uint32_t *order) {
+  if (!s) return fail(PBRT_HIP_ERR_INVALID, "export_bvh: null scene");
+  if (nodes && !s->bvh.nodes.empty()) std::memcpy(nodes, s->bvh.nodes.data(), s->bvh.nodes.size() * sizeof(BvhNode));
+  if (order && !s->bvh.order.empty()) std::memcpy(order, s->bvh.order.data(), s->bvh.order.size() * 4);
+  return PBRT_HIP_OK;
+}
+
+}  // extern "C"

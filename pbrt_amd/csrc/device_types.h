@@ -55,7 +55,7 @@ constexpr uint32_t kLdsBytesPerCu = 160u * 1024u;
 #endif
 constexpr uint32_t kTriStride = PBRT_TRI_STRIDE;
 // node steps of the production walk between two scheduling checks (kernel_walk.hpp trav_run): 3 for deep trees (C3 +1 %, C2 +2 % over
-// 2); the default path takes 2 in shallow trees, whose walks are a few steps long (capi.cpp render_launch; C4: 3 would cost 5 %)
+// 2); the default path takes 2 in shallow trees, whose walks are a few steps long (capi_render.cpp render_launch; C4: 3 would cost 5 %)
 #ifndef PBRT_STEPS_PER_CHECK
 #define PBRT_STEPS_PER_CHECK 3
 #endif
@@ -83,7 +83,7 @@ inline uint32_t sample_chunk_shift(uint32_t spp) {  // log2 K
 }
 
 // Sampler 2: the first kSobolNdRequests requests of a sample take their own pair of Sobol' dimensions (host_math.hpp
-// builds the 2 x kSobolNdRequests generator matrices; capi.cpp asserts the two constants agree)
+// builds the 2 x kSobolNdRequests generator matrices; capi_render.cpp asserts the two constants agree)
 constexpr uint32_t kSobolNdRequests = 64u;
 
 struct RenderStackPlan {
@@ -213,7 +213,7 @@ struct RayBatch {
   uint32_t stack_overflow_entries;
 };
 
-// One launch of the render kernel, decided on the host in one place (capi.cpp render_launch) from the scene, the render description
+// One launch of the render kernel, decided on the host in one place (capi_render.cpp render_launch) from the scene, the render description
 // and the film geometry.  launch_render maps it to an instantiation and computes nothing.
 enum RenderCounters : uint32_t {
   kCountNone = 0,
@@ -221,14 +221,14 @@ enum RenderCounters : uint32_t {
   kCountWalk = 2,   // PBRT_HIP_FLAG_WALK_COUNTERS: the production walk, counting
 };
 struct RenderLaunch {
-  // the variant (capi.cpp check_render_desc says which combinations exist)
+  // the variant (capi_render.cpp check_render_desc says which combinations exist)
   bool spheres;        // SPH
   RenderCounters counters;
   bool wide;           // WIDE: a box filter radius other than 0.5
   bool table_sampler;  // SND: samplers 2 and 3 (3.12, 3.13)
   bool mis, textured;  // render_kernel_x's MIS (3.14) and TEX (3.15)
   bool glass;          // render_kernel_x's GLS (3.16): the scene has a glass material
-  bool env;            // render_kernel_env (3.17): the scene has an environment map -- never with `wide` or the counters (capi.cpp check_render_desc)
+  bool env;            // render_kernel_env (3.17): the scene has an environment map -- never with `wide` or the counters (capi_render.cpp check_render_desc)
   RenderStackPlan plan;  // the production walk's stack: LDS rows, the overflow variant, HBM entries per lane
   uint32_t steps;        // production walk: node steps per scheduling check (STEPS)
   uint32_t exact_rows;   // exact walk: STACK, its stack rows of refs (and as many of entry distances)
@@ -236,7 +236,7 @@ struct RenderLaunch {
   uint32_t waves_per_cu;  // one-wave workgroups per CU: the plan's, clamped for the spheres' register budget
   uint32_t n_workgroups;  // the grid: waves_per_cu x the device's CUs, at most one per item of the largest pass
   uint32_t chunk_shift;   // log2 K, K = the sample chunks of a pixel
-  uint32_t passes;        // launches of a frame over one partial-sums buffer (capi.cpp partials_passes) ...
+  uint32_t passes;        // launches of a frame over one partial-sums buffer (capi_render.cpp partials_passes) ...
   uint32_t pass_tiles;    // ... and the super-tiles of the largest one
   uint32_t min_walkers, min_parked;  // traversal scheduling thresholds (RenderParams)
 };

@@ -1,5 +1,5 @@
 // envmap.hpp -- the host side of an environment-map infinite light: the record's validation and the tables
-// envmap_core.hpp samples from.  capi.cpp uploads what is built here; the debug hooks of pbrt_hip_debug.h export it.
+// envmap_core.hpp samples from.  capi_scene.cpp uploads what is built here; the debug hooks of pbrt_hip_debug.h export it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // envmap_core.hpp -- the arithmetic of an environment-map infinite light, written once for the device (kernels_env.hip:
-// render_kernel_env and the debug hook's kernel) and for the host (capi.cpp: pbrt_hip_envmap_eval_host, what the CPU tests run), in
+// render_kernel_env and the debug hook's kernel) and for the host (envmap.cpp: pbrt_hip_envmap_eval_host, what the CPU tests run), in
 // the manner of reinsert_core.hpp and quad_encode.hpp: fp32, one fixed order of operations, built with -ffp-contract=off, and no call
 // into libm / ocml -- atan, acos, sin and cos are the Cephes single-precision polynomials of cephes_poly.hpp, the ones the kernels use
 // for a sphere's (u, v) and for cosine sampling (kernel_math.hpp), sin / cos over the full range by an octant reduction.

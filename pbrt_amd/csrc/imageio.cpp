@@ -606,7 +606,7 @@ bool read_png(const char *name, std::vector<float> *rgb, int *w, int *h) {
 
 }  // namespace
 
-// The message behind pbrt_hip_last_error(): capi.cpp's when this file is part of the library; the sanitizer harnesses link this file alone.
+// The message behind pbrt_hip_last_error(): capi_scene.cpp's when this file is part of the library; the sanitizer harnesses link this file alone.
 namespace pbrt_hip { int fail(int code, const std::string &msg) __attribute__((weak)); }
 static int say(int code, const std::string &msg) { return pbrt_hip::fail ? pbrt_hip::fail(code, msg) : code; }
 

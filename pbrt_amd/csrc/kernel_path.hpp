@@ -78,7 +78,7 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
 
 // ---- the environment-map infinite light (the arithmetic is envmap_core.hpp's, shared with the host).  Used by the ENV
 // instantiation alone (kernels_env.hip render_kernel_env): nothing below is reachable from render_kernel / render_kernel_x. ----
-constexpr uint32_t kDevLightEnv = 4u;  // the light table's type word of the map's light (3 is an emissive triangle there: capi.cpp gather_inputs)
+constexpr uint32_t kDevLightEnv = 4u;  // the light table's type word of the map's light (3 is an emissive triangle there: capi_scene.cpp gather_inputs)
 __device__ __forceinline__ envmap::Map env_map(const RenderParams &R) {
   envmap::Map m;
   m.texels = R.env_texels;

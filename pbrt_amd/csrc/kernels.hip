@@ -17,6 +17,7 @@
 // kernel units: kernels_x.hip (render_kernel_x, the MIS / texture / glass variants) and kernels_env.hip (render_kernel_env, scenes with
 // an environment map); launch_render below decides the family.
 #include "kernel_path.hpp"
+#include "rgb_xyz.hpp"
 #include "with_bools.hpp"
 
 namespace pbrt_hip {
@@ -123,7 +124,7 @@ __global__ void __launch_bounds__(256, (COUNT ? 1 : (SPH ? 4 : PBRT_INTERSECT_WA
 }
 
 // n_prims = n_tris + the spheres: primitive t >= n_tris is sphere t - n_tris (its place in the vertex / index buffers is taken by a
-// degenerate proxy triangle spanning its box, so that every builder bounds it: capi.cpp) and gets a sphere's record
+// degenerate proxy triangle spanning its box, so that every builder bounds it: capi_scene.cpp) and gets a sphere's record
 __global__ void pack_tris_kernel(const float *P, const uint32_t *idx, const uint16_t *mat_id, const uint32_t *order,
                                  uint32_t n_prims, uint32_t n_tris, const float4 *spheres, float4 *tris) {
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
@@ -163,7 +164,7 @@ __global__ void assemble_kernel(const float4 *slab, float4 *film, int32_t w, int
 
 // Film::merge_film_tile (core/film.rs:313-326) for one pixel of a rank's slab: contrib_sum = the K = 2^kb partial sums of
 // its chunks added in chunk order, xyz = rgb_to_xyz(contrib_sum) (spectrum.rs:139-145), weight = spp.
-// (rank, world, n_local_super) are those of the LAUNCH that wrote `partials`: a frame rendered in P passes (capi.cpp partials_passes) hands the
+// (rank, world, n_local_super) are those of the LAUNCH that wrote `partials`: a frame rendered in P passes (capi_render.cpp partials_passes) hands the
 // rank's super-tiles j = pass + P * j' to pass `pass`, which is rank + world * pass of world * P; its tile j' lands at slab tile j0 + jstride * j'.
 __global__ void merge_kernel(const float4 *partials, float4 *slab, int32_t w, int32_t h, uint32_t rank, uint32_t world,
                              uint32_t n_local_super, float weight, uint32_t kb, uint32_t j0, uint32_t jstride) {
@@ -180,9 +181,10 @@ __global__ void merge_kernel(const float4 *partials, float4 *slab, int32_t w, in
       const float4 p = partials[((size_t)i << kb) + c];
       sum = sum + mk(p.x, p.y, p.z);
     }
-    o.x = 0.412453f * sum.x + 0.357580f * sum.y + 0.180423f * sum.z;
-    o.y = 0.212671f * sum.x + 0.715160f * sum.y + 0.072169f * sum.z;
-    o.z = 0.019334f * sum.x + 0.119193f * sum.y + 0.950227f * sum.z;
+    const Xyz c = rgb_to_xyz(sum.x, sum.y, sum.z);
+    o.x = c.x;
+    o.y = c.y;
+    o.z = c.z;
     o.w = weight;
   }
   slab[((size_t)(j0 + jstride * j) << 12) + (i & 4095u)] = o;
@@ -195,9 +197,10 @@ __global__ void film_from_acc_kernel(const unsigned long long *acc, float4 *film
   const float inv = 1.0f / kFixedOne;
   const V3 sum = {(float)(long long)acc[4 * i] * inv, (float)(long long)acc[4 * i + 1] * inv, (float)(long long)acc[4 * i + 2] * inv};
   float4 o;
-  o.x = 0.412453f * sum.x + 0.357580f * sum.y + 0.180423f * sum.z;
-  o.y = 0.212671f * sum.x + 0.715160f * sum.y + 0.072169f * sum.z;
-  o.z = 0.019334f * sum.x + 0.119193f * sum.y + 0.950227f * sum.z;
+  const Xyz c = rgb_to_xyz(sum.x, sum.y, sum.z);
+  o.x = c.x;
+  o.y = c.y;
+  o.z = c.z;
   o.w = (float)(long long)acc[4 * i + 3];
   film[i] = o;
 }
@@ -221,7 +224,7 @@ hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, siz
   return hipGetLastError();
 }
 
-// RenderLaunch -> the family and the instantiation; everything else was decided by capi.cpp render_launch.  render_kernel has the default
+// RenderLaunch -> the family and the instantiation; everything else was decided by capi_render.cpp render_launch.  render_kernel has the default
 // path, and one at a time a wide filter (WIDE) or the table samplers (SND); the counting walks only on the default path.  Every other
 // combination, without counters, is render_kernel_x's (kernels_x.hip).  The production walk's STACK is the LDS rows of the overflow
 // variant, or 0 for the whole stack in LDS; the exact walk's is its stack rows.

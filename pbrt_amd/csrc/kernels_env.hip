@@ -9,7 +9,7 @@
 //                       4 waves per SIMD.
 //   envmap_eval_kernel  envmap_core.hpp over arrays: pbrt_hip_envmap_eval_device, the hook that shows the device computes the host's bits.
 //
-// Combinations that do NOT exist (capi.cpp check_render_desc refuses them with PBRT_HIP_ERR_LIMIT): a box filter radius other than
+// Combinations that do NOT exist (capi_render.cpp check_render_desc refuses them with PBRT_HIP_ERR_LIMIT): a box filter radius other than
 // 0.5 (WIDE) and the counter flags.
 #include "kernel_path.hpp"
 #include "with_bools.hpp"
@@ -18,7 +18,7 @@ namespace pbrt_hip {
 namespace {
 
 // waves per SIMD the register allocator leaves room for: the body needs 101 .. 109 VGPRs (more than the 96 of 5 waves), which
-// the 128 of 4 waves hold without a spill -- one wave per SIMD more than the GLS instantiations' budget (capi.cpp kRenderWavesPerCuEnv)
+// the 128 of 4 waves hold without a spill -- one wave per SIMD more than the GLS instantiations' budget (capi_render.cpp kRenderWavesPerCuEnv)
 #ifndef PBRT_ENV_WAVES_PER_SIMD
 #define PBRT_ENV_WAVES_PER_SIMD 4
 #endif
@@ -52,7 +52,7 @@ __global__ void envmap_eval_kernel(const RenderParams R, int64_t n, const float 
 
 hipError_t launch_render_env(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
   if (R.n_items == 0) return hipSuccess;
-  if (L.wide || L.counters != kCountNone || !R.env_texels) return hipErrorInvalidValue;  // (refused with a message by capi.cpp check_render_desc)
+  if (L.wide || L.counters != kCountNone || !R.env_texels) return hipErrorInvalidValue;  // (refused with a message by capi_render.cpp check_render_desc)
   return with_bools([&](auto SPH, auto OVF, auto MIS, auto TEX, auto SND) {
     constexpr int STACK = OVF ? (int)kQuadLdsStackOvf : 0;
     hipLaunchKernelGGL((render_kernel_env<SPH, STACK, MIS, TEX, SND>), dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);

@@ -27,7 +27,6 @@
 
 #include "../../include/pbrt_hip.h"
 #include "capi_internal.hpp"
-#include "host_math.hpp"
 
 using namespace pbrt_hip;
 
@@ -141,6 +140,13 @@ struct pbrt_hip_multi {
 
 namespace {
 
+template <class T>
+int clone_array(DevBuf<T> *to, int device, const DevBuf<T> &from, int from_device, hipStream_t stream) {
+  HIP_TRY(to->alloc(from.n));
+  if (from.n) HIP_TRY(hipMemcpyPeerAsync(to->p, device, from.p, from_device, from.n * sizeof(T), stream));
+  return PBRT_HIP_OK;
+}
+
 // a copy of `src` (any device) on `device`: every array of the scene travels device to device
 int clone_scene(const pbrt_hip_scene *src, int device, pbrt_hip_scene **out) {
   std::unique_ptr<pbrt_hip_scene> s(new pbrt_hip_scene());
@@ -148,38 +154,19 @@ int clone_scene(const pbrt_hip_scene *src, int device, pbrt_hip_scene **out) {
   if (rc) return rc;
   s->desc = src->desc;
   s->bvh.depth = src->bvh.depth;  // (the host copy of the tree stays with the original: export / info use that one)
-  s->gpu_built = src->gpu_built;
-  s->n_quads_gpu = src->n_quads_gpu;
-  s->n_prims = src->n_prims;
-  s->build = src->build;
-  s->device_bytes = src->device_bytes;
+  static_cast<SceneTraits &>(*s) = *src;
   int can = 0;
   if (hipDeviceCanAccessPeer(&can, device, src->device) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(src->device, 0);  // (already enabled is fine)
   (void)hipGetLastError();
-#define CLONE(field)                                                                                                      \
-  do {                                                                                                                    \
-    HIP_TRY(s->field.alloc(src->field.n));                                                                                \
-    if (src->field.n)                                                                                                     \
-      HIP_TRY(hipMemcpyPeerAsync(s->field.p, device, src->field.p, src->device, src->field.n * sizeof(*src->field.p), s->stream)); \
-  } while (0)
-  CLONE(d_P); CLONE(d_idx); CLONE(d_order); CLONE(d_mat_id); CLONE(d_nodes); CLONE(d_quads);
-  CLONE(d_tris); CLONE(d_mats); CLONE(d_lights); CLONE(d_spheres); CLONE(d_tri_uv); CLONE(d_textures); CLONE(d_glass);
-  CLONE(d_env_texels); CLONE(d_env_marginal); CLONE(d_env_conditional);
-#undef CLONE
+  int arc = PBRT_HIP_OK;  // every array of the table that a clone carries (capi_internal.hpp SceneArrays says which and why)
+  SceneArrays::for_each([&](auto m, bool cloned) {
+    if (cloned && !arc) arc = clone_array(&((*s).*m), device, (*src).*m, src->device, s->stream);
+  });
+  if (arc) return arc;
   HIP_TRY(hipStreamSynchronize(s->stream));
   s->dev = src->dev;
-  s->dev.nodes = s->d_nodes.p;
-  s->dev.quads = s->d_quads.p;
-  s->dev.tris = s->d_tris.p;
-  s->dev.mats = s->d_mats.p;
-  s->dev.lights = s->d_lights.p;
-  s->dev.spheres = s->d_spheres.p;
-  s->textured = src->textured;
-  s->glass = src->glass;
-  s->env = src->env;
-  s->env_w = src->env_w; s->env_h = src->env_h;
-  for (int k = 0; k < 9; k++) s->env_m[k] = src->env_m[k];
-  for (int k = 0; k < 3; k++) s->env_c[k] = src->env_c[k];
+  bind_scene_arrays(s.get());
+  s->device_bytes = s->bytes();
   *out = s.release();
   return PBRT_HIP_OK;
 }
@@ -188,9 +175,8 @@ int multi_create(const pbrt_hip_scene_desc *d, int n_gpus, uint32_t flags, pbrt_
   const int ndev = pbrt_hip_device_count();
   if (ndev <= 0) return fail(PBRT_HIP_ERR_NO_DEVICE, "multi_create: no HIP device (there is no CPU fallback)");
   if (d->xres <= 0 || d->yres <= 0) return fail(PBRT_HIP_ERR_INVALID, "multi_create: resolution must be positive");
-  int32_t b[4];
-  film_cropped_bounds(d->xres, d->yres, d->crop, b);
-  const int32_t w = b[2] > b[0] ? b[2] - b[0] : 0, h = b[3] > b[1] ? b[3] - b[1] : 0;
+  const FilmGeom fg = film_geom(*d);
+  const int32_t w = fg.crop_w(), h = fg.crop_h();
   if (n_gpus <= 0) {
     // all visible devices -- but no more than there are 64x64 super-tiles to deal out (a 64x64 film on eight GPUs would
     // replicate the scene seven times for ranks that own nothing)
@@ -221,7 +207,7 @@ int multi_create(const pbrt_hip_scene_desc *d, int n_gpus, uint32_t flags, pbrt_
   }
   m->w = w;
   m->h = h;
-  m->n_px = (size_t)w * (size_t)h;
+  m->n_px = fg.crop_px();
   m->max_slab = shard_pixels(d->xres, d->yres, d->crop, 0, (uint32_t)n_gpus);  // rank 0 owns the most super-tiles
   if (m->loopback) m->done.assign(n_gpus, nullptr);
   for (int g = 0; g < n_gpus; g++) {
@@ -262,8 +248,7 @@ int ensure_buffers(pbrt_hip_multi *m, size_t count, bool gather) {
 int multi_render(pbrt_hip_multi *m, const pbrt_hip_render_desc *r, float *film, pbrt_hip_stats *per_gpu) {
   if (m->broken) return fail(PBRT_HIP_ERR_INTERNAL, "multi_render: an earlier collective failed and the communicators were aborted; create a new handle");
   const int n = m->n;
-  const float fx = r->filter_xwidth == 0.f ? 0.5f : r->filter_xwidth, fy = r->filter_ywidth == 0.f ? 0.5f : r->filter_ywidth;
-  const bool wide = fx != 0.5f || fy != 0.5f;  // accumulators of the whole window, summed instead of gathered
+  const bool wide = film_geom(m->scenes[0]->desc, r->filter_xwidth, r->filter_ywidth).wide;  // accumulators of the whole window, summed instead of gathered
   const size_t per_gpu_f4 = wide ? 2 * m->n_px : m->max_slab;
   int code = ensure_buffers(m, per_gpu_f4, !wide);
   if (code) return code;
@@ -361,12 +346,10 @@ extern "C" {
 int pbrt_hip_multi_create(const pbrt_hip_scene_desc *d, int n_gpus, uint32_t flags, pbrt_hip_multi **out) {
   if (!d || !out) return fail(PBRT_HIP_ERR_INVALID, "multi_create: null argument");
   *out = nullptr;
-  try {
+  return guarded([&]() -> int {
     DeviceRestore keep;
     return multi_create(d, n_gpus, flags, out);
-  } catch (const std::exception &e) {
-    return fail(PBRT_HIP_ERR_INTERNAL, e.what());
-  }
+  });
 }
 
 int pbrt_hip_multi_gpus(const pbrt_hip_multi *m) { return m ? m->n : 0; }
@@ -384,12 +367,10 @@ void pbrt_hip_multi_destroy(pbrt_hip_multi *m) { delete m; }
 
 int pbrt_hip_multi_render(pbrt_hip_multi *m, const pbrt_hip_render_desc *r, float *film, pbrt_hip_stats *per_gpu) {
   if (!m || !r) return fail(PBRT_HIP_ERR_INVALID, "multi_render: null argument");
-  try {
+  return guarded([&]() -> int {
     DeviceRestore keep;
     return multi_render(m, r, film, per_gpu);
-  } catch (const std::exception &e) {
-    return fail(PBRT_HIP_ERR_INTERNAL, e.what());
-  }
+  });
 }
 
 int pbrt_hip_multi_film_device(pbrt_hip_multi *m, void **d_film) {

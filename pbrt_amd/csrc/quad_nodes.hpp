@@ -1,6 +1,6 @@
 // quad_nodes.hpp -- the node arrays the kernels read, made on the host from a built binary tree: the child-pair records of the
 // canonical walk and the 4-wide quantised nodes of the production walk (the record and the collapse's rules:
-// quad_encode.hpp, shared with the device builder).  No HIP runtime call: the C boundary (capi.cpp) uploads what comes out.
+// quad_encode.hpp, shared with the device builder).  No HIP runtime call: the C boundary (capi_scene.cpp) uploads what comes out.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -4,7 +4,7 @@
 // function would be the tidy way to say this; the text is included instead because wrapping the body in a function -- forceinline or
 // not -- perturbs the register allocation of the production instantiation, whose machine code the committed counter profiles are
 // keyed by: pbrt_amd/isa_id.py; measured in round 5.)  In scope as well: `S` (DevScene) and `R` (RenderParams), the kernel's arguments.
-  // the walk's stack, rows of 64 lanes x 4 bytes as dynamic shared memory: the launch sizes it per scene (capi.cpp render_launch;
+  // the walk's stack, rows of 64 lanes x 4 bytes as dynamic shared memory: the launch sizes it per scene (capi_render.cpp render_launch;
   // exact walk: STACK rows of refs followed by STACK rows of entry distances)
   extern __shared__ uint32_t lds_stack[];
   const uint32_t lane = threadIdx.x;

@@ -8,7 +8,7 @@ tools/soak.sh).  The library has no hook that names the kernel a render launched
 same scene with its glass turned into mirrors, or its map into the constant sky of the map's mean, gives ANOTHER film -- the glass / map code
 ran and is seen --, for every render of the grid: each sampler, the wide filter's accumulators and the clamped film.  (The scene without
 primitives cannot show glass, whatever is rendered: no ray meets a surface.  There the scene's glass flag alone selects the instantiation,
-capi.cpp render_launch, the comparison with the oracle says that the `GLS` kernel leaves an empty scene alone, and only the map's negative
+capi_render.cpp render_launch, the comparison with the oracle says that the `GLS` kernel leaves an empty scene alone, and only the map's negative
 control applies.)"""
 import dataclasses
 import os
@@ -313,6 +313,42 @@ def test_crop_window_and_shards(gpu, oracle):
     with gpu.Scene(gl) as sc:
         parts = sum(sc.render_acc(WIDE, rank=r, world_size=3, **kw)[0] for r in range(3))
     assert np.array_equal(parts, oracle.OracleScene(gl).render_acc(WIDE, **kw)[0])
+
+
+def _clone_scene(with_map):
+    """the room of util.glass_room_scene without the wall the camera faces, on a 192 x 64 film -- three 64 x 64 super-tiles in one row, the
+    smallest film on which each of 3 ranks owns a tile and renders it from its own clone --: checkered walls with their corner (u, v), a
+    checkered sphere, a glass cube, a mirror sphere and, with_map, the 8 x 16 random map as the light seen through the opening"""
+    sd = _room(extra_parts=_cube((-0.9, 0.6, -0.9), (-0.1, 1.3, 0.2), M_GLASS), spheres=[[0.7, 1.1, -0.3, 0.45, M_MATTE], [0.1, 1.6, 0.9, 0.4, M_MIRROR]])
+    keep = np.r_[0:6, 8:len(sd.idx)]  # (util.cube_faces: triangles 6 and 7 are the wall y = 2)
+    quad_uv = np.array([[0, 0, 1, 0, 1, 1], [0, 0, 1, 1, 0, 1]], np.float32)  # (as util.checker_plane_scene)
+    sd = dataclasses.replace(sd, idx=sd.idx[keep], mat_id=sd.mat_id[keep], xres=192, yres=64, mat_tex=np.array([1, 0, 0, 0], np.uint32),
+                             textures=np.array([[0, .1, .2, .3, .8, .7, .6, 5.0, 3.0, 0.25, -0.5]], np.float32), tri_uv=np.tile(quad_uv, (len(keep) // 2, 1)))
+    return _with_map(sd) if with_map else sd.normalized()
+
+
+def test_clones_carry_every_scene_array(gpu, oracle, monkeypatch):
+    """pbrt_hip_render_multi with three ranks on this GPU (PBRT_HIP_MULTI_LOOPBACK): ranks 1 and 2 render from CLONES of the scene, so their
+    tiles show whether a clone carries the corner (u, v), the texture table, the glass table and the map's tables.  With the map under the
+    default filter (the slabs are gathered); without it under the wide box filter and Halton (the ranks' accumulators are added).  The film
+    depends on those arrays: the scene without its textures, and with its glass as mirrors, is another film."""
+    for with_map in (True, False):
+        sd = _clone_scene(with_map)
+        kw = dict(integrator=INTEGRATOR_PATH_MIS, max_depth=5, spp=(2, 2), seed=11)
+        if not with_map:
+            kw.update(sampler="halton", filter_width=WIDE)
+        ref = oracle.OracleScene(sd).render(**kw)[0]
+        with gpu.Scene(sd) as sc:
+            film = sc.render(**kw)[0]
+        assert_bit_equal(film, ref, f"one scene against the oracle {kw}")
+        for what, other in (("without its textures", dataclasses.replace(sd, mat_tex=np.zeros(4, np.uint32)).normalized()), ("with its glass as mirrors", _glass_as_mirror(sd))):
+            with gpu.Scene(other) as sc:
+                assert not np.array_equal(sc.render(**kw)[0], film), f"the scene {what} gives the same film {kw}"
+        with monkeypatch.context() as mp:
+            mp.setenv("PBRT_HIP_MULTI_LOOPBACK", "1")
+            three, _ = gpu.render_multi(sd, 3, **kw)
+        assert_bit_equal(three, film, f"three ranks, two of them on clones {kw}")
+        assert_bit_equal(three, ref, f"three ranks against the oracle {kw}")
 
 
 # ---- random scenes ----

@@ -350,7 +350,7 @@ def test_item_handout_is_scheduling_only(gpu, oracle, monkeypatch):
 
 
 def test_partial_sum_cap_renders_in_passes(gpu, oracle, monkeypatch):
-    """The partial film sums (16 K bytes per pixel) are capped (2 GiB; capi.cpp partials_passes): a frame beyond the cap renders in P
+    """The partial film sums (16 K bytes per pixel) are capped (2 GiB; capi_render.cpp partials_passes): a frame beyond the cap renders in P
     passes over one buffer, pass p taking the rank's super-tiles p, p + P, ... as rank `rank + world * p` of `world * P`.  With the cap
     turned down to one, two and five super-tiles per pass (12, 6 and 3 passes over this film's 4 x 3 super-tiles), alone and as one of
     three ranks: the one-pass film and the oracle's, bit for bit, and the canonical counters summed over the passes."""
@@ -1292,7 +1292,7 @@ def test_c4_window_at_full_spp(gpu, oracle, builder):
 
 def test_c4_frame_beyond_the_scratch_cap(gpu, oracle, monkeypatch):
     """C4's film at full size (4096 x 4096) with 32 x 16 = 512 spp: 16 chunks per pixel = 4.3 GB of partial sums, over the 2 GiB cap, so
-    the frame renders in two passes (capi.cpp partials_passes) -- the default behaviour, no knob.  The same frame with the cap lifted (one
+    the frame renders in two passes (capi_render.cpp partials_passes) -- the default behaviour, no knob.  The same frame with the cap lifted (one
     pass, the round-4 code path) is the same film bit for bit, and an 8 x 8 window of it is the oracle's."""
     sd = scenes.cornell_scene(4096, 4096)
     kw = dict(max_depth=16, spp=(32, 16), seed=0)

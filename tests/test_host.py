@@ -582,7 +582,7 @@ def test_production_kernels_do_not_spill():
     assert len(prod) >= 4, demangled
     for d, (_, vgpr, spill, scratch) in prod:
         assert spill == 0 and scratch == 0, f"{d}: {vgpr} VGPRs, {spill} spilled, {scratch} B scratch"
-        # the triangle-scene render kernels are launched at 5 waves per SIMD (capi.cpp: 20 one-wave workgroups per CU)
+        # the triangle-scene render kernels are launched at 5 waves per SIMD (capi_render.cpp: 20 one-wave workgroups per CU)
         # (also the instantiations for a box filter radius other than 0.5 and for the Sobol' sampler: the last two arguments)
         if re.search(r"render_kernel<false, false, false, \d+, \d+, (true|false), (true|false)>", d):
             assert vgpr <= 96, f"{d}: {vgpr} VGPRs do not fit 5 waves per SIMD"

@@ -90,7 +90,7 @@ SMALL_SCENES = {
 
 def with_sphere_proxies(sd):
     """(P, idx) with every sphere appended as the degenerate proxy triangle (c - r, c + r, c - r) the library's builders bound it by
-    (capi.cpp, round 6): primitive n_tris + s, whose box is the sphere's box [c - r, c + r] in fp32 -- the oracle's sphere_box."""
+    (capi_scene.cpp, round 6): primitive n_tris + s, whose box is the sphere's box [c - r, c + r] in fp32 -- the oracle's sphere_box."""
     sph = np.asarray(sd.spheres, np.float32).reshape(-1, 5)
     if len(sph) == 0:
         return sd.P, sd.idx

@@ -78,6 +78,31 @@ int pbrt_hip_envmap_eval_host(const float *rgb, uint32_t width, uint32_t height,
  * PBRT_HIP_ERR_INVALID for a scene without an environment map. */
 int pbrt_hip_envmap_eval_device(pbrt_hip_scene *scene, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf);
 
+/* ---- the kernels' building blocks (pbrt_amd/csrc/cephes_poly.hpp, kernel_math.hpp, envmap_core.hpp) ---- */
+/* The production functions over arrays on `device`, one element per thread of a tiny kernel that calls the headers the render kernels
+ * are built from (pbrt_amd/csrc/kernels_blocks.hip): what lets tests compare each of them with float64 and with the oracle's
+ * restatement, element by element.  in / out are HOST arrays of n elements; the hook copies them in and out on the device's default
+ * stream.  Floats per element, in -> out:
+ *   SIN, COS, ATAN_POS, ACOS   x -> poly_sin / poly_cos / poly_atan_pos / poly_acos
+ *   SINCOS                     x -> s, c of envmap::sincos_0_2pi
+ *   SPHERE_UV                  nx ny nz -> u, v
+ *   FRESNEL                    ci, r = eta_i / eta_t -> F, ct
+ *   COSINE_ABOUT               n (3), u1, u2 -> wi (3), z
+ *   SPHERE_HIT                 {centre, radius} (4), o (3), d (3), tmax -> hit (0 or 1), t (0 on a miss): sphere_hit alone, before the
+ *                              own-box rule the walk applies to what it returns
+ * PBRT_HIP_ERR_INVALID for an unknown op, a negative n or a null array. */
+#define PBRT_HIP_BLOCK_SIN 0u
+#define PBRT_HIP_BLOCK_COS 1u
+#define PBRT_HIP_BLOCK_ATAN_POS 2u
+#define PBRT_HIP_BLOCK_ACOS 3u
+#define PBRT_HIP_BLOCK_SINCOS 4u
+#define PBRT_HIP_BLOCK_SPHERE_UV 5u
+#define PBRT_HIP_BLOCK_FRESNEL 6u
+#define PBRT_HIP_BLOCK_COSINE_ABOUT 7u
+#define PBRT_HIP_BLOCK_SPHERE_HIT 8u
+#define PBRT_HIP_BLOCK_COUNT 9u
+int pbrt_hip_blocks_eval_device(int device, uint32_t op, int64_t n, const float *in, float *out);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

@@ -121,6 +121,8 @@ def lib(native=False):
         l.orc_envmap_tables.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         l.orc_envmap_eval.restype = C.c_int
         l.orc_envmap_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int64] + [C.c_void_p] * 5
+        l.orc_blocks_eval.restype = C.c_int
+        l.orc_blocks_eval.argtypes = [C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
         l.orc_quad_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
         _libs[native] = l
     return _libs[native]
@@ -435,6 +437,21 @@ def envmap_eval(rgb, world_to_light=None, u12=None, d=None):
     if lib().orc_envmap_eval(_p(rgb), w, h, _p(m), n, _p(u12) if u12 is not None else None, _p(d), _p(texel), _p(le), _p(pdf)) != 0:
         raise ValueError("orc_envmap_eval: bad argument")
     return d, texel, le, pdf
+
+
+# op codes of orc_blocks_eval (pbrt_oracle.h ORC_BLOCK_*): name -> (op, floats read, floats written per element)
+BLOCK_OPS = {"SIN": (0, 1, 1), "COS": (1, 1, 1), "ATAN_POS": (2, 1, 1), "ACOS": (3, 1, 1), "SINCOS": (4, 1, 2), "SPHERE_UV": (5, 3, 2),
+             "FRESNEL": (6, 2, 2), "COSINE_ABOUT": (7, 5, 4), "SPHERE_HIT": (8, 11, 2)}
+
+
+def blocks_eval(op, x):
+    """orc_blocks_eval: the oracle's building blocks over arrays.  x: (n, floats read) float32 -> (n, floats written) float32"""
+    code, w_in, w_out = BLOCK_OPS[op]
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, w_in)
+    out = np.zeros((len(x), w_out), np.float32)
+    if lib().orc_blocks_eval(code, len(x), _p(x), _p(out)) != 0:
+        raise ValueError("orc_blocks_eval: bad argument")
+    return out
 
 
 def film_from_acc(acc):

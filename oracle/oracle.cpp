@@ -434,20 +434,8 @@ class PathIntegrator {
         const float abs_o = std::fabs(cos_o);
         const float ci = abs_o < 1.0f ? abs_o : 1.0f;
         const float r = cos_o > 0.f ? 1.0f / eta : eta;  // eta_i / eta_t: entering where wo is on ng's side
-        const float one_minus = 1.0f - ci * ci;
-        const float s2i = one_minus > 0.f ? one_minus : 0.f;
-        const float s2t = (r * r) * s2i;
         float F, ct;
-        if (s2t >= 1.0f) {  // total internal reflection
-          F = 1.0f;
-          ct = 0.f;
-        } else {
-          ct = std::sqrt(1.0f - s2t);
-          const float e = 1.0f / r;
-          const float rpar = (e * ci - ct) / (e * ci + ct);
-          const float rper = (ci - e * ct) / (ci + e * ct);
-          F = 0.5f * (rpar * rpar + rper * rper);
-        }
+        glass_fresnel(ci, r, &F, &ct);
         const float u = sampler.Get1D();
         const bool reflect = u < F;
         if (reflect) {
@@ -979,6 +967,44 @@ int orc_envmap_eval(const float *rgb, uint32_t W, uint32_t H, const float M[9], 
     if (texel) texel[i] = k;
     if (le) { const Vec3 t = e.texel(k); le[3 * i] = t.x; le[3 * i + 1] = t.y; le[3 * i + 2] = t.z; }
     if (pdf) pdf[i] = env_pdf_omega(e.p_uv[k], st);
+  }
+  return 0;
+}
+// The building blocks over arrays (tests): element i reads kBlocks[op].in floats and writes kBlocks[op].out -- the restatements the render
+// path itself calls (oracle_math.hpp, oracle_scene.hpp Scene::sphere_hit, concentric_sample_disk / cosine_sample_about above), op codes
+// and layouts as the product's hook pbrt_hip_blocks_eval_device
+int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out) {
+  static const struct { uint32_t in, out; } kBlocks[ORC_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}};
+  if (op >= ORC_BLOCK_COUNT || n < 0 || !in || !out) return -1;
+  for (int64_t i = 0; i < n; i++) {
+    const float *x = in + i * kBlocks[op].in;
+    float *y = out + i * kBlocks[op].out;
+    switch (op) {
+      case ORC_BLOCK_SIN: y[0] = poly_sin(x[0]); break;
+      case ORC_BLOCK_COS: y[0] = poly_cos(x[0]); break;
+      case ORC_BLOCK_ATAN_POS: y[0] = poly_atan_pos(x[0]); break;
+      case ORC_BLOCK_ACOS: y[0] = poly_acos(x[0]); break;
+      case ORC_BLOCK_SINCOS: sincos_octants(x[0], &y[0], &y[1]); break;
+      case ORC_BLOCK_SPHERE_UV: sphere_uv(x[0], x[1], x[2], &y[0], &y[1]); break;
+      case ORC_BLOCK_FRESNEL: glass_fresnel(x[0], x[1], &y[0], &y[1]); break;
+      case ORC_BLOCK_COSINE_ABOUT: {
+        Vec3 wi;
+        y[3] = cosine_sample_about(v3(x[0], x[1], x[2]), x[3], x[4], &wi);
+        y[0] = wi.x; y[1] = wi.y; y[2] = wi.z;
+        break;
+      }
+      default: {  // ORC_BLOCK_SPHERE_HIT
+        orc_sphere sp{};
+        sp.c[0] = x[0]; sp.c[1] = x[1]; sp.c[2] = x[2]; sp.r = x[3];
+        Ray r;
+        r.o = v3(x[4], x[5], x[6]); r.d = v3(x[7], x[8], x[9]); r.tmax = x[10];
+        float th = 0.f;
+        const bool hit = Scene::sphere_hit(sp, r, &th);
+        y[0] = hit ? 1.0f : 0.f;
+        y[1] = hit ? th : 0.f;
+        break;
+      }
+    }
   }
   return 0;
 }

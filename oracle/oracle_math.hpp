@@ -230,7 +230,8 @@ static inline float poly_cos(float x) {
 
 // ---- a sphere's (u, v) for 2-D textures (pbrt-v3 Sphere::Intersect: u = phi / 2 pi with phi = atan2(y, x) in [0, 2 pi),
 // v = (theta - pi) / (0 - pi) with theta = acos(z)) on the unit normal n = (p - c) / r, the sphere's own frame being the world's axes.  atan
-// and asin are the Cephes single-precision polynomials written out (|error| < 2e-7), the same operations on CPU and GPU. ----
+// and asin are the Cephes single-precision polynomials written out (measured against float64, DESIGN.md 3.6: atan within 2.0 ulp, 1.4e-7
+// absolute; acos within 3.0e-7 absolute), the same operations on CPU and GPU. ----
 static inline float poly_atan_pos(float x) {  // x >= 0 (+inf included): atan(x) in [0, pi / 2]
   float y0 = 0.f;
   if (x > 2.414213562373095f) {
@@ -268,6 +269,27 @@ static inline void sphere_uv(float nx, float ny, float nz, float *u, float *v) {
   const float theta = poly_acos(zc);
   *u = phi * 0.15915494309189533577f;  // 1 / (2 pi)
   *v = (theta - 3.14159265358979323846f) / (0.f - 3.14159265358979323846f);
+}
+
+// ---- Fresnel reflectance of a smooth dielectric interface and the cosine of the refracted ray (pbrt-v3 FrDielectric):
+// ci = |cos theta_i| in [0, 1], r = eta_i / eta_t.  sin^2 theta_t = r^2 (1 - ci^2) >= 1 is total internal reflection: F = 1, ct = 0.
+// What the glass vertex of PathIntegrator::Li computes, by name so that orc_blocks_eval runs the same statements. ----
+static inline void glass_fresnel(float ci, float r, float *F, float *ct) {
+  const float one_minus = 1.0f - ci * ci;
+  const float s2i = one_minus > 0.f ? one_minus : 0.f;
+  const float s2t = (r * r) * s2i;
+  // (the comparison as the kernels make it: a NaN -- r = inf against a cosine of 1, 0 x inf -- is total reflection too, F = 1 and ct = 0 on both
+  // sides; tests/test_blocks_gpu.py compares the two off the domain as well)
+  if (s2t < 1.0f) {
+    *ct = std::sqrt(1.0f - s2t);
+    const float e = 1.0f / r;
+    const float rpar = (e * ci - *ct) / (e * ci + *ct);
+    const float rper = (ci - e * *ct) / (ci + e * *ct);
+    *F = 0.5f * (rpar * rpar + rper * rper);
+  } else {  // total internal reflection
+    *F = 1.0f;
+    *ct = 0.f;
+  }
 }
 
 // ---- the environment map's arithmetic, restated from the spec's text: the oracle's own declarations, nothing shared with

@@ -395,8 +395,8 @@ class Scene {
   }
 
   // ---- Sphere::Intersect, quadratic per lib.rs:181-203 ----
-  bool sphere_intersect(uint32_t s, const Ray &r, float *tt) const {
-    const orc_sphere &sp = spheres[s];
+  // the sphere test itself: the nearer root inside (kRayTMin, tmax), else the farther one (what orc_blocks_eval runs alone)
+  static bool sphere_hit(const orc_sphere &sp, const Ray &r, float *tt) {
     Vec3 oc = r.o - v3(sp.c[0], sp.c[1], sp.c[2]);
     float a = dot(r.d, r.d);
     float b = 2.0f * dot(r.d, oc);
@@ -408,6 +408,13 @@ class Scene {
       th = t1;
       if (!(th > kRayTMin && th < r.tmax)) return false;
     }
+    *tt = th;
+    return true;
+  }
+  bool sphere_intersect(uint32_t s, const Ray &r, float *tt) const {
+    const orc_sphere &sp = spheres[s];
+    float th;
+    if (!sphere_hit(sp, r, &th)) return false;
     // the own-box rule on the sphere's box [c - r, c + r]: the "vertices" lo, hi, lo
     Vec3 lo, hi;
     sphere_box(sp, &lo, &hi);

@@ -119,6 +119,7 @@ SYMBOLS = {
     "pbrt_hip_envmap_tables": (C.c_int, [_pf, _u32, _u32, _pf, _pf, _pf]),
     "pbrt_hip_envmap_eval_host": (C.c_int, [_pf, _u32, _u32, _pf, _i64, _pf, _pf, _pu32, _pf, _pf]),
     "pbrt_hip_envmap_eval_device": (C.c_int, [_vp, _i64, _pf, _pf, _pu32, _pf, _pf]),
+    "pbrt_hip_blocks_eval_device": (C.c_int, [C.c_int, _u32, _i64, _pf, _pf]),
 }
 
 _lib = None

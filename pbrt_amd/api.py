@@ -317,6 +317,21 @@ def envmap_eval_host(rgb, world_to_light=None, u12=None, d=None):
                         "pbrt_hip_envmap_eval_host", u12, d)
 
 
+# op codes of pbrt_hip_blocks_eval_device (include/pbrt_hip_debug.h PBRT_HIP_BLOCK_*): name -> (op, floats read, floats written per element)
+BLOCK_OPS = {"SIN": (0, 1, 1), "COS": (1, 1, 1), "ATAN_POS": (2, 1, 1), "ACOS": (3, 1, 1), "SINCOS": (4, 1, 2), "SPHERE_UV": (5, 3, 2),
+             "FRESNEL": (6, 2, 2), "COSINE_ABOUT": (7, 5, 4), "SPHERE_HIT": (8, 11, 2)}
+
+
+def blocks_eval(op, x, device=0):
+    """pbrt_hip_blocks_eval_device: the kernels' building blocks (csrc/cephes_poly.hpp, kernel_math.hpp, envmap_core.hpp) over arrays on
+    the device.  op: a name of BLOCK_OPS; x: (n, floats read) float32 -> (n, floats written) float32."""
+    code, w_in, w_out = BLOCK_OPS[op]
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, w_in)
+    out = np.zeros((len(x), w_out), np.float32)
+    check(lib().pbrt_hip_blocks_eval_device(int(device), code, len(x), _fp(x), _fp(out)), "pbrt_hip_blocks_eval_device")
+    return out
+
+
 def sobol_matrices():
     """pbrt_hip_sobol_matrices: (128, 32) uint32 generator matrices of sampler 2 (host only)"""
     out = np.zeros((128, 32), np.uint32)

@@ -1,0 +1,79 @@
+// kernels_blocks.hip -- the kernels' building blocks over arrays: pbrt_hip_blocks_eval_device, the hook that lets tests/ compare the
+// polynomials of cephes_poly.hpp, envmap_core.hpp's sincos_0_2pi and kernel_math.hpp's sphere_uv / glass_fresnel / cosine_about /
+// sphere_hit with a float64 reference and with the oracle's restatements, element by element, without a render around them.  In a
+// translation unit of its own so that the render and intersect kernels of kernels*.hip keep their names and their machine code.
+//
+//   blocks_eval_kernel  one element per thread, 256 threads per workgroup: switches on the op code and calls the PRODUCTION function
+//                       (nothing is restated here); kBlockWidth is how many floats an element reads and writes.
+#include "capi_internal.hpp"
+#include "envmap_core.hpp"
+#include "kernel_math.hpp"
+
+namespace pbrt_hip {
+namespace {
+
+struct BlockWidth {
+  uint32_t in, out;
+};
+// indexed by op (include/pbrt_hip_debug.h PBRT_HIP_BLOCK_*)
+constexpr BlockWidth kBlockWidth[PBRT_HIP_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}};
+
+__global__ void __launch_bounds__(256) blocks_eval_kernel(uint32_t op, int64_t n, uint32_t w_in, uint32_t w_out, const float *in, float *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float *x = in + i * (int64_t)w_in;
+  float *y = out + i * (int64_t)w_out;
+  switch (op) {
+    case PBRT_HIP_BLOCK_SIN: y[0] = poly_sin(x[0]); break;
+    case PBRT_HIP_BLOCK_COS: y[0] = poly_cos(x[0]); break;
+    case PBRT_HIP_BLOCK_ATAN_POS: y[0] = poly_atan_pos(x[0]); break;
+    case PBRT_HIP_BLOCK_ACOS: y[0] = poly_acos(x[0]); break;
+    case PBRT_HIP_BLOCK_SINCOS: envmap::sincos_0_2pi(x[0], &y[0], &y[1]); break;
+    case PBRT_HIP_BLOCK_SPHERE_UV: sphere_uv(x[0], x[1], x[2], &y[0], &y[1]); break;
+    case PBRT_HIP_BLOCK_FRESNEL: {
+      float F, ct;
+      glass_fresnel(x[0], x[1], F, ct);
+      y[0] = F; y[1] = ct;
+      break;
+    }
+    case PBRT_HIP_BLOCK_COSINE_ABOUT: {
+      V3 wi;
+      const float z = cosine_about(mk(x[0], x[1], x[2]), x[3], x[4], wi);
+      y[0] = wi.x; y[1] = wi.y; y[2] = wi.z; y[3] = z;
+      break;
+    }
+    case PBRT_HIP_BLOCK_SPHERE_HIT: {
+      float th = 0.f;
+      const bool hit = sphere_hit(make_float4(x[0], x[1], x[2], x[3]), mk(x[4], x[5], x[6]), mk(x[7], x[8], x[9]), x[10], th);
+      y[0] = hit ? 1.0f : 0.f;
+      y[1] = hit ? th : 0.f;  // (a miss leaves no distance)
+      break;
+    }
+    default: break;
+  }
+}
+
+}  // namespace
+}  // namespace pbrt_hip
+
+using namespace pbrt_hip;
+
+extern "C" int pbrt_hip_blocks_eval_device(int device, uint32_t op, int64_t n, const float *in, float *out) {
+  if (op >= PBRT_HIP_BLOCK_COUNT) return fail(PBRT_HIP_ERR_INVALID, "blocks_eval_device: unknown op");
+  if (n < 0 || !in || !out) return fail(PBRT_HIP_ERR_INVALID, "blocks_eval_device: null argument or negative count");
+  if (n == 0) return PBRT_HIP_OK;
+  return guarded([&]() -> int {
+    HIP_TRY(hipSetDevice(device));
+    const BlockWidth w = kBlockWidth[op];
+    DevBuf<float> d_in, d_out;
+    HIP_TRY(d_in.alloc(w.in * (size_t)n));
+    HIP_TRY(d_out.alloc(w.out * (size_t)n));
+    const hipStream_t stream = nullptr;  // the device's default stream
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, 4 * w.in * (size_t)n, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(blocks_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, op, n, w.in, w.out, d_in.p, d_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, 4 * w.out * (size_t)n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PBRT_HIP_OK;
+  });
+}

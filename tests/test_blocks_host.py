@@ -1,0 +1,75 @@
+"""The kernels' building blocks against float64, on the CPU: the oracle's restatements (oracle_math.hpp, oracle.cpp, oracle_scene.hpp) through
+orc_blocks_eval over the input sets of tests/blocks_ref.py, under the bounds written there and in DESIGN.md 3.5 / 3.6.  The device runs the same
+sets through pbrt_hip_blocks_eval_device in tests/test_blocks_gpu.py, bit-equal to what is checked here.  Parity between oracle and kernels
+cannot see a wrong coefficient or a wrong range threshold -- both restate the same fixed order of fp32 operations -- and a render sees one
+only once it moves an image: these tests do, element by element."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import blocks_ref as br
+from pbrt_amd import _lib, api
+
+
+@pytest.mark.parametrize("op", list(br.POLY_BOUND))
+def test_polynomials_against_float64(oracle, op):
+    """poly_sin, poly_cos, poly_atan_pos, poly_acos and the octant reduction of sin / cos over [0, 2 pi]: every 64th float32 pattern of the
+    domain and every pattern within 4096 of 0, of the domain's ends, of the range thresholds and of the multiples of pi / 4.  The bound is
+    DESIGN.md 3.6's table -- the error measured here + 0.5 ulp --, and the measured figure itself is pinned to 1 %: a change of the
+    arithmetic that moves it has to move the table."""
+    x, aux = br.inputs(op)
+    got = oracle.blocks_eval(op, x)
+    worst, at = br.check(op, x, aux, got)
+    print(f"{op}: {len(x)} inputs, largest error {worst:.4g} {br.POLY_BOUND[op][0]} at x = {at!r} (bound {br.POLY_BOUND[op][1]})")
+    assert abs(worst / br.POLY_MEASURED[op] - 1.0) < 0.01, (op, worst, br.POLY_MEASURED[op])
+
+
+@pytest.mark.parametrize("op", ["SPHERE_UV", "FRESNEL", "COSINE_ABOUT"])
+def test_composite_blocks_against_float64(oracle, op):
+    """sphere_uv (the seam, the poles, the axes, a clamped |nz|), the Fresnel term (grazing and normal incidence, the critical angle pattern by
+    pattern, matched indices) and cosine sampling about a normal (the disk's centre, rim and wedge diagonals; normals on the frame's
+    branch): bounds propagated in float64 per element from the polynomials', none taken from the outputs; each below 1e-5 on 99 % of the
+    elements, so that a bound blown up at a singular point cannot carry the test."""
+    x, aux = br.inputs(op)
+    figures = br.check(op, x, aux, oracle.blocks_eval(op, x))
+    print(f"{op}: {len(x)} inputs, largest error / bound and shares of the bounds below 1e-5: {figures}")
+
+
+def test_fresnel_clamps_a_cosine_above_one(oracle):
+    """1 - ci^2 is negative for a cosine that rounding carried above 1; the clamp in front of it keeps ct = 1 and F in [0, 1]"""
+    x = br.fresnel_above_one_inputs()
+    br.check_fresnel_above_one(x, oracle.blocks_eval("FRESNEL", x))
+
+
+def test_sphere_test_alone_against_float64(oracle):
+    """sphere_hit without a tree around it, over the ladder of distance / radius of util.SPHERE_LADDER: what test_oracle_selfcheck.py's
+    test_sphere_hits_against_float64 checks of the walks, of the function -- a failure there and not here is the walk's."""
+    x, parts = br.inputs("SPHERE_HIT")
+    for rung, m in br.check("SPHERE_HIT", x, parts, oracle.blocks_eval("SPHERE_HIT", x)).items():
+        print(f"D, r = {rung}: max |dt| {m['max_dt']:.3g}, max |dt| / bound {m['max_ratio']:.3f}, off the surface {m['off_surface_radii']:.3g} r, robust {m['robust']}")
+
+
+def test_oracle_hook_refuses_what_it_does_not_know(oracle):
+    """orc_blocks_eval refuses what it does not know, and an op's outputs have the documented shapes"""
+    with pytest.raises(KeyError):
+        oracle.blocks_eval("TAN", np.zeros(1, np.float32))
+    assert oracle.lib().orc_blocks_eval(99, 1, C.c_void_p(0), C.c_void_p(0)) == -1
+    assert oracle.lib().orc_blocks_eval(0, 1, C.c_void_p(0), C.c_void_p(0)) == -1
+    for op, (code, w_in, w_out) in oracle.BLOCK_OPS.items():
+        assert api.BLOCK_OPS[op] == (code, w_in, w_out)
+        assert oracle.blocks_eval(op, np.full((3, w_in), 0.5, np.float32)).shape == (3, w_out)
+    assert tuple(oracle.BLOCK_OPS) == br.ALL_OPS
+
+
+def test_device_hook_refuses_bad_arguments_before_it_touches_a_device():
+    """pbrt_hip_blocks_eval_device: PBRT_HIP_ERR_INVALID for an unknown op, a negative n, a null array -- decided before any HIP call, so
+    this runs without a GPU; n = 0 is nothing to do"""
+    f = _lib.lib().pbrt_hip_blocks_eval_device
+    a = np.zeros(16, np.float32)
+    p = a.ctypes.data_as(C.POINTER(C.c_float))
+    assert f(0, 9, 1, p, p) == -1 and f(0, 0xffffffff, 1, p, p) == -1
+    assert f(0, 0, -1, p, p) == -1
+    assert f(0, 0, 1, None, p) == -1 and f(0, 0, 1, p, None) == -1
+    assert b"blocks_eval_device" in _lib.lib().pbrt_hip_last_error()
+    assert f(0, 0, 0, p, p) == 0

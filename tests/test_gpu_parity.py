@@ -1394,6 +1394,22 @@ def test_closest_hits_equal_a_float64_brute_force_on_the_gpu(gpu, name, builder)
     check_hits_against_brute_force(sd, o, d, tmax, t, prim)
 
 
+@pytest.mark.parametrize("rung", range(4))
+def test_sphere_hits_against_float64(gpu, oracle, rung):
+    """tests/test_oracle_selfcheck.py's test of the same name through pbrt_hip_intersect (the production walk): the ladder of distance /
+    radius, every robust ray's sphere and t against float64 under the error model of util.sphere_hits_f64 -- and every ray, robust or
+    not, equal to the oracle bit for bit.  (The sphere test without a walk around it: tests/test_blocks_gpu.py, op SPHERE_HIT.)"""
+    from util import SPHERE_LADDER, check_sphere_hits, sphere_ladder_rays, sphere_ladder_scene
+    dist, radius = SPHERE_LADDER[rung]
+    sd = sphere_ladder_scene(radius)
+    o, d, tmax, kind = sphere_ladder_rays(dist, radius)
+    with gpu.Scene(sd) as sc:
+        t, prim = sc.intersect(o, d, tmax)[:2]
+    rt, rp = oracle.OracleScene(sd).intersect(o, d, tmax)[:2]
+    assert_bit_equal(prim, rp, "prim"); assert_bit_equal(t, rt, "t")
+    print(dist, radius, check_sphere_hits(sd.spheres, o, d, tmax, kind, t, prim))
+
+
 @pytest.mark.parametrize("max_depth", [2, 5])
 def test_path_integrator_agrees_with_an_independent_estimator_on_the_gpu(gpu, max_depth):
     """The HIP path against tests/independent_mc.py (float64 numpy, own random numbers, no light sampling: the emitter is collected only

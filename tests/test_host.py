@@ -26,7 +26,7 @@ def test_library_exports_every_declared_symbol():
     assert {"pbrt_hip_device_count", "pbrt_hip_scene_create", "pbrt_hip_render", "pbrt_hip_scene_destroy", "pbrt_hip_last_error",
             "pbrt_hip_render_multi", "pbrt_hip_multi_create", "pbrt_hip_load_file", "pbrt_hip_write_image"} <= stable
     assert {"pbrt_hip_scene_export_quads", "pbrt_hip_scene_export_bvh", "pbrt_hip_scene_walk_info", "pbrt_hip_render_stack_plan", "pbrt_hip_bvh_build_host",
-            "pbrt_hip_quad_build_host", "pbrt_hip_quad_build_host_ex", "pbrt_hip_tokenize", "pbrt_hip_loaded_state", "pbrt_hip_sobol_matrices"} <= hooks
+            "pbrt_hip_quad_build_host", "pbrt_hip_quad_build_host_ex", "pbrt_hip_tokenize", "pbrt_hip_loaded_state", "pbrt_hip_sobol_matrices", "pbrt_hip_blocks_eval_device"} <= hooks
     declared = stable | hooks
     assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
     l = _lib.lib()

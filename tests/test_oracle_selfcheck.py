@@ -492,6 +492,29 @@ def test_closest_hits_equal_a_float64_brute_force(oracle, name):
     check_hits_against_brute_force(sd, o, d, tmax, t, prim)
 
 
+@pytest.mark.parametrize("rung", range(4))
+def test_sphere_hits_against_float64(oracle, rung):
+    """A sphere's t against float64, ray by ray (util.sphere_hits_f64: the quadratic's roots from the textbook, nothing shared), over a
+    ladder of distance / radius = 3, 10, 100, 150 in scenes of spheres alone, through the BVH walk and the brute force: 20 000 rays a rung,
+    aimed at the sphere, starting inside it, starting 1e-4 off its surface on either side (what reflected and refracted rays start from),
+    and along its silhouette.  sphere_hit forms b and c in float32 before the float64 discriminant, so its error grows with (distance /
+    radius)^2: on every ROBUST ray -- hit or miss, the root chosen and the closest sphere cannot flip under the error model of
+    sphere_hits_f64, decided from float64 alone; at least 0.8 of each of the first three kinds -- hit or miss and the sphere equal
+    float64's and |t - t64| stays within the model's bound; over all rays hit or miss agrees at least as often as rays are robust.  The
+    figures printed are DESIGN.md 3.5's table: this pins the envelope of the arithmetic as it is, it does not improve it."""
+    from util import SPHERE_LADDER, check_sphere_hits, sphere_ladder_rays, sphere_ladder_scene
+    dist, radius = SPHERE_LADDER[rung]
+    sd = sphere_ladder_scene(radius)
+    o, d, tmax, kind = sphere_ladder_rays(dist, radius)
+    ref = oracle.OracleScene(sd)
+    t, prim = ref.intersect(o, d, tmax)[:2]
+    tb, primb = ref.intersect(o, d, tmax, brute_force=True)[:2]
+    assert_bit_equal(t, tb, "t: BVH against brute force"); assert_bit_equal(prim, primb, "prim: BVH against brute force")
+    m = check_sphere_hits(sd.spheres, o, d, tmax, kind, t, prim)
+    print(f"D / r = {dist / radius:.0f} (D {dist}, r {radius:.4g}): max |dt| {m['max_dt']:.3g}, max |dt| / bound {m['max_ratio']:.3f}, "
+          f"hit point off the surface {m['off_surface_radii']:.3g} r, robust {m['robust']}, hit-or-miss agreement {m['agree']:.5f}")
+
+
 @pytest.mark.parametrize("res", [(160, 160), (200, 120)])
 def test_checkerboard_on_a_sphere_closed_form(oracle, res):
     """A checkerboard Kd over a SPHERE's own (u, v) = (phi / 2 pi, 1 - theta / pi) (pbrt-v3 Sphere::Intersect; the path's atan / acos are

@@ -732,3 +732,153 @@ def glass_room_scene(extra_parts=(), spheres=(), eye=(0.0, -0.2, 0.1), look=(0.3
                      lights=np.zeros((0, 7), np.float32) if lights is None else np.array(lights, np.float32),
                      spheres=np.array(spheres, np.float32).reshape(-1, 5), cam_to_world=look_at(eye, look, (0, 0, 1))[1], fov=70.0, xres=res,
                      yres=res).normalized()
+
+
+# ---- sphere hits against float64, ray by ray (tests/test_oracle_selfcheck.py on the oracle's walks, tests/test_gpu_parity.py through
+# pbrt_hip_intersect, tests/test_blocks_*.py on the sphere test alone): the quadratic's roots from the textbook, and how far float32's
+# coefficients can move them ----
+U32 = 2.0 ** -24  # the unit roundoff of float32
+
+
+def _gamma(n):
+    return n * U32 / (1.0 - n * U32)
+
+
+def sphere_hits_f64(spheres, o, d, tmax, tmin=1e-4, walk=True):
+    """Closest hit of every ray against every sphere (spheres: (S, 4+) rows {centre, radius}), in float64 numpy: a t^2 + b t + c = 0 with
+    a = d.d, b = 2 d.(o - c), c = |o - c|^2 - r^2, the nearer root inside (tmin, tmax), else the farther.
+    -> dict: t (inf on a miss), prim (sphere index, -1 on a miss), bound (on the float32 path's t of the chosen sphere), robust.
+
+    THE ERROR MODEL.  The float32 path forms a, b, c in float32 (the dot products left to right, o - c first) and solves in float64; a
+    root moves by -(t^2 da + t db + dc) / (2 a t + b), and |2 a t + b| = sqrt(disc).  With u = 2^-24, gamma_n = n u / (1 - n u):
+      |da| <= gamma_3 a,  |db| <= 2 gamma_4 sum |d_i oc_i|,  |dc| <= gamma_6 (|oc|^2 + r^2)
+      bound(t) = (t^2 |da| + |t| |db| + |dc|) / sqrt(disc) + u |t|          (the last term: t itself is rounded to float32)
+    A ray is ROBUST when, for every sphere, |disc| exceeds 16 x its own perturbation 2 |b| |db| + 4 (a |dc| + |c| |da|) (hit or miss
+    cannot flip), both roots are further than their bounds from tmin and from tmax (the choice of the root cannot flip), and the closest
+    hit is ahead of every other sphere's by more than the two bounds.  walk=True (a hit that went through a tree: the own-box rule of
+    DESIGN.md 3.5 raises t to the entry of the sphere's box [c - r, c + r]) also asks that the box's entry, with 4 u of slack on every
+    term of its slab distances, stays below t - bound: then the rule changes nothing."""
+    S = np.asarray(spheres, np.float32)[:, :4].astype(np.float64)
+    o64, d64 = np.asarray(o, np.float32).astype(np.float64), np.asarray(d, np.float32).astype(np.float64)
+    tm = np.asarray(tmax, np.float32).astype(np.float64)[:, None]
+    oc = o64[:, None, :] - S[None, :, :3]                      # [N, S, 3]
+    r = S[None, :, 3]
+    a = (d64 * d64).sum(1)[:, None]
+    dd = d64[:, None, :]
+    b = 2.0 * (dd * oc).sum(2)
+    oc2 = (oc * oc).sum(2)
+    c = oc2 - r * r
+    da, db, dc = _gamma(3) * a, 2.0 * _gamma(4) * np.abs(dd * oc).sum(2), _gamma(6) * (oc2 + r * r)
+    disc = b * b - 4.0 * a * c
+    d_disc = 2.0 * np.abs(b) * db + 4.0 * (a * dc + np.abs(c) * da)
+    with np.errstate(all="ignore"):
+        rd = np.sqrt(np.maximum(disc, 0.0))
+        q = np.where(b < 0, -0.5 * (b - rd), -0.5 * (b + rd))
+        r0, r1 = q / a, c / q
+        t0, t1 = np.minimum(r0, r1), np.maximum(r0, r1)
+        bnd = lambda t: (t * t * da + np.abs(t) * db + dc) / rd + U32 * np.abs(t)
+        b0, b1 = bnd(t0), bnd(t1)
+        real = disc >= 0
+        ok0 = real & (t0 > tmin) & (t0 < tm)
+        ok1 = real & (t1 > tmin) & (t1 < tm)
+        th = np.where(ok0, t0, np.where(ok1, t1, np.inf))
+        tb = np.where(ok0, b0, np.where(ok1, b1, 0.0))
+        clear = lambda t, e: (np.abs(t - tmin) > e) & (np.abs(t - tm) > e)
+        sure = (np.abs(disc) > 16.0 * d_disc) & (~real | (clear(t0, b0) & clear(t1, b1)))
+        if walk:  # the entry of the sphere's own box, in the kernels' form (lo - o) * (1 / d) per axis, every term 4 u generous
+            lo, hi = (S[None, :, :3] - r[..., None]) - o64[:, None, :], (S[None, :, :3] + r[..., None]) - o64[:, None, :]
+            inv = 1.0 / dd
+            s0, s1 = lo * inv, hi * inv
+            slack = 4.0 * U32 * (np.abs(S[None, :, :3]) + r[..., None] + np.abs(o64[:, None, :])) * np.abs(inv) + 4.0 * U32 * np.maximum(np.abs(s0), np.abs(s1))
+            entry = np.nan_to_num(np.fmin(s0, s1) + slack, nan=-np.inf, posinf=np.inf).max(2)
+            sure &= ~np.isfinite(th) | (entry < th - tb)
+    k = np.argmin(th, axis=1)
+    rows = np.arange(len(k))
+    t_best, bound = th[rows, k], tb[rows, k]
+    others = th + 0.0
+    others[rows, k] = np.inf
+    ahead = (others - tb).min(1) if S.shape[0] > 1 else np.full(len(k), np.inf)
+    robust = sure.all(1) & (~np.isfinite(t_best) | (t_best + bound < ahead))
+    return {"t": t_best, "prim": np.where(np.isfinite(t_best), k, -1), "bound": bound, "robust": robust}
+
+
+# (distance, radius): distance / radius = 3, 10, 100 and 150.  The last rung was to be 1000 (10, 0.01), the regime of the soak's sphere clouds:
+# there NO aimed ray is robust -- disc = 4 (r^2 - p^2) at impact parameter p lies below 16 x its perturbation of about 56 u D^2 whenever
+# D / r exceeds 274 sqrt(1 - (p / r)^2).  The share of aimed rays (p uniform in [0, 0.9 r]) that are robust, from float64 alone: 0.98 at 100,
+# 0.93 at 125, 0.85 at 150, 0.81 at 160, 0.61 at 200, 0 at 250 -- so the rung is lowered to 150, the floor of 0.8 stays.
+SPHERE_LADDER = ((3.0, 1.0), (10.0, 1.0), (10.0, 0.1), (10.0, 10.0 / 150.0))
+SPHERE_LADDER_CENTRE = (0.3, -0.2, 0.1)
+SPHERE_RAY_KINDS = ("aimed", "inside", "spawned", "silhouette")
+
+
+def sphere_ladder_scene(radius):
+    """the rung's sphere at SPHERE_LADDER_CENTRE and seven bystanders of its radius 12 .. 20 radii away: spheres only, a tree to walk"""
+    from pbrt_amd.api import LIGHT_INFINITE, MATTE, SceneData, look_at
+    rng = np.random.default_rng(17)
+    v = rng.normal(size=(7, 3))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    c = np.concatenate([[SPHERE_LADDER_CENTRE], np.array(SPHERE_LADDER_CENTRE) + v * radius * rng.uniform(12.0, 20.0, (7, 1))])
+    sph = np.concatenate([c, np.full((8, 1), radius), np.zeros((8, 1))], 1).astype(np.float32)
+    return SceneData(P=np.zeros((0, 3), np.float32), idx=np.zeros((0, 3), np.uint32), mat_id=np.zeros(0, np.uint16),
+                     materials=np.array([[MATTE, .6, .5, .4, 0, 0, 0]], np.float32), lights=np.array([[LIGHT_INFINITE, 0, 0, 0, 1, 1, 1]], np.float32),
+                     spheres=sph, cam_to_world=look_at((0, -12, 0), SPHERE_LADDER_CENTRE, (0, 0, 1))[1], fov=30.0, xres=8, yres=8).normalized()
+
+
+def sphere_ladder_rays(dist, radius, n=20_000, seed=0):
+    """n rays with unit directions at the rung's sphere, a quarter of each kind (-> o, d, tmax, kind index):
+      aimed       from a shell at `dist` around the centre, at impact parameters uniform in [0, 0.9 r]
+      inside      origins inside the sphere (|o - c| < 0.9 r), any direction: the second root is taken
+      spawned     origins at p + n 1e-4 and p - n 1e-4 of surface points p, leaving the surface on their side: what a reflected and a
+                  refracted ray start from, where c = |o - c|^2 - r^2 cancels
+      silhouette  as aimed, impact parameters in [0.9 r, 1.2 r]"""
+    rng = np.random.default_rng(1234 + seed)
+    c = np.array(SPHERE_LADDER_CENTRE)
+    unit = lambda v: v / np.linalg.norm(v, axis=1, keepdims=True)
+    m = n // 4
+    kind = np.repeat(np.arange(4), m)
+
+    def aimed(lo, hi):
+        w = unit(rng.normal(size=(m, 3)))                      # from the centre towards the origin
+        e = unit(np.cross(w, rng.normal(size=(m, 3))))         # across
+        org = c + dist * w
+        return org, unit(c + e * (radius * rng.uniform(lo, hi, (m, 1))) - org)
+    o0, d0 = aimed(0.0, 0.9)
+    o1 = c + unit(rng.normal(size=(m, 3))) * radius * 0.9 * rng.uniform(0, 1, (m, 1)) ** (1 / 3)
+    d1 = unit(rng.normal(size=(m, 3)))
+    nrm = unit(rng.normal(size=(m, 3)))
+    side = np.where(np.arange(m) % 2 == 0, 1.0, -1.0)[:, None]
+    o2 = c + nrm * radius + nrm * side * 1e-4
+    t1, t2 = unit(np.cross(nrm, rng.normal(size=(m, 3)))), None
+    t2 = np.cross(nrm, t1)
+    u1, u2 = rng.uniform(0, 1, m), rng.uniform(0, 1, m)
+    cz = np.sqrt(0.04 + 0.96 * u1)                             # cosine to the normal in [0.2, 1]: not grazing
+    sz = np.sqrt(1 - cz * cz)
+    d2 = unit((t1 * np.cos(2 * np.pi * u2)[:, None] + t2 * np.sin(2 * np.pi * u2)[:, None]) * sz[:, None] + nrm * side * cz[:, None])
+    o3, d3 = aimed(0.9, 1.2)
+    o = np.concatenate([o0, o1, o2, o3]).astype(np.float32)
+    d = np.concatenate([d0, d1, d2, d3]).astype(np.float32)
+    return o, d, np.full(len(o), np.inf, np.float32), kind
+
+
+def check_sphere_hits(spheres, o, d, tmax, kind, t, prim, n_tris=0, walk=True):
+    """(t, prim) of float32 sphere hits (a miss: prim 0xffffffff) against sphere_hits_f64, as the issue of the float64 sphere tests states
+    it.  -> the rung's measurements: max |dt| and max |dt| / bound over the robust hits, the largest distance of a float32 hit point from
+    its sphere's surface in radii (all agreed hits), the robust share per kind of ray, the share of rays that agree on hit or miss"""
+    ref = sphere_hits_f64(spheres, o, d, tmax, walk=walk)
+    got = np.where(prim == 0xffffffff, -1, prim.astype(np.int64) - n_tris)
+    rb = ref["robust"]
+    share = {k: float(rb[kind == i].mean()) for i, k in enumerate(SPHERE_RAY_KINDS)}
+    assert min(share[k] for k in SPHERE_RAY_KINDS[:3]) >= 0.8, share   # (from float64 alone)
+    assert (got[rb] == ref["prim"][rb]).all(), np.flatnonzero(rb & (got != ref["prim"]))[:10]
+    hit = rb & (ref["prim"] >= 0)
+    dt = np.abs(t[hit].astype(np.float64) - ref["t"][hit])
+    ratio = dt / ref["bound"][hit]
+    assert hit.sum() > len(o) // 4 and (ratio <= 1.0).all(), (float(ratio.max()), np.flatnonzero(hit)[np.argmax(ratio)])
+    agree = float(((got >= 0) == (ref["prim"] >= 0)).mean())
+    assert agree >= rb.mean(), (agree, float(rb.mean()))
+    both = (got >= 0) & (got == ref["prim"])
+    S = np.asarray(spheres, np.float32)[:, :4].astype(np.float64)
+    p = o[both].astype(np.float64) + t[both].astype(np.float64)[:, None] * d[both].astype(np.float64)
+    off = np.abs(np.linalg.norm(p - S[got[both], :3], axis=1) - S[got[both], 3]) / S[got[both], 3]
+    return {"max_dt": float(dt.max()), "max_ratio": float(ratio.max()), "off_surface_radii": float(off.max()), "robust": share, "agree": agree,
+            "robust_all": float(rb.mean())}

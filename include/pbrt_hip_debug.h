@@ -78,7 +78,8 @@ int pbrt_hip_envmap_eval_host(const float *rgb, uint32_t width, uint32_t height,
  * PBRT_HIP_ERR_INVALID for a scene without an environment map. */
 int pbrt_hip_envmap_eval_device(pbrt_hip_scene *scene, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf);
 
-/* ---- the kernels' building blocks (pbrt_amd/csrc/cephes_poly.hpp, kernel_math.hpp, envmap_core.hpp) ---- */
+/* ---- the kernels' building blocks (pbrt_amd/csrc/cephes_poly.hpp, kernel_math.hpp, envmap_core.hpp,
+ * kernel_walk.hpp, tri_test.inc) ---- */
 /* The production functions over arrays on `device`, one element per thread of a tiny kernel that calls the headers the render kernels
  * are built from (pbrt_amd/csrc/kernels_blocks.hip): what lets tests compare each of them with float64 and with the oracle's
  * restatement, element by element.  in / out are HOST arrays of n elements; the hook copies them in and out on the device's default
@@ -90,6 +91,11 @@ int pbrt_hip_envmap_eval_device(pbrt_hip_scene *scene, int64_t n, const float *u
  *   COSINE_ABOUT               n (3), u1, u2 -> wi (3), z
  *   SPHERE_HIT                 {centre, radius} (4), o (3), d (3), tmax -> hit (0 or 1), t (0 on a miss): sphere_hit alone, before the
  *                              own-box rule the walk applies to what it returns
+ *   QUAD_STEP, QUAD_STEP_PK    the node's 16 words (raw bits in the float array), o (3), d (3), inv_parallel, tfar -> tn of children 0 .. 3,
+ *                              the hit mask (bit k = child k), the slot entered (4 = none): one step of the production walk (kernel_walk.hpp
+ *                              quad_step with the scalar and with the packed fma, the stand-in for 1 / 0 and the child selection around it)
+ *   TRI_HIT                    p0 p1 p2 (9), o (3), d (3), tmax -> valid (0 or 1), t, u, v (zeros on a miss): the leaf pass's triangle test
+ *                              (tri_test.inc: Moeller-Trumbore, the |det| cut, the own-box rule, t = max(th, entry))
  * PBRT_HIP_ERR_INVALID for an unknown op, a negative n or a null array. */
 #define PBRT_HIP_BLOCK_SIN 0u
 #define PBRT_HIP_BLOCK_COS 1u
@@ -100,7 +106,10 @@ int pbrt_hip_envmap_eval_device(pbrt_hip_scene *scene, int64_t n, const float *u
 #define PBRT_HIP_BLOCK_FRESNEL 6u
 #define PBRT_HIP_BLOCK_COSINE_ABOUT 7u
 #define PBRT_HIP_BLOCK_SPHERE_HIT 8u
-#define PBRT_HIP_BLOCK_COUNT 9u
+#define PBRT_HIP_BLOCK_QUAD_STEP 9u
+#define PBRT_HIP_BLOCK_QUAD_STEP_PK 10u
+#define PBRT_HIP_BLOCK_TRI_HIT 11u
+#define PBRT_HIP_BLOCK_COUNT 12u
 int pbrt_hip_blocks_eval_device(int device, uint32_t op, int64_t n, const float *in, float *out);
 
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */

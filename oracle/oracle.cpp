@@ -971,10 +971,11 @@ int orc_envmap_eval(const float *rgb, uint32_t W, uint32_t H, const float M[9], 
   return 0;
 }
 // The building blocks over arrays (tests): element i reads kBlocks[op].in floats and writes kBlocks[op].out -- the restatements the render
-// path itself calls (oracle_math.hpp, oracle_scene.hpp Scene::sphere_hit, concentric_sample_disk / cosine_sample_about above), op codes
+// path itself calls (oracle_math.hpp, oracle_scene.hpp Scene::sphere_hit / tri_hit, quad_walk.cpp's node step, concentric_sample_disk /
+// cosine_sample_about above), op codes
 // and layouts as the product's hook pbrt_hip_blocks_eval_device
 int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out) {
-  static const struct { uint32_t in, out; } kBlocks[ORC_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}};
+  static const struct { uint32_t in, out; } kBlocks[ORC_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}, {24, 6}, {24, 6}, {16, 4}};
   if (op >= ORC_BLOCK_COUNT || n < 0 || !in || !out) return -1;
   for (int64_t i = 0; i < n; i++) {
     const float *x = in + i * kBlocks[op].in;
@@ -991,6 +992,17 @@ int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out) {
         Vec3 wi;
         y[3] = cosine_sample_about(v3(x[0], x[1], x[2]), x[3], x[4], &wi);
         y[0] = wi.x; y[1] = wi.y; y[2] = wi.z;
+        break;
+      }
+      case ORC_BLOCK_QUAD_STEP:
+      case ORC_BLOCK_QUAD_STEP_PK: orc_quad_step_eval(x, y); break;
+      case ORC_BLOCK_TRI_HIT: {
+        Ray r;
+        r.o = v3(x[9], x[10], x[11]); r.d = v3(x[12], x[13], x[14]); r.tmax = x[15];
+        float tt = 0.f, u = 0.f, v = 0.f;
+        const bool hit = Scene::tri_hit(v3(x[0], x[1], x[2]), v3(x[3], x[4], x[5]), v3(x[6], x[7], x[8]), r, &tt, &u, &v);
+        y[0] = hit ? 1.0f : 0.f;
+        y[1] = hit ? tt : 0.f; y[2] = hit ? u : 0.f; y[3] = hit ? v : 0.f;
         break;
       }
       default: {  // ORC_BLOCK_SPHERE_HIT

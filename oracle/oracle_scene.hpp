@@ -349,6 +349,10 @@ class Scene {
   bool tri_intersect(uint32_t t, const Ray &r, float *tt, float *uu, float *vv) const {
     Vec3 p0, p1, p2;
     tri_verts(t, &p0, &p1, &p2);
+    return tri_hit(p0, p1, p2, r, tt, uu, vv);
+  }
+  // the test itself over three vertices, the own-box rule included (what orc_blocks_eval runs alone)
+  static bool tri_hit(Vec3 p0, Vec3 p1, Vec3 p2, const Ray &r, float *tt, float *uu, float *vv) {
     Vec3 e1 = p1 - p0, e2 = p2 - p0;
     Vec3 pv = cross(r.d, e2);
     float det = dot(e1, pv);

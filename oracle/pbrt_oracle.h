@@ -160,10 +160,15 @@ int orc_envmap_eval(const float *rgb, uint32_t W, uint32_t H, const float M[9], 
 /* ---- the building blocks over arrays (tests compare them with float64 and with the product's hook pbrt_hip_blocks_eval_device) ---- */
 /* floats per element, in -> out: SIN, COS, ATAN_POS, ACOS: x -> the polynomial; SINCOS: x in [0, 2 pi] -> s, c; SPHERE_UV: nx ny nz -> u, v;
  * FRESNEL: ci, r = eta_i / eta_t -> F, ct; COSINE_ABOUT: n (3), u1, u2 -> wi (3), z; SPHERE_HIT: {centre, radius} (4), o (3), d (3), tmax ->
- * hit (0 or 1), t (0 on a miss): the sphere test before the own-box rule.  0, or -1 for an unknown op, a negative n or a null array */
+ * hit (0 or 1), t (0 on a miss): the sphere test before the own-box rule; QUAD_STEP, QUAD_STEP_PK (one statement here): the node's 16 words
+ * as raw bits, o (3), d (3), inv_parallel, tfar -> tn of children 0 .. 3, the hit mask, the slot entered (4 = none): one step of
+ * quad_walk.cpp; TRI_HIT: p0 p1 p2 (9), o (3), d (3), tmax -> valid, t, u, v (zeros on a miss): Scene::tri_hit, the own-box rule included.
+ * 0, or -1 for an unknown op, a negative n or a null array */
 enum { ORC_BLOCK_SIN = 0, ORC_BLOCK_COS, ORC_BLOCK_ATAN_POS, ORC_BLOCK_ACOS, ORC_BLOCK_SINCOS, ORC_BLOCK_SPHERE_UV, ORC_BLOCK_FRESNEL,
-       ORC_BLOCK_COSINE_ABOUT, ORC_BLOCK_SPHERE_HIT, ORC_BLOCK_COUNT };
+       ORC_BLOCK_COSINE_ABOUT, ORC_BLOCK_SPHERE_HIT, ORC_BLOCK_QUAD_STEP, ORC_BLOCK_QUAD_STEP_PK, ORC_BLOCK_TRI_HIT, ORC_BLOCK_COUNT };
 int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out);
+/* one element of QUAD_STEP (quad_walk.cpp; what orc_blocks_eval calls): x = 24 floats, y = 6 */
+void orc_quad_step_eval(const float *x, float *y);
 /* camera ray for film point (fx, fy) */
 void orc_camera_ray(const orc_scene *s, float fx, float fy, float o[3], float d[3]);
 /* radiance of ONE pixel's samples (debug / fixtures): out = spp*3 floats */

@@ -5,7 +5,8 @@
 // builder emitted (pbrt_hip_quad_build_host*) finds the hits of the oracle's own BVH / of brute force -- the tie rule of
 // DESIGN.md 3.4 makes a hit independent of the tree, so any difference is a builder bug (a clipped or quantised box that
 // does not enclose what lies below it) -- and to count node steps / triangle tests per ray of a tree before it is ever
-// uploaded.  The arithmetic of one step follows the kernel instruction for instruction: node-relative planes
+// uploaded.  The arithmetic of one step -- stated ONCE, quad_step below, and held to float64 by tests/test_blocks_host.py -- follows the kernel
+// instruction for instruction: node-relative planes
 // t = fma(q, cell * inv, -(g +- 3 eps |g|)), the (1 + 2^-19) pad, NaN-ignoring min / max, nearest hit child first,
 // the other hit children stacked in slot order.  A lane of the kernel parks at a leaf until its triangles are tested, so
 // the per-ray sequence of steps is the sequential one written here.
@@ -22,8 +23,8 @@ namespace {
 
 constexpr float kInf = __builtin_huge_valf();
 constexpr float kRayTMin = 1e-4f;
-constexpr float kBoxPad = 0x1.000004p+0f;  // 1 + 2^-19
-constexpr float kOwnPad = 0x1.000001p+0f;  // 1 + 2^-21: the own-box rule of DESIGN.md 3.5
+constexpr float kBoxPad = 0x1.000004p+0f;  // MEANT as 1 + 2^-19, IS 1 + 2^-22 (six hex digits are 24 bits: DESIGN.md 3.4's finding, section 12 item 4)
+constexpr float kOwnPad = 0x1.000001p+0f;  // MEANT as 1 + 2^-21, IS 1: the literal is 1 + 2^-24 and rounds to 1 (DESIGN.md 3.5's finding, section 12 item 4): the own-box rule of DESIGN.md 3.5
 constexpr uint32_t kLeafRef = 0x80000000u, kDone = 0xffffffffu, kNoPrim = 0xffffffffu;
 
 inline float fminn(float a, float b) { return std::fmin(a, b); }  // IEEE minNum / maxNum: a NaN operand is ignored
@@ -63,6 +64,58 @@ bool box_test(const float *b, V3 o, V3 inv, float tfar) {
   return tn <= tf * kBoxPad;
 }
 
+// The kernel's finite stand-in for 1 / 0 on an axis the ray is parallel to (kernel_walk.hpp trav_run; pbrt_amd/csrc/host_math.hpp
+// inv_parallel_for_extent, restated): a power of two, 2^123 over the root box's largest extent rounded up to a power of two
+float inv_parallel_for_root(const float *b) {
+  const float extent = std::fmax(b[3] - b[0], std::fmax(b[4] - b[1], b[5] - b[2]));
+  int x = 0;
+  if (extent > 0.f && std::isfinite(extent)) (void)std::frexp(2.0f * extent, &x);
+  int e = 123 - x;
+  if (e > 120) e = 120;
+  if (e < -100) e = -100;
+  return std::ldexp(1.0f, e);
+}
+// the walk's inverse direction: 1 / d, the stand-in where d is exactly 0 (the kernel's walk_inv)
+V3 walk_inv(V3 d, V3 inv1, float big) {
+  return {d.x == 0.f ? std::copysign(big, inv1.x) : inv1.x, d.y == 0.f ? std::copysign(big, inv1.y) : inv1.y,
+          d.z == 0.f ? std::copysign(big, inv1.z) : inv1.z};
+}
+
+// ONE production node step (the kernel's quad_step, instruction for instruction): the four children of quad node W against
+// [kRayTMin, tfar] -> key[k] = the child's entry distance, hit[k].  walk(), child_passes() and the blocks op QUAD_STEP all call this.
+void quad_step(const uint32_t *W, V3 o, V3 inv, bool negx, bool negy, bool negz, float tfar, float key[4], bool hit[4]) {
+  const float gx = (o.x - as_f(W[0])) * inv.x, gy = (o.y - as_f(W[1])) * inv.y, gz = (o.z - as_f(W[2])) * inv.z;
+  constexpr float kMargin = 0x1.8p-22f;
+  const float gxn = std::fmaf(std::fabs(gx), kMargin, gx), gxf = std::fmaf(-std::fabs(gx), kMargin, gx);
+  const float gyn = std::fmaf(std::fabs(gy), kMargin, gy), gyf = std::fmaf(-std::fabs(gy), kMargin, gy);
+  const float gzn = std::fmaf(std::fabs(gz), kMargin, gz), gzf = std::fmaf(-std::fabs(gz), kMargin, gz);
+  const float cix = as_f(W[3]) * inv.x, ciy = as_f(W[10]) * inv.y, ciz = as_f(W[11]) * inv.z;
+  const uint32_t bnx = negx ? W[7] : W[4], bfx = negx ? W[4] : W[7];
+  const uint32_t bny = negy ? W[8] : W[5], bfy = negy ? W[5] : W[8];
+  const uint32_t bnz = negz ? W[9] : W[6], bfz = negz ? W[6] : W[9];
+  for (int k = 0; k < 4; k++) {
+    const float txn = std::fmaf((float)((bnx >> (8 * k)) & 0xffu), cix, -gxn), txf = std::fmaf((float)((bfx >> (8 * k)) & 0xffu), cix, -gxf);
+    const float tyn = std::fmaf((float)((bny >> (8 * k)) & 0xffu), ciy, -gyn), tyf = std::fmaf((float)((bfy >> (8 * k)) & 0xffu), ciy, -gyf);
+    const float tzn = std::fmaf((float)((bnz >> (8 * k)) & 0xffu), ciz, -gzn), tzf = std::fmaf((float)((bfz >> (8 * k)) & 0xffu), ciz, -gzf);
+    const float tn = fmaxn(fmaxn(txn, tyn), fmaxn(tzn, kRayTMin));
+    const float tf = fminn(fminn(txf, tyf), fminn(tzf, tfar));
+    hit[k] = tn <= tf * kBoxPad;
+    key[k] = tn;
+  }
+}
+// the child the step enters: the hit one of least key, the lowest slot on a tie; -1 when none is hit
+int nearest_child(const float key[4], const bool hit[4]) {
+  float kmin = kInf;
+  bool any_hit = false;
+  for (int k = 0; k < 4; k++)
+    if (hit[k]) { kmin = any_hit ? fminn(kmin, key[k]) : key[k]; any_hit = true; }
+  int nearest = -1;
+  for (int k = 0; k < 4 && nearest < 0; k++)
+    if (hit[k] && key[k] == kmin) nearest = k;
+  if (any_hit && nearest < 0) nearest = 3;  // (the kernel's n3 = none of the first three)
+  return nearest;
+}
+
 // measurement aid (tools/treetop_sim.py): when set, every node step adds one to its node's counter
 uint64_t *g_visits = nullptr;
 
@@ -76,20 +129,7 @@ void walk(const Tree &T, V3 o, V3 d, float tmax, bool any, Out *out) {
     const bool inside = o.x >= b[0] && o.x <= b[3] && o.y >= b[1] && o.y <= b[4] && o.z >= b[2] && o.z <= b[5];
     if (inside || box_test(b, o, inv1, tmax)) cur = (T.root_ref & kLeafRef) ? T.root_ref : 0u;
   }
-  // the kernel's stand-in for 1 / 0 (kernel_walk.hpp trav_run; pbrt_amd/csrc/host_math.hpp inv_parallel_for_extent, restated)
-  float big;
-  {
-    const float *b = T.root_box;
-    const float extent = std::fmax(b[3] - b[0], std::fmax(b[4] - b[1], b[5] - b[2]));
-    int x = 0;
-    if (extent > 0.f && std::isfinite(extent)) (void)std::frexp(2.0f * extent, &x);
-    int e = 123 - x;
-    if (e > 120) e = 120;
-    if (e < -100) e = -100;
-    big = std::ldexp(1.0f, e);
-  }
-  const V3 inv = {d.x == 0.f ? std::copysign(big, inv1.x) : inv1.x, d.y == 0.f ? std::copysign(big, inv1.y) : inv1.y,
-                  d.z == 0.f ? std::copysign(big, inv1.z) : inv1.z};
+  const V3 inv = walk_inv(d, inv1, inv_parallel_for_root(T.root_box));
   std::vector<uint32_t> stack;
   stack.reserve(64);
   // experiment (ORC_WALK_CULL=n): every stacked entry carries its entry distance rounded DOWN to its n top bits (32: exact);
@@ -123,26 +163,9 @@ void walk(const Tree &T, V3 o, V3 d, float tmax, bool any, Out *out) {
       r.steps++;
       if (g_visits) __atomic_fetch_add(&g_visits[cur / 64u], 1ull, __ATOMIC_RELAXED);
       const float tfar = fminn(r.t, tmax);
-      const float gx = (o.x - as_f(W[0])) * inv.x, gy = (o.y - as_f(W[1])) * inv.y, gz = (o.z - as_f(W[2])) * inv.z;
-      constexpr float kMargin = 0x1.8p-22f;
-      const float gxn = std::fmaf(std::fabs(gx), kMargin, gx), gxf = std::fmaf(-std::fabs(gx), kMargin, gx);
-      const float gyn = std::fmaf(std::fabs(gy), kMargin, gy), gyf = std::fmaf(-std::fabs(gy), kMargin, gy);
-      const float gzn = std::fmaf(std::fabs(gz), kMargin, gz), gzf = std::fmaf(-std::fabs(gz), kMargin, gz);
-      const float cix = as_f(W[3]) * inv.x, ciy = as_f(W[10]) * inv.y, ciz = as_f(W[11]) * inv.z;
-      const uint32_t bnx = negx ? W[7] : W[4], bfx = negx ? W[4] : W[7];
-      const uint32_t bny = negy ? W[8] : W[5], bfy = negy ? W[5] : W[8];
-      const uint32_t bnz = negz ? W[9] : W[6], bfz = negz ? W[6] : W[9];
       float key[4];
       bool hit[4];
-      for (int k = 0; k < 4; k++) {
-        const float txn = std::fmaf((float)((bnx >> (8 * k)) & 0xffu), cix, -gxn), txf = std::fmaf((float)((bfx >> (8 * k)) & 0xffu), cix, -gxf);
-        const float tyn = std::fmaf((float)((bny >> (8 * k)) & 0xffu), ciy, -gyn), tyf = std::fmaf((float)((bfy >> (8 * k)) & 0xffu), ciy, -gyf);
-        const float tzn = std::fmaf((float)((bnz >> (8 * k)) & 0xffu), ciz, -gzn), tzf = std::fmaf((float)((bfz >> (8 * k)) & 0xffu), ciz, -gzf);
-        const float tn = fmaxn(fmaxn(txn, tyn), fmaxn(tzn, kRayTMin));
-        const float tf = fminn(fminn(txf, tyf), fminn(tzf, tfar));
-        hit[k] = tn <= tf * kBoxPad;
-        key[k] = tn;
-      }
+      quad_step(W, o, inv, negx, negy, negz, tfar, key, hit);
       if (T.exact) {  // experiment: what the walk would cost with full-precision child boxes
         const float *E = T.exact + (size_t)(cur / 64u) * 24u;
         for (int k = 0; k < 4; k++) {
@@ -156,14 +179,8 @@ void walk(const Tree &T, V3 o, V3 d, float tmax, bool any, Out *out) {
           key[k] = tn;
         }
       }
-      float kmin = kInf;
-      bool any_hit = false;
-      for (int k = 0; k < 4; k++)
-        if (hit[k]) { kmin = any_hit ? fminn(kmin, key[k]) : key[k]; any_hit = true; }
-      int nearest = -1;
-      for (int k = 0; k < 4 && nearest < 0; k++)
-        if (hit[k] && key[k] == kmin) nearest = k;
-      if (any_hit && nearest < 0) nearest = 3;  // (the kernel's n3 = none of the first three)
+      const int nearest = nearest_child(key, hit);
+      const bool any_hit = nearest >= 0;
       static const int order_mode = std::getenv("ORC_WALK_ORDER") ? std::atoi(std::getenv("ORC_WALK_ORDER")) : 0;
       if (order_mode == 1) {  // experiment: the other hit children stacked by entry distance, the farthest deepest
         int ks[4], m = 0;
@@ -250,23 +267,12 @@ void walk(const Tree &T, V3 o, V3 d, float tmax, bool any, Out *out) {
 
 }  // namespace
 
-// The production node step's test of child k of quad node W against [kRayTMin, tfar] -- the arithmetic of walk() above, for one child
+// The production node step's test of child k of quad node W against [kRayTMin, tfar]: quad_step above, one child of it
 static bool child_passes(const uint32_t *W, int k, V3 o, V3 inv, bool negx, bool negy, bool negz, float tfar) {
-  const float gx = (o.x - as_f(W[0])) * inv.x, gy = (o.y - as_f(W[1])) * inv.y, gz = (o.z - as_f(W[2])) * inv.z;
-  constexpr float kMargin = 0x1.8p-22f;
-  const float gxn = std::fmaf(std::fabs(gx), kMargin, gx), gxf = std::fmaf(-std::fabs(gx), kMargin, gx);
-  const float gyn = std::fmaf(std::fabs(gy), kMargin, gy), gyf = std::fmaf(-std::fabs(gy), kMargin, gy);
-  const float gzn = std::fmaf(std::fabs(gz), kMargin, gz), gzf = std::fmaf(-std::fabs(gz), kMargin, gz);
-  const float cix = as_f(W[3]) * inv.x, ciy = as_f(W[10]) * inv.y, ciz = as_f(W[11]) * inv.z;
-  const uint32_t bnx = negx ? W[7] : W[4], bfx = negx ? W[4] : W[7];
-  const uint32_t bny = negy ? W[8] : W[5], bfy = negy ? W[5] : W[8];
-  const uint32_t bnz = negz ? W[9] : W[6], bfz = negz ? W[6] : W[9];
-  const float txn = std::fmaf((float)((bnx >> (8 * k)) & 0xffu), cix, -gxn), txf = std::fmaf((float)((bfx >> (8 * k)) & 0xffu), cix, -gxf);
-  const float tyn = std::fmaf((float)((bny >> (8 * k)) & 0xffu), ciy, -gyn), tyf = std::fmaf((float)((bfy >> (8 * k)) & 0xffu), ciy, -gyf);
-  const float tzn = std::fmaf((float)((bnz >> (8 * k)) & 0xffu), ciz, -gzn), tzf = std::fmaf((float)((bfz >> (8 * k)) & 0xffu), ciz, -gzf);
-  const float tn = fmaxn(fmaxn(txn, tyn), fmaxn(tzn, kRayTMin));
-  const float tf = fminn(fminn(txf, tyf), fminn(tzf, tfar));
-  return tn <= tf * kBoxPad;
+  float key[4];
+  bool hit[4];
+  quad_step(W, o, inv, negx, negy, negz, tfar, key, hit);
+  return hit[k];
 }
 
 // What the own-box rule of DESIGN.md 3.5 PROMISES, checked node by node on a product builder's quantised tree: for ray i and a triangle
@@ -296,16 +302,7 @@ extern "C" void orc_quad_path_check(const uint32_t *quads, uint32_t n_quads, con
     const V3 oo = {o[3 * i], o[3 * i + 1], o[3 * i + 2]}, dd = {d[3 * i], d[3 * i + 1], d[3 * i + 2]};
     const V3 inv1 = {1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z};
     const bool negx = inv1.x < 0.f, negy = inv1.y < 0.f, negz = inv1.z < 0.f;
-    float big;
-    {
-      const float extent = std::fmax(root_box[3] - root_box[0], std::fmax(root_box[4] - root_box[1], root_box[5] - root_box[2]));
-      int x = 0;
-      if (extent > 0.f && std::isfinite(extent)) (void)std::frexp(2.0f * extent, &x);
-      int e = 123 - x;
-      e = e > 120 ? 120 : (e < -100 ? -100 : e);
-      big = std::ldexp(1.0f, e);
-    }
-    const V3 inv = {dd.x == 0.f ? std::copysign(big, inv1.x) : inv1.x, dd.y == 0.f ? std::copysign(big, inv1.y) : inv1.y, dd.z == 0.f ? std::copysign(big, inv1.z) : inv1.z};
+    const V3 inv = walk_inv(dd, inv1, inv_parallel_for_root(root_box));
     const bool inside = oo.x >= root_box[0] && oo.x <= root_box[3] && oo.y >= root_box[1] && oo.y <= root_box[4] && oo.z >= root_box[2] && oo.z <= root_box[5];
     if (!inside && !box_test(root_box, oo, inv1, th[i])) fails[i]++;
     Up u = slot_up[slot_of[tri[i]]];
@@ -315,6 +312,24 @@ extern "C" void orc_quad_path_check(const uint32_t *quads, uint32_t n_quads, con
       u = node_up[u.node];
     }
   }
+}
+
+// The blocks op QUAD_STEP / QUAD_STEP_PK (orc_blocks_eval; the host has one fma, the two ops are the same statement): x = the node's 16
+// words as raw bits, o (3), d (3), inv_parallel, tfar -> y = tn of children 0 .. 3, the hit mask, the slot entered (4 = none) -- with
+// what walk() does around the step: the true 1 / d and its signs, the stand-in on a parallel axis
+extern "C" void orc_quad_step_eval(const float *x, float *y) {
+  uint32_t W[16];
+  std::memcpy(W, x, sizeof W);
+  const V3 o = {x[16], x[17], x[18]}, d = {x[19], x[20], x[21]};
+  const V3 inv1 = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+  const V3 inv = walk_inv(d, inv1, x[22]);
+  float key[4];
+  bool hit[4];
+  quad_step(W, o, inv, inv1.x < 0.f, inv1.y < 0.f, inv1.z < 0.f, x[23], key, hit);
+  for (int k = 0; k < 4; k++) y[k] = key[k];
+  y[4] = (float)((hit[0] ? 1 : 0) | (hit[1] ? 2 : 0) | (hit[2] ? 4 : 0) | (hit[3] ? 8 : 0));
+  const int nearest = nearest_child(key, hit);
+  y[5] = nearest < 0 ? 4.0f : (float)nearest;
 }
 
 // per-node visit counters of the walks that follow (n_quads uint64 words, or null to stop counting)

@@ -19,8 +19,8 @@ constexpr float kInf = __builtin_huge_valf();
 constexpr float kRayTMin = 1e-4f;
 constexpr float kSpawnEps = 1e-4f;
 constexpr float kShadowShrink = 0.9999f;
-constexpr float kBoxPad = 0x1.000004p+0f;  // 1 + 2^-19: the node test's far-side pad (pbrt-v3 pads by 1 + 2 gamma(3) = 1 + 6 * 2^-24)
-constexpr float kOwnPad = 0x1.000001p+0f;  // 1 + 2^-21: the own-box rule's pad (3.5), strictly inside kBoxPad
+constexpr float kBoxPad = 0x1.000004p+0f;  // MEANT as 1 + 2^-19, IS 1 + 2^-22 (six hex digits are 24 bits: DESIGN.md 3.4's finding, section 12 item 4): the node test's far-side pad (pbrt-v3 pads by 1 + 2 gamma(3) = 1 + 6 * 2^-24)
+constexpr float kOwnPad = 0x1.000001p+0f;  // MEANT as 1 + 2^-21, IS 1: the literal is 1 + 2^-24 and rounds to 1 (DESIGN.md 3.5's finding, section 12 item 4): the own-box rule's pad (3.5), strictly inside kBoxPad
 constexpr float kInvPi = 0.31830988618379067154f;
 constexpr float kPiOver4 = 0.78539816339744830961f;
 constexpr float kOneMinusEps = 0x1.fffffcp-1f;  // 1 - f32::EPSILON = 1 - 2^-23, core/rng.rs:19 (NOT pbrt-v3's 1 - 2^-24)

@@ -158,6 +158,65 @@ __device__ __forceinline__ void trav_begin(const DevScene &S, Trav &T, uint32_t 
   }
 }
 
+// The production walk's inverse direction: 1 / d, with the scene's finite stand-in for 1 / 0 on an axis the ray is parallel to
+// (trav_run below says why)
+__device__ __forceinline__ V3 walk_inv(const V3 d, const V3 inv1, const float inv_parallel) {
+  return V3{d.x == 0.f ? copysignf(inv_parallel, inv1.x) : inv1.x, d.y == 0.f ? copysignf(inv_parallel, inv1.y) : inv1.y,
+            d.z == 0.f ? copysignf(inv_parallel, inv1.z) : inv1.z};
+}
+
+// One node step's arithmetic (trav_run below; comments at its call): the four children of quantised node words W0 .. W2 against
+// [kRayTMin, tfar] -> key[k] = the child's entry distance, hit[k].  A function of its own so that pbrt_hip_blocks_eval_device
+// (kernels_blocks.hip) runs the walk's own statement over arrays; SCALAR_FMA: the 24 plane fmas scalar or packed (the same bits).
+template <bool SCALAR_FMA>
+__device__ __forceinline__ void quad_step(const uint4 W0, const uint4 W1, const uint4 W2, const V3 o, const V3 inv, const bool negx,
+                                          const bool negy, const bool negz, const float tfar, float (&key)[4], bool (&hit)[4]) {
+  const float gx = (o.x - __uint_as_float(W0.x)) * inv.x, gy = (o.y - __uint_as_float(W0.y)) * inv.y;
+  const float gz = (o.z - __uint_as_float(W0.z)) * inv.z;
+  // g +- 3 eps |g| as one fma each (|x| and -x are operand modifiers): rounded once instead of twice, at least
+  // g +- 5/2 eps |g|, still beyond the 2 eps |g| the margin has to cover
+  constexpr float kMargin = 0x1.8p-22f;
+  const float gxn = __builtin_fmaf(fabsf(gx), kMargin, gx), gxf = __builtin_fmaf(-fabsf(gx), kMargin, gx);  // near, far: subtracted below
+  const float gyn = __builtin_fmaf(fabsf(gy), kMargin, gy), gyf = __builtin_fmaf(-fabsf(gy), kMargin, gy);
+  const float gzn = __builtin_fmaf(fabsf(gz), kMargin, gz), gzf = __builtin_fmaf(-fabsf(gz), kMargin, gz);
+  const float cix = __uint_as_float(W0.w) * inv.x, ciy = __uint_as_float(W2.z) * inv.y, ciz = __uint_as_float(W2.w) * inv.z;
+  // near / far planes by the sign of the inverse direction: one select per axis serves all four
+  // children (a dword holds the four children's bytes of one plane)
+  const uint32_t bnx = negx ? W1.w : W1.x, bfx = negx ? W1.x : W1.w;
+  const uint32_t bny = negy ? W2.x : W1.y, bfy = negy ? W1.y : W2.x;
+  const uint32_t bnz = negz ? W2.y : W1.z, bfz = negz ? W1.z : W2.y;
+  // How the 24 plane fmas are issued.  A gfx950 SIMD issues, per quad-cycle, one instruction of any kind plus one of
+  // the "simple" class (fma, mul, add, logic, right shift, mov) from another wave; a packed instruction goes alone
+  // (tools/ubench/valu_pairing.hip, profiles/r03w_valu_pairing_ubench.txt).  This step has three converts / min /
+  // max / compares / selects for every simple instruction, so 24 scalar v_fma_f32 ride along with them where 12
+  // v_pk_fma_f32 take 12 quad-cycles of their own -- but they are 12 more instructions for a wave that issues one
+  // every ~5 cycles at best.  Measured (profiles/r03w_scalar_fma_ab.txt): trees that sit in L2 (no wait to hide: C4
+  // +4.7 %, C2 +1.6 %) gain from the scalar form; the deep trees of the overflow variant, whose waves spend their time
+  // waiting for nodes, lose (C3 -0.8 %, 12 M triangles -6.5 %) and keep the packed one ({near, far} of a child side by
+  // side; IEEE per element: the same bits either way).
+  const f32x2 gxx = {gxn, gxf}, gyy = {gyn, gyf}, gzz = {gzn, gzf}, cxx = {cix, cix}, cyy = {ciy, ciy}, czz = {ciz, ciz};
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const float qxn = (float)((bnx >> (8 * k)) & 0xffu), qxf = (float)((bfx >> (8 * k)) & 0xffu);
+    const float qyn = (float)((bny >> (8 * k)) & 0xffu), qyf = (float)((bfy >> (8 * k)) & 0xffu);
+    const float qzn = (float)((bnz >> (8 * k)) & 0xffu), qzf = (float)((bfz >> (8 * k)) & 0xffu);
+    f32x2 tx, ty, tz;  // {near, far}
+    if (SCALAR_FMA) {
+      tx = f32x2{__builtin_fmaf(qxn, cix, -gxn), __builtin_fmaf(qxf, cix, -gxf)};
+      ty = f32x2{__builtin_fmaf(qyn, ciy, -gyn), __builtin_fmaf(qyf, ciy, -gyf)};
+      tz = f32x2{__builtin_fmaf(qzn, ciz, -gzn), __builtin_fmaf(qzf, ciz, -gzf)};
+    } else {
+      tx = __builtin_elementwise_fma(f32x2{qxn, qxf}, cxx, -gxx);
+      ty = __builtin_elementwise_fma(f32x2{qyn, qyf}, cyy, -gyy);
+      tz = __builtin_elementwise_fma(f32x2{qzn, qzf}, czz, -gzz);
+    }
+    const float tn = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, kRayTMin));
+    const float tf = fminf(fminf(tx.y, ty.y), fminf(tz.y, tfar));
+    hit[k] = tn <= tf * kBoxPad;
+    key[k] = tn;
+  }
+}
+
 // The traversal loop of a whole wave ("while-while" with parked leaves) over the child-pair nodes.
 // Every lane walks its own ray through the binary tree of DESIGN.md 3.3 in the order of 3.4 (near
 // child by the sign of the split axis first, far child pushed); one step fetches ONE 64-byte record
@@ -191,9 +250,7 @@ __device__ __forceinline__ void trav_run(const DevScene &S, Trav &T, uint32_t *s
 #ifdef PBRT_INV_INF  // A-B switch: the walk as it was before the stand-in (tools/experiments/README.md, round 5)
   const V3 inv = inv1;
 #else
-  const V3 inv = EXACT ? inv1
-                       : V3{d.x == 0.f ? copysignf(S.inv_parallel, inv1.x) : inv1.x, d.y == 0.f ? copysignf(S.inv_parallel, inv1.y) : inv1.y,
-                            d.z == 0.f ? copysignf(S.inv_parallel, inv1.z) : inv1.z};
+  const V3 inv = EXACT ? inv1 : walk_inv(d, inv1, S.inv_parallel);
 #endif
   const char *nodes = reinterpret_cast<const char *>(S.nodes);
   const char *quads = reinterpret_cast<const char *>(S.quads);
@@ -275,53 +332,9 @@ __device__ __forceinline__ void trav_run(const DevScene &S, Trav &T, uint32_t *s
       // parallel to the slab (d = 0) has the scene's finite stand-in for 1 / 0 in inv (above): t is then
       // negative huge or positive huge by the side of the plane the origin is on; an inv that is infinite
       // because d is a denormal yields NaN or +-inf, which fmin / fmax ignore or keep conservative.
-      const float gx = (o.x - __uint_as_float(W0.x)) * inv.x, gy = (o.y - __uint_as_float(W0.y)) * inv.y;
-      const float gz = (o.z - __uint_as_float(W0.z)) * inv.z;
-      // g +- 3 eps |g| as one fma each (|x| and -x are operand modifiers): rounded once instead of twice, at least
-      // g +- 5/2 eps |g|, still beyond the 2 eps |g| the margin has to cover
-      constexpr float kMargin = 0x1.8p-22f;
-      const float gxn = __builtin_fmaf(fabsf(gx), kMargin, gx), gxf = __builtin_fmaf(-fabsf(gx), kMargin, gx);  // near, far: subtracted below
-      const float gyn = __builtin_fmaf(fabsf(gy), kMargin, gy), gyf = __builtin_fmaf(-fabsf(gy), kMargin, gy);
-      const float gzn = __builtin_fmaf(fabsf(gz), kMargin, gz), gzf = __builtin_fmaf(-fabsf(gz), kMargin, gz);
-      const float cix = __uint_as_float(W0.w) * inv.x, ciy = __uint_as_float(W2.z) * inv.y, ciz = __uint_as_float(W2.w) * inv.z;
-      // near / far planes by the sign of the inverse direction: one select per axis serves all four
-      // children (a dword holds the four children's bytes of one plane)
-      const uint32_t bnx = negx ? W1.w : W1.x, bfx = negx ? W1.x : W1.w;
-      const uint32_t bny = negy ? W2.x : W1.y, bfy = negy ? W1.y : W2.x;
-      const uint32_t bnz = negz ? W2.y : W1.z, bfz = negz ? W1.z : W2.y;
-      // How the 24 plane fmas are issued.  A gfx950 SIMD issues, per quad-cycle, one instruction of any kind plus one of
-      // the "simple" class (fma, mul, add, logic, right shift, mov) from another wave; a packed instruction goes alone
-      // (tools/ubench/valu_pairing.hip, profiles/r03w_valu_pairing_ubench.txt).  This step has three converts / min /
-      // max / compares / selects for every simple instruction, so 24 scalar v_fma_f32 ride along with them where 12
-      // v_pk_fma_f32 take 12 quad-cycles of their own -- but they are 12 more instructions for a wave that issues one
-      // every ~5 cycles at best.  Measured (profiles/r03w_scalar_fma_ab.txt): trees that sit in L2 (no wait to hide: C4
-      // +4.7 %, C2 +1.6 %) gain from the scalar form; the deep trees of the overflow variant, whose waves spend their time
-      // waiting for nodes, lose (C3 -0.8 %, 12 M triangles -6.5 %) and keep the packed one ({near, far} of a child side by
-      // side; IEEE per element: the same bits either way).
-      constexpr bool kScalarFma = OVFR == 0u;
-      const f32x2 gxx = {gxn, gxf}, gyy = {gyn, gyf}, gzz = {gzn, gzf}, cxx = {cix, cix}, cyy = {ciy, ciy}, czz = {ciz, ciz};
       float key[4];
       bool hit[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const float qxn = (float)((bnx >> (8 * k)) & 0xffu), qxf = (float)((bfx >> (8 * k)) & 0xffu);
-        const float qyn = (float)((bny >> (8 * k)) & 0xffu), qyf = (float)((bfy >> (8 * k)) & 0xffu);
-        const float qzn = (float)((bnz >> (8 * k)) & 0xffu), qzf = (float)((bfz >> (8 * k)) & 0xffu);
-        f32x2 tx, ty, tz;  // {near, far}
-        if (kScalarFma) {
-          tx = f32x2{__builtin_fmaf(qxn, cix, -gxn), __builtin_fmaf(qxf, cix, -gxf)};
-          ty = f32x2{__builtin_fmaf(qyn, ciy, -gyn), __builtin_fmaf(qyf, ciy, -gyf)};
-          tz = f32x2{__builtin_fmaf(qzn, ciz, -gzn), __builtin_fmaf(qzf, ciz, -gzf)};
-        } else {
-          tx = __builtin_elementwise_fma(f32x2{qxn, qxf}, cxx, -gxx);
-          ty = __builtin_elementwise_fma(f32x2{qyn, qyf}, cyy, -gyy);
-          tz = __builtin_elementwise_fma(f32x2{qzn, qzf}, czz, -gzz);
-        }
-        const float tn = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, kRayTMin));
-        const float tf = fminf(fminf(tx.y, ty.y), fminf(tz.y, tfar));
-        hit[k] = tn <= tf * kBoxPad;
-        key[k] = tn;
-      }
+      quad_step<OVFR == 0u>(W0, W1, W2, o, inv, negx, negy, negz, tfar, key, hit);
       // (an unused child slot holds kEmptyLeafRef behind an inverted box: if a degenerate ray gets through that box the
       // lane parks at a leaf without triangles and pops -- no test for it here)
 #ifdef PBRT_PRIO_SELECT  // (A-B: raised priority from the child selection on)
@@ -330,13 +343,7 @@ __device__ __forceinline__ void trav_run(const DevScene &S, Trav &T, uint32_t *s
       // The nearest child hit is entered, the other hit ones are stacked in slot order.  Order affects only
       // speed (tie rule of 3.4) -- but a lot: visiting the hit children in slot order alone costs C3 49 node steps per
       // ray instead of 41 (measured, r02), and sorting the stacked ones cost more than it saved (r01).
-#pragma unroll
-      // (a missed child's key is a NaN with all bits set -- an inline constant of the select, where +inf would need a
-      // register; fminf ignores it, and when every child is missed nothing below uses kmin)
-      for (int k = 0; k < 4; k++) key[k] = hit[k] ? key[k] : __uint_as_float(0xffffffffu);
-      const float kmin = fminf(fminf(key[0], key[1]), fminf(key[2], key[3]));
-      const bool n0 = key[0] == kmin, n1 = !n0 && key[1] == kmin, n2 = !n0 && !n1 && key[2] == kmin;
-      const bool n3 = !n0 && !n1 && !n2;
+#include "quad_nearest.inc"
       const bool any_hit = hit[0] || hit[1] || hit[2] || hit[3];
       const uint32_t nearest = n0 ? W3.x : (n1 ? W3.y : (n2 ? W3.z : W3.w));
       // Overflow variant (trees whose worst-case stack bound exceeds the LDS part): one wave-uniform test per step -- is
@@ -393,41 +400,7 @@ __device__ __forceinline__ void trav_run(const DevScene &S, Trav &T, uint32_t *s
           const float4 c = EXP_TRI_LOAD(reinterpret_cast<const float4 *>(tris + slot * (16u * kTriStride) + 32u));
           wave_prio(PBRT_PRIO_ARITH);
           if (COUNT) ct++;
-              // Moeller-Trumbore, operation order of DESIGN.md 3.5
-          const V3 p0 = xyz(a);
-          const V3 e1 = xyz(b) - p0, e2 = xyz(c) - p0;
-          const V3 pv = cross(d, e2);
-          const float det = dot(e1, pv);
-          // Branch-free from here: every lane of the pass computes u, v and t (a degenerate triangle's 1 / det is inf or
-          // NaN and fails the tests below like any miss) and the hit record is updated by selects.  The nested early-outs
-          // this replaces skipped work only when ALL lanes of the pass failed the same test, and the compiler paid for
-          // them with copies of the six hit-record registers at every level (about 50 v_mov per pass).
-          const float idet = 1.0f / det;
-          const V3 tv = o - p0;
-          const float u = dot(tv, pv) * idet;
-          const V3 qv = cross(tv, e1);
-          const float v = dot(d, qv) * idet;
-          const float th = dot(e2, qv) * idet;
-          // The own-box rule (round 6): the ray must MEET the triangle's own box -- the node test of 3.4 on it: slab distances
-          // of the three vertices with the TRUE 1 / d (two roundings each, as the canonical node test; p0 - o = -tv exactly), their min / max
-          // per axis, pad kOwnPad < kBoxPad -- and the hit's distance is at least the box's entry: t = max(th, entry).  Monotone arithmetic:
-          // every enclosing box of every tree then passes its own test while the walk's best hit is still >= t, so an accepted hit is reached
-          // by every walk and a hit is a function of (ray, triangle) alone.  (Raising t instead of rejecting: a triangle flat in an axis plane
-          // has entry = exit = the plane's slab distance, which Moeller-Trumbore's t misses by rounding.)
-#ifdef PBRT_NO_OWN_BOX_RULE  // A-B switch: the leaf pass as it was until round 5 (what the rule costs; films differ where it rejects)
-          const bool in_own_box = true;
-          const float tsnap = th;
-#else
-          const V3 w1 = xyz(b) - o, w2 = xyz(c) - o;
-          const float x0 = (-tv.x) * inv1.x, x1 = w1.x * inv1.x, x2 = w2.x * inv1.x;
-          const float y0 = (-tv.y) * inv1.y, y1 = w1.y * inv1.y, y2 = w2.y * inv1.y;
-          const float z0 = (-tv.z) * inv1.z, z1 = w1.z * inv1.z, z2 = w2.z * inv1.z;
-          const float otn = fmaxf(fmaxf(fminf(fminf(x0, x1), x2), fminf(fminf(y0, y1), y2)), fmaxf(fminf(fminf(z0, z1), z2), kRayTMin));
-          const float otf = fminf(fminf(fmaxf(fmaxf(x0, x1), x2), fmaxf(fmaxf(y0, y1), y2)), fmaxf(fmaxf(z0, z1), z2));
-          const bool in_own_box = otn <= otf * kOwnPad;
-          const float tsnap = fmaxf(th, otn);
-#endif
-          bool valid = in_own_box && !(fabsf(det) < 1e-8f) && (u >= 0.f) && (v >= 0.f) && (u + v <= 1.0f) && (th > kRayTMin) && (tsnap < T.tmax);
+#include "tri_test.inc"
           float ht = tsnap, hu = u, hv = v;
           if (SPH && __float_as_uint(c.w) != 0u) {
             // a SPHERE's record (round 6: spheres are primitives of the tree): {centre, primitive id}{radius, -, -, material}

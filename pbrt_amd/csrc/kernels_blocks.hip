@@ -1,6 +1,6 @@
 // kernels_blocks.hip -- the kernels' building blocks over arrays: pbrt_hip_blocks_eval_device, the hook that lets tests/ compare the
-// polynomials of cephes_poly.hpp, envmap_core.hpp's sincos_0_2pi and kernel_math.hpp's sphere_uv / glass_fresnel / cosine_about /
-// sphere_hit with a float64 reference and with the oracle's restatements, element by element, without a render around them.  In a
+// polynomials of cephes_poly.hpp, envmap_core.hpp's sincos_0_2pi, kernel_math.hpp's sphere_uv / glass_fresnel / cosine_about /
+// sphere_hit and the walk's node step and triangle test (kernel_walk.hpp quad_step / walk_inv, quad_nearest.inc, tri_test.inc) with a float64 reference and with the oracle's restatements, element by element, without a render around them.  In a
 // translation unit of its own so that the render and intersect kernels of kernels*.hip keep their names and their machine code.
 //
 //   blocks_eval_kernel  one element per thread, 256 threads per workgroup: switches on the op code and calls the PRODUCTION function
@@ -8,6 +8,7 @@
 #include "capi_internal.hpp"
 #include "envmap_core.hpp"
 #include "kernel_math.hpp"
+#include "kernel_walk.hpp"
 
 namespace pbrt_hip {
 namespace {
@@ -16,7 +17,7 @@ struct BlockWidth {
   uint32_t in, out;
 };
 // indexed by op (include/pbrt_hip_debug.h PBRT_HIP_BLOCK_*)
-constexpr BlockWidth kBlockWidth[PBRT_HIP_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}};
+constexpr BlockWidth kBlockWidth[PBRT_HIP_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}, {24, 6}, {24, 6}, {16, 4}};
 
 __global__ void __launch_bounds__(256) blocks_eval_kernel(uint32_t op, int64_t n, uint32_t w_in, uint32_t w_out, const float *in, float *out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -47,6 +48,38 @@ __global__ void __launch_bounds__(256) blocks_eval_kernel(uint32_t op, int64_t n
       const bool hit = sphere_hit(make_float4(x[0], x[1], x[2], x[3]), mk(x[4], x[5], x[6]), mk(x[7], x[8], x[9]), x[10], th);
       y[0] = hit ? 1.0f : 0.f;
       y[1] = hit ? th : 0.f;  // (a miss leaves no distance)
+      break;
+    }
+    case PBRT_HIP_BLOCK_QUAD_STEP:
+    case PBRT_HIP_BLOCK_QUAD_STEP_PK: {
+      // what trav_run does around the step: the true 1 / d and its signs, the stand-in on a parallel axis
+      const uint32_t *w = reinterpret_cast<const uint32_t *>(x);  // the node's 16 words as they are
+      const uint4 W0 = make_uint4(w[0], w[1], w[2], w[3]), W1 = make_uint4(w[4], w[5], w[6], w[7]), W2 = make_uint4(w[8], w[9], w[10], w[11]);
+      const V3 o = mk(x[16], x[17], x[18]), d = mk(x[19], x[20], x[21]);
+      const V3 inv1 = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+      const bool negx = inv1.x < 0.f, negy = inv1.y < 0.f, negz = inv1.z < 0.f;
+      const V3 inv = walk_inv(d, inv1, x[22]);
+      float key[4];
+      bool hit[4];
+      if (op == PBRT_HIP_BLOCK_QUAD_STEP) quad_step<true>(W0, W1, W2, o, inv, negx, negy, negz, x[23], key, hit);
+      else quad_step<false>(W0, W1, W2, o, inv, negx, negy, negz, x[23], key, hit);
+      for (int k = 0; k < 4; k++) y[k] = key[k];
+      y[4] = (float)((hit[0] ? 1 : 0) | (hit[1] ? 2 : 0) | (hit[2] ? 4 : 0) | (hit[3] ? 8 : 0));
+#include "quad_nearest.inc"
+      y[5] = !(hit[0] || hit[1] || hit[2] || hit[3]) ? 4.0f : (n0 ? 0.f : (n1 ? 1.0f : (n2 ? 2.0f : (n3 ? 3.0f : 4.0f))));
+      break;
+    }
+    case PBRT_HIP_BLOCK_TRI_HIT: {
+      const float4 a = make_float4(x[0], x[1], x[2], 0.f), b = make_float4(x[3], x[4], x[5], 0.f), c = make_float4(x[6], x[7], x[8], 0.f);
+      const V3 o = mk(x[9], x[10], x[11]), d = mk(x[12], x[13], x[14]);
+      const V3 inv1 = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+      Trav T;
+      T.tmax = x[15];
+#include "tri_test.inc"
+      y[0] = valid ? 1.0f : 0.f;
+      y[1] = valid ? tsnap : 0.f;  // (zeros on a miss)
+      y[2] = valid ? u : 0.f;
+      y[3] = valid ? v : 0.f;
       break;
     }
     default: break;

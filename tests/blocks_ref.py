@@ -1,5 +1,6 @@
 """Input sets, float64 references and error bounds of the building-block tests (tests/test_blocks_host.py on the oracle's restatements,
-tests/test_blocks_gpu.py on the device through pbrt_hip_blocks_eval_device).
+tests/test_blocks_gpu.py on the device through pbrt_hip_blocks_eval_device).  The walk's node step and triangle test have theirs in
+tests/walk_ref.py.
 
 The references are numpy float64 written from the mathematics -- np.sin / np.cos / np.arctan / np.arccos, pbrt-v3's FrDielectric formula,
 the concentric disk map, the sphere's (phi / 2 pi, 1 - theta / pi), the quadratic's roots (util.sphere_hits_f64) -- and share no line with
@@ -11,6 +12,8 @@ DESIGN.md 3.6's table.  The composite operations' bounds are derived from those 
 element; nothing is taken from the outputs under test.  check(...) functions return the figures they assert on, so that a caller can
 print them."""
 import numpy as np
+
+import walk_ref as wr
 
 U = 2.0 ** -24                      # the unit roundoff of float32
 F32 = np.float32
@@ -387,7 +390,21 @@ def wild_inputs(op):
     return None
 
 
-ALL_OPS = ("SIN", "COS", "ATAN_POS", "ACOS", "SINCOS", "SPHERE_UV", "FRESNEL", "COSINE_ABOUT", "SPHERE_HIT")
+ALL_OPS = ("SIN", "COS", "ATAN_POS", "ACOS", "SINCOS", "SPHERE_UV", "FRESNEL", "COSINE_ABOUT", "SPHERE_HIT", "QUAD_STEP", "QUAD_STEP_PK", "TRI_HIT")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# QUAD_STEP, QUAD_STEP_PK and TRI_HIT: the walk's node step and triangle test (tests/walk_ref.py).  TRI_HIT's set here is the flat triangles
+# and the exact-arithmetic rays; its ladder of rungs has tests of its own (2^14 rays a rung: a size at a time)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def tri_hit_inputs():
+    flat, _ = wr.tri_flat_inputs()
+    exact = wr.tri_exact_inputs()
+    return np.concatenate([flat, exact]), len(flat)
+
+
+def check_tri_hit_sets(x, n_flat, got):
+    return {"flat": wr.check_tri_rays(x[:n_flat], got[:n_flat], flat=True), "exact": wr.check_tri_exact(x[n_flat:], got[n_flat:])}
 
 
 def inputs(op):
@@ -396,6 +413,10 @@ def inputs(op):
         return poly_inputs(op)[:, None], None
     if op == "SPHERE_HIT":
         return sphere_hit_inputs()
+    if op in ("QUAD_STEP", "QUAD_STEP_PK"):
+        return wr.quad_step_inputs()
+    if op == "TRI_HIT":
+        return tri_hit_inputs()
     return {"SPHERE_UV": sphere_uv_inputs, "FRESNEL": fresnel_inputs, "COSINE_ABOUT": cosine_inputs}[op](), None
 
 
@@ -405,4 +426,8 @@ def check(op, x, aux, got):
         return check_poly(op, x[:, 0], got)
     if op == "SPHERE_HIT":
         return check_sphere_hit(aux, got)
+    if op in ("QUAD_STEP", "QUAD_STEP_PK"):
+        return wr.check_quad_step(x, aux, got)
+    if op == "TRI_HIT":
+        return check_tri_hit_sets(x, aux, got)
     return {"SPHERE_UV": check_sphere_uv, "FRESNEL": check_fresnel, "COSINE_ABOUT": check_cosine_about}[op](x, got)

@@ -1,5 +1,6 @@
 """The kernels' building blocks against float64, on the CPU: the oracle's restatements (oracle_math.hpp, oracle.cpp, oracle_scene.hpp) through
-orc_blocks_eval over the input sets of tests/blocks_ref.py, under the bounds written there and in DESIGN.md 3.5 / 3.6.  The device runs the same
+orc_blocks_eval over the input sets of tests/blocks_ref.py and tests/walk_ref.py (the walk's node step and triangle test), under the bounds written
+there and in DESIGN.md 3.4 / 3.5 / 3.6.  The device runs the same
 sets through pbrt_hip_blocks_eval_device in tests/test_blocks_gpu.py, bit-equal to what is checked here.  Parity between oracle and kernels
 cannot see a wrong coefficient or a wrong range threshold -- both restate the same fixed order of fp32 operations -- and a render sees one
 only once it moves an image: these tests do, element by element."""
@@ -50,6 +51,43 @@ def test_sphere_test_alone_against_float64(oracle):
         print(f"D, r = {rung}: max |dt| {m['max_dt']:.3g}, max |dt| / bound {m['max_ratio']:.3f}, off the surface {m['off_surface_radii']:.3g} r, robust {m['robust']}")
 
 
+def test_node_step_against_float64(oracle):
+    """One step of the production walk (oracle/quad_walk.cpp quad_step, what walk(), orc_quad_path_check and the op all call) against the
+    float64 statement of tests/walk_ref.py over about 2^18 (node, ray) pairs: no false negative, the near planes outside the true ones and no
+    further than the roundings and the margin put them (QUAD_C = 9), no hit beyond that model, the slot entered, the unused slots, a ray
+    that meets a real node's exact child box let in.  Prints the largest observed fractions of the bounds."""
+    x, aux = br.inputs("QUAD_STEP")
+    got = oracle.blocks_eval("QUAD_STEP", x)
+    figures = br.wr.check_quad_step(x, aux, got, oracle.blocks_eval("QUAD_STEP_PK", x))
+    print("QUAD_STEP:", figures)
+    assert figures["pairs"] >= 250_000 and figures["on the domain"] >= 0.9 * figures["pairs"] and figures["must hit"] >= 100_000
+    assert 0.25 <= figures["largest fraction of the inward bound"] <= 1.0 and 0.25 <= figures["largest fraction of the outward bound"] <= 1.0
+
+
+@pytest.mark.parametrize("size", br.wr.TRI_SIZES)
+def test_triangle_test_against_float64(oracle, size):
+    """Moeller-Trumbore + the |det| cut + the own-box rule (Scene::tri_hit) over the ladder aspect x distance / size x |d| of one size, 2^14
+    rays a rung, against float64 with a running error bound per ray (tests/walk_ref.py): on the ASSERTED rungs at least half of the rays
+    are robust by float64 alone, hit-or-miss equals float64's on every robust ray and |dt|, |du|, |dv| stay within their bounds; on ALL rays
+    an accepted hit lies at or beyond its own box's entry and its ray meets that box.  Prints DESIGN.md 3.5's table, the rungs that are
+    measured and not asserted included."""
+    x, parts = br.wr.tri_hit_inputs(size)
+    table = br.wr.check_tri_hit(parts, x, oracle.blocks_eval("TRI_HIT", x))
+    assert sum(m["asserted"] for m in table.values()) >= (2 if size < 1 else 9)
+    for (aspect, dist, _, dlen), m in table.items():
+        print(f"aspect {aspect:g} dist/size {dist:g} size {size:g} |d| {dlen:g}: {'asserted' if m['asserted'] else 'NOT ASSERTED'} robust {m['robust']:.3f} "
+              f"max |dt| {m['max_dt']:.3g} |duv| {m['max_duv']:.3g} err/bound t {m['ratio_t']:.3f} u {m['ratio_u']:.3f} v {m['ratio_v']:.3f} "
+              f"equal {m['equal']:.4f} (robust: {m['robust_equal']}) lost to the det cut {m['lost_to_cut']:.3f}")
+
+
+def test_flat_triangles_and_exact_rays(oracle):
+    """triangles flat in an axis plane and slivers rotated in it: every ray robustly inside in u, v and t is a hit, whatever the condition
+    number (no holes, at unit level); rays whose arithmetic is exact: the edges and vertices count, u + v = 1 included, and a ray through
+    a corner of the triangle's own box is let in"""
+    x, aux = br.inputs("TRI_HIT")
+    print("TRI_HIT:", br.check("TRI_HIT", x, aux, oracle.blocks_eval("TRI_HIT", x)))
+
+
 def test_oracle_hook_refuses_what_it_does_not_know(oracle):
     """orc_blocks_eval refuses what it does not know, and an op's outputs have the documented shapes"""
     with pytest.raises(KeyError):
@@ -68,7 +106,7 @@ def test_device_hook_refuses_bad_arguments_before_it_touches_a_device():
     f = _lib.lib().pbrt_hip_blocks_eval_device
     a = np.zeros(16, np.float32)
     p = a.ctypes.data_as(C.POINTER(C.c_float))
-    assert f(0, 9, 1, p, p) == -1 and f(0, 0xffffffff, 1, p, p) == -1
+    assert f(0, 12, 1, p, p) == -1 and f(0, 0xffffffff, 1, p, p) == -1
     assert f(0, 0, -1, p, p) == -1
     assert f(0, 0, 1, None, p) == -1 and f(0, 0, 1, p, None) == -1
     assert b"blocks_eval_device" in _lib.lib().pbrt_hip_last_error()

@@ -7,6 +7,8 @@
 //      on BASELINE C3, 6.5 % on C2;
 //   3. the dynamic-programming collapse into the quantised 4-wide nodes the production walk reads (its rules and
 //      the record: quad_encode.hpp, which the host builder of quad_nodes.cpp calls too).
+// On the host a function per stage (sah_build, reinsert, collapse, below the kernels): each owns its scratch as typed DevBufs
+// (dev_buf.hpp) and they hand on one BinaryTree; gpu_build_quads checks its arguments, times and calls them.
 // 0.13 s for 1M triangles (34 ms without stage 2: PBRT_HIP_SCENE_PLAIN_TREE) against the host's second.  Round 1's LBVH and PLOC
 // builders are records now (tools/experiments/r01_lbvh_ploc_builders.hip.txt).
 // The reference has no accelerator at all (core/api.rs:237 is a name), so there is nothing to conform to but the RESULT:
@@ -24,6 +26,7 @@
 #include <rocprim/device/device_radix_sort.hpp>  // (rocPRIM directly: hipCUB is its CUDA-compatibility face)
 #include <rocprim/device/device_scan.hpp>
 
+#include "dev_buf.hpp"
 #include "device_types.h"
 #include "quad_encode.hpp"
 #include "quad_nodes.hpp"
@@ -691,296 +694,359 @@ __global__ void collapse_kernel(const CollapseItem *items, uint32_t *level_count
   quad::pack_record(quads + 4 * (size_t)it.quad, me_lo, grid, ref);
 }
 
-struct Tmp {
-  void *p = nullptr;
-  ~Tmp() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <class T> T *as() { return (T *)p; }
-};
-
 }  // namespace
 
+// ---- the host side: three stages over typed scratch that its stage owns (dev_buf.hpp; sizes are ELEMENT counts) ----
 #define GB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
-hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_tris, uint32_t *d_order, uint4 *d_quads,
-                           uint32_t quad_capacity, uint32_t flags, GpuBuildInfo *info, hipStream_t stream) {
-  const int n = (int)n_tris;
-  if (n < 2) return hipErrorInvalidValue;  // (the caller builds trees of fewer than two triangles on the host)
-  if (quad_capacity + 1u < n_tris) return hipErrorInvalidValue;  // a quad per interior node of the binary tree at most
-  const dim3 block(256), grid_t((n_tris + 255u) / 256u);
-  Tmp bounds, keys, keys_out, vals, sort_tmp, child, par_i, par_l, visits, bx, q0, q1, counters, level_counts;
-  GB_TRY(bounds.alloc(6 * 4));
-  GB_TRY(keys.alloc(4 * (size_t)n));
-  GB_TRY(keys_out.alloc(4 * (size_t)n));
-  GB_TRY(vals.alloc(4 * (size_t)n));
-  GB_TRY(child.alloc(8 * (size_t)n));
-  GB_TRY(par_i.alloc(4 * (size_t)n));
-  GB_TRY(par_l.alloc(4 * (size_t)n));
-  GB_TRY(visits.alloc(4 * (size_t)n));
-  GB_TRY(bx.alloc(24 * (size_t)(2 * n)));
-  GB_TRY(q0.alloc(sizeof(CollapseItem) * (size_t)n));
-  GB_TRY(q1.alloc(sizeof(CollapseItem) * (size_t)n));
-  GB_TRY(counters.alloc(2 * 4));
-  GB_TRY(level_counts.alloc(64 * 4));
-  size_t sort_bytes = 0;
-  GB_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys.as<uint32_t>(), keys_out.as<uint32_t>(), vals.as<uint32_t>(), d_order, (size_t)n, 0u, 30u, stream));
-  GB_TRY(sort_tmp.alloc(sort_bytes));
+namespace {
 
-  struct Events {  // (destroyed on every exit, early returns of GB_TRY included)
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } ev;
-  GB_TRY(hipEventCreate(&ev.a));
-  GB_TRY(hipEventCreate(&ev.b));
-  const hipEvent_t e0 = ev.a, e1 = ev.b;
-  GB_TRY(hipEventRecord(e0, stream));
-  const uint32_t init_bounds[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+// Records of more than one word, as the kernels index them; every size and every offset on the host is written with these.
+constexpr size_t kBoxWords = 3;                              // a node's box: three 64-bit words (box_store / box_load)
+constexpr size_t kCbWords = 6;                               // a segment's centre bounds: min xyz, max xyz (sah_bounds_kernel)
+constexpr size_t kBucketWords = kBinWords / kSahBuckets;     // a bucket of a segment's kBinWords of bins: count, box lo xyz, hi xyz
+constexpr size_t kDpFWords = 4 * 3, kDpFlWords = 3;          // DpTables: F(k = 1..4, d = 1..3) per interior node, Fl(d) per leaf
+
+template <class T>
+hipError_t copy_on_device(T *dst, const T *src, size_t count, hipStream_t stream) {
+  return hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToDevice, stream);
+}
+template <class T>
+hipError_t zero_on_device(T *p, size_t count, hipStream_t stream) { return hipMemsetAsync(p, 0, count * sizeof(T), stream); }
+
+// rocPRIM's temporary storage.  Never empty: rocPRIM reads a null pointer as "tell me the size" and then does NOTHING, and a DevBuf
+// of no elements has p == nullptr.  (Every other buffer here is sized from n >= 2 and cannot be empty.)
+hipError_t alloc_rocprim_tmp(DevBuf<char> &tmp, size_t bytes) { return tmp.alloc(std::max<size_t>(bytes, 1)); }
+
+struct Events {  // (destroyed on every exit, early returns of GB_TRY included)
+  hipEvent_t a = nullptr, b = nullptr;
+  ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  hipError_t create() { GB_TRY(hipEventCreate(&a)); return hipEventCreate(&b); }
+};
+
+// The binary tree that passes from stage to stage, n leaves of one triangle each.  Node ids: interior nodes [0, n - 1), the root 0;
+// in `boxes` the leaf of slot k follows them as node (n - 1) + k.  The leaf order itself (slot -> triangle) is the caller's d_order.
+//                                      written by                                        read by
+//   child            [2 n]             sah_build; reinsert (ri_emit_kernel)              reinsert (ri_links_kernel), collapse
+//   parent_internal  [n]               sah_build; reinsert (ri_emit_kernel)              collapse (the dynamic programme)
+//   parent_leaf      [n]               sah_build; reinsert (ri_emit_kernel)              collapse (the dynamic programme)
+//   boxes            [kBoxWords 2 n]   sah_build; reinsert (refits, leaves renumbered)   reinsert, collapse
+//   visits           [n]               arrival counters of the bottom-up kernels of reinsert and collapse: zeroed by whoever launches one,
+//                                      nothing is handed over in it (it lives here so that the stages share one allocation)
+struct BinaryTree {
+  int n = 0;
+  DevBuf<uint32_t> child, parent_internal, parent_leaf, visits;
+  DevBuf<unsigned long long> boxes;
+  hipError_t alloc(int n_tris) {
+    n = n_tris;
+    GB_TRY(child.alloc(2 * (size_t)n));
+    GB_TRY(parent_internal.alloc((size_t)n));
+    GB_TRY(parent_leaf.alloc((size_t)n));
+    GB_TRY(visits.alloc((size_t)n));
+    return boxes.alloc(kBoxWords * 2 * (size_t)n);
+  }
+};
+
+// Stage 1: Morton keys, the radix sort, and the level-synchronous binned SAH build over the sorted triangles.  Fills `t` and d_order.
+hipError_t sah_build(const float *d_P, const uint32_t *d_idx, BinaryTree &t, uint32_t *d_order, hipStream_t stream) {
+  const int n = t.n;
+  const uint32_t n_tris = (uint32_t)n;
+  const dim3 block(256), grid_t((n_tris + 255u) / 256u);
+  DevBuf<uint32_t> bounds, keys, keys_out, vals;
+  DevBuf<char> sort_tmp;
+  GB_TRY(bounds.alloc(kCbWords));
+  GB_TRY(keys.alloc((size_t)n));
+  GB_TRY(keys_out.alloc((size_t)n));
+  GB_TRY(vals.alloc((size_t)n));
+  size_t sort_bytes = 0;
+  GB_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys.p, keys_out.p, vals.p, d_order, (size_t)n, 0u, 30u, stream));
+  GB_TRY(alloc_rocprim_tmp(sort_tmp, sort_bytes));
+  const uint32_t init_bounds[kCbWords] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
   GB_TRY(hipMemcpyAsync(bounds.p, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(centroid_bounds_kernel, dim3((n_tris + 2047u) / 2048u), block, 0, stream, d_P, d_idx, n_tris, bounds.as<uint32_t>());
-  hipLaunchKernelGGL(morton_kernel, grid_t, block, 0, stream, d_P, d_idx, n_tris, bounds.as<uint32_t>(), keys.as<uint32_t>(), vals.as<uint32_t>());
+  hipLaunchKernelGGL(centroid_bounds_kernel, dim3((n_tris + 2047u) / 2048u), block, 0, stream, d_P, d_idx, n_tris, bounds.p);
+  hipLaunchKernelGGL(morton_kernel, grid_t, block, 0, stream, d_P, d_idx, n_tris, bounds.p, keys.p, vals.p);
   GB_TRY(hipGetLastError());
-  GB_TRY(rocprim::radix_sort_pairs(sort_tmp.p, sort_bytes, keys.as<uint32_t>(), keys_out.as<uint32_t>(), vals.as<uint32_t>(), d_order, (size_t)n, 0u, 30u, stream));
+  GB_TRY(rocprim::radix_sort_pairs(sort_tmp.p, sort_bytes, keys.p, keys_out.p, vals.p, d_order, (size_t)n, 0u, 30u, stream));
   {
     // ---- top-down binned SAH ----
     const size_t cap = (size_t)n / 2 + 2;  // segments of >= 2 triangles on one level
-    Tmp tlo, thi, ids_b, seg_a, seg_b, cb, bins, split, active, cbase, flags, scan, scan_tmp, segtab;
-    GB_TRY(tlo.alloc(12 * (size_t)n)); GB_TRY(thi.alloc(12 * (size_t)n));
-    GB_TRY(ids_b.alloc(4 * (size_t)n)); GB_TRY(seg_a.alloc(4 * (size_t)n)); GB_TRY(seg_b.alloc(4 * (size_t)n));
-    GB_TRY(cb.alloc(24 * cap)); GB_TRY(bins.alloc(4 * (size_t)kBinWords * cap)); GB_TRY(split.alloc(sizeof(SahSplit) * cap));
-    GB_TRY(active.alloc(4 * cap)); GB_TRY(cbase.alloc(4 * cap)); GB_TRY(flags.alloc(4 * (size_t)n)); GB_TRY(scan.alloc(4 * (size_t)n));
-    GB_TRY(segtab.alloc(4 * 6 * cap));
+    DevBuf<float> tlo, thi;
+    DevBuf<uint32_t> ids_b, seg_a, seg_b, cb, bins, active, cbase, flags, scan, segtab;
+    DevBuf<SahSplit> split;
+    DevBuf<char> scan_tmp;
+    GB_TRY(tlo.alloc(3 * (size_t)n)); GB_TRY(thi.alloc(3 * (size_t)n));
+    GB_TRY(ids_b.alloc((size_t)n)); GB_TRY(seg_a.alloc((size_t)n)); GB_TRY(seg_b.alloc((size_t)n));
+    GB_TRY(cb.alloc(kCbWords * cap)); GB_TRY(bins.alloc(kBinWords * cap)); GB_TRY(split.alloc(cap));
+    GB_TRY(active.alloc(cap)); GB_TRY(cbase.alloc(cap)); GB_TRY(flags.alloc((size_t)n)); GB_TRY(scan.alloc((size_t)n));
+    GB_TRY(segtab.alloc(2 * 3 * cap));  // this level's table and the next one's: three arrays each (SahSegs)
     size_t scan_bytes = 0;
-    GB_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flags.as<uint32_t>(), scan.as<uint32_t>(), 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    GB_TRY(scan_tmp.alloc(scan_bytes));
-    SahSegs cur_s{segtab.as<uint32_t>(), segtab.as<uint32_t>() + cap, segtab.as<uint32_t>() + 2 * cap};
-    SahSegs nxt_s{segtab.as<uint32_t>() + 3 * cap, segtab.as<uint32_t>() + 4 * cap, segtab.as<uint32_t>() + 5 * cap};
-    hipLaunchKernelGGL(sah_tri_boxes_kernel, grid_t, block, 0, stream, d_P, d_idx, n_tris, tlo.as<float>(), thi.as<float>());
+    GB_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flags.p, scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+    GB_TRY(alloc_rocprim_tmp(scan_tmp, scan_bytes));
+    SahSegs cur_s{segtab.p, segtab.p + cap, segtab.p + 2 * cap};
+    SahSegs nxt_s{segtab.p + 3 * cap, segtab.p + 4 * cap, segtab.p + 5 * cap};
+    hipLaunchKernelGGL(sah_tri_boxes_kernel, grid_t, block, 0, stream, d_P, d_idx, n_tris, tlo.p, thi.p);
     // level 0: one segment [0, n) = node 0, triangles in Morton order (d_order holds the sorted ids)
-    uint32_t *ids_in = d_order, *ids_out = ids_b.as<uint32_t>(), *seg_in = seg_a.as<uint32_t>(), *seg_out = seg_b.as<uint32_t>();
-    GB_TRY(hipMemsetAsync(seg_in, 0, 4 * (size_t)n, stream));
+    uint32_t *ids_in = d_order, *ids_out = ids_b.p, *seg_in = seg_a.p, *seg_out = seg_b.p;
+    GB_TRY(zero_on_device(seg_in, (size_t)n, stream));
     const uint32_t seg0[3] = {0u, (uint32_t)n, 0u};
-    GB_TRY(hipMemcpyAsync(cur_s.start, &seg0[0], 4, hipMemcpyHostToDevice, stream));
-    GB_TRY(hipMemcpyAsync(cur_s.end, &seg0[1], 4, hipMemcpyHostToDevice, stream));
-    GB_TRY(hipMemcpyAsync(cur_s.node, &seg0[2], 4, hipMemcpyHostToDevice, stream));
+    GB_TRY(hipMemcpyAsync(cur_s.start, &seg0[0], sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GB_TRY(hipMemcpyAsync(cur_s.end, &seg0[1], sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GB_TRY(hipMemcpyAsync(cur_s.node, &seg0[2], sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     GB_TRY(hipStreamSynchronize(stream));  // (seg0 is a local)
     uint32_t n_seg = 1u, next_node = 1u;
     for (uint32_t level = 0; n_seg > 0u; level++) {
       if (level > 4096u) return hipErrorUnknown;  // (halving past kSahMedianLevel ends every segment long before)
       const dim3 gs((n_seg + 127u) / 128u), b128(128);
-      // centre bounds: min words ~0, max words 0 (a strided memset over the second half of every 24-byte record)
-      GB_TRY(hipMemsetAsync(cb.p, 0xff, 24 * (size_t)n_seg, stream));
-      GB_TRY(hipMemset2DAsync((char *)cb.p + 12, 24, 0, 12, n_seg, stream));
-      GB_TRY(hipMemsetAsync(bins.p, 0, 4 * (size_t)kBinWords * n_seg, stream));
-      hipLaunchKernelGGL(sah_bounds_kernel, grid_t, block, 0, stream, ids_in, seg_in, n, tlo.as<float>(), thi.as<float>(), cb.as<uint32_t>());
-      hipLaunchKernelGGL(sah_prepare_kernel, gs, b128, 0, stream, (int)n_seg, cb.as<uint32_t>(), split.as<SahSplit>());
-      // bins: counts 0, box lo words ~0 (hi words 0 already)
-      GB_TRY(hipMemset2DAsync((char *)bins.p + 4, 28, 0xff, 12, (size_t)n_seg * kSahBuckets, stream));
-      hipLaunchKernelGGL(sah_bins_kernel, grid_t, block, 0, stream, ids_in, seg_in, n, tlo.as<float>(), thi.as<float>(), split.as<SahSplit>(), bins.as<uint32_t>());
-      hipLaunchKernelGGL(sah_split_kernel, gs, b128, 0, stream, (int)n_seg, cur_s, bins.as<uint32_t>(), split.as<SahSplit>(), level, bx.as<unsigned long long>(),
-                         active.as<uint32_t>());
-      GB_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, active.as<uint32_t>(), cbase.as<uint32_t>(), 0u, (size_t)n_seg, rocprim::plus<uint32_t>(), stream));
-      hipLaunchKernelGGL(sah_flags_kernel, grid_t, block, 0, stream, ids_in, seg_in, n, tlo.as<float>(), thi.as<float>(), cur_s, split.as<SahSplit>(), flags.as<uint32_t>());
-      GB_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, flags.as<uint32_t>(), scan.as<uint32_t>(), 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-      hipLaunchKernelGGL(sah_scatter_kernel, grid_t, block, 0, stream, ids_in, seg_in, n, cur_s, split.as<SahSplit>(), flags.as<uint32_t>(), scan.as<uint32_t>(),
-                         cbase.as<uint32_t>(), ids_out, seg_out);
-      hipLaunchKernelGGL(sah_children_kernel, gs, b128, 0, stream, (int)n_seg, cur_s, split.as<SahSplit>(), cbase.as<uint32_t>(), next_node, child.as<uint32_t>(), nxt_s,
-                         par_i.as<uint32_t>(), par_l.as<uint32_t>());
+      // centre bounds: min words ~0, max words 0 (a strided memset over the second half of every record)
+      GB_TRY(hipMemsetAsync(cb.p, 0xff, kCbWords * sizeof(uint32_t) * n_seg, stream));
+      GB_TRY(hipMemset2DAsync(cb.p + kCbWords / 2, kCbWords * sizeof(uint32_t), 0, kCbWords / 2 * sizeof(uint32_t), n_seg, stream));
+      GB_TRY(zero_on_device(bins.p, kBinWords * (size_t)n_seg, stream));
+      hipLaunchKernelGGL(sah_bounds_kernel, grid_t, block, 0, stream, ids_in, seg_in, n, tlo.p, thi.p, cb.p);
+      hipLaunchKernelGGL(sah_prepare_kernel, gs, b128, 0, stream, (int)n_seg, cb.p, split.p);
+      // bins: counts 0, box lo words (the three behind a bucket's count) ~0 (hi words 0 already)
+      GB_TRY(hipMemset2DAsync(bins.p + 1, kBucketWords * sizeof(uint32_t), 0xff, 3 * sizeof(uint32_t), (size_t)n_seg * kSahBuckets, stream));
+      hipLaunchKernelGGL(sah_bins_kernel, grid_t, block, 0, stream, ids_in, seg_in, n, tlo.p, thi.p, split.p, bins.p);
+      hipLaunchKernelGGL(sah_split_kernel, gs, b128, 0, stream, (int)n_seg, cur_s, bins.p, split.p, level, t.boxes.p, active.p);
+      GB_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, active.p, cbase.p, 0u, (size_t)n_seg, rocprim::plus<uint32_t>(), stream));
+      hipLaunchKernelGGL(sah_flags_kernel, grid_t, block, 0, stream, ids_in, seg_in, n, tlo.p, thi.p, cur_s, split.p, flags.p);
+      GB_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, flags.p, scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
+      hipLaunchKernelGGL(sah_scatter_kernel, grid_t, block, 0, stream, ids_in, seg_in, n, cur_s, split.p, flags.p, scan.p, cbase.p, ids_out, seg_out);
+      hipLaunchKernelGGL(sah_children_kernel, gs, b128, 0, stream, (int)n_seg, cur_s, split.p, cbase.p, next_node, t.child.p, nxt_s,
+                         t.parent_internal.p, t.parent_leaf.p);
       GB_TRY(hipGetLastError());
       uint32_t last[2];  // exclusive sum and count of the last segment: the next level's segment count
-      GB_TRY(hipMemcpyAsync(&last[0], cbase.as<uint32_t>() + (n_seg - 1u), 4, hipMemcpyDeviceToHost, stream));
-      GB_TRY(hipMemcpyAsync(&last[1], active.as<uint32_t>() + (n_seg - 1u), 4, hipMemcpyDeviceToHost, stream));
+      GB_TRY(hipMemcpyAsync(&last[0], cbase.p + (n_seg - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      GB_TRY(hipMemcpyAsync(&last[1], active.p + (n_seg - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
       GB_TRY(hipStreamSynchronize(stream));
       n_seg = last[0] + last[1];
       next_node += n_seg;
-      { uint32_t *t = ids_in; ids_in = ids_out; ids_out = t; }
-      { uint32_t *t = seg_in; seg_in = seg_out; seg_out = t; }
-      { SahSegs t = cur_s; cur_s = nxt_s; nxt_s = t; }
+      std::swap(ids_in, ids_out);
+      std::swap(seg_in, seg_out);
+      std::swap(cur_s, nxt_s);
     }
     // leaf boxes and the final leaf order (slot k holds triangle ids[k])
-    hipLaunchKernelGGL(sah_leaf_boxes_kernel, grid_t, block, 0, stream, ids_in, n, tlo.as<float>(), thi.as<float>(), bx.as<unsigned long long>(), ids_out);
-    if (ids_out != d_order) GB_TRY(hipMemcpyAsync(d_order, ids_out, 4 * (size_t)n, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(sah_leaf_boxes_kernel, grid_t, block, 0, stream, ids_in, n, tlo.p, thi.p, t.boxes.p, ids_out);
+    if (ids_out != d_order) GB_TRY(copy_on_device(d_order, ids_out, (size_t)n, stream));
     GB_TRY(hipGetLastError());
     GB_TRY(hipStreamSynchronize(stream));  // (the scratch above is freed when this block ends)
   }
+  return hipSuccess;
+}
 
-  // ---- parallel re-insertion: the built tree optimised before it is collapsed (reinsert_core.hpp) ----
-  // Passes of search / lock / check / apply / refit until a pass moves fewer than one node in 1024, `passes` at most, or the
-  // searches have looked at more than kVisitBudget nodes per node of the tree in total (a mesh of coincident boxes, where
-  // nothing prunes a search, costs a bounded amount).  The host reads two numbers per pass.
-  info->reinsert_passes = 0;
-  info->reinsert_moves = 0;
-  info->reinsert_ms = 0.f;
-  info->reinsert_cost_before = info->reinsert_cost_after = 0.;
-  info->reinsert_undone = 0;
-  {
-    reins::StopRule stop;  // (shared with the host run of the pass: reinsert_core.hpp)
-    int passes = stop.max_passes;
-    uint32_t mu = 1;
-    reins::Search sp;
-    if (const char *v = debug_knob("PBRT_HIP_GPU_REINSERT")) passes = std::atoi(v);
-    if (const char *v = debug_knob("PBRT_HIP_REINSERT_MU")) mu = (uint32_t)std::max(1, std::atoi(v));
-    if (const char *v = debug_knob("PBRT_HIP_REINSERT_VISITS")) sp.max_visits = (uint32_t)std::max(1, std::atoi(v));
-    if (const char *v = debug_knob("PBRT_HIP_REINSERT_MIN_REL")) sp.min_rel = (float)std::atof(v);
-    if (const char *v = debug_knob("PBRT_HIP_REINSERT_QK")) sp.qk = (float)std::atof(v);
-    if (const char *v = debug_knob("PBRT_HIP_REINSERT_QW")) sp.qw = (float)std::atof(v);
-    const bool full_refit = debug_knob("PBRT_HIP_REINSERT_FULL_REFIT") != nullptr;  // (A-B: every box every pass, as until round 4)
-    if (!(flags & kGpuBuildReinsert)) passes = 0;
-    // Small trees are left as built: below StopRule::min_tris triangles (where the collapse is the greedy one, too) a walk is a handful
-    // of steps in L1 and the surface-area objective decides nothing measurable -- BASELINE C4's 36 triangles rendered 2 % SLOWER with
-    // the four moves the pass found (15 quad nodes instead of 19, profiles/r04p5_c4_ab.txt).  The test suite lowers the threshold
-    // (tests/conftest.py) so that trees of 8 .. 300 triangles keep exercising the pass.
-    uint32_t min_tris = stop.min_tris;
-    if (const char *v = debug_knob("PBRT_HIP_REINSERT_MIN_TRIS")) min_tris = (uint32_t)std::max(8, std::atoi(v));
-    if (n_tris >= min_tris && n >= 8 && passes > 0) {
-      const uint32_t n_int = (uint32_t)n - 1u, n_nodes = 2u * n_int + 1u;
-      const dim3 grid_n((n_nodes + 255u) / 256u), grid_i((n_int + 255u) / 256u);
-      Tmp par, kid, mv_y, mv_lca, mv_gain, lock, holds, stats, cnt, newslot, order2, leaf_bx, par_b, kid_b, bx_b;
-      GB_TRY(par.alloc(4 * (size_t)n_nodes)); GB_TRY(kid.alloc(8 * (size_t)n_int));
-      GB_TRY(mv_y.alloc(4 * (size_t)n_nodes)); GB_TRY(mv_lca.alloc(4 * (size_t)n_nodes)); GB_TRY(mv_gain.alloc(4 * (size_t)n_nodes));
-      GB_TRY(lock.alloc(8 * (size_t)n_nodes)); GB_TRY(holds.alloc(4 * (size_t)n_nodes)); GB_TRY(stats.alloc(5 * 8));
-      GB_TRY(cnt.alloc(4 * (size_t)n_int)); GB_TRY(newslot.alloc(4 * (size_t)n)); GB_TRY(order2.alloc(4 * (size_t)n)); GB_TRY(leaf_bx.alloc(24 * (size_t)n));
-      // the tree as it stood before the pass in flight (links + interior boxes): a pass that raises the summed area is undone
-      GB_TRY(par_b.alloc(4 * (size_t)n_nodes)); GB_TRY(kid_b.alloc(8 * (size_t)n_int)); GB_TRY(bx_b.alloc(24 * (size_t)n_int));
-      Events rev;
-      GB_TRY(hipEventCreate(&rev.a));
-      GB_TRY(hipEventCreate(&rev.b));
-      GB_TRY(hipEventRecord(rev.a, stream));
-      const reins::Tree t{n_int, par.as<uint32_t>(), kid.as<uint32_t>(), bx.as<unsigned long long>()};
-      hipLaunchKernelGGL(ri_links_kernel, grid_i, block, 0, stream, n, child.as<uint32_t>(), par.as<uint32_t>(), kid.as<uint32_t>());
-      // stats: [0] visits [1] found [2] applied (summed over the passes); [3] the tree's cost in fixed point, [4] its scale (ri_cost_kernel)
-      GB_TRY(hipMemsetAsync(stats.p, 0, 5 * 8, stream));
-      hipLaunchKernelGGL(ri_cost_kernel, grid_i, block, 0, stream, t, stats.as<unsigned long long>() + 3);
-      unsigned long long h_stats[5] = {0, 0, 0, 0, 0}, applied_before = 0, cost = 0;
-      GB_TRY(hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, stream));
-      GB_TRY(hipStreamSynchronize(stream));
-      cost = h_stats[3];
-      const double cost_unit = std::ldexp(1.0, -((int)h_stats[4] - 1024));
-      info->reinsert_cost_before = info->reinsert_cost_after = (double)cost * cost_unit;
-      int done = 0;
-      for (int pass = 0; pass < passes; pass++) {
-        GB_TRY(hipMemcpyAsync(par_b.p, par.p, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, stream));
-        GB_TRY(hipMemcpyAsync(kid_b.p, kid.p, 8 * (size_t)n_int, hipMemcpyDeviceToDevice, stream));
-        GB_TRY(hipMemcpyAsync(bx_b.p, bx.p, 24 * (size_t)n_int, hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL(ri_search_kernel, grid_n, block, 0, stream, t, sp, (uint32_t)pass, mu, mv_y.as<uint32_t>(), mv_lca.as<uint32_t>(), mv_gain.as<float>(),
-                           stats.as<unsigned long long>());
-        GB_TRY(hipMemsetAsync(lock.p, 0, 8 * (size_t)n_nodes, stream));
-        hipLaunchKernelGGL(ri_lock_kernel, grid_n, block, 0, stream, t, mv_y.as<uint32_t>(), mv_gain.as<float>(), lock.as<unsigned long long>());
-        hipLaunchKernelGGL(ri_hold_kernel, grid_n, block, 0, stream, t, mv_y.as<uint32_t>(), mv_gain.as<float>(), lock.as<unsigned long long>(), holds.as<uint32_t>());
-        hipLaunchKernelGGL(ri_free_kernel, grid_n, block, 0, stream, t, mv_y.as<uint32_t>(), mv_lca.as<uint32_t>(), mv_gain.as<float>(), holds.as<uint32_t>());
-        // (mv_lca has served: the apply kernel leaves there the grandparent every moved node came from)
-        hipLaunchKernelGGL(ri_apply_kernel, grid_n, block, 0, stream, t, mv_y.as<uint32_t>(), mv_lca.as<uint32_t>(), stats.as<unsigned long long>());
-        GB_TRY(hipMemsetAsync(visits.p, 0, 4 * (size_t)n, stream));
-        if (full_refit) {
-          hipLaunchKernelGGL(ri_refit_kernel<false>, grid_t, block, 0, stream, t, visits.as<uint32_t>(), cnt.as<uint32_t>());
-        } else {
-          hipLaunchKernelGGL(ri_mark_kernel, grid_n, block, 0, stream, t, mv_y.as<uint32_t>(), mv_lca.as<uint32_t>(), visits.as<uint32_t>());
-          hipLaunchKernelGGL(ri_refit_dirty_kernel, grid_i, block, 0, stream, t, visits.as<uint32_t>());
-        }
-        GB_TRY(hipMemsetAsync(stats.as<unsigned long long>() + 3, 0, 8, stream));
-        hipLaunchKernelGGL(ri_cost_kernel, grid_i, block, 0, stream, t, stats.as<unsigned long long>() + 3);
-        GB_TRY(hipGetLastError());
-        GB_TRY(hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, stream));
-        GB_TRY(hipStreamSynchronize(stream));
-        const unsigned long long applied = h_stats[2] - applied_before;
-        if (h_stats[3] > cost) {
-          // The moves of a pass hold six link nodes each, not their paths, so their gains need not add up: one pass in a
-          // thousand or so comes out with MORE summed area than it went in with.  Such a pass is undone and ends the passes.
-          GB_TRY(hipMemcpyAsync(par.p, par_b.p, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, stream));
-          GB_TRY(hipMemcpyAsync(kid.p, kid_b.p, 8 * (size_t)n_int, hipMemcpyDeviceToDevice, stream));
-          GB_TRY(hipMemcpyAsync(bx.p, bx_b.p, 24 * (size_t)n_int, hipMemcpyDeviceToDevice, stream));
-          h_stats[2] = applied_before;
-          info->reinsert_undone = 1;
-          break;
-        }
-        done = pass + 1;
-        cost = h_stats[3];
-        applied_before = h_stats[2];
-        if (reins::stop_after_pass(stop, applied, h_stats[0], n_nodes)) break;
-      }
-      info->reinsert_cost_after = (double)cost * cost_unit;
-      // child order, leaf counts, leaves renumbered in depth-first order, and back to the builder's arrays
-      hipLaunchKernelGGL(ri_order_kernel, grid_i, block, 0, stream, t);
-      GB_TRY(hipMemsetAsync(visits.p, 0, 4 * (size_t)n, stream));
-      // (the leaves below every node; the boxes are right already -- the last pass refitted what it moved)
-      hipLaunchKernelGGL((ri_refit_kernel<true, false>), grid_t, block, 0, stream, t, visits.as<uint32_t>(), cnt.as<uint32_t>());
-      hipLaunchKernelGGL(ri_leafpos_kernel, grid_t, block, 0, stream, t, cnt.as<uint32_t>(), newslot.as<uint32_t>());
-      hipLaunchKernelGGL(ri_emit_kernel, grid_i, block, 0, stream, t, newslot.as<uint32_t>(), child.as<uint32_t>(), par_i.as<uint32_t>(), par_l.as<uint32_t>());
-      hipLaunchKernelGGL(ri_leaves_kernel, grid_t, block, 0, stream, t, newslot.as<uint32_t>(), d_order, order2.as<uint32_t>(), leaf_bx.as<unsigned long long>());
-      GB_TRY(hipGetLastError());
-      GB_TRY(hipMemcpyAsync(d_order, order2.p, 4 * (size_t)n, hipMemcpyDeviceToDevice, stream));
-      GB_TRY(hipMemcpyAsync(bx.as<unsigned long long>() + 3 * (size_t)n_int, leaf_bx.p, 24 * (size_t)n, hipMemcpyDeviceToDevice, stream));
-      GB_TRY(hipEventRecord(rev.b, stream));
-      GB_TRY(hipStreamSynchronize(stream));  // (the scratch above is freed when this block ends)
-      float rms = 0.f;
-      GB_TRY(hipEventElapsedTime(&rms, rev.a, rev.b));
-      info->reinsert_passes = (uint32_t)done;
-      info->reinsert_moves = (uint32_t)std::min<unsigned long long>(h_stats[2], 0xffffffffull);
-      info->reinsert_ms = rms;
+// The debug knobs of stage 2 (PBRT_HIP_GPU_REINSERT, PBRT_HIP_REINSERT_*), read in one place; without them, the defaults of reinsert_core.hpp
+struct ReinsertKnobs {
+  reins::StopRule stop;  // (shared with the host run of the pass: reinsert_core.hpp)
+  int passes = stop.max_passes;
+  uint32_t mu = 1;
+  reins::Search search;
+  bool full_refit = false;  // (A-B: every box every pass, as until round 4)
+  // Small trees are left as built: below StopRule::min_tris triangles (where the collapse is the greedy one, too) a walk is a handful
+  // of steps in L1 and the surface-area objective decides nothing measurable -- BASELINE C4's 36 triangles rendered 2 % SLOWER with
+  // the four moves the pass found (15 quad nodes instead of 19, profiles/r04p5_c4_ab.txt).  The test suite lowers the threshold
+  // (tests/conftest.py) so that trees of 8 .. 300 triangles keep exercising the pass.
+  uint32_t min_tris = stop.min_tris;
+};
+ReinsertKnobs read_reinsert_knobs() {
+  ReinsertKnobs k;
+  if (const char *v = debug_knob("PBRT_HIP_GPU_REINSERT")) k.passes = std::atoi(v);
+  if (const char *v = debug_knob("PBRT_HIP_REINSERT_MU")) k.mu = (uint32_t)std::max(1, std::atoi(v));
+  if (const char *v = debug_knob("PBRT_HIP_REINSERT_VISITS")) k.search.max_visits = (uint32_t)std::max(1, std::atoi(v));
+  if (const char *v = debug_knob("PBRT_HIP_REINSERT_MIN_REL")) k.search.min_rel = (float)std::atof(v);
+  if (const char *v = debug_knob("PBRT_HIP_REINSERT_QK")) k.search.qk = (float)std::atof(v);
+  if (const char *v = debug_knob("PBRT_HIP_REINSERT_QW")) k.search.qw = (float)std::atof(v);
+  k.full_refit = debug_knob("PBRT_HIP_REINSERT_FULL_REFIT") != nullptr;
+  if (const char *v = debug_knob("PBRT_HIP_REINSERT_MIN_TRIS")) k.min_tris = (uint32_t)std::max(8, std::atoi(v));
+  return k;
+}
+
+// Stage 2: parallel re-insertion, the built tree optimised before it is collapsed (reinsert_core.hpp).  `t` and
+// d_order come in and go out; `st` says what was done (nothing, for a tree below the threshold).
+// Passes of search / lock / check / apply / refit until a pass moves fewer than one node in 1024, `passes` at most, or the
+// searches have looked at more than kVisitBudget nodes per node of the tree in total (a mesh of coincident boxes, where
+// nothing prunes a search, costs a bounded amount).  The host reads two numbers per pass.
+hipError_t reinsert(BinaryTree &t, uint32_t *d_order, ReinsertStats &st, hipStream_t stream) {
+  const ReinsertKnobs knobs = read_reinsert_knobs();
+  const int n = t.n;
+  if ((uint32_t)n < knobs.min_tris || n < 8 || knobs.passes <= 0) return hipSuccess;
+  const uint32_t n_int = (uint32_t)n - 1u, n_nodes = 2u * n_int + 1u;
+  const dim3 block(256), grid_t(((uint32_t)n + 255u) / 256u), grid_n((n_nodes + 255u) / 256u), grid_i((n_int + 255u) / 256u);
+  DevBuf<uint32_t> par, kid, mv_y, mv_lca, holds, cnt, newslot, order2, par_b, kid_b;
+  DevBuf<float> mv_gain;
+  DevBuf<unsigned long long> lock, stats, leaf_bx, bx_b;
+  GB_TRY(par.alloc(n_nodes)); GB_TRY(kid.alloc(2 * (size_t)n_int));
+  GB_TRY(mv_y.alloc(n_nodes)); GB_TRY(mv_lca.alloc(n_nodes)); GB_TRY(mv_gain.alloc(n_nodes));
+  GB_TRY(lock.alloc(n_nodes)); GB_TRY(holds.alloc(n_nodes)); GB_TRY(stats.alloc(5));
+  GB_TRY(cnt.alloc(n_int)); GB_TRY(newslot.alloc((size_t)n)); GB_TRY(order2.alloc((size_t)n)); GB_TRY(leaf_bx.alloc(kBoxWords * (size_t)n));
+  // the tree as it stood before the pass in flight (links + interior boxes): a pass that raises the summed area is undone
+  GB_TRY(par_b.alloc(n_nodes)); GB_TRY(kid_b.alloc(2 * (size_t)n_int)); GB_TRY(bx_b.alloc(kBoxWords * (size_t)n_int));
+  Events ev;
+  GB_TRY(ev.create());
+  GB_TRY(hipEventRecord(ev.a, stream));
+  const reins::Tree rt{n_int, par.p, kid.p, t.boxes.p};
+  hipLaunchKernelGGL(ri_links_kernel, grid_i, block, 0, stream, n, t.child.p, par.p, kid.p);
+  // stats: [0] visits [1] found [2] applied (summed over the passes); [3] the tree's cost in fixed point, [4] its scale (ri_cost_kernel)
+  unsigned long long *const d_cost = stats.p + 3;
+  GB_TRY(zero_on_device(stats.p, stats.n, stream));
+  hipLaunchKernelGGL(ri_cost_kernel, grid_i, block, 0, stream, rt, d_cost);
+  unsigned long long h_stats[5] = {0, 0, 0, 0, 0}, applied_before = 0, cost = 0;
+  GB_TRY(hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, stream));
+  GB_TRY(hipStreamSynchronize(stream));
+  cost = h_stats[3];
+  const double cost_unit = std::ldexp(1.0, -((int)h_stats[4] - 1024));
+  st.cost_before = st.cost_after = (double)cost * cost_unit;
+  int done = 0;
+  for (int pass = 0; pass < knobs.passes; pass++) {
+    GB_TRY(copy_on_device(par_b.p, par.p, n_nodes, stream));
+    GB_TRY(copy_on_device(kid_b.p, kid.p, 2 * (size_t)n_int, stream));
+    GB_TRY(copy_on_device(bx_b.p, t.boxes.p, kBoxWords * (size_t)n_int, stream));
+    hipLaunchKernelGGL(ri_search_kernel, grid_n, block, 0, stream, rt, knobs.search, (uint32_t)pass, knobs.mu, mv_y.p, mv_lca.p, mv_gain.p, stats.p);
+    GB_TRY(zero_on_device(lock.p, n_nodes, stream));
+    hipLaunchKernelGGL(ri_lock_kernel, grid_n, block, 0, stream, rt, mv_y.p, mv_gain.p, lock.p);
+    hipLaunchKernelGGL(ri_hold_kernel, grid_n, block, 0, stream, rt, mv_y.p, mv_gain.p, lock.p, holds.p);
+    hipLaunchKernelGGL(ri_free_kernel, grid_n, block, 0, stream, rt, mv_y.p, mv_lca.p, mv_gain.p, holds.p);
+    // (mv_lca has served: the apply kernel leaves there the grandparent every moved node came from)
+    hipLaunchKernelGGL(ri_apply_kernel, grid_n, block, 0, stream, rt, mv_y.p, mv_lca.p, stats.p);
+    GB_TRY(zero_on_device(t.visits.p, (size_t)n, stream));
+    if (knobs.full_refit) {
+      hipLaunchKernelGGL(ri_refit_kernel<false>, grid_t, block, 0, stream, rt, t.visits.p, cnt.p);
+    } else {
+      hipLaunchKernelGGL(ri_mark_kernel, grid_n, block, 0, stream, rt, mv_y.p, mv_lca.p, t.visits.p);
+      hipLaunchKernelGGL(ri_refit_dirty_kernel, grid_i, block, 0, stream, rt, t.visits.p);
     }
+    GB_TRY(zero_on_device(d_cost, 1, stream));
+    hipLaunchKernelGGL(ri_cost_kernel, grid_i, block, 0, stream, rt, d_cost);
+    GB_TRY(hipGetLastError());
+    GB_TRY(hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, stream));
+    GB_TRY(hipStreamSynchronize(stream));
+    const unsigned long long applied = h_stats[2] - applied_before;
+    if (h_stats[3] > cost) {
+      // The moves of a pass hold six link nodes each, not their paths, so their gains need not add up: one pass in a
+      // thousand or so comes out with MORE summed area than it went in with.  Such a pass is undone and ends the passes.
+      GB_TRY(copy_on_device(par.p, par_b.p, n_nodes, stream));
+      GB_TRY(copy_on_device(kid.p, kid_b.p, 2 * (size_t)n_int, stream));
+      GB_TRY(copy_on_device(t.boxes.p, bx_b.p, kBoxWords * (size_t)n_int, stream));
+      h_stats[2] = applied_before;
+      st.undone = 1;
+      break;
+    }
+    done = pass + 1;
+    cost = h_stats[3];
+    applied_before = h_stats[2];
+    if (reins::stop_after_pass(knobs.stop, applied, h_stats[0], n_nodes)) break;
   }
+  st.cost_after = (double)cost * cost_unit;
+  // child order, leaf counts, leaves renumbered in depth-first order, and back to the builder's arrays
+  hipLaunchKernelGGL(ri_order_kernel, grid_i, block, 0, stream, rt);
+  GB_TRY(zero_on_device(t.visits.p, (size_t)n, stream));
+  // (the leaves below every node; the boxes are right already -- the last pass refitted what it moved)
+  hipLaunchKernelGGL((ri_refit_kernel<true, false>), grid_t, block, 0, stream, rt, t.visits.p, cnt.p);
+  hipLaunchKernelGGL(ri_leafpos_kernel, grid_t, block, 0, stream, rt, cnt.p, newslot.p);
+  hipLaunchKernelGGL(ri_emit_kernel, grid_i, block, 0, stream, rt, newslot.p, t.child.p, t.parent_internal.p, t.parent_leaf.p);
+  hipLaunchKernelGGL(ri_leaves_kernel, grid_t, block, 0, stream, rt, newslot.p, d_order, order2.p, leaf_bx.p);
+  GB_TRY(hipGetLastError());
+  GB_TRY(copy_on_device(d_order, order2.p, (size_t)n, stream));
+  GB_TRY(copy_on_device(t.boxes.p + kBoxWords * (size_t)n_int, leaf_bx.p, kBoxWords * (size_t)n, stream));  // (the leaves follow the interior nodes)
+  GB_TRY(hipEventRecord(ev.b, stream));
+  GB_TRY(hipStreamSynchronize(stream));  // (the scratch above is freed when this function returns)
+  GB_TRY(hipEventElapsedTime(&st.ms, ev.a, ev.b));
+  st.passes = (uint32_t)done;
+  st.moves = (uint32_t)std::min<unsigned long long>(h_stats[2], 0xffffffffull);
+  return hipSuccess;
+}
 
-  // top-down collapse, one launch per level of the quad tree.  The host does not know how many items a level holds
-  // (the kernel reads the count the level above left on the device) nor how deep the tree is: it launches kBatch
-  // levels blind -- level L holds at most min(4^L, n) items -- and looks at the device once per batch.
-  // Which descendants become a quad node's children: the host's choice (quad_nodes.cpp collapse_rule: the dynamic programme for
-  // trees of quad::kDpCollapseMinTris triangles and more, else the greedy largest-area rule); there is no plain rule here.
-  const bool use_dp = collapse_rule(n_tris, /*has_plain=*/false) == kCollapseDp;
-  Tmp dpF, dpFl, dpG;
+// Stage 3: the top-down collapse into quad nodes, one launch per level of the quad tree.  The host does not know how many items a
+// level holds (the kernel reads the count the level above left on the device) nor how deep the tree is: it launches kBatch
+// levels blind -- level L holds at most min(4^L, n) items -- and looks at the device once per batch.
+// Which descendants become a quad node's children: the host's choice (quad_nodes.cpp collapse_rule: the dynamic programme for
+// trees of quad::kDpCollapseMinTris triangles and more, else the greedy largest-area rule); there is no plain rule here.
+struct CollapseResult {
+  uint32_t n_quads, stack_need, levels;
+  float root_box[6];  // {lo.x lo.y lo.z hi.x hi.y hi.z} of the root
+};
+// Writes d_quads and `out`.  `done` is recorded behind the last read-back, so that the synchronisation which brings the results
+// home completes the caller's timing too.
+hipError_t collapse(const BinaryTree &t, uint4 *d_quads, hipEvent_t done, CollapseResult &out, hipStream_t stream) {
+  const int n = t.n;
+  DevBuf<CollapseItem> q0, q1;
+  DevBuf<uint32_t> counters, level_counts;
+  GB_TRY(q0.alloc((size_t)n));
+  GB_TRY(q1.alloc((size_t)n));
+  GB_TRY(counters.alloc(2));
+  GB_TRY(level_counts.alloc(64));
+  const bool use_dp = collapse_rule((uint32_t)n, /*has_plain=*/false) == kCollapseDp;
+  DevBuf<float> dpF, dpFl, dpG;
   DpTables dp{nullptr, nullptr, nullptr};
   if (use_dp) {
-    GB_TRY(dpF.alloc(48 * (size_t)n));
-    GB_TRY(dpFl.alloc(12 * (size_t)n));
-    GB_TRY(dpG.alloc(4 * (size_t)n));
-    dp = DpTables{dpF.as<float>(), dpFl.as<float>(), dpG.as<float>()};
-    GB_TRY(hipMemsetAsync(visits.p, 0, 4 * (size_t)n, stream));
-    hipLaunchKernelGGL(collapse_dp_kernel, grid_t, block, 0, stream, n, child.as<uint32_t>(), par_i.as<uint32_t>(), par_l.as<uint32_t>(), visits.as<uint32_t>(),
-                       bx.as<unsigned long long>(), dp);
+    GB_TRY(dpF.alloc(kDpFWords * (size_t)n));
+    GB_TRY(dpFl.alloc(kDpFlWords * (size_t)n));
+    GB_TRY(dpG.alloc((size_t)n));
+    dp = DpTables{dpF.p, dpFl.p, dpG.p};
+    GB_TRY(zero_on_device(t.visits.p, (size_t)n, stream));
+    hipLaunchKernelGGL(collapse_dp_kernel, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, stream, n, t.child.p, t.parent_internal.p, t.parent_leaf.p,
+                       t.visits.p, t.boxes.p, dp);
     GB_TRY(hipGetLastError());
   }
+  const auto kernel = use_dp ? collapse_kernel<true> : collapse_kernel<false>;
   constexpr uint32_t kBatch = 48;
+  static_assert(kBatch + 1 <= 64, "level_counts holds a batch's counts and the first count of the next");
   const CollapseItem root{0u, 0u, 0u};  // the binary tree's root, quad 0, nothing on the stack
   GB_TRY(hipMemcpyAsync(q0.p, &root, sizeof(root), hipMemcpyHostToDevice, stream));
   uint32_t h_counters[2] = {1u, 0u};  // quad 0 is the root's
   GB_TRY(hipMemcpyAsync(counters.p, h_counters, sizeof(h_counters), hipMemcpyHostToDevice, stream));
   uint32_t levels = 0;
-  CollapseItem *cur = q0.as<CollapseItem>(), *nxt = q1.as<CollapseItem>();
+  CollapseItem *cur = q0.p, *nxt = q1.p;
   for (uint32_t first = 1;;) {  // `first`: items of the batch's first level
     std::vector<uint32_t> zeros(kBatch + 1, 0u);
     zeros[0] = first;
-    GB_TRY(hipMemcpyAsync(level_counts.p, zeros.data(), 4 * zeros.size(), hipMemcpyHostToDevice, stream));
+    GB_TRY(hipMemcpyAsync(level_counts.p, zeros.data(), sizeof(uint32_t) * zeros.size(), hipMemcpyHostToDevice, stream));
     GB_TRY(hipStreamSynchronize(stream));  // (zeros is a local)
     uint64_t bound = first;
     for (uint32_t l = 0; l < kBatch; l++) {
       const uint32_t cap = (uint32_t)std::min<uint64_t>(bound, (uint64_t)n);
-      if (use_dp)
-        hipLaunchKernelGGL(collapse_kernel<true>, dim3((cap + 127u) / 128u), dim3(128), 0, stream, cur, level_counts.as<uint32_t>() + l, n,
-                           child.as<uint32_t>(), bx.as<unsigned long long>(), d_quads, nxt, counters.as<uint32_t>(), dp);
-      else
-        hipLaunchKernelGGL(collapse_kernel<false>, dim3((cap + 127u) / 128u), dim3(128), 0, stream, cur, level_counts.as<uint32_t>() + l, n,
-                           child.as<uint32_t>(), bx.as<unsigned long long>(), d_quads, nxt, counters.as<uint32_t>(), dp);
-      CollapseItem *t = cur; cur = nxt; nxt = t;
+      hipLaunchKernelGGL(kernel, dim3((cap + 127u) / 128u), dim3(128), 0, stream, cur, level_counts.p + l, n,
+                         t.child.p, t.boxes.p, d_quads, nxt, counters.p, dp);
+      std::swap(cur, nxt);
       bound = std::min<uint64_t>(bound * 4u, (uint64_t)n);
     }
     GB_TRY(hipGetLastError());
     std::vector<uint32_t> got(kBatch + 1);
-    GB_TRY(hipMemcpyAsync(got.data(), level_counts.p, 4 * got.size(), hipMemcpyDeviceToHost, stream));
+    GB_TRY(hipMemcpyAsync(got.data(), level_counts.p, sizeof(uint32_t) * got.size(), hipMemcpyDeviceToHost, stream));
     GB_TRY(hipStreamSynchronize(stream));
     for (uint32_t l = 0; l < kBatch && got[l]; l++) levels++;
     first = got[kBatch];
     if (!first) break;
   }
   GB_TRY(hipMemcpyAsync(h_counters, counters.p, sizeof(h_counters), hipMemcpyDeviceToHost, stream));
-  float root_box[6];  // {lo.x lo.y lo.z hi.x hi.y hi.z} of the root
-  GB_TRY(hipMemcpyAsync(root_box, bx.p, 24, hipMemcpyDeviceToHost, stream));
-  GB_TRY(hipEventRecord(e1, stream));
-  GB_TRY(hipStreamSynchronize(stream));
-  float ms = 0.f;
-  GB_TRY(hipEventElapsedTime(&ms, e0, e1));
-  info->n_quads = h_counters[0];
-  info->stack_need = h_counters[1];
-  info->levels = levels;
-  for (int a = 0; a < 3; a++) { info->root_lo[a] = root_box[a]; info->root_hi[a] = root_box[3 + a]; }
-  info->build_ms = ms;
+  GB_TRY(hipMemcpyAsync(out.root_box, t.boxes.p, sizeof(out.root_box), hipMemcpyDeviceToHost, stream));  // (node 0's kBoxWords words are six floats)
+  GB_TRY(hipEventRecord(done, stream));
+  GB_TRY(hipStreamSynchronize(stream));  // (h_counters is a local; the scratch above is freed when this function returns)
+  out.n_quads = h_counters[0];
+  out.stack_need = h_counters[1];
+  out.levels = levels;
+  return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_tris, uint32_t *d_order, uint4 *d_quads,
+                           uint32_t quad_capacity, uint32_t flags, GpuBuildInfo *info, hipStream_t stream) {
+  if (n_tris < 2u || n_tris > 0x7fffffffu) return hipErrorInvalidValue;  // (the caller builds trees of fewer than two triangles on the host)
+  if (quad_capacity + 1u < n_tris) return hipErrorInvalidValue;  // a quad per interior node of the binary tree at most
+  BinaryTree tree;
+  GB_TRY(tree.alloc((int)n_tris));
+  Events ev;
+  GB_TRY(ev.create());
+  GB_TRY(hipEventRecord(ev.a, stream));
+  GB_TRY(sah_build(d_P, d_idx, tree, d_order, stream));
+  info->reinsert = ReinsertStats{};
+  if (flags & kGpuBuildReinsert) GB_TRY(reinsert(tree, d_order, info->reinsert, stream));
+  CollapseResult c{};
+  GB_TRY(collapse(tree, d_quads, ev.b, c, stream));
+  GB_TRY(hipEventElapsedTime(&info->build_ms, ev.a, ev.b));
+  info->n_quads = c.n_quads;
+  info->stack_need = c.stack_need;
+  info->levels = c.levels;
+  for (int a = 0; a < 3; a++) { info->root_lo[a] = c.root_box[a]; info->root_hi[a] = c.root_box[3 + a]; }
   return hipSuccess;
 }
 

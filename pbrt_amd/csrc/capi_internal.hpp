@@ -1,4 +1,4 @@
-// capi_internal.hpp -- what the translation units behind the C ABI share: error reporting, device buffers, the scene object with the
+// capi_internal.hpp -- what the translation units behind the C ABI share: error reporting, the scene object (its buffers: dev_buf.hpp) with the
 // table of its arrays, and the film geometry (capi_scene.cpp makes single-GPU scenes, capi_render.cpp renders them, multi_gpu.cpp
 // replicates them across the devices of a node).
 #pragma once
@@ -6,11 +6,11 @@
 
 #include <exception>
 #include <string>
-#include <utility>
 
 #include "../../include/pbrt_hip.h"
 #include "../../include/pbrt_hip_debug.h"
 #include "bvh_build.hpp"
+#include "dev_buf.hpp"
 #include "device_types.h"
 
 namespace pbrt_hip {
@@ -23,42 +23,10 @@ int guarded(F &&body) {
   try { return body(); } catch (const std::exception &e) { return fail(PBRT_HIP_ERR_INTERNAL, e.what()); }
 }
 
-// A device allocation that the buffer owns: freed by its destructor, on whichever device is current then.  n and p change only
-// when hipMalloc succeeds; after a failure the buffer is empty (n == 0, p == nullptr), so a later grow() tries again.
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-  DevBuf &operator=(DevBuf o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }  // (moves only: o is moved into)
-  ~DevBuf() { release(); }
-  // frees what the buffer holds and allocates `count` elements (contents undefined)
-  hipError_t alloc(size_t count) {
-    release();
-    if (count == 0) return hipSuccess;
-    T *q = nullptr;
-    const hipError_t e = hipMalloc((void **)&q, count * sizeof(T));
-    if (e == hipSuccess) { p = q; n = count; }
-    return e;
-  }
-  // grow-only scratch: allocated anew (contents lost) when it holds fewer than `need` elements
-  hipError_t grow(size_t need) { return n < need ? alloc(need) : hipSuccess; }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
-// A scene's build time and GpuBuildInfo's re-insertion statistics (zeros for a host build; build_ms a double: the host path times itself)
+// A scene's build time (a double: the host path times itself) and the device builder's re-insertion statistics (zeros for a host build)
 struct BuildStats {
   double build_ms = 0.0;
-  uint32_t reinsert_passes = 0, reinsert_moves = 0;
-  double reinsert_ms = 0.0;
-  double reinsert_cost_before = 0.0, reinsert_cost_after = 0.0;  // summed half surface area of the interior nodes
-  uint32_t reinsert_undone = 0;
+  ReinsertStats reinsert;
 };
 
 // A scene's own stream (of pbrt_hip_render()) and the events that time a render.  A base of pbrt_hip_scene: base classes are

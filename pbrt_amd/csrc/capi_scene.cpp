@@ -369,7 +369,8 @@ int build_tree(pbrt_hip_scene *s, const SceneInputs &in, Builder builder) {
                             s->stream));
     if (gb.stack_need + 1u > 4096u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: device-built tree too deep");
     HIP_TRY(launch_pack_tris(s->d_P.p, s->d_idx.p, s->d_mat_id.p, s->d_order.p, np, D.n_tris, s->d_spheres.p, s->d_tris.p, s->stream));
-    s->build = {gb.build_ms, gb.reinsert_passes, gb.reinsert_moves, gb.reinsert_ms, gb.reinsert_cost_before, gb.reinsert_cost_after, gb.reinsert_undone};
+    s->build.build_ms = gb.build_ms;
+    s->build.reinsert = gb.reinsert;
     s->n_quads_gpu = gb.n_quads;
     D.n_nodes = 2u * np - 1u;
     D.root_ref = 0u;
@@ -603,17 +604,17 @@ int pbrt_hip_scene_build_info(const pbrt_hip_scene *s, uint32_t *gpu_built, doub
 
 int pbrt_hip_scene_optimize_info(const pbrt_hip_scene *s, uint32_t *passes, uint32_t *moves, double *ms) {
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "optimize_info: null scene");
-  if (passes) *passes = s->build.reinsert_passes;
-  if (moves) *moves = s->build.reinsert_moves;
-  if (ms) *ms = s->build.reinsert_ms;
+  if (passes) *passes = s->build.reinsert.passes;
+  if (moves) *moves = s->build.reinsert.moves;
+  if (ms) *ms = s->build.reinsert.ms;
   return PBRT_HIP_OK;
 }
 
 int pbrt_hip_scene_optimize_cost(const pbrt_hip_scene *s, double *before, double *after, uint32_t *undone) {
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "optimize_cost: null scene");
-  if (before) *before = s->build.reinsert_cost_before;
-  if (after) *after = s->build.reinsert_cost_after;
-  if (undone) *undone = s->build.reinsert_undone;
+  if (before) *before = s->build.reinsert.cost_before;
+  if (after) *after = s->build.reinsert.cost_after;
+  if (undone) *undone = s->build.reinsert.undone;
   return PBRT_HIP_OK;
 }
 

@@ -262,14 +262,19 @@ hipError_t launch_pack_uv(const float *tri_uv, const uint32_t *order, uint32_t n
 hipError_t launch_merge(const float4 *partials, float4 *slab, int32_t w, int32_t h, uint32_t rank, uint32_t world,
                         uint32_t n_local_super, uint32_t spp, hipStream_t stream, uint32_t j0 = 0, uint32_t jstride = 1);
 // bvh_gpu.hip: the accelerator built on the device.  d_order (n_tris) and d_quads (>= n_tris nodes of 4 uint4) are outputs.
+// What the tree's optimisation by parallel re-insertion (reinsert_core.hpp) did: THE definition, held by GpuBuildInfo and by a scene's
+// BuildStats (capi_internal.hpp) and reported by pbrt_hip_scene_optimize_info / _optimize_cost.  All zero where no pass ran.
+struct ReinsertStats {
+  uint32_t passes = 0, moves = 0;  // passes kept, moves applied in them
+  float ms = 0.f;                  // (hipEventElapsedTime's float; the C ABI widens it)
+  double cost_before = 0.0, cost_after = 0.0;  // summed half surface area of the interior nodes before the first and after the last kept pass
+  uint32_t undone = 0;                         // 1: a pass raised that sum, was undone and ended the passes
+};
 struct GpuBuildInfo {
   uint32_t n_quads, stack_need, levels;
   float root_lo[3], root_hi[3];
   float build_ms;  // everything, the optimisation included
-  uint32_t reinsert_passes, reinsert_moves;  // the tree's optimisation by parallel re-insertion (reinsert_core.hpp)
-  float reinsert_ms;
-  double reinsert_cost_before, reinsert_cost_after;  // summed half surface area of the interior nodes before the first and after the last kept pass
-  uint32_t reinsert_undone;                           // 1: a pass raised that sum, was undone and ended the passes
+  ReinsertStats reinsert;
 };
 constexpr uint32_t kGpuBuildReinsert = 1u;  // flags of gpu_build_quads: optimise the binary tree by re-insertion before the collapse
 hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_tris, uint32_t *d_order, uint4 *d_quads,

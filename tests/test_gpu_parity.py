@@ -4,6 +4,8 @@ comparison, executed in the same order on both sides with FMA contraction off (D
 so the film, the hit records and the visit counters must be identical, not merely close.
 (BASELINE.json asks for PSNR >= 50 dB; identical images are PSNR = inf.)"""
 import dataclasses
+import functools
+import json
 import os
 
 import numpy as np
@@ -1529,7 +1531,7 @@ def test_device_reinsertion_cuts_the_walks_work(gpu, oracle):
     with gpu.Scene(sd, builder="gpu") as sc:
         quads, order = sc.export_quads()
     assert np.array_equal(order, out["gpu"][3][1]), "leaf order differs between two device builds"
-    rows = lambda q: q[np.lexsort(q[:, :12].T[::-1])][:, :12]  # a node's origin, cells and child planes (words 0-11), sorted
+    from util import sorted_quad_rows as rows  # a node's origin, cells and child planes (words 0-11), sorted
     assert quads.shape == out["gpu"][3][0].shape and np.array_equal(rows(quads), rows(out["gpu"][3][0])), "quad nodes differ between two device builds"
     # the objective the passes lower, and its guard: the summed area of the interior nodes fell, by more than a tenth
     assert 0 < bi["reinsert_area_after"] < 0.9 * bi["reinsert_area_before"], bi
@@ -1540,7 +1542,7 @@ def test_device_refit_of_what_moved_equals_the_full_refit(gpu, monkeypatch):
     seventy; ri_mark_kernel / ri_refit_dirty_kernel).  The tree that comes out must be the one a refit of EVERY box after every pass
     makes (PBRT_HIP_REINSERT_FULL_REFIT: the round-4 kernel, kept for this comparison), word for word -- the searches of the next
     pass read those boxes, so a single stale box would change moves -- on 100k triangles and on the degenerate `ties` scene."""
-    rows = lambda q: q[np.lexsort(q[:, :12].T[::-1])][:, :12]
+    from util import sorted_quad_rows as rows
     for make in (lambda: scenes.random_mesh_scene(100_000, 64, 64), SMALL_SCENES["ties"], SMALL_SCENES["mesh20k"]):
         sd = make()
         got = {}
@@ -1557,6 +1559,27 @@ def test_device_refit_of_what_moved_equals_the_full_refit(gpu, monkeypatch):
         assert np.array_equal(oa, ob) and qa.shape == qb.shape and np.array_equal(rows(qa), rows(qb)), "sparse refit changed the tree"
         assert (ia["reinsert_passes"], ia["reinsert_moves"], ia["reinsert_area_after"]) == (ib["reinsert_passes"], ib["reinsert_moves"], ib["reinsert_area_after"])
         assert ia["reinsert_moves"] > 0
+
+
+@functools.lru_cache(maxsize=None)
+def _recorded_device_trees():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "device_trees.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("builder", ["gpu", "gpu-plain"])
+@pytest.mark.parametrize("name", ["mesh1k", "mesh20k", "cornell", "ties", "deep", "check_sphere", "spheres2k"])
+def test_device_built_trees_are_the_recorded_ones(gpu, name, builder):
+    """The device builder makes THE tree that tests/golden/device_trees.json records (make_golden_device_trees.py), not just a valid
+    one: quad count, stack need, re-insertion passes, moves and summed areas, the leaf order and the quad nodes' words 0-11 (rows
+    sorted) are equal.  The scenes reach every branch of the builder's host code: the greedy collapse (mesh1k, cornell: fewer than
+    1024 triangles) and the dynamic programme, several re-insertion passes (mesh20k), degenerate boxes (ties), many levels (deep),
+    proxy triangles (spheres2k, check_sphere); "gpu-plain" skips the re-insertion."""
+    from util import device_tree_record
+    want = _recorded_device_trees()[f"{name}/{builder}"]
+    with gpu.Scene(SMALL_SCENES[name](), builder=builder) as sc:
+        got = device_tree_record(sc)
+    assert got == want, {k: (got[k], want[k]) for k in want if got.get(k) != want[k]}
 
 
 def test_device_build_of_coincident_boxes_is_bounded(gpu, oracle):

@@ -194,6 +194,26 @@ def deep_tree_scene(xres=32, yres=32, k=400):
 SMALL_SCENES["deep"] = deep_tree_scene
 
 
+def sorted_quad_rows(quads):
+    """Words 0-11 of every quad node (its origin, cells and child planes), the rows sorted: what two builds of one tree have in common.
+    The child references (words 12-15) depend on the order in which the collapse's atomics numbered the nodes, so they stay out."""
+    return quads[np.lexsort(quads[:, :12].T[::-1])][:, :12]
+
+
+def device_tree_record(sc):
+    """What tests/golden/device_trees.json pins of a device-built scene (make_golden_device_trees.py records it, test_gpu_parity.py
+    compares it): the tree's counts, the re-insertion statistics (the areas as float.hex()) and hashes of the leaf order and of
+    sorted_quad_rows."""
+    import hashlib
+    quads, order = sc.export_quads()
+    info, bi = sc.info(), sc.build_info()
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a, np.uint32).tobytes()).hexdigest()
+    return {"n_quads": int(info["quad_nodes"]), "quad_stack_need": int(info["quad_stack_need"]),
+            "reinsert_passes": int(bi["reinsert_passes"]), "reinsert_moves": int(bi["reinsert_moves"]),
+            "reinsert_area_before": float(bi["reinsert_area_before"]).hex(), "reinsert_area_after": float(bi["reinsert_area_after"]).hex(),
+            "leaf_order_sha256": sha(order), "quad_rows_sha256": sha(sorted_quad_rows(quads))}
+
+
 # ---- closed forms that do not pass through the oracle (tests/test_oracle_selfcheck.py on the oracle, tests/test_gpu_parity.py on
 # the HIP path): the anchors of the path loop (A9) that are independent of the kernel's twin ----
 def _icosphere(levels):

@@ -96,6 +96,13 @@ int pbrt_hip_envmap_eval_device(pbrt_hip_scene *scene, int64_t n, const float *u
  *                              quad_step with the scalar and with the packed fma, the stand-in for 1 / 0 and the child selection around it)
  *   TRI_HIT                    p0 p1 p2 (9), o (3), d (3), tmax -> valid (0 or 1), t, u, v (zeros on a miss): the leaf pass's triangle test
  *                              (tri_test.inc: Moeller-Trumbore, the |det| cut, the own-box rule, t = max(th, entry))
+ *   MIS_W_LIGHT, MIS_W_BSDF    pl, pb -> the power heuristic's weight of the light sample, pl^2 / (pl^2 + pb^2), and of the BSDF-sampled ray,
+ *                              pb^2 / (pb^2 + pl^2) (kernel_math.hpp mis_weight_light / mis_weight_bsdf)
+ *   LIGHT                      the light's five float4 records as the scene's light table holds them (20 floats: word 0 = the raw bits of the
+ *                              device type -- 0 point, 1 distant, 2 constant sky, 3 emissive triangle --, words 1 .. 3 = p0; a triangle: 4 .. 6 =
+ *                              p1, 7 = area, 8 .. 10 = p2, 16 .. 18 = unit normal; 12 .. 14 = the colour), po (3), nf (3), kd (3), u1, u2, nL as
+ *                              a float, mis (0 or 1) -> accepted (0 or 1), Ld (3), wi (3), tmax (zeros where the light is ruled out): one call of
+ *                              kernel_path.hpp sample_light, mis handed in as the literal the render kernels hand in
  * PBRT_HIP_ERR_INVALID for an unknown op, a negative n or a null array. */
 #define PBRT_HIP_BLOCK_SIN 0u
 #define PBRT_HIP_BLOCK_COS 1u
@@ -109,7 +116,10 @@ int pbrt_hip_envmap_eval_device(pbrt_hip_scene *scene, int64_t n, const float *u
 #define PBRT_HIP_BLOCK_QUAD_STEP 9u
 #define PBRT_HIP_BLOCK_QUAD_STEP_PK 10u
 #define PBRT_HIP_BLOCK_TRI_HIT 11u
-#define PBRT_HIP_BLOCK_COUNT 12u
+#define PBRT_HIP_BLOCK_MIS_W_LIGHT 12u
+#define PBRT_HIP_BLOCK_MIS_W_BSDF 13u
+#define PBRT_HIP_BLOCK_LIGHT 14u
+#define PBRT_HIP_BLOCK_COUNT 15u
 int pbrt_hip_blocks_eval_device(int device, uint32_t op, int64_t n, const float *in, float *out);
 
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */

@@ -382,7 +382,7 @@ class PathIntegrator {
             scene.tri_verts(h.prim, &p0, &p1, &p2);
             const float area = 0.5f * length(cross(p1 - p0, p2 - p0));
             const float pl = ((h.t * h.t) / (cl * area)) / nLf;
-            const float w = (pb * pb) / (pb * pb + pl * pl);
+            const float w = mis_weight_bsdf(pb, pl);
             L = L + (beta * le) * w;
           }
         } else if (!hit && scene.has_infinite) {
@@ -395,7 +395,7 @@ class PathIntegrator {
           float pdf;
           const Vec3 le = env_radiance(ray.d, &pdf);
           const float pl = pdf / nLf;
-          const float w = (pb * pb) / (pb * pb + pl * pl);
+          const float w = mis_weight_bsdf(pb, pl);
           if (g_debug_li) std::fprintf(stderr, "ORC   map escape pb %a pl %a w %a\n", pb, pl, w);
           L = L + (beta * le) * w;
         }
@@ -524,7 +524,7 @@ class PathIntegrator {
     float scale = (cs / pdf) * nLf;
     if (mis_) {
       const float pl = pdf / nLf, pbl = cs * kInvPi;
-      scale = scale * ((pl * pl) / (pl * pl + pbl * pbl));
+      scale = scale * mis_weight_light(pl, pbl);
     }
     *Ld = (f * (scene.env_c * scene.env.texel(k))) * scale;
     sh->o = po;
@@ -590,7 +590,7 @@ class PathIntegrator {
       float scale = (((cs * cl) * l.area) / dist2) * nLf;
       if (mis) {
         const float pl = (dist2 / (cl * l.area)) / nLf, pbl = cs * kInvPi;
-        scale = scale * ((pl * pl) / (pl * pl + pbl * pbl));
+        scale = scale * mis_weight_light(pl, pbl);
       }
       *Ld = (f * l.c) * scale;
       sh->d = wi;
@@ -975,7 +975,7 @@ int orc_envmap_eval(const float *rgb, uint32_t W, uint32_t H, const float M[9], 
 // cosine_sample_about above), op codes
 // and layouts as the product's hook pbrt_hip_blocks_eval_device
 int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out) {
-  static const struct { uint32_t in, out; } kBlocks[ORC_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}, {24, 6}, {24, 6}, {16, 4}};
+  static const struct { uint32_t in, out; } kBlocks[ORC_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}, {24, 6}, {24, 6}, {16, 4}, {2, 1}, {2, 1}, {33, 8}};
   if (op >= ORC_BLOCK_COUNT || n < 0 || !in || !out) return -1;
   for (int64_t i = 0; i < n; i++) {
     const float *x = in + i * kBlocks[op].in;
@@ -1003,6 +1003,23 @@ int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out) {
         const bool hit = Scene::tri_hit(v3(x[0], x[1], x[2]), v3(x[3], x[4], x[5]), v3(x[6], x[7], x[8]), r, &tt, &u, &v);
         y[0] = hit ? 1.0f : 0.f;
         y[1] = hit ? tt : 0.f; y[2] = hit ? u : 0.f; y[3] = hit ? v : 0.f;
+        break;
+      }
+      case ORC_BLOCK_MIS_W_LIGHT: y[0] = mis_weight_light(x[0], x[1]); break;
+      case ORC_BLOCK_MIS_W_BSDF: y[0] = mis_weight_bsdf(x[1], x[0]); break;
+      case ORC_BLOCK_LIGHT: {  // the device's five records of a light (word 0 = the bits of its type there: 3 is an emissive triangle)
+        LightRec l{};
+        std::memcpy(&l.type, &x[0], 4);
+        l.p0 = v3(x[1], x[2], x[3]); l.p1 = v3(x[4], x[5], x[6]); l.area = x[7]; l.p2 = v3(x[8], x[9], x[10]);
+        l.c = v3(x[12], x[13], x[14]); l.n = v3(x[16], x[17], x[18]);
+        Vec3 Ld = v3(0.f, 0.f, 0.f);
+        Ray sh;
+        sh.d = v3(0.f, 0.f, 0.f); sh.tmax = 0.f;
+        const bool ok = PathIntegrator::sample_light(l, v3(x[20], x[21], x[22]), v3(x[23], x[24], x[25]), v3(x[26], x[27], x[28]), x[29], x[30], x[31], &Ld, &sh, x[32] != 0.f);
+        y[0] = ok ? 1.0f : 0.f;
+        y[1] = ok ? Ld.x : 0.f; y[2] = ok ? Ld.y : 0.f; y[3] = ok ? Ld.z : 0.f;
+        y[4] = ok ? sh.d.x : 0.f; y[5] = ok ? sh.d.y : 0.f; y[6] = ok ? sh.d.z : 0.f;
+        y[7] = ok ? sh.tmax : 0.f;
         break;
       }
       default: {  // ORC_BLOCK_SPHERE_HIT

@@ -292,6 +292,22 @@ static inline void glass_fresnel(float ci, float r, float *F, float *ct) {
   }
 }
 
+// ---- the power heuristic's two weights, by name so that orc_blocks_eval runs the same statements: pl = the density light
+// sampling has for a direction, pb = the BSDF's; the light sample's pl^2 / (pl^2 + pb^2) and the bounce ray's pb^2 / (pb^2 + pl^2) ----
+// The ends of the range: pl^2 = +inf (pl >= 2^64) would make the light's weight inf / inf -- it is the limit, 1; both squares zero (densities
+// below 2^-75, which no render reaches) would make 0 / 0 -- the larger density takes the whole weight.  Elsewhere the expression's own bits.
+static inline float mis_weight_light(float pl, float pb) {
+  const float a = pl * pl, d = a + pb * pb;
+  if (a == kInf) return 1.0f;
+  if (d == 0.f) return pl >= pb ? 1.0f : 0.f;
+  return a / d;
+}
+static inline float mis_weight_bsdf(float pb, float pl) {
+  const float b = pb * pb, d = b + pl * pl;
+  if (d == 0.f) return pb > pl ? 1.0f : 0.f;
+  return b / d;
+}
+
 // ---- the environment map's arithmetic, restated from the spec's text: the oracle's own declarations, nothing shared with
 // the product.  fp32, one order of operations, no libm on the path: atan / acos are the polynomials above, sin / cos those of 3.6 carried
 // over [0, 2 pi] by Cephes' octant reduction. ----

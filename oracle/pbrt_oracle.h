@@ -162,10 +162,14 @@ int orc_envmap_eval(const float *rgb, uint32_t W, uint32_t H, const float M[9], 
  * FRESNEL: ci, r = eta_i / eta_t -> F, ct; COSINE_ABOUT: n (3), u1, u2 -> wi (3), z; SPHERE_HIT: {centre, radius} (4), o (3), d (3), tmax ->
  * hit (0 or 1), t (0 on a miss): the sphere test before the own-box rule; QUAD_STEP, QUAD_STEP_PK (one statement here): the node's 16 words
  * as raw bits, o (3), d (3), inv_parallel, tfar -> tn of children 0 .. 3, the hit mask, the slot entered (4 = none): one step of
- * quad_walk.cpp; TRI_HIT: p0 p1 p2 (9), o (3), d (3), tmax -> valid, t, u, v (zeros on a miss): Scene::tri_hit, the own-box rule included.
+ * quad_walk.cpp; TRI_HIT: p0 p1 p2 (9), o (3), d (3), tmax -> valid, t, u, v (zeros on a miss): Scene::tri_hit, the own-box rule included;
+ * MIS_W_LIGHT, MIS_W_BSDF: pl, pb -> pl^2 / (pl^2 + pb^2), pb^2 / (pb^2 + pl^2) (oracle_math.hpp mis_weight_light / mis_weight_bsdf); LIGHT: a
+ * light as the device's table holds it (20 floats: the bits of the type -- 3 = emissive triangle --, p0, p1, area, p2, 0, colour, 0, normal, 0),
+ * po (3), nf (3), kd (3), u1, u2, nL, mis (0 or 1) -> accepted, Ld (3), wi (3), tmax (zeros where ruled out): PathIntegrator::sample_light.
  * 0, or -1 for an unknown op, a negative n or a null array */
 enum { ORC_BLOCK_SIN = 0, ORC_BLOCK_COS, ORC_BLOCK_ATAN_POS, ORC_BLOCK_ACOS, ORC_BLOCK_SINCOS, ORC_BLOCK_SPHERE_UV, ORC_BLOCK_FRESNEL,
-       ORC_BLOCK_COSINE_ABOUT, ORC_BLOCK_SPHERE_HIT, ORC_BLOCK_QUAD_STEP, ORC_BLOCK_QUAD_STEP_PK, ORC_BLOCK_TRI_HIT, ORC_BLOCK_COUNT };
+       ORC_BLOCK_COSINE_ABOUT, ORC_BLOCK_SPHERE_HIT, ORC_BLOCK_QUAD_STEP, ORC_BLOCK_QUAD_STEP_PK, ORC_BLOCK_TRI_HIT,
+       ORC_BLOCK_MIS_W_LIGHT, ORC_BLOCK_MIS_W_BSDF, ORC_BLOCK_LIGHT, ORC_BLOCK_COUNT };
 int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out);
 /* one element of QUAD_STEP (quad_walk.cpp; what orc_blocks_eval calls): x = 24 floats, y = 6 */
 void orc_quad_step_eval(const float *x, float *y);

@@ -320,7 +320,8 @@ def envmap_eval_host(rgb, world_to_light=None, u12=None, d=None):
 # op codes of pbrt_hip_blocks_eval_device (include/pbrt_hip_debug.h PBRT_HIP_BLOCK_*): name -> (op, floats read, floats written per element)
 BLOCK_OPS = {"SIN": (0, 1, 1), "COS": (1, 1, 1), "ATAN_POS": (2, 1, 1), "ACOS": (3, 1, 1), "SINCOS": (4, 1, 2), "SPHERE_UV": (5, 3, 2),
              "FRESNEL": (6, 2, 2), "COSINE_ABOUT": (7, 5, 4), "SPHERE_HIT": (8, 11, 2),
-             "QUAD_STEP": (9, 24, 6), "QUAD_STEP_PK": (10, 24, 6), "TRI_HIT": (11, 16, 4)}
+             "QUAD_STEP": (9, 24, 6), "QUAD_STEP_PK": (10, 24, 6), "TRI_HIT": (11, 16, 4),
+             "MIS_W_LIGHT": (12, 2, 1), "MIS_W_BSDF": (13, 2, 1), "LIGHT": (14, 33, 8)}
 
 
 def blocks_eval(op, x, device=0):

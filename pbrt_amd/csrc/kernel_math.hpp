@@ -132,6 +132,24 @@ __device__ __forceinline__ float cosine_about(V3 n, float u1, float u2, V3 &wi) 
   return z;
 }
 
+// The power heuristic's two weights: pl = the density light sampling has for a direction, pb = the BSDF's.
+// mis_weight_light is the light sample's pl^2 / (pl^2 + pb^2), mis_weight_bsdf the bounce ray's pb^2 / (pb^2 + pl^2).  The ends of the range:
+// from pl = 2^64 upwards pl^2 is +inf and the quotient inf / inf -- the light's weight is its limit there, 1 (a tiny emitter far away or seen
+// at a grazing angle: pl = d^2 / (cos A nL)), the bounce ray's comes out as 0 by itself; where BOTH squares round to zero (densities below
+// 2^-75: no render reaches it, pb >= 2^-24 / pi) the quotient is 0 / 0 and the larger density takes the whole weight.  Everywhere else the
+// value is the expression's, bit for bit.
+__device__ __forceinline__ float mis_weight_light(float pl, float pb) {
+  const float a = pl * pl, d = a + pb * pb;
+  if (a == kInf) return 1.0f;
+  if (d == 0.f) return pl >= pb ? 1.0f : 0.f;
+  return a / d;
+}
+__device__ __forceinline__ float mis_weight_bsdf(float pb, float pl) {
+  const float b = pb * pb, d = b + pl * pl;
+  if (d == 0.f) return pb > pl ? 1.0f : 0.f;
+  return b / d;
+}
+
 struct HitRec {
   float t;
   uint32_t prim;  // triangle id (or n_tris + sphere index); kNoPrim on a miss

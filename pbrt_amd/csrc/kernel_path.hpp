@@ -68,7 +68,7 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
     float scale = (((cs * cl) * l1.w) / dist2) * nLf;
     if (mis) {
       const float pl = (dist2 / (cl * l1.w)) / nLf, pbl = cs * kInvPi;
-      scale = scale * ((pl * pl) / (pl * pl + pbl * pbl));
+      scale = scale * mis_weight_light(pl, pbl);
     }
     Ld = (f * lc) * scale;
     tmax = dist * kShadowShrink;
@@ -110,7 +110,7 @@ __device__ __forceinline__ bool sample_env_light(const RenderParams &R, V3 nf, V
   float scale = (cs / pdf) * nLf;
   if (mis) {
     const float pl = pdf / nLf, pbl = cs * kInvPi;
-    scale = scale * ((pl * pl) / (pl * pl + pbl * pbl));
+    scale = scale * mis_weight_light(pl, pbl);
   }
   Ld = (f * (mk(R.env_c[0], R.env_c[1], R.env_c[2]) * xyz(tx))) * scale;
   tmax = kInf;

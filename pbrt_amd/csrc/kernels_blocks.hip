@@ -1,6 +1,6 @@
 // kernels_blocks.hip -- the kernels' building blocks over arrays: pbrt_hip_blocks_eval_device, the hook that lets tests/ compare the
 // polynomials of cephes_poly.hpp, envmap_core.hpp's sincos_0_2pi, kernel_math.hpp's sphere_uv / glass_fresnel / cosine_about /
-// sphere_hit and the walk's node step and triangle test (kernel_walk.hpp quad_step / walk_inv, quad_nearest.inc, tri_test.inc) with a float64 reference and with the oracle's restatements, element by element, without a render around them.  In a
+// sphere_hit / mis_weight_light / mis_weight_bsdf, kernel_path.hpp's sample_light and the walk's node step and triangle test (kernel_walk.hpp quad_step / walk_inv, quad_nearest.inc, tri_test.inc) with a float64 reference and with the oracle's restatements, element by element, without a render around them.  In a
 // translation unit of its own so that the render and intersect kernels of kernels*.hip keep their names and their machine code.
 //
 //   blocks_eval_kernel  one element per thread, 256 threads per workgroup: switches on the op code and calls the PRODUCTION function
@@ -8,6 +8,7 @@
 #include "capi_internal.hpp"
 #include "envmap_core.hpp"
 #include "kernel_math.hpp"
+#include "kernel_path.hpp"
 #include "kernel_walk.hpp"
 
 namespace pbrt_hip {
@@ -17,7 +18,7 @@ struct BlockWidth {
   uint32_t in, out;
 };
 // indexed by op (include/pbrt_hip_debug.h PBRT_HIP_BLOCK_*)
-constexpr BlockWidth kBlockWidth[PBRT_HIP_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}, {24, 6}, {24, 6}, {16, 4}};
+constexpr BlockWidth kBlockWidth[PBRT_HIP_BLOCK_COUNT] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 2}, {3, 2}, {2, 2}, {5, 4}, {11, 2}, {24, 6}, {24, 6}, {16, 4}, {2, 1}, {2, 1}, {33, 8}};
 
 __global__ void __launch_bounds__(256) blocks_eval_kernel(uint32_t op, int64_t n, uint32_t w_in, uint32_t w_out, const float *in, float *out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -80,6 +81,26 @@ __global__ void __launch_bounds__(256) blocks_eval_kernel(uint32_t op, int64_t n
       y[1] = valid ? tsnap : 0.f;  // (zeros on a miss)
       y[2] = valid ? u : 0.f;
       y[3] = valid ? v : 0.f;
+      break;
+    }
+    case PBRT_HIP_BLOCK_MIS_W_LIGHT: y[0] = mis_weight_light(x[0], x[1]); break;
+    case PBRT_HIP_BLOCK_MIS_W_BSDF: y[0] = mis_weight_bsdf(x[1], x[0]); break;
+    case PBRT_HIP_BLOCK_LIGHT: {
+      // the light's records in a local table (no alignment asked of the input row), light 0 of a scene that holds nothing else
+      float4 rec[5];
+      for (int k = 0; k < 5; k++) rec[k] = make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
+      DevScene S{};
+      S.lights = rec;
+      const V3 po = mk(x[20], x[21], x[22]), nf = mk(x[23], x[24], x[25]), kd = mk(x[26], x[27], x[28]);
+      V3 Ld = {0.f, 0.f, 0.f}, wi = {0.f, 0.f, 0.f};
+      float tmax = 0.f;
+      // mis as the render kernels hand it in: a literal (their MIS template argument)
+      const bool ok = x[32] != 0.f ? sample_light(S, 0u, po, nf, kd, x[29], x[30], x[31], Ld, wi, tmax, true)
+                                   : sample_light(S, 0u, po, nf, kd, x[29], x[30], x[31], Ld, wi, tmax, false);
+      y[0] = ok ? 1.0f : 0.f;
+      y[1] = ok ? Ld.x : 0.f; y[2] = ok ? Ld.y : 0.f; y[3] = ok ? Ld.z : 0.f;
+      y[4] = ok ? wi.x : 0.f; y[5] = ok ? wi.y : 0.f; y[6] = ok ? wi.z : 0.f;
+      y[7] = ok ? tmax : 0.f;
       break;
     }
     default: break;

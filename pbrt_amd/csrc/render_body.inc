@@ -138,7 +138,7 @@
               if ((le.x > 0.f || le.y > 0.f || le.z > 0.f) && cl > 0.f) {
                 const float pb = rec_load(rec, kRecLpend).w;
                 const float pl = ((h.t * h.t) / (cl * tri_area)) / nLf;
-                const float w = (pb * pb) / (pb * pb + pl * pl);
+                const float w = mis_weight_bsdf(pb, pl);
                 P.L = P.L + (P.beta * le) * w;
               }
             } else if (!hit && S.has_inf) {
@@ -152,7 +152,7 @@
               const V3 le = env_le(R, T.d, &pdf_l);
               const float pb = rec_load(rec, kRecLpend).w;
               const float pl = pdf_l / nLf;
-              const float w = (pb * pb) / (pb * pb + pl * pl);
+              const float w = mis_weight_bsdf(pb, pl);
               P.L = P.L + (P.beta * le) * w;
             }
           }

@@ -1,5 +1,5 @@
 """The kernels' building blocks on the device (pbrt_hip_blocks_eval_device: a tiny kernel that calls cephes_poly.hpp, envmap_core.hpp,
-kernel_math.hpp and the walk's node step and triangle test -- kernel_walk.hpp quad_step, quad_nearest.inc, tri_test.inc -- themselves) over the input sets of tests/blocks_ref.py: every output equal to the oracle's bit for bit -- NaN and inf
+kernel_math.hpp, kernel_path.hpp's sample_light and the walk's node step and triangle test -- kernel_walk.hpp quad_step, quad_nearest.inc, tri_test.inc -- themselves) over the input sets of tests/blocks_ref.py: every output equal to the oracle's bit for bit -- NaN and inf
 included --, and the float64 bounds of tests/test_blocks_host.py on the device's own values."""
 import numpy as np
 import pytest
@@ -55,7 +55,10 @@ def test_fresnel_clamps_a_cosine_above_one(gpu, oracle):
 
 def test_device_hook_refuses_an_unknown_op(gpu):
     from pbrt_amd import _lib
-    a = np.zeros(4, np.float32)
-    with pytest.raises(_lib.PbrtHipError) as e:
-        _lib.check(_lib.lib().pbrt_hip_blocks_eval_device(0, 99, 4, a.ctypes.data_as(_lib._pf), a.ctypes.data_as(_lib._pf)), "pbrt_hip_blocks_eval_device")
-    assert e.value.code == -1
+    from pbrt_amd import api
+    a = np.zeros(64, np.float32)
+    for op in (len(api.BLOCK_OPS), 99):  # PBRT_HIP_BLOCK_COUNT itself, and beyond
+        with pytest.raises(_lib.PbrtHipError) as e:
+            _lib.check(_lib.lib().pbrt_hip_blocks_eval_device(0, op, 1, a.ctypes.data_as(_lib._pf), a.ctypes.data_as(_lib._pf)), "pbrt_hip_blocks_eval_device")
+        assert e.value.code == -1
+    assert len(api.BLOCK_OPS) == 15

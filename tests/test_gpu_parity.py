@@ -1162,6 +1162,22 @@ def test_mis_integrator_matches_oracle(gpu, oracle, name, depth, spp, seed):
         assert_bit_equal(sc.render(**wkw)[0], o.render(**wkw)[0], f"{name}, MIS + sampler 2 under a wide box filter")
 
 
+def test_far_tiny_emitter_matches_oracle_and_twin(gpu, oracle):
+    """tests/test_oracle_selfcheck.py test_far_tiny_emitter_keeps_its_samples_and_equals_the_twin on the HIP path: an emitter whose
+    light-sampling density squared is +inf in float32 (the light's weight is its limit, 1) -- the film bit-equal to the
+    oracle's and equal to the float64 twin's at the bar of the fixed MIS cases"""
+    import independent_twin as tw
+    from util import FAR_TINY_EMITTER_KW as kw, far_tiny_emitter_scene
+    sd = far_tiny_emitter_scene()
+    with gpu.Scene(sd) as sc:
+        film, _ = sc.render(**kw)
+    assert_bit_equal(film, oracle.OracleScene(sd).render(**kw)[0], "far tiny emitter, MIS")
+    twin = tw.render(sd, **kw)
+    rel = np.abs(twin[..., :3] - film[..., :3]) / np.maximum(np.abs(film[..., :3]), 1e-3 * film[..., :3].max())
+    assert tw.psnr_db(twin, film) >= 90.0 and (rel.max(-1) < 1e-4).mean() >= 0.99, (tw.psnr_db(twin, film), (rel.max(-1) < 1e-4).mean())
+    assert np.array_equal(twin[..., 3], film[..., 3])
+
+
 def test_mis_closes_the_heavy_tail_of_the_emitting_box_on_the_gpu(gpu):
     """tests/test_oracle_selfcheck.py's closed form for integrator 2 on the HIP path itself: inside the emitting, reflecting CUBE --
     where light sampling alone leaves a heavy tail -- every pixel is Le sum rho^i to 0.1 % at 6 x 24^2 x 64 samples."""

@@ -797,6 +797,28 @@ def test_oracle_image_equals_an_independent_float64_implementation_of_the_spec(o
     assert tw.psnr_db(tw.render(sd, **dict(kw, max_depth=3)), film) < 40.0
 
 
+def test_far_tiny_emitter_keeps_its_samples_and_equals_the_twin(oracle):
+    """util.far_tiny_emitter_scene: an emissive triangle of area 2^-40 at height 2^13 over a floor and a wall under a point light, MIS, depth 4,
+    32 x 32 at 16 spp.  The triangle's light-sampling density is pl >= 2^65 at every vertex that picks it, pl^2 = +inf in float32, and the
+    plain power heuristic inf / inf = NaN: the NaN went through Ld into the sample's radiance, and the sanitiser before the film zeroed the
+    WHOLE sample, the point light's share and every other vertex's with it (6 samples in 10 of this frame, 11 dB against the twin).  The
+    weight's limit is 1 there: the film equals the float64 twin's at the bar of the fixed MIS cases above (>= 90 dB, 99 % of
+    the pixels to 1e-4, the weights exactly), and no sample of the frame comes out black -- every camera ray meets a surface both lights reach."""
+    import independent_twin as tw
+    from util import FAR_TINY_EMITTER_KW as kw, far_tiny_emitter_scene
+    sd = far_tiny_emitter_scene()
+    o = oracle.OracleScene(sd)
+    twin, (film, _) = tw.render(sd, **kw), o.render(**kw)
+    rel = np.abs(twin[..., :3] - film[..., :3]) / np.maximum(np.abs(film[..., :3]), 1e-3 * film[..., :3].max())
+    print("far tiny emitter:", tw.psnr_db(twin, film), "dB,", (rel.max(-1) < 1e-4).mean(), "of the pixels to 1e-4")
+    assert tw.psnr_db(twin, film) >= 90.0 and (rel.max(-1) < 1e-4).mean() >= 0.99, (tw.psnr_db(twin, film), (rel.max(-1) < 1e-4).mean())
+    assert np.array_equal(twin[..., 3], film[..., 3])
+    samples = np.concatenate([o.pixel_samples(x, y, **kw) for y in range(sd.yres) for x in range(sd.xres)])
+    black = (samples == 0).all(1)
+    assert len(samples) == 16 * sd.xres * sd.yres and not black.any(), (int(black.sum()), len(samples))
+    assert np.isfinite(samples).all()
+
+
 def test_oracle_equals_the_independent_implementation_on_random_scenes(oracle):
     """The comparison above on scenes nobody chose: the first 120 seeds of the soak's generator (util.random_twin_case: 0 ... 300 triangles with
     duplicates and degenerate ones, emissive triangles, mirrors, 0 ... 4 spheres, up to four lights of every kind, suns along axes, crop windows,

@@ -261,6 +261,40 @@ def furnace_scene(rho, le=1.0, res=24, shape="sphere"):
                      cam_to_world=look_at((0.1, -0.2, 0.05), (0.4, 1.0, 0.3), (0, 0, 1))[1], fov=70.0, xres=res, yres=res).normalized()
 
 
+def far_tiny_emitter_scene(res=32):
+    """A matte floor (3 x 3 quads) and a back wall that fill the frame, a bright point light above the floor, and ONE emissive triangle of area
+    2^-40 at height 2^13 that faces the floor: 21 triangles, two lights.  The light-sampling density of the triangle's sample is
+    pl = (d^2 / (cos A)) / nL = 2^26 2^40 / 2 = 2^65 seen from the floor, more from the wall (a grazing cos): pl^2 is +inf in float32 at
+    EVERY vertex that picks the triangle -- half of all vertices.  Its radiance 2^66 makes its estimate (f Le) (A / d^2) nL
+    of the order of the point light's.  Every camera ray meets floor or wall, and both lights reach every point of both: no sample of the
+    frame is black."""
+    from pbrt_amd.api import LIGHT_POINT, MATTE, SceneData, look_at
+    V, I, M = [], [], []
+
+    def quad(p0, p1, p2, p3, m):
+        I.extend([[len(V), len(V) + 1, len(V) + 2], [len(V), len(V) + 2, len(V) + 3]])
+        V.extend([p0, p1, p2, p3])
+        M.extend([m, m])
+
+    xs, ys = np.linspace(-4.0, 4.0, 4), np.linspace(-6.0, 2.0, 4)
+    for i in range(3):
+        for j in range(3):
+            quad((xs[i], ys[j], 0), (xs[i + 1], ys[j], 0), (xs[i + 1], ys[j + 1], 0), (xs[i], ys[j + 1], 0), 0)
+    quad((-4, 2, 0), (4, 2, 0), (4, 2, 8), (-4, 2, 8), 1)
+    h = 2.0 ** 13
+    I.append([len(V), len(V) + 1, len(V) + 2])   # (0, 2^-19, 0) x (2^-20, 0, 0) = (0, 0, -2^-39): area 2^-40, normal -z
+    V.extend([(0, 0, h), (0, 2.0 ** -19, h), (2.0 ** -20, 0, h)])
+    M.append(2)
+    le = 2.0 ** 66
+    mats = [[MATTE, 0.6, 0.55, 0.5, 0, 0, 0], [MATTE, 0.3, 0.4, 0.6, 0, 0, 0], [MATTE, 0, 0, 0, 1.5 * le, le, 0.5 * le]]
+    return SceneData(P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16), materials=np.array(mats, np.float32),
+                     lights=np.array([[LIGHT_POINT, 0, 0, 3, 40, 40, 40]], np.float32),
+                     cam_to_world=look_at((0, -4, 2), (0, 1, 0.7), (0, 0, 1))[1], fov=40.0, xres=res, yres=res).normalized()
+
+
+FAR_TINY_EMITTER_KW = dict(integrator=2, max_depth=4, spp=(4, 4), seed=4)
+
+
 def furnace_expectation(rho, max_depth, le=1.0):
     return le * sum(rho ** i for i in range(max_depth + 1))
 

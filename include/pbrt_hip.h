@@ -68,7 +68,8 @@ typedef struct {
  * empty marker): pbrt-v3's Checkerboard2DTexture over a UVMapping2D, point-sampled (aamode "none": no ray differentials here):
  * (s, t) = (su u + du, sv v + dv); tex1 where floor(s) + floor(t) is even, tex2 where odd.  64 bytes. */
 typedef struct {
-  uint32_t type;  /* 0 = checkerboard, dimension 2, "uv" mapping; 1 = this slot is the environment-map record below */
+  uint32_t type;  /* 0 = checkerboard, dimension 2, "uv" mapping; 1 = this slot is the environment-map record below; 2 = the shading
+                     normals' record, pbrt_hip_normals */
   float tex1[3], tex2[3];
   float su, sv, du, dv; /* "float uscale" / "vscale" / "udelta" / "vdelta" */
   uint32_t pad[5];
@@ -95,6 +96,28 @@ typedef struct {
   float world_to_light[9]; /* row-major 3 x 3 rotation: the inverse of the light's CTM */
   uint32_t pad;
 } pbrt_hip_envmap;
+
+/* Shape "trianglemesh" "normal N" / "plymesh" with nx ny nz and "bool shadingnormals" "true" (the reference reads neither): per-corner shading normals.
+ * A slot of `textures` whose first word is 2 IS this record -- 64 bytes, read with memcpy like the environment map's.  At a triangle hit
+ * the three corner normals are interpolated with the hit's barycentrics in the order of the hit point, normalised and turned to the side
+ * of the WINDING's normal ng (pbrt-v3 turns ng towards N instead: a deliberate difference -- one-sided emission and everything else that
+ * hangs on ng stays where it was); matte and mirror scatter about that shading normal, a light sample and a bounce count only on the
+ * geometric front side as well.  A triangle whose interpolated normal is zero (all three corners zero = "this mesh has none") or not
+ * finite is shaded flat.  Spheres keep their analytic normal; a GLASS triangle ignores its normals (3.16 keeps ng).
+ * Refused before any device work (the message holds "normal"): more than one such slot (PBRT_HIP_ERR_LIMIT); n_tris other than the
+ * description's, a NULL tri_n, a component that is not finite, a matte kd_tex that names the slot (PBRT_HIP_ERR_INVALID).  A scene with the
+ * slot runs the NRM kernels (kernels_n.hip render_kernel_n); they exist for every integrator and sampler, with and without spheres,
+ * textures, glass and an environment map, and NOT for: a box filter radius other than 0.5, the counter flags (both PBRT_HIP_ERR_LIMIT at
+ * render, the message names the combination). */
+#define PBRT_HIP_TEXTURE_NORMALS 2u
+typedef struct {
+  uint32_t type;        /* = 2 */
+  uint32_t n_tris;      /* must equal desc.n_tris */
+  uint32_t reserved[2]; /* = 0 */
+  const float *tri_n;   /* host, 9 * n_tris: the normals of the three corners of every triangle, world space, any length; a zero
+                           normal = "none"; copied during the call */
+  uint32_t pad[10];
+} pbrt_hip_normals;
 
 /* LightSource "point" / "distant" / "infinite" (api.rs:334-351 make_light: todo!() for all).
  * Type 3 is the infinite light with an environment map: c = the factor on the texels (L x scale, infinite.rs:54), `pad`
@@ -195,7 +218,9 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.7 (gfx950; struct sizes of 0.6)": 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.8 (gfx950; struct sizes of 0.6, as 0.7)": 0.8 = texture-table slot type 2, the shading normals,
+                                       inside the same struct sizes ("as 0.7": a test of the environment map looks for "0.7" the way the
+                                       glass test looks for "0.6"); 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
                                        end, pbrt_hip_material.pad became kd_tex, flags 0 of scene_create_ex = the device builder); 0.6 =
                                        material type 2, glass, inside the same struct sizes; 0.7 = light type 3 and texture-table
                                        slot type 1, the environment map, again inside the same struct sizes.  The "(... struct sizes of 0.6)"

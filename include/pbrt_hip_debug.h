@@ -122,6 +122,14 @@ int pbrt_hip_envmap_eval_device(pbrt_hip_scene *scene, int64_t n, const float *u
 #define PBRT_HIP_BLOCK_COUNT 15u
 int pbrt_hip_blocks_eval_device(int device, uint32_t op, int64_t n, const float *in, float *out);
 
+/* ---- shading normals (pbrt_amd/csrc/shading_normal.inc is the one statement of the arithmetic) ---- */
+/* The text the NRM render kernels include at a triangle hit, over arrays on `device` (a tiny kernel of kernels_n.hip that includes the same
+ * file).  Floats per element, in (17): the corner normals n0 n1 n2 (9), the winding's unit normal ng (3), the barycentrics b1, b2, wo (3);
+ * out (4): nsf (3) -- the interpolated, normalised normal turned to ng's side and then to wo's geometric side --, fell_back (0 or 1: the
+ * interpolated normal was zero or not finite, nsf is +-ng bit for bit).  in / out are HOST arrays; PBRT_HIP_ERR_INVALID for a negative
+ * n or a null array. */
+int pbrt_hip_shading_normal_eval_device(int device, int64_t n, const float *in, float *out);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

@@ -21,6 +21,12 @@ class EnvMap(C.Structure):
                 ("world_to_light", C.c_float * 9), ("pad", C.c_uint32)]
 
 
+class Normals(C.Structure):
+    """pbrt_hip_normals: what a slot of the texture table IS when its first word is 2; 64 bytes like Texture"""
+    _fields_ = [("type", C.c_uint32), ("n_tris", C.c_uint32), ("reserved", C.c_uint32 * 2), ("tri_n", C.POINTER(C.c_float)),
+                ("pad", C.c_uint32 * 10)]
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_uint32), ("p", C.c_float * 3), ("c", C.c_float * 3), ("pad", C.c_float)]
 
@@ -120,6 +126,7 @@ SYMBOLS = {
     "pbrt_hip_envmap_eval_host": (C.c_int, [_pf, _u32, _u32, _pf, _i64, _pf, _pf, _pu32, _pf, _pf]),
     "pbrt_hip_envmap_eval_device": (C.c_int, [_vp, _i64, _pf, _pf, _pu32, _pf, _pf]),
     "pbrt_hip_blocks_eval_device": (C.c_int, [C.c_int, _u32, _i64, _pf, _pf]),
+    "pbrt_hip_shading_normal_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
 }
 
 _lib = None

@@ -9,7 +9,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import EnvMap, Light, Material, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
+from ._lib import EnvMap, Light, Material, Normals, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
 
 MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
@@ -42,7 +42,9 @@ class SceneData:
     a `materials` row (GLASS, Kr rgb, Kt rgb) -- a glass surface does not emit -- and `mat_eta[i]` = its index of refraction (an empty
     `mat_eta` = 1.5 for every glass row; the entries of other rows are not read).  An environment map: a `lights` row
     (LIGHT_ENVMAP, 0, 0, 0, c rgb) -- c the factor on the texels -- and `envmap` = its (H, W, 3) texels, row 0 = the light's +z, with
-    `envmap_world_to_light` = the 3 x 3 rotation; the record travels in a slot appended to the texture table (fill_desc)."""
+    `envmap_world_to_light` = the 3 x 3 rotation; the record travels in a slot appended to the texture table (fill_desc).  Shading normals
+    (DESIGN.md 3.18): `tri_n` rows: the normals of a triangle's three corners (n0 xyz, n1 xyz, n2 xyz), world space, any length, zeros = the
+    triangle has none; empty = the scene has none.  Its record travels in a slot of its own behind the checkerboards and the map."""
     P: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
     idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.uint32))
     mat_id: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint16))
@@ -60,6 +62,7 @@ class SceneData:
     mat_eta: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.float32))
     envmap: np.ndarray = field(default_factory=lambda: np.zeros((0, 0, 3), np.float32))
     envmap_world_to_light: np.ndarray = field(default_factory=lambda: np.eye(3, dtype=np.float32))
+    tri_n: np.ndarray = field(default_factory=lambda: np.zeros((0, 9), np.float32))
 
     def normalized(self):
         self.P = np.ascontiguousarray(self.P, np.float32).reshape(-1, 3)
@@ -82,7 +85,9 @@ class SceneData:
         self.envmap = np.ascontiguousarray(self.envmap, np.float32)
         assert self.envmap.ndim == 3 and self.envmap.shape[2] == 3
         self.envmap_world_to_light = np.ascontiguousarray(self.envmap_world_to_light, np.float32).reshape(3, 3)
+        self.tri_n = np.ascontiguousarray(self.tri_n, np.float32).reshape(-1, 9)
         assert self.idx.shape[0] == self.mat_id.shape[0] and self.tri_uv.shape[0] in (0, self.idx.shape[0])
+        assert self.tri_n.shape[0] in (0, self.idx.shape[0])
         return self
 
     def crop_size(self):
@@ -104,9 +109,10 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
             mats[i].kd_tex = int(eta.view(np.uint32)[0])
     texs = None
     has_env = sd.envmap.size > 0  # the map's record takes a slot of its own behind the checkerboards (include/pbrt_hip.h pbrt_hip_envmap)
-    if len(sd.textures) or has_env:
+    has_nrm = sd.tri_n.shape[0] > 0  # the normals' record: the last slot (include/pbrt_hip.h pbrt_hip_normals)
+    if len(sd.textures) or has_env or has_nrm:
         tex_t = tex_t or dict(desc._fields_)["textures"]._type_  # (the Texture class of the caller's own struct mirror)
-        texs = (tex_t * (len(sd.textures) + int(has_env)))()
+        texs = (tex_t * (len(sd.textures) + int(has_env) + int(has_nrm)))()
         for i, t in enumerate(sd.textures):
             texs[i].type = int(t[0])
             texs[i].tex1[:] = [float(x) for x in t[1:4]]
@@ -117,8 +123,12 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
             e.world_to_light[:] = [float(x) for x in sd.envmap_world_to_light.reshape(-1)]
             assert C.sizeof(e) == C.sizeof(tex_t)
             C.memmove(C.byref(texs, len(sd.textures) * C.sizeof(tex_t)), C.byref(e), C.sizeof(e))
+        if has_nrm:
+            nr = Normals(type=2, n_tris=sd.tri_n.shape[0], tri_n=_fp(sd.tri_n))
+            assert C.sizeof(nr) == C.sizeof(tex_t)
+            C.memmove(C.byref(texs, (len(sd.textures) + int(has_env)) * C.sizeof(tex_t)), C.byref(nr), C.sizeof(nr))
         desc.textures = texs
-    desc.n_textures = len(sd.textures) + int(has_env)
+    desc.n_textures = len(sd.textures) + int(has_env) + int(has_nrm)
     if sd.tri_uv.shape[0]:
         desc.tri_uv = _fp(sd.tri_uv)
     lights = (light_t * max(len(sd.lights), 1))()
@@ -331,6 +341,15 @@ def blocks_eval(op, x, device=0):
     x = np.ascontiguousarray(x, np.float32).reshape(-1, w_in)
     out = np.zeros((len(x), w_out), np.float32)
     check(lib().pbrt_hip_blocks_eval_device(int(device), code, len(x), _fp(x), _fp(out)), "pbrt_hip_blocks_eval_device")
+    return out
+
+
+def shading_normal_eval(x, device=0):
+    """pbrt_hip_shading_normal_eval_device: csrc/shading_normal.inc over arrays on the device.  x: (n, 17) float32 rows (n0, n1, n2, ng, b1,
+    b2, wo) -> (n, 4) float32 rows (nsf, fell_back), DESIGN.md 3.18"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 17)
+    out = np.zeros((len(x), 4), np.float32)
+    check(lib().pbrt_hip_shading_normal_eval_device(int(device), len(x), _fp(x), _fp(out)), "pbrt_hip_shading_normal_eval_device")
     return out
 
 

@@ -55,6 +55,10 @@ struct SceneArrays {
   // an environment-map infinite light: texels {r, g, b, p_uv}, the marginal and conditional CDFs (envmap.hpp EnvTables)
   DevBuf<float4> d_env_texels;
   DevBuf<float> d_env_marginal, d_env_conditional;
+  // shading normals: the corner normals as uploaded (9 floats per triangle, triangle order) and in leaf-slot order
+  // (3 x float4 {n, 0} per slot); both empty for a scene without them
+  DevBuf<float> d_tri_n_in;
+  DevBuf<float4> d_tri_n;
   // the canonical walk's triangle records and leaf order of a device-built scene (ensure_canonical)
   DevBuf<float4> d_tris_exact;
   DevBuf<uint32_t> d_order_exact;
@@ -68,6 +72,8 @@ struct SceneArrays {
     f(&SceneArrays::d_tri_uv_in, false);  // (read by pack_uv during scene creation and by nothing after it)
     f(&SceneArrays::d_tri_uv, true); f(&SceneArrays::d_textures, true); f(&SceneArrays::d_glass, true);
     f(&SceneArrays::d_env_texels, true); f(&SceneArrays::d_env_marginal, true); f(&SceneArrays::d_env_conditional, true);
+    f(&SceneArrays::d_tri_n_in, false);  // (read by pack_nrm during scene creation and by nothing after it: released there)
+    f(&SceneArrays::d_tri_n, true);
     f(&SceneArrays::d_tris_exact, false); f(&SceneArrays::d_order_exact, false);  // (canonical_ready is not copied: a clone makes its own on first use)
   }
   // bytes on the device: pbrt_hip_scene_info's device_bytes
@@ -77,7 +83,7 @@ struct SceneArrays {
     return total;
   }
 };
-static_assert(sizeof(SceneArrays) == 19 * sizeof(DevBuf<float>), "an array of SceneArrays is missing from SceneArrays::for_each");
+static_assert(sizeof(SceneArrays) == 21 * sizeof(DevBuf<float>), "an array of SceneArrays is missing from SceneArrays::for_each");
 
 // What a scene is beside its arrays, its host tree and its description: plain values, which a clone takes in one assignment
 struct SceneTraits {
@@ -89,6 +95,7 @@ struct SceneTraits {
   bool env = false;       // an environment-map light: render_kernel_env renders the scene; the map's size, world_to_light and the light's factor
   uint32_t env_w = 0, env_h = 0;
   float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
+  bool normals = false;  // the texture table held a pbrt_hip_normals record: render_kernel_n renders the scene
   BuildStats build;
 };
 }  // namespace pbrt_hip

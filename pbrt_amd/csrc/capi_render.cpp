@@ -109,6 +109,8 @@ constexpr uint32_t kMinWalkers = 36, kMinWalkersShallow = 20, kShallowStackNeed 
 constexpr uint32_t kRenderWavesPerCuSpheres = 12;
 // a scene with an environment map: render_kernel_env's register budget is 4 waves per SIMD (kernels_env.hip)
 constexpr uint32_t kRenderWavesPerCuEnv = 16;
+// a scene with shading normals: render_kernel_n's register budget is 4 waves per SIMD as well (kernels_n.hip)
+constexpr uint32_t kRenderWavesPerCuN = 16;
 // the production walk's stack plan under the A-B knobs PBRT_HIP_FORCE_OVERFLOW_VARIANT (the overflow variant for every tree) and
 // PBRT_HIP_PREFER_LDS_STACK (the whole stack in LDS whenever it fits kQuadLdsStack rows, whatever the occupancy), read once
 RenderStackPlan stack_plan(uint32_t quad_stack_need) {
@@ -140,8 +142,14 @@ int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
   const bool wide = filter_is_wide(fx, fy);
   if (wide && counting)
     return fail(PBRT_HIP_ERR_INVALID, "render: the counter flags need the default box filter (radius 0.5)");
+  // shading normals: render_kernel_n exists without counters and for the default box filter (kernels_n.hip); asked before
+  // the map, as launch_render asks
+  if (s->normals && counting)
+    return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for a scene with shading normals");
+  if (s->normals && wide)
+    return fail(PBRT_HIP_ERR_LIMIT, "render: shading normals with a box filter radius other than 0.5 is a combination the library does not build");
   // an environment map: render_kernel_env exists without counters and for the default box filter (kernels_env.hip).
-  // Asked first, so that a scene with a map is told of the map whatever else it holds (glass, textures)
+  // Asked before what follows, so that a scene with a map is told of the map whatever else it holds (glass, textures)
   if (s->env && counting)
     return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for a scene with an environment map");
   // (textures, the MIS integrator, the table samplers and a wide box filter combine freely -- render_kernel_x --; only the counting
@@ -190,10 +198,11 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
   L.textured = s->textured;
   L.glass = s->glass;
   L.env = s->env;
+  L.normals = s->normals;
   const bool shallow = s->dev.quad_stack_need <= kShallowStackNeed;
   L.plan = stack_plan(s->dev.quad_stack_need);
   L.lds_bytes = L.plan.rows * 256u;
-  const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured && !L.glass && !L.env;
+  const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured && !L.glass && !L.env && !L.normals;
   L.steps = default_path && !L.plan.overflow && shallow ? 2u : PBRT_STEPS_PER_CHECK;
   if (L.counters == kCountExact) {
     const int ce = ensure_canonical(s);
@@ -206,6 +215,7 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
   // (the instantiations for another filter radius and for the table samplers fit the 96 VGPRs of 5 waves per SIMD like the default one)
   L.waves_per_cu = (L.spheres || L.glass) ? std::min(kRenderWavesPerCuSpheres, L.plan.waves_per_cu) : L.plan.waves_per_cu;  // (glass: the spheres' budget, kernels_x.hip)
   if (L.env) L.waves_per_cu = std::min(kRenderWavesPerCuEnv, L.plan.waves_per_cu);  // (whatever else the scene holds: render_kernel_env's own budget)
+  if (L.normals) L.waves_per_cu = std::min(kRenderWavesPerCuN, L.plan.waves_per_cu);  // (likewise: render_kernel_n's own budget)
   L.chunk_shift = sample_chunk_shift(r->spp_x * r->spp_y);
   const uint32_t n_chunks = 1u << L.chunk_shift;  // K: DESIGN.md 3.1
   L.passes = fg.wide ? 1u : partials_passes(sh.n_local, n_chunks);
@@ -263,6 +273,7 @@ void scene_render_params(const pbrt_hip_scene *s, RenderParams *R) {
   R->env_w = s->env_w; R->env_h = s->env_h;
   for (int k = 0; k < 9; k++) R->env_m[k] = s->env_m[k];
   for (int k = 0; k < 3; k++) R->env_c[k] = s->env_c[k];
+  R->tri_n = s->d_tri_n.p;
 }
 }  // namespace
 
@@ -303,6 +314,23 @@ int pbrt_hip_envmap_eval_device(pbrt_hip_scene *s, int64_t n, const float *u12, 
     if (le) HIP_TRY(hipMemcpyAsync(le, d_le.p, 12 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
     if (pdf) HIP_TRY(hipMemcpyAsync(pdf, d_pdf.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+  });
+}
+
+int pbrt_hip_shading_normal_eval_device(int device, int64_t n, const float *in, float *out) {
+  if (n < 0 || !in || !out) return fail(PBRT_HIP_ERR_INVALID, "shading_normal_eval_device: null argument or negative count");
+  if (n == 0) return PBRT_HIP_OK;
+  return guarded([&]() -> int {
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<float> d_in, d_out;
+    HIP_TRY(d_in.alloc(17 * (size_t)n));
+    HIP_TRY(d_out.alloc(4 * (size_t)n));
+    const hipStream_t stream = nullptr;  // the device's default stream
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, 4 * 17 * (size_t)n, hipMemcpyHostToDevice, stream));
+    HIP_TRY(launch_shading_normal_eval(n, d_in.p, d_out.p, stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, 4 * 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return PBRT_HIP_OK;
   });
 }

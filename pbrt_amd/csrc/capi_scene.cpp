@@ -95,6 +95,20 @@ bool kd_textured(const pbrt_hip_material &m) { return m.kd_tex != 0u && m.type =
 uint32_t light_env_slot(const pbrt_hip_light &l) { uint32_t u; std::memcpy(&u, &l.pad, 4); return u; }
 // a glass material's index of refraction: the float whose bits ride in kd_tex
 float glass_eta(const pbrt_hip_material &m) { float e; std::memcpy(&e, &m.kd_tex, 4); return e; }
+// the shading normals' record: a slot of the texture table whose first word is 2, read as the environment map's is
+bool is_normals_slot(const pbrt_hip_texture *textures, uint32_t index) { return textures[index].type == PBRT_HIP_TEXTURE_NORMALS; }
+pbrt_hip_normals normals_slot(const pbrt_hip_texture *textures, uint32_t index) {
+  static_assert(sizeof(pbrt_hip_normals) == sizeof(pbrt_hip_texture), "a pbrt_hip_normals is one slot of the texture table");
+  pbrt_hip_normals n;
+  std::memcpy(&n, textures + index, sizeof(n));
+  return n;
+}
+// the table's normals record into *out; false: the table holds none (check_scene_desc has refused a second one)
+bool find_normals(const pbrt_hip_scene_desc &d, pbrt_hip_normals *out) {
+  for (uint32_t i = 0; i < d.n_textures && d.textures; i++)
+    if (is_normals_slot(d.textures, i)) { *out = normals_slot(d.textures, i); return true; }
+  return false;
+}
 // glass is an interface between index 1 and eta: eta = 1 (index-matched: nothing reflects, nothing bends) is legal; 16 is four times
 // the densest real dielectric and keeps eta^2 and 1 / eta^2 -- the radiance scale of a refraction -- far from fp32's ends
 constexpr float kGlassEtaMin = 1.0f, kGlassEtaMax = 16.0f;
@@ -158,8 +172,22 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
   for (uint32_t i = 0; i < d->n_mats; i++)  // (image textures for Kd do not exist: a type-1 slot is a light's map)
     if (kd_textured(d->mats[i]) && is_envmap_slot(d->textures, d->mats[i].kd_tex - 1u))
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names an environment map, which is not a texture for Kd");
+  for (uint32_t i = 0; i < d->n_mats; i++)
+    if (kd_textured(d->mats[i]) && is_normals_slot(d->textures, d->mats[i].kd_tex - 1u))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names the shading normals' record, which is not a texture for Kd");
+  uint32_t n_normals = 0;
   for (uint32_t i = 0; i < d->n_textures; i++) {
     const pbrt_hip_texture &tx = d->textures[i];
+    if (is_normals_slot(d->textures, i)) {  // the shading normals' record
+      const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": shading normals: ";
+      if (++n_normals > 1u) return fail(PBRT_HIP_ERR_LIMIT, what + "more than one normals record (type 2)");
+      const pbrt_hip_normals nr = normals_slot(d->textures, i);
+      if (nr.n_tris != d->n_tris) return fail(PBRT_HIP_ERR_INVALID, what + "n_tris is " + std::to_string(nr.n_tris) + ", the description has " + std::to_string(d->n_tris) + " triangles");
+      if (!nr.tri_n) return fail(PBRT_HIP_ERR_INVALID, what + "tri_n is NULL");
+      for (size_t k = 0; k < 9 * (size_t)nr.n_tris; k++)
+        if (!std::isfinite(nr.tri_n[k])) return fail(PBRT_HIP_ERR_INVALID, what + "component " + std::to_string(k % 9) + " of triangle " + std::to_string(k / 9) + " is not finite");
+      continue;
+    }
     if (is_envmap_slot(d->textures, i)) {  // an environment map's record
       const int rc = envmap_check(envmap_slot(d->textures, i), "scene_create: texture slot " + std::to_string(i + 1) + ": ");
       if (rc) return rc;
@@ -316,7 +344,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
     in->textures.resize(3 * (size_t)d.n_textures);
     for (uint32_t i = 0; i < d.n_textures; i++) {
       const pbrt_hip_texture &tx = d.textures[i];
-      if (is_envmap_slot(d.textures, i)) continue;  // (an environment map's slot: no material names it, its records stay zero)
+      if (is_envmap_slot(d.textures, i) || is_normals_slot(d.textures, i)) continue;  // (an environment map's / the normals' slot: no material names it, its records stay zero)
       in->textures[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
       in->textures[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
       in->textures[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
@@ -344,6 +372,11 @@ int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const SceneIn
     for (int k = 0; k < 3; k++) s->env_c[k] = in.env_c[k];
   }
   if (in.textured_tris) HIP_TRY(upload(&s->d_tri_uv_in, d.tri_uv, 6 * (size_t)d.n_tris, s->stream));
+  pbrt_hip_normals nr;
+  if (find_normals(d, &nr)) {  // (the caller's array: it outlives the call, and the stream is synchronised before the call returns)
+    HIP_TRY(upload(&s->d_tri_n_in, nr.tri_n, 9 * (size_t)d.n_tris, s->stream));
+    s->normals = in.n_prims > 0;  // (a scene without a primitive has no hit to shade and no leaf slot to hold a normal)
+  }
   DevScene &D = s->dev;
   D.n_tris = d.n_tris;  // (the triangles: a hit's primitive id >= this is sphere id - n_tris)
   D.n_spheres = d.n_spheres;
@@ -474,7 +507,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.7 (gfx950; struct sizes of 0.6)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.8 (gfx950; struct sizes of 0.6, as 0.7)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif
@@ -563,7 +596,12 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
       HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));
       HIP_TRY(launch_pack_uv(s->d_tri_uv_in.p, s->d_order.p, in.n_prims, d->n_tris, s->d_tri_uv.p, s->stream));
     }
+    if (s->normals) {  // corner normals into leaf-slot order likewise; a sphere's proxy slot gets zeros
+      HIP_TRY(s->d_tri_n.alloc(3 * (size_t)in.n_prims));
+      HIP_TRY(launch_pack_nrm(s->d_tri_n_in.p, s->d_order.p, in.n_prims, d->n_tris, s->d_tri_n.p, s->stream));
+    }
     HIP_TRY(hipStreamSynchronize(s->stream));
+    s->d_tri_n_in.release();  // (the gather was its one reader: a scene with normals costs 48 bytes per leaf slot)
     bind_scene_arrays(s.get());
     s->device_bytes = s->bytes();
     set_view(&s->dev, *d);

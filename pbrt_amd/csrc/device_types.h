@@ -196,6 +196,9 @@ struct RenderParams {
   uint32_t env_w, env_h;
   float env_m[9];
   float env_c[3];
+  // shading normals (render_kernel_n): the corner normals of every leaf slot, 3 x float4 {n, 0}, world space, any length
+  // (zeros = the triangle has none; a sphere's proxy slot: zeros), read at a shaded triangle hit alone.  At the end, for the reason given above.
+  const float4 *tri_n;
 };
 // 2^24 fixed-point units per unit of radiance, a component clamped to [0, 2^15]
 constexpr float kFixedOne = 16777216.0f, kFixedMax = 32768.0f;
@@ -229,6 +232,7 @@ struct RenderLaunch {
   bool mis, textured;  // render_kernel_x's MIS (3.14) and TEX (3.15)
   bool glass;          // render_kernel_x's GLS (3.16): the scene has a glass material
   bool env;            // render_kernel_env (3.17): the scene has an environment map -- never with `wide` or the counters (capi_render.cpp check_render_desc)
+  bool normals;        // render_kernel_n (3.18): the scene carries shading normals -- never with `wide` or the counters either; asked before `env`
   RenderStackPlan plan;  // the production walk's stack: LDS rows, the overflow variant, HBM entries per lane
   uint32_t steps;        // production walk: node steps per scheduling check (STEPS)
   uint32_t exact_rows;   // exact walk: STACK, its stack rows of refs (and as many of entry distances)
@@ -249,6 +253,12 @@ hipError_t launch_render_x(const DevScene &S, const RenderParams &R, const Rende
 // (pbrt_hip_envmap_eval_device: u12 != nullptr samples into d, else d is looked up; R's env_* fields are the map)
 hipError_t launch_render_env(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t stream);
 hipError_t launch_envmap_eval(const RenderParams &R, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf, hipStream_t stream);
+// kernels_n.hip: the launch of a scene with shading normals (3.18; launch_render asks this first and hands over), the gather of the corner
+// normals (9 floats per triangle, triangle order) into leaf-slot order (3 x float4 per slot; a sphere's proxy slot: zeros), and
+// shading_normal.inc over device arrays (pbrt_hip_shading_normal_eval_device: 17 floats in, 4 out per element)
+hipError_t launch_render_n(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t stream);
+hipError_t launch_pack_nrm(const float *tri_n, const uint32_t *order, uint32_t n_prims, uint32_t n_tris, float4 *out, hipStream_t stream);
+hipError_t launch_shading_normal_eval(int64_t n, const float *in, float *out, hipStream_t stream);
 // fixed-point accumulators -> film pixels {X, Y, Z, weight}
 hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, size_t n_px, hipStream_t stream);
 hipError_t launch_acc_add(unsigned long long *dst, const unsigned long long *src, size_t n, hipStream_t stream);  // dst[i] += src[i]

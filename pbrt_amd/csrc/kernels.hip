@@ -39,6 +39,7 @@ template <bool SPH, bool COUNT, bool EXACT, int STACK, int STEPS = PBRT_STEPS_PE
 __global__ void __launch_bounds__(64, (COUNT ? 1 : (SPH ? 3 : PBRT_RENDER_WAVES_PER_SIMD))) render_kernel(const DevScene S, const RenderParams R) {
   constexpr bool MIS = false, TEX = false, GLS = false;  // (the variants: kernels_x.hip render_kernel_x)
   constexpr bool ENV = false;                            // (an environment map: kernels_env.hip render_kernel_env)
+  constexpr bool NRM = false;                            // (shading normals: kernels_n.hip render_kernel_n)
   (void)MIS;
   (void)GLS;
   (void)ENV;
@@ -230,6 +231,7 @@ hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, siz
 // variant, or 0 for the whole stack in LDS; the exact walk's is its stack rows.
 hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
   if (R.n_items == 0) return hipSuccess;
+  if (L.normals) return launch_render_n(S, R, L, st);  // a scene with shading normals, whatever else it holds: kernels_n.hip
   if (L.env) return launch_render_env(S, R, L, st);  // a scene with an environment map: kernels_env.hip
   auto go = [&](void (*kernel)(DevScene, RenderParams)) {
     hipLaunchKernelGGL(kernel, dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);

@@ -25,6 +25,7 @@ namespace {
 template <bool SPH, int STACK, bool MIS, bool TEX, bool SND>
 __global__ void __launch_bounds__(64, PBRT_ENV_WAVES_PER_SIMD) render_kernel_env(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false, WIDE = false, GLS = true, ENV = true;
+  constexpr bool NRM = false;  // (shading normals: kernels_n.hip render_kernel_n)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
 #include "render_body.inc"
 }

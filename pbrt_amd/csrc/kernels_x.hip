@@ -16,6 +16,7 @@ template <bool SPH, int STACK, bool MIS, bool TEX, bool SND, bool WIDE, bool GLS
 __global__ void __launch_bounds__(64, ((SPH || GLS) ? 3 : PBRT_RENDER_WAVES_PER_SIMD)) render_kernel_x(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false;
   constexpr bool ENV = false;  // (an environment map: kernels_env.hip render_kernel_env)
+  constexpr bool NRM = false;  // (shading normals: kernels_n.hip render_kernel_n)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
   (void)ENV;
 #include "render_body.inc"

@@ -173,13 +173,16 @@ bool parse_ply(const unsigned char *data, size_t n, PlyMesh *out, std::string *e
       have_vertices = true;
       if (e.count >= 0xffffffffull / 3) return fail(err, "too many vertices");
       n_verts = e.count;
-      int ix = -1, iy = -1, iz = -1, iu = -1, iv = -1;
+      int ix = -1, iy = -1, iz = -1, iu = -1, iv = -1, inx = -1, iny = -1, inz = -1;
       for (size_t k = 0; k < e.props.size(); k++) {
         const std::string &nm = e.props[k].name;
         if (e.props[k].list) continue;
         if (nm == "x") ix = (int)k;
         else if (nm == "y") iy = (int)k;
         else if (nm == "z") iz = (int)k;
+        else if (nm == "nx") inx = (int)k;
+        else if (nm == "ny") iny = (int)k;
+        else if (nm == "nz") inz = (int)k;
         else if (nm == "u" || nm == "s" || nm == "texture_u" || nm == "texture_s") iu = (int)k;
         else if (nm == "v" || nm == "t" || nm == "texture_v" || nm == "texture_t") iv = (int)k;
       }
@@ -187,6 +190,8 @@ bool parse_ply(const unsigned char *data, size_t n, PlyMesh *out, std::string *e
       const bool has_uv = iu >= 0 && iv >= 0;
       out->P.resize(3 * (size_t)e.count);
       if (has_uv) out->uv.resize(2 * (size_t)e.count);
+      const bool has_n = inx >= 0 && iny >= 0 && inz >= 0;
+      if (has_n) out->N.resize(3 * (size_t)e.count);
       for (uint64_t r = 0; r < e.count; r++)
         for (size_t k = 0; k < e.props.size(); k++) {
           const Prop &p = e.props[k];
@@ -203,6 +208,9 @@ bool parse_ply(const unsigned char *data, size_t n, PlyMesh *out, std::string *e
           else if ((int)k == iz) out->P[3 * r + 2] = (float)v;
           else if (has_uv && (int)k == iu) out->uv[2 * r] = (float)v;
           else if (has_uv && (int)k == iv) out->uv[2 * r + 1] = (float)v;
+          else if (has_n && (int)k == inx) out->N[3 * r] = (float)v;
+          else if (has_n && (int)k == iny) out->N[3 * r + 1] = (float)v;
+          else if (has_n && (int)k == inz) out->N[3 * r + 2] = (float)v;
         }
     } else {
       const bool is_face = e.name == "face";

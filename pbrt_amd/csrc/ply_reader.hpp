@@ -3,7 +3,8 @@
 // returns NotImplemented, parser.rs:300); this is the data format on the input side of the render path, read into the same arrays a
 // "trianglemesh" fills.  What pbrt-v3's reader (plymesh.cpp) takes is taken here: element "vertex" with x y z and optionally (u, v) /
 // (s, t) / (texture_u, texture_v) / (texture_s, texture_t); element "face" with the list "vertex_indices" / "vertex_index", triangles and
-// quads (a quad becomes (0 1 2) and (3 0 2), as there); normals and every other property or element are skipped.
+// quads (a quad becomes (0 1 2) and (3 0 2), as there); the vertex normals nx ny nz (used when the shape asks for
+// them); every other property or element is skipped.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -14,6 +15,7 @@ namespace pbrt_hip {
 struct PlyMesh {
   std::vector<float> P;       // 3 per vertex
   std::vector<float> uv;      // 2 per vertex, or empty
+  std::vector<float> N;       // 3 per vertex (nx ny nz), or empty
   std::vector<uint32_t> idx;  // 3 per triangle
   uint32_t skipped_faces = 0;  // faces with other than 3 or 4 vertices
 };

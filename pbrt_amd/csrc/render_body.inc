@@ -1,6 +1,7 @@
 // render_body.inc -- the body of render_kernel (kernels.hip) and of render_kernel_x (kernels_x.hip), included once in each: the two are the same
-// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV in scope (kernels_env.hip
-// includes it a third time, for render_kernel_env, the one kernel with ENV = true).  (A shared __device__
+// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV, NRM in scope (kernels_env.hip
+// includes it a third time, for render_kernel_env, the one kernel with ENV = true, and kernels_n.hip a fourth, for render_kernel_n, the one
+// with NRM = true: interpolated shading normals, DESIGN.md 3.18).  (A shared __device__
 // function would be the tidy way to say this; the text is included instead because wrapping the body in a function -- forceinline or
 // not -- perturbs the register allocation of the production instantiation, whose machine code the committed counter profiles are
 // keyed by: pbrt_amd/isa_id.py; measured in round 5.)  In scope as well: `S` (DevScene) and `R` (RenderParams), the kernel's arguments.
@@ -162,6 +163,18 @@
           if (hit && P.bounces < R.max_depth) {
             const V3 nf = dot(ng, wo) < 0.f ? -ng : ng;
             const V3 po = p + nf * kSpawnEps;
+            // NRM (DESIGN.md 3.18): a triangle's corner normals interpolated like the hit point give the shading normal nsh, which takes nf's
+            // place where matte and mirror scatter; `smooth` = the triangle had a usable one (else nsh is nf and nothing below differs)
+            V3 nsh = nf;
+            bool smooth = false;
+            if (NRM && (!SPH || h.prim < S.n_tris)) {
+              const float4 q0 = R.tri_n[3u * h.slot], q1 = R.tri_n[3u * h.slot + 1u], q2 = R.tri_n[3u * h.slot + 2u];
+              const V3 sn_n0 = xyz(q0), sn_n1 = xyz(q1), sn_n2 = xyz(q2);
+              const float sn_b1 = h.b1, sn_b2 = h.b2;
+#include "shading_normal.inc"
+              nsh = nsf;
+              smooth = !sn_fell_back;
+            }
             V3 k = {m0.y, m0.z, m0.w};
             if (TEX && __float_as_uint(m1.w) != 0u) {
               // Kd from a texture (DESIGN.md 3.15; pbrt-v3 Checkerboard2DTexture over UVMapping2D, aamode none): the triangle's corner
@@ -216,13 +229,14 @@
                 li = min(li, nL - 1u);
                 V3 Ld;
                 if (ENV && __float_as_uint(S.lights[5 * li].x) == kDevLightEnv) {  // the environment map's light (3.17): the same (u1, u2)
-                  if (sample_env_light(R, nf, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS)) {
+                  // (NRM: a light sample counts only from the geometric front side as well)
+                  if (sample_env_light(R, nsh, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS) && (!(NRM && smooth) || dot(sh_d, nf) > 0.f)) {
                     need_shadow = true;
                     lpend = P.beta * Ld;
                     if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
                   }
                 } else
-                if (sample_light(S, li, po, nf, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS)) {
+                if (sample_light(S, li, po, nsh, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS) && (!(NRM && smooth) || dot(sh_d, nf) > 0.f)) {
                   need_shadow = true;
                   lpend = P.beta * Ld;
                   if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
@@ -234,18 +248,19 @@
               } else {
                 float u1, u2;
                 sample_2d<SND>(P, sobol, spp_mask, u1, u2, R.sobol_mat, halton);
-                const float z = cosine_about(nf, u1, u2, P.wi_next);
+                const float z = cosine_about(nsh, u1, u2, P.wi_next);
                 EXP_DEBUG_PIXEL("HIP s %u   cos u1 %a u2 %a z %a nf %a %a %a wi %a %a %a\n", P.s, u1, u2, z, nf.x, nf.y, nf.z, P.wi_next.x, P.wi_next.y, P.wi_next.z);
-                if (z == 0.f) alive = false;
+                if (z == 0.f || (NRM && smooth && !(dot(P.wi_next, nf) > 0.f))) alive = false;  // (NRM: the lobe reflects to the geometric front side only)
                 else { P.beta = P.beta * k; P.specular = false; }
                 // MIS: the pending light sample and, beside it, the density the bounce ray was drawn with (read where it lands)
                 if (MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, z * kInvPi));
               }
             } else {  // mirror
-              const float c = dot(wo, nf);
-              P.wi_next = -wo + nf * (2.0f * c);
+              const float c = dot(wo, nsh);
+              P.wi_next = -wo + nsh * (2.0f * c);
               P.beta = P.beta * k;
               P.specular = true;
+              if (NRM && smooth && !(dot(P.wi_next, nf) > 0.f)) alive = false;
             }
             if (alive && P.beta.x == 0.f && P.beta.y == 0.f && P.beta.z == 0.f) alive = false;
             if (alive && P.bounces > 3u) {

@@ -181,6 +181,12 @@ void xf_vector(const float m[16], const float v[3], float out[3]) {
   out[1] = m[4] * v[0] + m[5] * v[1] + m[6] * v[2];
   out[2] = m[8] * v[0] + m[9] * v[1] + m[10] * v[2];
 }
+// a normal through the inverse transpose of m's 3 x 3, given m's inverse (Transform::operator()(Normal3f) of pbrt-v3)
+void xf_normal(const float inv[16], const float n[3], float out[3]) {
+  out[0] = inv[0] * n[0] + inv[4] * n[1] + inv[8] * n[2];
+  out[1] = inv[1] * n[0] + inv[5] * n[1] + inv[9] * n[2];
+  out[2] = inv[2] * n[0] + inv[6] * n[1] + inv[10] * n[2];
+}
 bool swaps_handedness(const float m[16]) {
   const float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) +
                     m[2] * (m[4] * m[9] - m[5] * m[8]);
@@ -264,7 +270,7 @@ struct Api {
   // reference, parser.rs:283-289).  An object's shapes are kept in world space as of their own CTM (their ObjectToWorld); an instance
   // appends a copy moved by the CTM at the ObjectInstance (InstanceToWorld): the BVH is over flattened geometry, instances cost memory.
   struct ObjectDef {
-    std::vector<float> P, tri_uv;
+    std::vector<float> P, tri_uv, tri_n;
     std::vector<uint32_t> idx;
     std::vector<uint16_t> mat_id;
     std::vector<pbrt_hip_sphere> spheres;
@@ -274,6 +280,8 @@ struct Api {
   std::string object_name;
   ObjectDef stash;  // the scene's own arrays while an object is being defined (shape() always appends to out->...)
   bool warned_object_light = false;
+  bool any_normals = false;           // some mesh of the file carried normals: the scene gets a pbrt_hip_normals record
+  bool warned_glass_normals = false;  // (said once per file)
   // instancing multiplies geometry (instances x the object's triangles): a bound on what a small file can ask for (the tests lower it)
   const size_t kMaxSceneTriangles = [] {
     const char *on = std::getenv("PBRT_HIP_DEBUG_KNOBS"), *v = std::getenv("PBRT_HIP_MAX_SCENE_TRIANGLES");
@@ -439,8 +447,11 @@ struct Api {
   }
 
   // vertices (object space) + triangles of one mesh shape, through the CTM, into the scene's arrays
-  void add_mesh(const float *P, uint32_t nv, const uint32_t *tri, size_t n_tri, const float *uv, uint16_t mid) {
+  // (N: per-vertex normals, object space, or nullptr: they go through the inverse transpose of the CTM and are flattened to the corners of
+  // every triangle -- DESIGN.md 3.18; a mesh without them gets zero rows, "none")
+  void add_mesh(const float *P, uint32_t nv, const uint32_t *tri, size_t n_tri, const float *uv, uint16_t mid, const float *N = nullptr) {
     const float *M = ctm[0].m;
+    if (N) any_normals = true;
     const uint32_t base = (uint32_t)(out->P.size() / 3);
     for (uint32_t v = 0; v < nv; v++) {
       float q[3];
@@ -459,7 +470,22 @@ struct Api {
       const float dflt[6] = {0.f, 0.f, 1.f, 0.f, 1.f, 1.f};
       for (int v = 0; v < 3; v++)
         for (int k = 0; k < 2; k++) out->tri_uv.push_back(uv ? uv[2 * (size_t)corner[v] + k] : dflt[2 * (flip && v ? 3 - v : v) + k]);
+      for (int v = 0; v < 3; v++) {  // (a swapped winding takes its corners' normals with it)
+        float q[3] = {0.f, 0.f, 0.f};
+        if (N) xf_normal(ctm[0].inv, N + 3 * (size_t)corner[v], q);
+        out->tri_n.insert(out->tri_n.end(), q, q + 3);
+      }
     }
+  }
+
+  // a mesh's normals as they will be used: a glass triangle ignores its normals (DESIGN.md 3.16 keeps ng; 3.18) -- said once per file
+  const float *usable_normals(const float *N, const MaterialDef &m) {
+    if (!N || m.type != PBRT_HIP_MATERIAL_GLASS) return N;
+    if (!warned_glass_normals) {
+      warned_glass_normals = true;
+      warn("a glass mesh has normals \"N\": glass refracts about the geometric normal, its shading normals are ignored");
+    }
+    return nullptr;
   }
 
   void shape(const std::string &name, const ParamSet &ps) {
@@ -516,8 +542,13 @@ struct Api {
       std::vector<uint32_t> tri(pi->nums.size());
       for (size_t i = 0; i < tri.size(); i++)  // (a negative or huge index becomes one that is out of range)
         tri[i] = (pi->nums[i] >= 0 && pi->nums[i] < 4294967295.0) ? (uint32_t)pi->nums[i] : 0xffffffffu;
-      add_mesh(P.data(), nv, tri.data(), tri.size() / 3, puv ? uv.data() : nullptr, mid);
-      ps.find("N", "normal"); ps.find("S", "vector3");
+      // per-vertex shading normals: "normal N" 
+      const ParamItem *pn = ps.find("N", "normal");
+      if (pn && pn->nums.size() != 3 * (size_t)nv) { warn("trianglemesh: \"N\" does not hold one normal per vertex: ignored (the mesh renders flat)"); pn = nullptr; }
+      std::vector<float> N;
+      if (pn) N.assign(pn->nums.begin(), pn->nums.end());
+      add_mesh(P.data(), nv, tri.data(), tri.size() / 3, puv ? uv.data() : nullptr, mid, usable_normals(pn ? N.data() : nullptr, shape_mat));
+      ps.find("S", "vector3");
     } else if (name == "plymesh") {  // pbrt-v3 CreatePLYMesh (plymesh.cpp): the mesh of a PLY file, relative names against the scene file's directory
       const std::string fn = ps.one_string("filename", "");
       if (fn.empty()) { warn("plymesh without a \"string filename\": skipped"); return; }
@@ -528,7 +559,12 @@ struct Api {
       if (mesh.skipped_faces) warn("plymesh \"" + fn + "\": " + std::to_string(mesh.skipped_faces) + " faces with other than 3 or 4 vertices ignored");
       if (mesh.idx.empty()) { warn("plymesh \"" + fn + "\": no faces: skipped"); return; }
       if (out->idx.size() / 3 + mesh.idx.size() / 3 > kMaxSceneTriangles) { warn("plymesh \"" + fn + "\": scene would pass 2^24 triangles: skipped"); return; }
-      add_mesh(mesh.P.data(), (uint32_t)(mesh.P.size() / 3), mesh.idx.data(), mesh.idx.size() / 3, mesh.uv.empty() ? nullptr : mesh.uv.data(), mid);
+      // The file's nx ny nz become shading normals on request: "bool shadingnormals" "true".  Off by default: the oracle
+      // -- what every scene file's film is held to bit for bit -- knows nothing of normals, and a PLY file that happens to carry them
+      // renders as it always did until it does.
+      const bool want_n = ps.one_bool("shadingnormals", false) && !mesh.N.empty();
+      add_mesh(mesh.P.data(), (uint32_t)(mesh.P.size() / 3), mesh.idx.data(), mesh.idx.size() / 3, mesh.uv.empty() ? nullptr : mesh.uv.data(), mid,
+               usable_normals(want_n ? mesh.N.data() : nullptr, shape_mat));
       if (ps.find("alpha", "texture", "float") || ps.find("shadowalpha", "texture", "float")) warn("plymesh: alpha / shadowalpha are not supported (opaque)");
     } else {
       warn("Shape \"" + name + "\" is not supported by this path: skipped");
@@ -538,7 +574,7 @@ struct Api {
   }
 
   void swap_geometry(ObjectDef &d) {
-    out->P.swap(d.P); out->tri_uv.swap(d.tri_uv); out->idx.swap(d.idx); out->mat_id.swap(d.mat_id); out->spheres.swap(d.spheres);
+    out->P.swap(d.P); out->tri_uv.swap(d.tri_uv); out->tri_n.swap(d.tri_n); out->idx.swap(d.idx); out->mat_id.swap(d.mat_id); out->spheres.swap(d.spheres);
   }
   void object_begin(const std::string &name) {  // pbrtObjectBegin: an AttributeBegin, then shapes go to the named object
     if (in_object) { warn("ObjectBegin called inside of instance definition"); return; }
@@ -580,6 +616,14 @@ struct Api {
       const float *uv = d.tri_uv.data() + 2 * t;
       const float c[6] = {uv[0], uv[1], uv[2 * o1], uv[2 * o1 + 1], uv[2 * o2], uv[2 * o2 + 1]};
       out->tri_uv.insert(out->tri_uv.end(), c, c + 6);
+      // the corner normals: through the instance's transform, permuted with the corners
+      const float *nn = d.tri_n.data() + 3 * t;
+      const int corner[3] = {0, o1, o2};
+      for (int v = 0; v < 3; v++) {
+        float q[3];
+        xf_normal(ctm[0].inv, nn + 3 * corner[v], q);
+        out->tri_n.insert(out->tri_n.end(), q, q + 3);
+      }
     }
     out->mat_id.insert(out->mat_id.end(), d.mat_id.begin(), d.mat_id.end());
     const float ex[3] = {1, 0, 0};
@@ -1122,6 +1166,20 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
     bool textured = false;
     for (uint16_t m : out->mat_id) textured = textured || (out->mats[m].type == PBRT_HIP_MATERIAL_MATTE && out->mats[m].kd_tex != 0u);
     if (!textured) { out->tri_uv.clear(); out->tri_uv.shrink_to_fit(); }
+  }
+  // shading normals travel only when some mesh has them: then their record is the LAST slot of the texture table; a file
+  // without them keeps the description it always had
+  if (!api.any_normals) {
+    out->tri_n.clear(); out->tri_n.shrink_to_fit();
+  } else {
+    pbrt_hip_normals nr{};
+    nr.type = PBRT_HIP_TEXTURE_NORMALS;
+    nr.n_tris = (uint32_t)out->mat_id.size();
+    nr.tri_n = out->tri_n.data();  // (the vector is not touched again)
+    pbrt_hip_texture slot{};
+    static_assert(sizeof slot == sizeof nr, "the normals' record takes one slot of the texture table");
+    std::memcpy(&slot, &nr, sizeof slot);
+    out->textures.push_back(slot);
   }
   if (!api.camera_set) mat_identity(out->cam_to_world);
   // (round 6: spheres are primitives of the BVH like triangles -- the warning that hundreds of them cost every ray a loop is gone; what

@@ -69,6 +69,9 @@ struct LoadedScene {
   std::vector<pbrt_hip_sphere> spheres;
   std::vector<pbrt_hip_texture> textures;  // checkerboards named by a material's "texture Kd" 
   std::vector<float> tri_uv;               // 6 per triangle (corner u, v); empty when no material is textured
+  // Shading normals: 9 per triangle -- the world-space normals of its three corners, zeros for a triangle of a mesh without
+  // them --, EMPTY when no mesh of the file has normals; else the last slot of `textures` is the pbrt_hip_normals record that points into it.
+  std::vector<float> tri_n;
   // LightSource "infinite" "string mapname" (DESIGN.md 3.17): the image as read (3 x width x height, row 0 = theta 0).  The slot of
   // `textures` that is its pbrt_hip_envmap record points into it, and the light (type 3) carries that slot's number; at most one.
   std::vector<float> env_rgb;

@@ -6,7 +6,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import EnvMap, RenderDesc, SceneDesc, check, lib
+from ._lib import EnvMap, Normals, RenderDesc, SceneDesc, check, lib
 from .api import GLASS, SceneData
 
 
@@ -44,15 +44,21 @@ def _collect(h):
         # `envmap`, the other slots stay the checkerboards -- numbered as they are while the map's slot is the last one, as the parser leaves
         # it unless a texture is declared after the light (such a scene's texture numbers are remapped here)
         env_slots = [i for i in range(d.n_textures) if d.textures[i].type == 1]
-        tex_slots = [i for i in range(d.n_textures) if d.textures[i].type != 1]
+        # (the shading normals' record, DESIGN.md 3.18, is a slot whose first word is 2: it becomes `tri_n`)
+        nrm_slots = [i for i in range(d.n_textures) if d.textures[i].type == 2]
+        tex_slots = [i for i in range(d.n_textures) if d.textures[i].type not in (1, 2)]
         renum = {0: 0, **{i + 1: k + 1 for k, i in enumerate(tex_slots)}}
         envmap, env_m = np.zeros((0, 0, 3), np.float32), np.eye(3, dtype=np.float32)
         if env_slots:
             e = EnvMap.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[env_slots[0]]), C.sizeof(EnvMap))))
             envmap = arr(e.rgb, 3 * e.width * e.height, np.float32).reshape(e.height, e.width, 3)
             env_m = np.array(list(e.world_to_light), np.float32).reshape(3, 3)
+        tri_n = np.zeros((0, 9), np.float32)
+        if nrm_slots:
+            nr = Normals.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[nrm_slots[0]]), C.sizeof(Normals))))
+            tri_n = arr(nr.tri_n, 9 * nr.n_tris, np.float32).reshape(-1, 9)
         sd = SceneData(
-            envmap=envmap, envmap_world_to_light=env_m,
+            tri_n=tri_n, envmap=envmap, envmap_world_to_light=env_m,
             P=arr(d.P, 3 * d.n_verts, np.float32).reshape(-1, 3), idx=arr(d.idx, 3 * d.n_tris, np.uint32).reshape(-1, 3),
             mat_id=arr(d.mat_id, d.n_tris, np.uint16),
             materials=np.array([[d.mats[i].type, *d.mats[i].k, *d.mats[i].le] for i in range(d.n_mats)], np.float32).reshape(-1, 7),

@@ -7,6 +7,8 @@
   cornell_scene       C4: Cornell-style box
   glass_sphere_scene  a glass sphere and a glass cube in a Cornell-style box (= scenes/glass_sphere.pbrt)
   envmap_scene        a matte ground, a glass and a mirror sphere under an environment map (= scenes/envmap_spheres.pbrt)
+  icosphere_scene     C1 with its sphere tessellated, with or without shading normals
+  smooth_mesh_scene   two octahedra with per-vertex normals over a flat ground (= scenes/smooth_mesh.pbrt)
 """
 import numpy as np
 
@@ -64,6 +66,73 @@ def sphere_scene(xres=1024, yres=1024, crop=(0.0, 1.0, 0.0, 1.0)):
         lights=np.array([[LIGHT_POINT, 2, 2, 3, 10, 10, 10]], np.float32),
         spheres=np.array([[0, 0, 0, 1, 0]], np.float32),
         cam_to_world=_camera((3, 4, 1.5), (0.5, 0.5, 0), (0, 0, 1)), fov=45.0, xres=xres, yres=yres, crop=crop,
+    ).normalized()
+
+
+def icosphere(level):
+    """(P[n, 3] float64 on the unit sphere, idx[m, 3]) of an icosahedron subdivided `level` times, every face wound so that its normal
+    points outwards: 20 x 4^level triangles"""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    P = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    P = [np.array(p, np.float64) / np.linalg.norm(p) for p in P]
+    F = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(level)):
+        mid, G = {}, []
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                m = P[a] + P[b]
+                P.append(m / np.linalg.norm(m))
+                mid[key] = len(P) - 1
+            return mid[key]
+
+        for a, b, c in F:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            G += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        F = G
+    return np.array(P, np.float64), np.array(F, np.uint32)
+
+
+def icosphere_scene(level=4, smooth=True, xres=1024, yres=1024, crop=(0.0, 1.0, 0.0, 1.0), centre=(0.0, 0.0, 0.0), radius=1.0):
+    """C1's scene (sphere_scene's camera, light and material) with the sphere tessellated into 20 x 4^level triangles whose vertices lie on
+    it.  smooth: every corner carries the normal p - c of its vertex -- deliberately not unit length (the radius is its length) --, else the
+    scene has no normals and renders faceted."""
+    U, F = icosphere(level)
+    c = np.asarray(centre, np.float64)
+    P = (c + radius * U).astype(np.float32)
+    kw = {}
+    if smooth:
+        kw["tri_n"] = (P.astype(np.float64) - c)[F].reshape(-1, 9).astype(np.float32)
+    return SceneData(
+        P=P, idx=F, mat_id=np.zeros(len(F), np.uint16),
+        materials=np.array([_mat(MATTE, (0.5, 0.5, 0.5))], np.float32),
+        lights=np.array([[LIGHT_POINT, 2, 2, 3, 10, 10, 10]], np.float32),
+        cam_to_world=_camera((3, 4, 1.5), (0.5, 0.5, 0), (0, 0, 1)), fov=45.0, xres=xres, yres=yres, crop=crop, **kw,
+    ).normalized()
+
+
+def smooth_mesh_scene(xres=128, yres=128, crop=(0.0, 1.0, 0.0, 1.0)):
+    """The shading normals' scene, array for array what scenes/smooth_mesh.pbrt loads to: a flat matte ground z = 0 without
+    normals (zero rows of `tri_n`) and two octahedra of radius 0.9 at (-1.1, 0, 1) and (1.1, 0, 1), a matte and a mirror one, whose
+    corners carry their vertex's position about the centre as the normal; a point light and a constant sky."""
+    GROUND, BALL, MIRROR_M = range(3)
+    mats = [_mat(MATTE, (0.5, 0.48, 0.45)), _mat(MATTE, (0.7, 0.3, 0.25)), _mat(MIRROR, (0.9, 0.9, 0.9))]
+    verts, tris = _quad((-6, -6, 0), (6, -6, 0), (6, 6, 0), (-6, 6, 0))
+    P, I, M, N = [np.array(verts, np.float32)], [np.array(tris, np.uint32)], [GROUND, GROUND], [np.zeros((2, 9), np.float32)]
+    octa = np.array([(.9, 0, 0), (-.9, 0, 0), (0, .9, 0), (0, -.9, 0), (0, 0, .9), (0, 0, -.9)], np.float32)
+    faces = np.array([(0, 2, 4), (2, 1, 4), (1, 3, 4), (3, 0, 4), (2, 0, 5), (1, 2, 5), (3, 1, 5), (0, 3, 5)], np.uint32)
+    for centre, m in (((-1.1, 0, 1), BALL), ((1.1, 0, 1), MIRROR_M)):
+        base = sum(len(p) for p in P)
+        P.append(octa + np.array(centre, np.float32))  # (fp32, as the parser's Translate moves the vertices)
+        I.append(faces + np.uint32(base))
+        M += [m] * len(faces)
+        N.append(octa[faces].reshape(-1, 9))
+    return SceneData(
+        P=np.concatenate(P), idx=np.concatenate(I), mat_id=np.array(M, np.uint16), materials=np.array(mats, np.float32),
+        lights=np.array([[LIGHT_POINT, 2, -3, 5, 40, 38, 34], [LIGHT_INFINITE, 0, 0, 0, .3, .35, .4]], np.float32),
+        tri_n=np.concatenate(N), cam_to_world=_camera((0, -5, 2.2), (0, 0, 0.8), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
     ).normalized()
 
 

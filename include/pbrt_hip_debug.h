@@ -32,6 +32,12 @@ int pbrt_hip_scene_walk_info(const pbrt_hip_scene *scene, uint32_t *quad_nodes, 
  * 64 x 4 bytes per wave, one-wave workgroups a CU holds at once with them (the grid is this x the CU count), and the
  * entries per lane kept in an HBM overflow area (non-zero = the overflow variant of the kernel). */
 int pbrt_hip_render_stack_plan(uint32_t stack_need, uint32_t *lds_rows, uint32_t *waves_per_cu, uint32_t *overflow_entries);
+/* The same for the default path's launch (no counters, box filter radius 0.5, samplers 0 / 1, no MIS, textures, glass, map or shading
+ * normals), whose overflow variant keeps three 1 KB path-state records per wave in LDS behind a shorter stack: the stack's rows, the
+ * bytes of the records behind them (0 = the records are in HBM: every tree that keeps its whole stack in LDS), the workgroups per CU
+ * and the overflow entries per lane.  Every other launch is pbrt_hip_render_stack_plan's. */
+int pbrt_hip_render_stack_layout(uint32_t stack_need, uint32_t *stack_rows, uint32_t *record_bytes, uint32_t *waves_per_cu,
+                                 uint32_t *overflow_entries);
 /* the librccl the in-library multi-GPU path uses (pbrt_hip_multi_*: loaded on first use by dlopen): its file name -- it must be the one
  * that belongs to the HIP runtime of the process (beside the loaded libamdhip64), whichever host loaded that.  No device is touched. */
 int pbrt_hip_rccl_library(char *path, size_t cap);

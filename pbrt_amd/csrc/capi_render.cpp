@@ -113,10 +113,11 @@ constexpr uint32_t kRenderWavesPerCuEnv = 16;
 constexpr uint32_t kRenderWavesPerCuN = 16;
 // the production walk's stack plan under the A-B knobs PBRT_HIP_FORCE_OVERFLOW_VARIANT (the overflow variant for every tree) and
 // PBRT_HIP_PREFER_LDS_STACK (the whole stack in LDS whenever it fits kQuadLdsStack rows, whatever the occupancy), read once
-RenderStackPlan stack_plan(uint32_t quad_stack_need) {
+// (lds_records: the launch is the default path's, whose overflow instantiation keeps path records 0..2 in LDS behind a shorter stack)
+RenderStackPlan stack_plan(uint32_t quad_stack_need, bool lds_records) {
   static const bool force_overflow = debug_knob("PBRT_HIP_FORCE_OVERFLOW_VARIANT") != nullptr;
   static const bool prefer_lds = debug_knob("PBRT_HIP_PREFER_LDS_STACK") != nullptr;
-  return render_stack_plan(quad_stack_need, force_overflow, prefer_lds);
+  return render_stack_plan(quad_stack_need, force_overflow, prefer_lds, lds_records);
 }
 // (samplers 2 and 3 -- Sobol' proper and Halton -- share one instantiation of the kernel: "the table samplers")
 bool is_table_sampler(uint32_t sampler) { return sampler == PBRT_HIP_SAMPLER_SOBOL_ND || sampler == PBRT_HIP_SAMPLER_HALTON; }
@@ -200,9 +201,9 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
   L.env = s->env;
   L.normals = s->normals;
   const bool shallow = s->dev.quad_stack_need <= kShallowStackNeed;
-  L.plan = stack_plan(s->dev.quad_stack_need);
-  L.lds_bytes = L.plan.rows * 256u;
   const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured && !L.glass && !L.env && !L.normals;
+  L.plan = stack_plan(s->dev.quad_stack_need, default_path);
+  L.lds_bytes = (L.plan.rows + L.plan.record_rows) * 256u;
   L.steps = default_path && !L.plan.overflow && shallow ? 2u : PBRT_STEPS_PER_CHECK;
   if (L.counters == kCountExact) {
     const int ce = ensure_canonical(s);
@@ -247,7 +248,8 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
     HIP_TRY(s->d_halton.alloc(kHaltonDims * 4));
     HIP_TRY(hipMemcpy(s->d_halton.p, tab, sizeof(tab), hipMemcpyHostToDevice));
   }
-  // float4 records: 5 x 64 per one-wave workgroup (kernel_path.hpp LaneRecords); with another box filter radius 16 x 2 x 64 more
+  // float4 records: 5 x 64 per one-wave workgroup (kernel_path.hpp LaneRecords; a kernel with records 0..2 in LDS uses the last two and keeps
+  // the stride: 26 MB at most, and one layout for every instantiation); with another box filter radius 16 x 2 x 64 more
   // behind them (kWideSlotFloat4: a chunk's sums per footprint)
   HIP_TRY(s->d_lane_state.grow((size_t)L.n_workgroups * (L.wide ? 320 + 2048 : 320)));
   if (!L.wide) {
@@ -257,7 +259,8 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
     if (s->d_partials.n / 4 > need) s->d_partials.release();
     HIP_TRY(s->d_partials.grow(need));
   }
-  // the overflow variant keeps kQuadLdsStackOvf rows per lane in LDS; deeper entries (rare) go here
+  // the overflow variant keeps kQuadLdsStackOvf rows per lane in LDS (the default path's: kQuadLdsWalkRows, its path records behind them);
+  // deeper entries (rare) go here
   HIP_TRY(s->d_stack_overflow.grow((size_t)L.n_workgroups * 64 * L.plan.extra_entries));
   return PBRT_HIP_OK;
 }
@@ -280,8 +283,17 @@ void scene_render_params(const pbrt_hip_scene *s, RenderParams *R) {
 extern "C" {
 
 int pbrt_hip_render_stack_plan(uint32_t stack_need, uint32_t *lds_rows, uint32_t *waves_per_cu, uint32_t *overflow_entries) {
-  const RenderStackPlan p = stack_plan(stack_need);
+  const RenderStackPlan p = stack_plan(stack_need, false);
   if (lds_rows) *lds_rows = p.rows;
+  if (waves_per_cu) *waves_per_cu = p.waves_per_cu;
+  if (overflow_entries) *overflow_entries = p.extra_entries;
+  return PBRT_HIP_OK;
+}
+
+int pbrt_hip_render_stack_layout(uint32_t stack_need, uint32_t *stack_rows, uint32_t *record_bytes, uint32_t *waves_per_cu, uint32_t *overflow_entries) {
+  const RenderStackPlan p = stack_plan(stack_need, true);
+  if (stack_rows) *stack_rows = p.rows;
+  if (record_bytes) *record_bytes = p.record_rows * 256u;
   if (waves_per_cu) *waves_per_cu = p.waves_per_cu;
   if (overflow_entries) *overflow_entries = p.extra_entries;
   return PBRT_HIP_OK;

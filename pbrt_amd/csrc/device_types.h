@@ -46,6 +46,24 @@ constexpr uint32_t kQuadLdsStack = 40, kQuadLdsStackOvf = 30;
 // percentile, 23 at most over 40 000 rays; 1 M triangles: 7.6 / 17 / 20), so the HBM overflow area is a safety net, not a
 // path; and more resident waves help this latency-bound workload (r03q / r03r: 20 waves with 30 rows 217 ms, 18 waves with
 // 35 rows 219 ms, 16 waves 224 ms).
+//
+// The walk does not use 30 rows either, and the default path's overflow instantiations (render_kernel without counters, wide filter
+// or table sampler) spend twelve of them on the path state instead: records 0..2 of kernel_path.hpp PathState, 1 KB per wave each,
+// lie in LDS behind kQuadLdsWalkRows stack rows -- 18 + 12 rows are the same six granules, so the 20 waves stay -- and the service
+// stage's three loads and three stores per visit never reach the L2 that the tree wants.  Entries beyond the 18
+// rows go to the HBM overflow area like those beyond the 30.  A -DPBRT_QUAD_LDS_STACK below 20 is taken as the walk's rows themselves
+// (the records follow them: 12 -> 24 rows); -DPBRT_PATH_RECORDS_HBM builds the records in HBM everywhere (A-B).
+constexpr uint32_t kPathRecordRows = 12u;
+#ifdef PBRT_PATH_RECORDS_HBM
+constexpr bool kLdsPathRecords = false;
+#else
+constexpr bool kLdsPathRecords = true;
+#endif
+constexpr uint32_t kQuadLdsWalkRows = kQuadLdsStackOvf >= kPathRecordRows + 8u ? kQuadLdsStackOvf - kPathRecordRows : kQuadLdsStackOvf;
+// (the two readings meet at 20: 20 -> 8 walk rows + 12, 19 -> 19 + 12 = 31 rows, a granule more and 18 waves.  The walk needs its sentinel,
+// a scratch row and room for one step's four pushes before its overflow test; the records' 16-byte accesses need the rows' 256-byte grain)
+static_assert(kQuadLdsWalkRows >= 8u, "PBRT_QUAD_LDS_STACK: the walk's LDS part needs at least 8 rows");
+static_assert((kQuadLdsWalkRows * 256u) % 16u == 0u && (kPathRecordRows * 256u) == 3u * 1024u, "path records 0..2: three 16-byte-aligned 1 KB rows behind the stack");
 constexpr uint32_t kLdsGranule = 1280u;
 constexpr uint32_t kLdsBytesPerCu = 160u * 1024u;
 // float4 per triangle record in `tris`: {p0, id}{p1, material}{p2, 0} + one of padding -- a 64-byte record never straddles
@@ -87,12 +105,15 @@ inline uint32_t sample_chunk_shift(uint32_t spp) {  // log2 K
 constexpr uint32_t kSobolNdRequests = 64u;
 
 struct RenderStackPlan {
-  uint32_t rows;           // LDS rows per wave
-  bool overflow;           // the overflow variant (rows == kQuadLdsStackOvf)
+  uint32_t rows;           // LDS rows of the walk's stack per wave
+  bool overflow;           // the overflow variant (rows == kQuadLdsStackOvf, or kQuadLdsWalkRows with the path records behind them)
   uint32_t waves_per_cu;   // one-wave workgroups a CU holds at once with these rows (at most 20: 5 per SIMD by registers)
   uint32_t extra_entries;  // HBM entries per lane beyond the LDS part (overflow variant)
+  uint32_t record_rows;    // LDS rows behind the stack's that hold path records 0..2 (kPathRecordRows, or 0: the records are in HBM)
 };
-inline RenderStackPlan render_stack_plan(uint32_t quad_stack_need, bool force_overflow, bool prefer_lds = false) {
+// lds_records: the plan of a launch whose overflow instantiation keeps the path records in LDS (the default path's, see above); every
+// other launch, and every tree that keeps its whole stack in LDS, has them in HBM
+inline RenderStackPlan render_stack_plan(uint32_t quad_stack_need, bool force_overflow, bool prefer_lds = false, bool lds_records = false) {
   RenderStackPlan p;
   const uint32_t need_rows = quad_stack_need + 2u;
   auto waves = [](uint32_t rows) {
@@ -102,8 +123,9 @@ inline RenderStackPlan render_stack_plan(uint32_t quad_stack_need, bool force_ov
   p.rows = need_rows < 8u ? 8u : need_rows;
   // (20 waves with the overflow variant beat 18 or 16 waves with the whole stack in LDS: C2 +1 %, C3 +4 %)
   p.overflow = force_overflow || need_rows > kQuadLdsStack || (waves(p.rows) < waves(kQuadLdsStackOvf) && !prefer_lds);
-  if (p.overflow) p.rows = kQuadLdsStackOvf;
-  p.waves_per_cu = waves(p.rows);
+  p.record_rows = p.overflow && lds_records && kLdsPathRecords ? kPathRecordRows : 0u;
+  if (p.overflow) p.rows = p.record_rows ? kQuadLdsWalkRows : kQuadLdsStackOvf;
+  p.waves_per_cu = waves(p.rows + p.record_rows);
   p.extra_entries = p.overflow && need_rows > p.rows ? need_rows - p.rows : 0u;
   return p;
 }

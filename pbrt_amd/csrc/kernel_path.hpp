@@ -148,6 +148,7 @@ struct PathState {
 struct LaneRecords {
   char *base;    // wave-uniform: record 2 of lane 0
   uint32_t off;  // lane * 16
+  uint32_t lds;  // the LDS form of records 0..2 (below): LDS byte address of record 0 of lane 0; else unused
 };
 constexpr int32_t kRecL = -2048, kRecBeta = -1024, kRecWi = 0, kRecLpend = 1024, kRecSum = 2048;  // byte offsets
 __device__ __forceinline__ float4 rec_load(const LaneRecords &r, int32_t k) {
@@ -160,14 +161,37 @@ __device__ __forceinline__ void rec_store(const LaneRecords &r, int32_t k, float
   asm volatile("" : "+v"(o));
   *reinterpret_cast<float4 *>(r.base + o + k) = v;
 }
-__device__ __forceinline__ void path_store(const LaneRecords &rec, const PathState &P) {
-  rec_store(rec, kRecL, make_float4(P.L.x, P.L.y, P.L.z,
-                                    __uint_as_float(P.s | (P.bounces << 20) | (P.specular ? 1u << 30 : 0u) | (P.cont ? 1u << 31 : 0u))));
-  rec_store(rec, kRecBeta, make_float4(P.beta.x, P.beta.y, P.beta.z, __uint_as_float((uint32_t)P.rng.state)));
-  rec_store(rec, kRecWi, make_float4(P.wi_next.x, P.wi_next.y, P.wi_next.z, __uint_as_float((uint32_t)(P.rng.state >> 32))));
+// The LDS form of records 0..2 (device_types.h kLdsPathRecords; LDS = render_body.inc's LREC): record k of the lane at r.lds + k KB +
+// lane * 16, r.lds = the LDS byte address behind the walk's stack rows -- a link-time constant, so the record's place is the
+// ds_read_b128 / ds_write_b128's immediate offset and the address register holds the lane's 16 bytes alone (opaque, as above).
+struct alignas(16) LdsRec { float x, y, z, w; };  // (four scalar accesses of a 16-byte-aligned record: the compiler joins them into one b128)
+typedef __attribute__((address_space(3))) LdsRec lds_rec;
+template <bool LDS>
+__device__ __forceinline__ float4 path_rec_load(const LaneRecords &r, int32_t k) {
+  if (!LDS) return rec_load(r, k);
+  uint32_t o = r.off;
+  asm volatile("" : "+v"(o));
+  const lds_rec *p = (const lds_rec *)(uintptr_t)(r.lds + (uint32_t)(k - kRecL) + o);
+  return make_float4(p->x, p->y, p->z, p->w);
 }
+template <bool LDS>
+__device__ __forceinline__ void path_rec_store(const LaneRecords &r, int32_t k, float4 v) {
+  if (!LDS) { rec_store(r, k, v); return; }
+  uint32_t o = r.off;
+  asm volatile("" : "+v"(o));
+  lds_rec *p = (lds_rec *)(uintptr_t)(r.lds + (uint32_t)(k - kRecL) + o);
+  p->x = v.x; p->y = v.y; p->z = v.z; p->w = v.w;
+}
+template <bool LDS = false>
+__device__ __forceinline__ void path_store(const LaneRecords &rec, const PathState &P) {
+  path_rec_store<LDS>(rec, kRecL, make_float4(P.L.x, P.L.y, P.L.z,
+                                    __uint_as_float(P.s | (P.bounces << 20) | (P.specular ? 1u << 30 : 0u) | (P.cont ? 1u << 31 : 0u))));
+  path_rec_store<LDS>(rec, kRecBeta, make_float4(P.beta.x, P.beta.y, P.beta.z, __uint_as_float((uint32_t)P.rng.state)));
+  path_rec_store<LDS>(rec, kRecWi, make_float4(P.wi_next.x, P.wi_next.y, P.wi_next.z, __uint_as_float((uint32_t)(P.rng.state >> 32))));
+}
+template <bool LDS = false>
 __device__ __forceinline__ void path_load(const LaneRecords &rec, PathState &P) {
-  const float4 a = rec_load(rec, kRecL), b = rec_load(rec, kRecBeta), c = rec_load(rec, kRecWi);
+  const float4 a = path_rec_load<LDS>(rec, kRecL), b = path_rec_load<LDS>(rec, kRecBeta), c = path_rec_load<LDS>(rec, kRecWi);
   P.L = {a.x, a.y, a.z};
   P.beta = {b.x, b.y, b.z};
   P.wi_next = {c.x, c.y, c.z};

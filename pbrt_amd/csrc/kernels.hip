@@ -33,6 +33,9 @@ namespace {
 // fixed-point accumulators with atomics, instead of to its chunk's partial sum.
 // SND: sampler 2, the Sobol' sampler with its own dimensions per request (3.12): generator-matrix lookups in the service stage.
 // (Both variants keep the default path's register budget: 5 waves per SIMD, no spill -- tests/test_host.py.)
+constexpr bool render_kernel_lds_records(bool count, bool exact, int stack, bool wide, bool snd) {
+  return kLdsPathRecords && !count && !exact && !wide && !snd && stack != 0;
+}
 template <bool SPH, bool COUNT, bool EXACT, int STACK, int STEPS = PBRT_STEPS_PER_CHECK, bool WIDE = false, bool SND = false>
 // (scenes with spheres -- C0 / C1: a handful of primitives, nothing to gain from occupancy -- get the register budget
 // of 3 waves per SIMD: the f64 quadratic of lib.rs:181-203 does not fit 128 VGPRs beside the path state)
@@ -40,6 +43,8 @@ __global__ void __launch_bounds__(64, (COUNT ? 1 : (SPH ? 3 : PBRT_RENDER_WAVES_
   constexpr bool MIS = false, TEX = false, GLS = false;  // (the variants: kernels_x.hip render_kernel_x)
   constexpr bool ENV = false;                            // (an environment map: kernels_env.hip render_kernel_env)
   constexpr bool NRM = false;                            // (shading normals: kernels_n.hip render_kernel_n)
+  // the default path's overflow instantiations keep path records 0..2 in LDS behind a shorter stack (device_types.h kLdsPathRecords)
+  constexpr bool LREC = render_kernel_lds_records(COUNT, EXACT, STACK, WIDE, SND);
   (void)MIS;
   (void)GLS;
   (void)ENV;
@@ -260,6 +265,8 @@ hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderL
     } else if constexpr (!COUNT && !SND && !WIDE && STACK == 0) {
       return go(L.steps == 2 ? render_kernel<SPH, false, false, 0, 2> : render_kernel<SPH, false, false, 0>);
     } else {
+      // (the host's plan and the instantiation must agree on where path records 0..2 live: the launch's LDS is sized by the plan)
+      if (render_kernel_lds_records(COUNT, false, STACK, WIDE, SND) != (L.plan.record_rows != 0u)) return hipErrorInvalidValue;
       return go(render_kernel<SPH, COUNT, false, STACK, PBRT_STEPS_PER_CHECK, WIDE, SND>);
     }
   }, L.spheres, L.plan.overflow, L.counters == kCountWalk, L.table_sampler, L.wide);

@@ -26,6 +26,7 @@ template <bool SPH, int STACK, bool MIS, bool TEX, bool SND>
 __global__ void __launch_bounds__(64, PBRT_ENV_WAVES_PER_SIMD) render_kernel_env(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false, WIDE = false, GLS = true, ENV = true;
   constexpr bool NRM = false;  // (shading normals: kernels_n.hip render_kernel_n)
+  constexpr bool LREC = false;  // (path records in LDS: the default path alone, kernels.hip render_kernel)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
 #include "render_body.inc"
 }

@@ -31,6 +31,7 @@ namespace {
 template <bool SPH, int STACK, bool MIS, bool TEX, bool SND, bool ENV>
 __global__ void __launch_bounds__(64, PBRT_NRM_WAVES_PER_SIMD) render_kernel_n(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false, WIDE = false, GLS = true, NRM = true;
+  constexpr bool LREC = false;  // (path records in LDS: the default path alone, kernels.hip render_kernel)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
 #include "render_body.inc"
 }

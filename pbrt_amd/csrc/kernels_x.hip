@@ -17,6 +17,7 @@ __global__ void __launch_bounds__(64, ((SPH || GLS) ? 3 : PBRT_RENDER_WAVES_PER_
   constexpr bool COUNT = false, EXACT = false;
   constexpr bool ENV = false;  // (an environment map: kernels_env.hip render_kernel_env)
   constexpr bool NRM = false;  // (shading normals: kernels_n.hip render_kernel_n)
+  constexpr bool LREC = false;  // (path records in LDS: the default path alone, kernels.hip render_kernel)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
   (void)ENV;
 #include "render_body.inc"

@@ -1,5 +1,5 @@
 // render_body.inc -- the body of render_kernel (kernels.hip) and of render_kernel_x (kernels_x.hip), included once in each: the two are the same
-// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV, NRM in scope (kernels_env.hip
+// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV, NRM, LREC in scope (kernels_env.hip
 // includes it a third time, for render_kernel_env, the one kernel with ENV = true, and kernels_n.hip a fourth, for render_kernel_n, the one
 // with NRM = true: interpolated shading normals, DESIGN.md 3.18).  (A shared __device__
 // function would be the tidy way to say this; the text is included instead because wrapping the body in a function -- forceinline or
@@ -45,7 +45,10 @@
   const bool direct_only = R.integrator == 1u;
   const TravTuning tune = {R.min_walkers, R.min_parked};
 
-  const LaneRecords rec = {reinterpret_cast<char *>(R.lane_state + (size_t)blockIdx.x * 320u + 128u), lane * 16u};
+  // the production walk's LDS rows (0 = the whole stack in LDS); with LREC path records 0..2 lie in LDS behind them (kernel_path.hpp)
+  constexpr uint32_t WROWS = (!EXACT && STACK != 0) ? (LREC ? kQuadLdsWalkRows : (uint32_t)STACK) : 0u;
+  const LaneRecords rec = {reinterpret_cast<char *>(R.lane_state + (size_t)blockIdx.x * 320u + 128u), lane * 16u,
+                           LREC ? lds_addr(lds_stack) + WROWS * kRowBytes : 0u};
   uint32_t state = ST_FETCH;
   if (WIDE) wide_slots_clear(R.wide_slots, lane);  // the lane's footprint slots start empty, and every flush leaves them so
   uint32_t region = blockIdx.x % R.n_regions;  // the part of the pixel list this wave draws from
@@ -70,7 +73,7 @@
     float rtmax = kInf;
     int32_t xr = 0, yr = 0;
     if (serve && state != ST_FETCH) {
-      path_load(rec, P);
+      path_load<LREC>(rec, P);
       pixel_xy(item_pixel(item), xr, yr);
       P.rng.inc = ((((seq0 + (uint64_t)(R.seq_y0 + yr) * (uint64_t)R.seq_w + (uint64_t)(R.seq_x0 + xr)) << kb) + ((item >> 6) & chunk_mask)) << 1) | 1u;
       PROBE_SEC(1);
@@ -484,14 +487,14 @@
         }
       }
       PROBE_SEC(7);
-      path_store(rec, P);
+      path_store<LREC>(rec, P);
       EXP_RAY_LOG(launch, ro, rd, rtmax, launch_any);
       if (launch) trav_begin<EXACT>(S, T, stk, ro, rd, rtmax, launch_any, c_nodes);
     }
     PROBE_SEC(8);
     if (__ballot(state != ST_DONE) == 0ull) break;
     wave_prio(PBRT_PRIO_ARITH);  // traversal arithmetic at priority 0, its fetches at 3 (trav_run)
-    trav_run<EXACT, COUNT, ((!EXACT && STACK != 0) ? (uint32_t)STACK : 0u), STEPS, SPH>(S, T, stk, stkt, ovf, state != ST_DONE, tune, c_nodes, c_tris);
+    trav_run<EXACT, COUNT, WROWS, STEPS, SPH>(S, T, stk, stkt, ovf, state != ST_DONE, tune, c_nodes, c_tris);
     wave_prio(PBRT_PRIO_SERVICE);  // the service stage of the next round: its lanes are not tracing while it lasts
     PROBE_SEC(0);
   }

@@ -7,18 +7,21 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export PROBE_COUNTERS=1
 i=0
 # (a group that starts with "ISSUE:" is the vector issue port's occupancy, tools/pmc_issue.sh / profiles/r03c_issue_counter_calibration.txt:
 # its counters come from ONE pass -- the others repeat elsewhere -- and are kept apart as ISSUE_<name>)
 while read -r group; do
   [ -z "$group" ] && continue
   i=$((i+1))
+  # (the probe's ray count and walk counters are read from pass 1's log alone: the other passes skip the two counting renders)
+  if [ $i = 1 ]; then export PROBE_COUNTERS=1; else unset PROBE_COUNTERS; fi
   prefix=""
   case "$group" in ISSUE:*) prefix="ISSUE_"; group=${group#ISSUE: };; esac
   echo "$prefix" > $OUT/p$i.prefix
   timeout 600 rocprofv3 --pmc $group --kernel-trace --output-format csv -d $OUT/p$i -- python3 $R/tools/pmc_probe.py "$@" > $OUT/p$i.log 2>&1
-  echo "pass $i rc=$? : $group"
+  rc=$?
+  echo "pass $i rc=$rc : $group"
+  if [ $rc -ne 0 ]; then echo "pass $i failed: no further pass is started"; break; fi
 done <<'GROUPS'
 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA
 SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_THREAD_CYCLES_VALU SQ_INST_CYCLES_VMEM_RD SQ_ACTIVE_INST_LDS SQ_INSTS_BRANCH

@@ -117,7 +117,7 @@ def main():
                 if res:  # what the compiler allocated (code-object notes) + the launch's dynamic LDS (the walk's stack)
                     summary.update({"vgpr": res["vgpr_count"], "sgpr": res["sgpr_count"], "vgpr_spill": res["vgpr_spill_count"], "scratch_bytes": res["private_segment_fixed_size"],
                                     "lds_bytes": (res["group_segment_fixed_size"] or 0) + summary.get("lds_dynamic_bytes", 0),
-                                    "resources_source": "code-object notes (NT_AMDGPU_METADATA) + render_stack_plan rows x 256 B of dynamic LDS"})
+                                    "resources_source": "code-object notes (NT_AMDGPU_METADATA) + the launch's dynamic LDS (pbrt_hip_render_stack_layout: stack rows x 256 B + path-record bytes)"})
         except Exception as e:  # noqa: BLE001
             summary["kernel_isa_id_error"] = repr(e)[:200]
         # FETCH_SIZE calibrated for this access shape (tools/fetch_size_calibration.sh): known bytes per counted byte of

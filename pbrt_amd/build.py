@@ -14,11 +14,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.abspath(os.environ.get("PBRT_HIP_LIB_DIR") or os.path.join(HERE, "lib"))
 LIB_PATH = os.path.join(LIB_DIR, "libpbrt_hip.so")
 CLI_PATH = os.path.join(LIB_DIR, "pbrt")  # the C++ command line (csrc/pbrt_main.cpp)
-# (the three kernel units first: they take the longest, and the pool below starts the units in this order.  Each holds one family of
-# render kernels -- kernels.hip render_kernel, kernels_x.hip render_kernel_x, kernels_env.hip render_kernel_env -- built
-# from the same headers, kernel_math.hpp / kernel_walk.hpp / kernel_path.hpp, and render_body.inc; they compile side by side.
-# kernels_blocks.hip holds the debug hook that runs the headers' building blocks over arrays and no render kernel; kernels_n.hip holds
-# render_kernel_n, the family of scenes with shading normals, the normals' gather and their hook)
+# (the render-kernel units first: they take the longest, and the pool below starts the units in this order.  Each holds one family of
+# render kernels (csrc/render_variant.hpp says which), built from the same headers, kernel_math.hpp / kernel_walk.hpp / kernel_path.hpp,
+# and render_body.inc; they compile side by side.  kernels_blocks.hip holds the debug hook that runs the headers' building blocks over
+# arrays and no render kernel)
 SOURCES = ["kernels.hip", "kernels_x.hip", "kernels_n.hip", "kernels_env.hip", "bvh_gpu.hip", "kernels_blocks.hip", "capi_scene.cpp", "capi_render.cpp", "capi_load.cpp", "multi_gpu.cpp", "bvh_build.cpp", "quad_nodes.cpp", "reinsert_batch.cpp", "imageio.cpp",
            "scene_parser.cpp", "ply_reader.cpp", "envmap.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -102,15 +102,6 @@ uint32_t tuning(const char *name, uint32_t dflt, long cap = 64) {
 // min_walkers: 36 for deep trees (long walks: C3 +1 % over 32), 20 for shallow ones, where a frame is mostly shading and
 // the shading stage should wait for more lanes (C4 +12 % over 36)
 constexpr uint32_t kMinWalkers = 36, kMinWalkersShallow = 20, kShallowStackNeed = 16, kMinParked = 16;
-// persistent one-wave workgroups of the render kernel per CU = what a CU holds at once: render_stack_plan (device_types.h:
-// 20 with up to 30 LDS rows -- 5 waves per SIMD by the kernel's 96 VGPRs --, fewer with more rows); the kernel for scenes
-// with spheres has the register budget of 3 waves per SIMD.  The grid is this x the device's CU count (hipDeviceProp_t;
-// render_launch)
-constexpr uint32_t kRenderWavesPerCuSpheres = 12;
-// a scene with an environment map: render_kernel_env's register budget is 4 waves per SIMD (kernels_env.hip)
-constexpr uint32_t kRenderWavesPerCuEnv = 16;
-// a scene with shading normals: render_kernel_n's register budget is 4 waves per SIMD as well (kernels_n.hip)
-constexpr uint32_t kRenderWavesPerCuN = 16;
 // the production walk's stack plan under the A-B knobs PBRT_HIP_FORCE_OVERFLOW_VARIANT (the overflow variant for every tree) and
 // PBRT_HIP_PREFER_LDS_STACK (the whole stack in LDS whenever it fits kQuadLdsStack rows, whatever the occupancy), read once
 // (lds_records: the launch is the default path's, whose overflow instantiation keeps path records 0..2 in LDS behind a shorter stack)
@@ -119,8 +110,21 @@ RenderStackPlan stack_plan(uint32_t quad_stack_need, bool lds_records) {
   static const bool prefer_lds = debug_knob("PBRT_HIP_PREFER_LDS_STACK") != nullptr;
   return render_stack_plan(quad_stack_need, force_overflow, prefer_lds, lds_records);
 }
-// (samplers 2 and 3 -- Sobol' proper and Halton -- share one instantiation of the kernel: "the table samplers")
-bool is_table_sampler(uint32_t sampler) { return sampler == PBRT_HIP_SAMPLER_SOBOL_ND || sampler == PBRT_HIP_SAMPLER_HALTON; }
+// The switches of a render (render_variant.hpp), from the scene, the render description and the film geometry.  (Samplers 2 and 3 --
+// Sobol' proper and Halton -- share one instantiation of the kernel: "the table samplers".)
+RenderVariant render_variant(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGeom &fg) {
+  RenderVariant v{};
+  v.spheres = s->dev.n_spheres > 0;
+  v.wide = fg.wide;
+  v.table_sampler = r->sampler == PBRT_HIP_SAMPLER_SOBOL_ND || r->sampler == PBRT_HIP_SAMPLER_HALTON;
+  v.mis = r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS;
+  v.textured = s->textured;
+  v.glass = s->glass;
+  v.env = s->env;
+  v.normals = s->normals;
+  v.counters = (r->flags & PBRT_HIP_FLAG_COUNTERS) ? kCountExact : ((r->flags & PBRT_HIP_FLAG_WALK_COUNTERS) ? kCountWalk : kCountNone);
+  return v;
+}
 
 int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
   if (!s || !r) return fail(PBRT_HIP_ERR_INVALID, "render: null argument");
@@ -128,9 +132,6 @@ int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
   if (r->world_size == 0 || r->rank >= r->world_size) return fail(PBRT_HIP_ERR_INVALID, "render: rank must be < world_size");
   if (r->integrator > PBRT_HIP_INTEGRATOR_PATH_MIS) return fail(PBRT_HIP_ERR_INVALID, "render: unknown integrator");
   if (r->sampler > PBRT_HIP_SAMPLER_HALTON) return fail(PBRT_HIP_ERR_INVALID, "render: unknown sampler");
-  const bool counting = (r->flags & (PBRT_HIP_FLAG_COUNTERS | PBRT_HIP_FLAG_WALK_COUNTERS)) != 0u;
-  if (is_table_sampler(r->sampler) && counting)
-    return fail(PBRT_HIP_ERR_INVALID, "render: the counter flags are not available with the Sobol' / Halton samplers (samplers 2, 3)");
   // the kernels pack the sample index into 20 bits and the bounce count into 10 (kernel_path.hpp path_store): beyond that a
   // persistent wave would never see its pixel finish
   if ((uint64_t)r->spp_x * (uint64_t)r->spp_y > PBRT_HIP_MAX_SPP)
@@ -140,29 +141,12 @@ int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
   const float fx = filter_radius(r->filter_xwidth), fy = filter_radius(r->filter_ywidth);
   if (!(fx > 0.f) || !(fy > 0.f) || !std::isfinite(fx) || !std::isfinite(fy)) return fail(PBRT_HIP_ERR_INVALID, "render: the filter radii must be positive");
   if (fx > 16.f || fy > 16.f) return fail(PBRT_HIP_ERR_LIMIT, "render: filter radius above 16 pixels");
-  const bool wide = filter_is_wide(fx, fy);
-  if (wide && counting)
-    return fail(PBRT_HIP_ERR_INVALID, "render: the counter flags need the default box filter (radius 0.5)");
-  // shading normals: render_kernel_n exists without counters and for the default box filter (kernels_n.hip); asked before
-  // the map, as launch_render asks
-  if (s->normals && counting)
-    return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for a scene with shading normals");
-  if (s->normals && wide)
-    return fail(PBRT_HIP_ERR_LIMIT, "render: shading normals with a box filter radius other than 0.5 is a combination the library does not build");
-  // an environment map: render_kernel_env exists without counters and for the default box filter (kernels_env.hip).
-  // Asked before what follows, so that a scene with a map is told of the map whatever else it holds (glass, textures)
-  if (s->env && counting)
-    return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for a scene with an environment map");
-  // (textures, the MIS integrator, the table samplers and a wide box filter combine freely -- render_kernel_x --; only the counting
-  // instantiations exist for the default path alone)
-  if ((s->textured || r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS) && counting)
-    return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for textured materials / the MIS integrator");
-  if (s->glass && counting)
-    return fail(PBRT_HIP_ERR_LIMIT, "render: the counter flags are not available for a scene with a glass material");
-  if (s->env && wide)
-    return fail(PBRT_HIP_ERR_LIMIT, "render: an environment map with a box filter radius other than 0.5 is a combination the library does not build");
+  // the combinations of switches the library does not build
+  const FilmGeom fg = film_geom(s, r);
+  const RenderRefusal refusal = render_variant_refusal(render_variant(s, r, fg));
+  if (refusal.code != PBRT_HIP_OK) return fail(refusal.code, refusal.text);
   if (!(r->max_sample_luminance >= 0.f)) return fail(PBRT_HIP_ERR_INVALID, "render: max_sample_luminance must be >= 0 (0 = none)");
-  if (wide) {
+  if (fg.wide) {
     // the fixed-point film: a sample adds at most 2^39 units to a pixel's int64 accumulator, and a pixel receives
     // at most spp x footprint samples (from every rank together: the N-rank reduce adds the same samples) -- 2^24 of them fit
     const uint64_t foot = (uint64_t)(2 * (int)std::ceil(fx) + 1) * (uint64_t)(2 * (int)std::ceil(fy) + 1);
@@ -191,21 +175,14 @@ uint32_t partials_passes(uint32_t n_local, uint32_t n_chunks) {
 // device-built scene gets here on first use.
 int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGeom &fg, const Shard &sh, RenderLaunch *out) {
   RenderLaunch L{};
-  L.spheres = s->dev.n_spheres > 0;
-  L.counters = (r->flags & PBRT_HIP_FLAG_COUNTERS) ? kCountExact : ((r->flags & PBRT_HIP_FLAG_WALK_COUNTERS) ? kCountWalk : kCountNone);
-  L.wide = fg.wide;
-  L.table_sampler = is_table_sampler(r->sampler);
-  L.mis = r->integrator == PBRT_HIP_INTEGRATOR_PATH_MIS;
-  L.textured = s->textured;
-  L.glass = s->glass;
-  L.env = s->env;
-  L.normals = s->normals;
+  L.variant = render_variant(s, r, fg);
+  L.family = render_family(L.variant);
   const bool shallow = s->dev.quad_stack_need <= kShallowStackNeed;
-  const bool default_path = L.counters == kCountNone && !L.wide && !L.table_sampler && !L.mis && !L.textured && !L.glass && !L.env && !L.normals;
+  const bool default_path = render_default_path(L.variant);
   L.plan = stack_plan(s->dev.quad_stack_need, default_path);
   L.lds_bytes = (L.plan.rows + L.plan.record_rows) * 256u;
   L.steps = default_path && !L.plan.overflow && shallow ? 2u : PBRT_STEPS_PER_CHECK;
-  if (L.counters == kCountExact) {
+  if (L.variant.counters == kCountExact) {
     const int ce = ensure_canonical(s);
     if (ce) return ce;
     // the exact walk holds at most depth - 1 entries (refs + entry distances): the smallest of the instantiated row counts that fits
@@ -213,10 +190,9 @@ int render_launch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, const FilmGe
     L.exact_rows = held > 40 ? 64 : held > 32 ? 40 : held > 26 ? 32 : held > 20 ? 26 : 20;
     L.lds_bytes = L.exact_rows * 512u;
   }
-  // (the instantiations for another filter radius and for the table samplers fit the 96 VGPRs of 5 waves per SIMD like the default one)
-  L.waves_per_cu = (L.spheres || L.glass) ? std::min(kRenderWavesPerCuSpheres, L.plan.waves_per_cu) : L.plan.waves_per_cu;  // (glass: the spheres' budget, kernels_x.hip)
-  if (L.env) L.waves_per_cu = std::min(kRenderWavesPerCuEnv, L.plan.waves_per_cu);  // (whatever else the scene holds: render_kernel_env's own budget)
-  if (L.normals) L.waves_per_cu = std::min(kRenderWavesPerCuN, L.plan.waves_per_cu);  // (likewise: render_kernel_n's own budget)
+  // persistent one-wave workgroups per CU = what a CU holds at once, by the variant's registers and the plan's LDS; the grid is this x
+  // the device's CU count (hipDeviceProp_t)
+  L.waves_per_cu = render_waves_per_cu(L.variant, L.plan.waves_per_cu);
   L.chunk_shift = sample_chunk_shift(r->spp_x * r->spp_y);
   const uint32_t n_chunks = 1u << L.chunk_shift;  // K: DESIGN.md 3.1
   L.passes = fg.wide ? 1u : partials_passes(sh.n_local, n_chunks);
@@ -251,8 +227,8 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
   // float4 records: 5 x 64 per one-wave workgroup (kernel_path.hpp LaneRecords; a kernel with records 0..2 in LDS uses the last two and keeps
   // the stride: 26 MB at most, and one layout for every instantiation); with another box filter radius 16 x 2 x 64 more
   // behind them (kWideSlotFloat4: a chunk's sums per footprint)
-  HIP_TRY(s->d_lane_state.grow((size_t)L.n_workgroups * (L.wide ? 320 + 2048 : 320)));
-  if (!L.wide) {
+  HIP_TRY(s->d_lane_state.grow((size_t)L.n_workgroups * (L.variant.wide ? 320 + 2048 : 320)));
+  if (!L.variant.wide) {
     const size_t need = (size_t)L.pass_tiles * 4096u * (1u << L.chunk_shift);  // one float4 per item of a pass
     // (C3 1.07 GB in one pass; C4's 4096^2 x 16 chunks on one GPU: 3 passes over 1.43 GB; the buffer follows the frame: released when a
     // later render needs less than a quarter of it)
@@ -434,12 +410,12 @@ int pbrt_hip_render_device(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, voi
       R.n_items = n_pass * 4096u * n_chunks;
       if (pass > 0)  // the hand-out positions start again; the ray counters (the first 64 bytes) run on
         HIP_TRY(hipMemsetAsync(s->d_counters.p + 8, 0, 72 * sizeof(unsigned long long), st));
-      HIP_TRY(launch_render(L.counters == kCountExact ? s->dev_exact : s->dev, R, L, st));
+      HIP_TRY(launch_render(L.variant.counters == kCountExact ? s->dev_exact : s->dev, R, L, st));
       if (!fg.wide) HIP_TRY(launch_merge(R.partials, (float4 *)d_slab, sh.w, sh.h, R.rank, R.world, n_pass, spp, st, pass, L.passes));
     }
     HIP_TRY(hipEventRecord(s->ev1, st));
     s->pending = true;
-    s->pending_counters = L.counters != kCountNone;
+    s->pending_counters = L.variant.counters != kCountNone;
     // samples = pixels of this rank's super-tiles that lie inside the film
     uint64_t px = 0;
     for (uint32_t j = 0; j < sh.n_local; j++) {

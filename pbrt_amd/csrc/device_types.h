@@ -17,6 +17,8 @@
 
 #include <cstdlib>
 
+#include "render_variant.hpp"
+
 namespace pbrt_hip {
 
 // Tuning / A-B knobs (PBRT_HIP_MIN_WALKERS, PBRT_HIP_COLLAPSE, PBRT_HIP_TREE, ...) are read from the environment
@@ -77,10 +79,7 @@ constexpr uint32_t kTriStride = PBRT_TRI_STRIDE;
 #ifndef PBRT_STEPS_PER_CHECK
 #define PBRT_STEPS_PER_CHECK 3
 #endif
-#ifndef PBRT_RENDER_MAX_WAVES_PER_CU  // 4 SIMDs x the waves per SIMD the render kernel's register budget allows (kernel_path.hpp)
-#define PBRT_RENDER_MAX_WAVES_PER_CU 20
-#endif
-constexpr uint32_t kRenderMaxWavesPerCu = PBRT_RENDER_MAX_WAVES_PER_CU;
+constexpr uint32_t kRenderMaxWavesPerCu = PBRT_RENDER_MAX_WAVES_PER_CU;  // (render_variant.hpp: 4 SIMDs x the largest register budget)
 
 // An unused child slot of a quad node holds the ref of a leaf with no triangles (and an inverted box: lower planes 255,
 // upper planes 0).  The box rejects it except for degenerate rays / flat nodes, and then the walk parks at an empty leaf and
@@ -240,26 +239,14 @@ struct RayBatch {
 
 // One launch of the render kernel, decided on the host in one place (capi_render.cpp render_launch) from the scene, the render description
 // and the film geometry.  launch_render maps it to an instantiation and computes nothing.
-enum RenderCounters : uint32_t {
-  kCountNone = 0,
-  kCountExact = 1,  // PBRT_HIP_FLAG_COUNTERS: the exact walk of the canonical tree (render_kernel<..., EXACT>)
-  kCountWalk = 2,   // PBRT_HIP_FLAG_WALK_COUNTERS: the production walk, counting
-};
 struct RenderLaunch {
-  // the variant (capi_render.cpp check_render_desc says which combinations exist)
-  bool spheres;        // SPH
-  RenderCounters counters;
-  bool wide;           // WIDE: a box filter radius other than 0.5
-  bool table_sampler;  // SND: samplers 2 and 3 (3.12, 3.13)
-  bool mis, textured;  // render_kernel_x's MIS (3.14) and TEX (3.15)
-  bool glass;          // render_kernel_x's GLS (3.16): the scene has a glass material
-  bool env;            // render_kernel_env (3.17): the scene has an environment map -- never with `wide` or the counters (capi_render.cpp check_render_desc)
-  bool normals;        // render_kernel_n (3.18): the scene carries shading normals -- never with `wide` or the counters either; asked before `env`
+  RenderVariant variant;  // the switches, and the family that renders them (render_variant.hpp says which combinations exist)
+  RenderFamily family;
   RenderStackPlan plan;  // the production walk's stack: LDS rows, the overflow variant, HBM entries per lane
   uint32_t steps;        // production walk: node steps per scheduling check (STEPS)
   uint32_t exact_rows;   // exact walk: STACK, its stack rows of refs (and as many of entry distances)
   uint32_t lds_bytes;    // dynamic shared memory per one-wave workgroup
-  uint32_t waves_per_cu;  // one-wave workgroups per CU: the plan's, clamped for the spheres' register budget
+  uint32_t waves_per_cu;  // one-wave workgroups per CU: the plan's, clamped for the variant's register budget (render_waves_per_cu)
   uint32_t n_workgroups;  // the grid: waves_per_cu x the device's CUs, at most one per item of the largest pass
   uint32_t chunk_shift;   // log2 K, K = the sample chunks of a pixel
   uint32_t passes;        // launches of a frame over one partial-sums buffer (capi_render.cpp partials_passes) ...

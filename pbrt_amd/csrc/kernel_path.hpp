@@ -47,7 +47,7 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
     return true;
   } else {
     // (an emissive triangle: device type 3.  Device type 4, an environment map, never arrives here: a kernel with ENV takes it before
-    // this chain, and launch_render's first question is L.env -- launch_render_env returns an error for what it does not build, it does not fall back)
+    // this chain, and a scene with a map is rendered by a family with ENV alone: render_variant.hpp render_family)
     const float4 l1 = S.lights[5 * li + 1];
     const float4 l2 = S.lights[5 * li + 2];
     const float4 l4 = S.lights[5 * li + 4];
@@ -118,11 +118,6 @@ __device__ __forceinline__ bool sample_env_light(const RenderParams &R, V3 nf, V
 }
 
 enum : uint32_t { ST_NEW = 0, ST_CLOSEST = 1, ST_SHADOW = 2, ST_DONE = 3, ST_FETCH = 4 };
-
-// waves per SIMD the register allocator must leave room for (launch_bounds' 2nd argument)
-#ifndef PBRT_RENDER_WAVES_PER_SIMD
-#define PBRT_RENDER_WAVES_PER_SIMD 5
-#endif
 
 // Path state of one work item (a CHUNK of a pixel's samples) while its lane is busy walking the BVH:
 // five 16-byte records per lane in HBM, laid out [record][lane] per wave so that a wave's access is one coalesced

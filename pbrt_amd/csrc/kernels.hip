@@ -13,9 +13,9 @@
 //                    vertex / index buffers.
 //   assemble_kernel  scatters a rank's tile-major slab into the row-major film.
 //
-// The building blocks are headers (kernel_math.hpp, kernel_walk.hpp, kernel_path.hpp) and render_body.inc, shared with the two other
-// kernel units: kernels_x.hip (render_kernel_x, the MIS / texture / glass variants) and kernels_env.hip (render_kernel_env, scenes with
-// an environment map); launch_render below decides the family.
+// The building blocks are headers (kernel_math.hpp, kernel_walk.hpp, kernel_path.hpp) and render_body.inc, shared with the other kernel
+// units, each of which holds one more family of render kernels.  render_variant.hpp says which family renders what and with which
+// register budget; launch_render below hands a launch to its family's unit.
 #include "kernel_path.hpp"
 #include "rgb_xyz.hpp"
 #include "with_bools.hpp"
@@ -32,19 +32,15 @@ namespace {
 // WIDE: a box filter radius other than 0.5: a sample is added to every pixel within the radius, into
 // fixed-point accumulators with atomics, instead of to its chunk's partial sum.
 // SND: sampler 2, the Sobol' sampler with its own dimensions per request (3.12): generator-matrix lookups in the service stage.
-// (Both variants keep the default path's register budget: 5 waves per SIMD, no spill -- tests/test_host.py.)
-constexpr bool render_kernel_lds_records(bool count, bool exact, int stack, bool wide, bool snd) {
-  return kLdsPathRecords && !count && !exact && !wide && !snd && stack != 0;
+// (Both variants keep the default path's register budget, no spill -- tests/test_host.py.)  What the switches stand for in render_variant.hpp:
+constexpr RenderVariant default_variant(bool sph, bool count, bool exact, bool wide, bool snd) {
+  return {sph, wide, snd, false, false, false, false, false, count ? (exact ? kCountExact : kCountWalk) : kCountNone};
 }
 template <bool SPH, bool COUNT, bool EXACT, int STACK, int STEPS = PBRT_STEPS_PER_CHECK, bool WIDE = false, bool SND = false>
-// (scenes with spheres -- C0 / C1: a handful of primitives, nothing to gain from occupancy -- get the register budget
-// of 3 waves per SIMD: the f64 quadratic of lib.rs:181-203 does not fit 128 VGPRs beside the path state)
-__global__ void __launch_bounds__(64, (COUNT ? 1 : (SPH ? 3 : PBRT_RENDER_WAVES_PER_SIMD))) render_kernel(const DevScene S, const RenderParams R) {
-  constexpr bool MIS = false, TEX = false, GLS = false;  // (the variants: kernels_x.hip render_kernel_x)
-  constexpr bool ENV = false;                            // (an environment map: kernels_env.hip render_kernel_env)
-  constexpr bool NRM = false;                            // (shading normals: kernels_n.hip render_kernel_n)
-  // the default path's overflow instantiations keep path records 0..2 in LDS behind a shorter stack (device_types.h kLdsPathRecords)
-  constexpr bool LREC = render_kernel_lds_records(COUNT, EXACT, STACK, WIDE, SND);
+__global__ void __launch_bounds__(64, (COUNT ? 1 : render_waves_per_simd(RenderFamily::kDefault, SPH, false))) render_kernel(const DevScene S, const RenderParams R) {
+  constexpr bool MIS = false, TEX = false, GLS = false, ENV = false, NRM = false;  // (the other families': render_variant.hpp)
+  // the plain default path's overflow instantiations keep path records 0..2 in LDS behind a shorter stack (device_types.h kLdsPathRecords)
+  constexpr bool LREC = kLdsPathRecords && STACK != 0 && render_default_path(default_variant(SPH, COUNT, EXACT, WIDE, SND));
   (void)MIS;
   (void)GLS;
   (void)ENV;
@@ -230,19 +226,24 @@ hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, siz
   return hipGetLastError();
 }
 
-// RenderLaunch -> the family and the instantiation; everything else was decided by capi_render.cpp render_launch.  render_kernel has the default
-// path, and one at a time a wide filter (WIDE) or the table samplers (SND); the counting walks only on the default path.  Every other
-// combination, without counters, is render_kernel_x's (kernels_x.hip).  The production walk's STACK is the LDS rows of the overflow
-// variant, or 0 for the whole stack in LDS; the exact walk's is its stack rows.
+// RenderLaunch -> the family's launcher and the instantiation; everything else was decided by capi_render.cpp render_launch, and which
+// instantiations exist by render_variant.hpp.  The production walk's STACK is the LDS rows of the overflow variant, or 0 for the whole
+// stack in LDS; the exact walk's is its stack rows.
 hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
   if (R.n_items == 0) return hipSuccess;
-  if (L.normals) return launch_render_n(S, R, L, st);  // a scene with shading normals, whatever else it holds: kernels_n.hip
-  if (L.env) return launch_render_env(S, R, L, st);  // a scene with an environment map: kernels_env.hip
+  const RenderVariant &V = L.variant;
+  switch (L.family) {
+    case RenderFamily::kN: return launch_render_n(S, R, L, st);
+    case RenderFamily::kEnv: return launch_render_env(S, R, L, st);
+    case RenderFamily::kX: return launch_render_x(S, R, L, st);
+    case RenderFamily::kDefault: break;
+    default: return hipErrorInvalidValue;
+  }
   auto go = [&](void (*kernel)(DevScene, RenderParams)) {
     hipLaunchKernelGGL(kernel, dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
     return hipGetLastError();
   };
-  if (L.counters == kCountExact)
+  if (V.counters == kCountExact)
     return with_bools([&](auto SPH) {
       switch (L.exact_rows) {
         case 20: return go(render_kernel<SPH, true, true, 20>);
@@ -252,24 +253,21 @@ hipError_t launch_render(const DevScene &S, const RenderParams &R, const RenderL
         case 64: return go(render_kernel<SPH, true, true, 64>);
       }
       return hipErrorInvalidValue;
-    }, L.spheres);
-  if (L.glass || L.mis || L.textured || (L.table_sampler && L.wide)) return launch_render_x(S, R, L, st);  // the variants: kernels_x.hip
-  // (ray log / phase probe builds wrap the default path's launch: experiments.inc)
-  const bool experiment = kExperimentLaunch && L.counters == kCountNone && !L.wide && !L.table_sampler;
+    }, V.spheres);
+  // (ray log / phase probe builds wrap the plain default path's launch: experiments.inc)
+  const bool experiment = kExperimentLaunch && render_default_path(V);
   hipError_t e = hipSuccess;
   if (experiment && experiment_launch_begin(&e)) return e;
   e = with_bools([&](auto SPH, auto OVF, auto COUNT, auto SND, auto WIDE) {
     constexpr int STACK = OVF ? (int)kQuadLdsStackOvf : 0;
-    if constexpr ((COUNT && (SND || WIDE)) || (SND && WIDE)) {  // (SND && WIDE without counters went to render_kernel_x above)
-      return hipErrorInvalidValue;
-    } else if constexpr (!COUNT && !SND && !WIDE && STACK == 0) {
+    constexpr RenderVariant v = default_variant(SPH, COUNT, false, WIDE, SND);
+    if constexpr (render_default_path(v) && STACK == 0) {  // (the one launch with a choice of STEPS: capi_render.cpp render_launch)
       return go(L.steps == 2 ? render_kernel<SPH, false, false, 0, 2> : render_kernel<SPH, false, false, 0>);
-    } else {
-      // (the host's plan and the instantiation must agree on where path records 0..2 live: the launch's LDS is sized by the plan)
-      if (render_kernel_lds_records(COUNT, false, STACK, WIDE, SND) != (L.plan.record_rows != 0u)) return hipErrorInvalidValue;
+    } else if constexpr (render_family_builds(RenderFamily::kDefault, v)) {
       return go(render_kernel<SPH, COUNT, false, STACK, PBRT_STEPS_PER_CHECK, WIDE, SND>);
     }
-  }, L.spheres, L.plan.overflow, L.counters == kCountWalk, L.table_sampler, L.wide);
+    return hipErrorInvalidValue;
+  }, V.spheres, L.plan.overflow, V.counters == kCountWalk, V.table_sampler, V.wide);
   if (experiment) experiment_launch_end(st);
   return e;
 }

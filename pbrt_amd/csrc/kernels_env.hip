@@ -5,27 +5,22 @@
 //
 //   render_kernel_env   render_body.inc with ENV = true: a ray that escapes collects the map (envmap_core.hpp lookup), the map is a light
 //                       of the one-light direct estimate (Distribution2D sampling, MIS against the cosine-sampled bounce ray).  GLS = true
-//                       always (a glass table that is never read costs nothing, and the instantiations halve); a register budget of
-//                       4 waves per SIMD.
+//                       always (a glass table that is never read costs nothing, and the instantiations halve).
 //   envmap_eval_kernel  envmap_core.hpp over arrays: pbrt_hip_envmap_eval_device, the hook that shows the device computes the host's bits.
 //
-// Combinations that do NOT exist (capi_render.cpp check_render_desc refuses them with PBRT_HIP_ERR_LIMIT): a box filter radius other than
-// 0.5 (WIDE) and the counter flags.
+// Combinations that do NOT exist (render_variant.hpp refuses them with PBRT_HIP_ERR_LIMIT): a box filter radius other than 0.5 (WIDE) and
+// the counter flags.
 #include "kernel_path.hpp"
 #include "with_bools.hpp"
 
 namespace pbrt_hip {
 namespace {
 
-// waves per SIMD the register allocator leaves room for: the body needs 101 .. 109 VGPRs (more than the 96 of 5 waves), which
-// the 128 of 4 waves hold without a spill -- one wave per SIMD more than the GLS instantiations' budget (capi_render.cpp kRenderWavesPerCuEnv)
-#ifndef PBRT_ENV_WAVES_PER_SIMD
-#define PBRT_ENV_WAVES_PER_SIMD 4
-#endif
+// (the register budget: render_variant.hpp)
 template <bool SPH, int STACK, bool MIS, bool TEX, bool SND>
-__global__ void __launch_bounds__(64, PBRT_ENV_WAVES_PER_SIMD) render_kernel_env(const DevScene S, const RenderParams R) {
+__global__ void __launch_bounds__(64, render_waves_per_simd(RenderFamily::kEnv, SPH, true)) render_kernel_env(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false, WIDE = false, GLS = true, ENV = true;
-  constexpr bool NRM = false;  // (shading normals: kernels_n.hip render_kernel_n)
+  constexpr bool NRM = false;   // (shading normals: another family's, render_variant.hpp)
   constexpr bool LREC = false;  // (path records in LDS: the default path alone, kernels.hip render_kernel)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
 #include "render_body.inc"
@@ -54,12 +49,16 @@ __global__ void envmap_eval_kernel(const RenderParams R, int64_t n, const float 
 
 hipError_t launch_render_env(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
   if (R.n_items == 0) return hipSuccess;
-  if (L.wide || L.counters != kCountNone || !R.env_texels) return hipErrorInvalidValue;  // (refused with a message by capi_render.cpp check_render_desc)
+  if (!R.env_texels) return hipErrorInvalidValue;
+  const RenderVariant &V = L.variant;
   return with_bools([&](auto SPH, auto OVF, auto MIS, auto TEX, auto SND) {
     constexpr int STACK = OVF ? (int)kQuadLdsStackOvf : 0;
-    hipLaunchKernelGGL((render_kernel_env<SPH, STACK, MIS, TEX, SND>), dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
-    return hipGetLastError();
-  }, L.spheres, L.plan.overflow, L.mis, L.textured, L.table_sampler);
+    if constexpr (render_family_builds(RenderFamily::kEnv, RenderVariant{SPH, false, SND, MIS, TEX, true, true, false, kCountNone})) {
+      hipLaunchKernelGGL((render_kernel_env<SPH, STACK, MIS, TEX, SND>), dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
+      return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
+  }, V.spheres, L.plan.overflow, V.mis, V.textured, V.table_sampler);
 }
 
 hipError_t launch_envmap_eval(const RenderParams &R, int64_t n, const float *u12, float *d, uint32_t *texel, float *le, float *pdf, hipStream_t stream) {

@@ -6,30 +6,23 @@
 //                               three 16-byte loads) are interpolated like the hit point and take the geometric normal's place where matte
 //                               and mirror scatter.  GLS = true always (as render_kernel_env), ENV a template argument: 64 instantiations,
 //                               so that a smooth mesh renders under every integrator and sampler, with spheres, checkerboards, glass
-//                               elsewhere in the scene and under an environment map.  A register budget of 4 waves per SIMD.
+//                               elsewhere in the scene and under an environment map.
 //   pack_nrm_kernel             the corner normals (triangle order, as uploaded) gathered into leaf-slot order, beside pack_uv_kernel's (u, v).
 //   shading_normal_eval_kernel  shading_normal.inc over arrays: pbrt_hip_shading_normal_eval_device, the hook that lets a test compare
 //                               the statements the render kernel runs with float64, element by element.
 //
-// Combinations that do NOT exist (capi_render.cpp check_render_desc refuses them with PBRT_HIP_ERR_LIMIT): a box filter radius other than
-// 0.5 (WIDE) and the counter flags.
+// Combinations that do NOT exist (render_variant.hpp refuses them with PBRT_HIP_ERR_LIMIT): a box filter radius other than 0.5 (WIDE) and
+// the counter flags.
 #include "kernel_path.hpp"
 #include "with_bools.hpp"
 
 namespace pbrt_hip {
 namespace {
 
-// waves per SIMD the register allocator leaves room for: 4, the 128 VGPRs of render_kernel_env's budget (a granule of 8: 512 / 4).  The
-// body with ENV needs 101 .. 109 VGPRs before the normals; the three corner normals and the interpolated one are live only between the
-// hit's material fetch and the scatter, and the 64 instantiations allocate 98 .. 108 VGPRs, no AGPRs, no spill, no scratch -- more than
-// the 96 of 5 waves, inside the budget below (tests/test_normals_host.py reads the budget from the NRM_VGPR_BUDGET line and holds every
-// instantiation to it; capi_render.cpp kRenderWavesPerCuN is the waves x 4 SIMDs)
-#ifndef PBRT_NRM_WAVES_PER_SIMD
-#define PBRT_NRM_WAVES_PER_SIMD 4
-#endif
-// NRM_VGPR_BUDGET 128  (VGPRs + AGPRs of every render_kernel_n instantiation: what 4 waves per SIMD leave a wave)
+// (the register budget: render_variant.hpp.  The three corner normals and the interpolated one are live only between the hit's material
+// fetch and the scatter; tests/test_normals_host.py holds every instantiation to the budget)
 template <bool SPH, int STACK, bool MIS, bool TEX, bool SND, bool ENV>
-__global__ void __launch_bounds__(64, PBRT_NRM_WAVES_PER_SIMD) render_kernel_n(const DevScene S, const RenderParams R) {
+__global__ void __launch_bounds__(64, render_waves_per_simd(RenderFamily::kN, SPH, true)) render_kernel_n(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false, WIDE = false, GLS = true, NRM = true;
   constexpr bool LREC = false;  // (path records in LDS: the default path alone, kernels.hip render_kernel)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
@@ -65,13 +58,16 @@ __global__ void __launch_bounds__(256) shading_normal_eval_kernel(int64_t n, con
 
 hipError_t launch_render_n(const DevScene &S, const RenderParams &R, const RenderLaunch &L, hipStream_t st) {
   if (R.n_items == 0) return hipSuccess;
-  // (refused with a message by capi_render.cpp check_render_desc; an error here, never another kernel)
-  if (L.wide || L.counters != kCountNone || !R.tri_n || (L.env && !R.env_texels)) return hipErrorInvalidValue;
+  const RenderVariant &V = L.variant;
+  if (!R.tri_n || (V.env && !R.env_texels)) return hipErrorInvalidValue;
   return with_bools([&](auto SPH, auto OVF, auto MIS, auto TEX, auto SND, auto ENV) {
     constexpr int STACK = OVF ? (int)kQuadLdsStackOvf : 0;
-    hipLaunchKernelGGL((render_kernel_n<SPH, STACK, MIS, TEX, SND, ENV>), dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
-    return hipGetLastError();
-  }, L.spheres, L.plan.overflow, L.mis, L.textured, L.table_sampler, L.env);
+    if constexpr (render_family_builds(RenderFamily::kN, RenderVariant{SPH, false, SND, MIS, TEX, true, ENV, true, kCountNone})) {
+      hipLaunchKernelGGL((render_kernel_n<SPH, STACK, MIS, TEX, SND, ENV>), dim3(L.n_workgroups), dim3(64), L.lds_bytes, st, S, R);
+      return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
+  }, V.spheres, L.plan.overflow, V.mis, V.textured, V.table_sampler, V.env);
 }
 
 hipError_t launch_pack_nrm(const float *tri_n, const uint32_t *order, uint32_t n_prims, uint32_t n_tris, float4 *out, hipStream_t stream) {

@@ -1,7 +1,6 @@
-// render_body.inc -- the body of render_kernel (kernels.hip) and of render_kernel_x (kernels_x.hip), included once in each: the two are the same
-// program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV, NRM, LREC in scope (kernels_env.hip
-// includes it a third time, for render_kernel_env, the one kernel with ENV = true, and kernels_n.hip a fourth, for render_kernel_n, the one
-// with NRM = true: interpolated shading normals, DESIGN.md 3.18).  (A shared __device__
+// render_body.inc -- the body of every family of render kernels (render_variant.hpp), included once in each family's kernel unit: they are the
+// same program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV, NRM, LREC in scope -- template
+// arguments where the family has the switch, constants where it does not.  (A shared __device__
 // function would be the tidy way to say this; the text is included instead because wrapping the body in a function -- forceinline or
 // not -- perturbs the register allocation of the production instantiation, whose machine code the committed counter profiles are
 // keyed by: pbrt_amd/isa_id.py; measured in round 5.)  In scope as well: `S` (DevScene) and `R` (RenderParams), the kernel's arguments.

@@ -377,7 +377,9 @@ def test_env_instantiations_hold_their_register_budget():
     names = [isa_id.normalise(d) for d in isa_id._demangle(syms)]
     env = [(n, s) for n, s in zip(names, syms) if re.fullmatch(r"render_kernel_env<(true|false),\d+,(true|false),(true|false),(true|false)>", n)]
     assert len(env) == 32, len(env)  # SPH x STACK x MIS x TEX x SND
-    budget = 512 // 4  # 4 waves per SIMD (kernels_env.hip PBRT_ENV_WAVES_PER_SIMD): 128 VGPRs, a whole number of granules
+    import render_variant_table
+    budget = 512 // render_variant_table.waves_per_simd("env")  # (render_variant.hpp)
+    assert budget == 128  # 4 waves per SIMD: a whole number of granules
     for stack in ("0", "30"):
         assert [n for n, _ in env if n.split(",")[1] == stack], stack
     for n, s in env:

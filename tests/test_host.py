@@ -114,7 +114,7 @@ def test_every_kernel_is_defined_in_one_code_object():
     from pbrt_amd import isa_id
     counts = isa_id.kernel_definition_counts(_lib.LIB_PATH)
     assert set(counts) == set(isa_id.kernel_ids_by_symbol(_lib.LIB_PATH)) and len(counts) >= 100
-    for family in ("render_kernelI", "render_kernel_xI", "render_kernel_envI", "intersect_kernelI", "merge_kernel", "pack_tris_kernel"):
+    for family in ("render_kernelI", "render_kernel_xI", "render_kernel_envI", "render_kernel_nI", "intersect_kernelI", "merge_kernel", "pack_tris_kernel"):
         assert any(family in n for n in counts), family
     assert {n: c for n, c in counts.items() if c != 1} == {}
 

@@ -102,7 +102,7 @@ def deepest_stacks(oracle, sd, quads, order, monkeypatch):
 def test_film_and_walk_counters(gpu, oracle):
     """20 000 random triangles on the host builder's tree (stack bound 29: the overflow variant), 64 x 64 at 2 x 2 spp, depth 8, stratified:
     the film -- rendered by the instantiation with the records in LDS -- is the oracle's.  The walk counters come from the COUNTING
-    instantiation, which keeps its records in HBM and its 30 rows (kernels.hip render_kernel_lds_records): comparing them with the totals
+    instantiation, which keeps its records in HBM and its 30 rows (render_variant.hpp render_default_path): comparing them with the totals
     recorded before the records moved (tests/golden/) checks that the counting kernel and the tree were left alone, not the new path -- the
     film assertion is what covers that here."""
     sd = scenes.random_mesh_scene(20_000, 64, 64)

@@ -344,11 +344,11 @@ def test_icosphere_scene():
 
 def test_nrm_instantiations_hold_their_register_budget():
     """render_kernel_n exists for both stack variants, with and without spheres, MIS, textures, the table samplers and an environment
-    map -- 64 kernels in a translation unit of their own --, spills nothing, uses no scratch, and fits the budget kernels_n.hip states."""
-    src = open(os.path.join(ROOT, "pbrt_amd", "csrc", "kernels_n.hip")).read()
-    budget = int(re.search(r"NRM_VGPR_BUDGET (\d+)", src).group(1))
-    waves = int(re.search(r"#define PBRT_NRM_WAVES_PER_SIMD (\d+)", src).group(1))
-    assert budget == 512 // waves and budget % 8 == 0  # 512 VGPRs per SIMD lane on gfx950, handed out in granules of 8
+    map -- 64 kernels in a translation unit of their own --, spills nothing, uses no scratch, and fits the budget render_variant.hpp states."""
+    import render_variant_table
+    waves = render_variant_table.waves_per_simd("n")
+    budget = 512 // waves
+    assert budget == 128 and budget % 8 == 0  # 512 VGPRs per SIMD lane on gfx950, handed out in granules of 8: what 4 waves per SIMD leave a wave
     syms = sorted(isa_id.kernel_ids_by_symbol(_lib.LIB_PATH))
     names = [isa_id.normalise(d) for d in isa_id._demangle(syms)]
     nrm = [(n, s) for n, s in zip(names, syms) if re.fullmatch(r"render_kernel_n<(true|false),\d+(,(true|false)){4}>", n)]

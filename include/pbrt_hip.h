@@ -69,7 +69,7 @@ typedef struct {
  * (s, t) = (su u + du, sv v + dv); tex1 where floor(s) + floor(t) is even, tex2 where odd.  64 bytes. */
 typedef struct {
   uint32_t type;  /* 0 = checkerboard, dimension 2, "uv" mapping; 1 = this slot is the environment-map record below; 2 = the shading
-                     normals' record, pbrt_hip_normals */
+                     normals' record, pbrt_hip_normals; 3 = the pixel filter's record, pbrt_hip_pixel_filter */
   float tex1[3], tex2[3];
   float su, sv, du, dv; /* "float uscale" / "vscale" / "udelta" / "vdelta" */
   uint32_t pad[5];
@@ -118,6 +118,35 @@ typedef struct {
                            normal = "none"; copied during the call */
   uint32_t pad[10];
 } pbrt_hip_normals;
+
+/* PixelFilter "triangle" / "gaussian" / "mitchell" / "sinc" (pbrt-v3's TriangleFilter, GaussianFilter, MitchellFilter,
+ * LanczosSincFilter and FilmTile::AddSample; the reference builds Film's 16 x 16 filter table, film.rs:113-123, and has nothing that
+ * uses it).  A slot of `textures` whose first word is 3 IS this record -- 64 bytes, read with memcpy like the environment map's.  The box
+ * is not a kind: a scene without the record is filtered as before.  With the record, pbrt_hip_render_desc.filter_xwidth / ywidth stay the
+ * radii rx, ry (0 = the kind's default: 2 x 2 for kinds 1 .. 3, 4 x 4 for kind 4), and a sample at film point p adds w x L to every pixel
+ * (x, y) of the cropped window with |x + 0.5 - p.x| <= rx, |y + 0.5 - p.y| <= ry -- the box's footprint --, w from the 16 x 16 table of
+ * pbrt_hip_filter_table.  The film is the fixed-point film of every wide filter (pbrt_hip_render_acc below) at EVERY radius, 0.5
+ * included; its fourth accumulator is the sum of the weights in units of 2^-24, not a sample count.
+ *   kind 1 triangle   max(0, rx - |x|) max(0, ry - |y|)
+ *   kind 2 gaussian   g(x, rx) g(y, ry), g(d, r) = max(0, exp(-alpha d^2) - exp(-alpha r^2)); param[0] = alpha (pbrt-v3's default: 2)
+ *   kind 3 mitchell   M(x / rx) M(y / ry), M of pbrt-v3's Mitchell1D; param[0] = B, param[1] = C (1/3 each)
+ *   kind 4 sinc       W(x, rx) W(y, ry), W(x, r) = 0 beyond r, else sinc(|x|) sinc(|x| / tau), sinc(x) = 1 below 1e-5, else
+ *                     sin(pi x) / (pi x); param[0] = tau (3)
+ * Refused at scene creation before any device work (the message holds "filter"): more than one such slot (PBRT_HIP_ERR_LIMIT); an unknown
+ * kind, a parameter that is not finite, alpha <= 0 or tau <= 0, a matte kd_tex that names the slot (PBRT_HIP_ERR_INVALID).  A render is a
+ * wide-filter render: not with an environment map, shading normals or the counter flags, and refused with PBRT_HIP_ERR_LIMIT when spp x
+ * footprint x ceil(largest |table entry|) passes 2^24 (the accumulators could wrap). */
+#define PBRT_HIP_TEXTURE_FILTER 3u
+#define PBRT_HIP_FILTER_TRIANGLE 1u
+#define PBRT_HIP_FILTER_GAUSSIAN 2u
+#define PBRT_HIP_FILTER_MITCHELL 3u
+#define PBRT_HIP_FILTER_SINC 4u
+typedef struct {
+  uint32_t type;  /* = 3 */
+  uint32_t kind;  /* PBRT_HIP_FILTER_*: 1 .. 4 */
+  float param[2]; /* gaussian: alpha; mitchell: B, C; sinc: tau; the others 0 */
+  uint32_t pad[12];
+} pbrt_hip_pixel_filter;
 
 /* LightSource "point" / "distant" / "infinite" (api.rs:334-351 make_light: todo!() for all).
  * Type 3 is the infinite light with an environment map: c = the factor on the texels (L x scale, infinite.rs:54), `pad`
@@ -197,8 +226,9 @@ typedef struct {
   uint32_t rank, world_size; /* this process renders the 64x64 super-tiles t with t % world_size == rank */
   uint32_t flags;
   uint32_t sampler;          /* PBRT_HIP_SAMPLER_* */
-  float filter_xwidth, filter_ywidth; /* PixelFilter "box" "float xwidth" / "ywidth" (box.rs:57-61): the filter's radii in
-                                         pixels.  0 = the default 0.5 (a sample lands in its own pixel, film.rs:264-273 needs
+  float filter_xwidth, filter_ywidth; /* PixelFilter "float xwidth" / "ywidth" (box.rs:57-61): the filter's radii in pixels -- the box's,
+                                         or those of the scene's pbrt_hip_pixel_filter record -- then 0 = that kind's default, and the film is
+                                         the fixed-point one at every radius.  The box: 0 = the default 0.5 (a sample lands in its own pixel, film.rs:264-273 needs
                                          no tile overlap).  Any other radius in (0, 16]: every sample inside the sample bounds
                                          (film.rs:166-175) adds, weight 1, to all pixels within the radius; the film is then
                                          accumulated in 64-bit fixed point -- see pbrt_hip_render_acc below */
@@ -218,9 +248,10 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.8 (gfx950; struct sizes of 0.6, as 0.7)": 0.8 = texture-table slot type 2, the shading normals,
-                                       inside the same struct sizes ("as 0.7": a test of the environment map looks for "0.7" the way the
-                                       glass test looks for "0.6"); 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.9 (gfx950; struct sizes of 0.6, as 0.7 and 0.8)": 0.9 = texture-table slot type 3, the pixel
+                                       filter, inside the same struct sizes; 0.8 = texture-table slot type 2, the shading normals,
+                                       likewise ("as 0.7 and 0.8": tests of the environment map and of the normals look for "0.7" and "0.8"
+                                       the way the glass test looks for "0.6"); 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
                                        end, pbrt_hip_material.pad became kd_tex, flags 0 of scene_create_ex = the device builder); 0.6 =
                                        material type 2, glass, inside the same struct sizes; 0.7 = light type 3 and texture-table
                                        slot type 1, the environment map, again inside the same struct sizes.  The "(... struct sizes of 0.6)"
@@ -309,6 +340,14 @@ int64_t pbrt_hip_render_buffer_bytes(const pbrt_hip_scene *scene, const pbrt_hip
 int pbrt_hip_render_acc(pbrt_hip_scene *scene, const pbrt_hip_render_desc *desc, int64_t *acc, pbrt_hip_stats *stats);
 int pbrt_hip_film_from_acc_device(const pbrt_hip_scene *scene, const void *d_acc, void *d_film_xyzw, void *stream);
 void pbrt_hip_film_from_acc(const int64_t *acc, int64_t n_pixels, float *film_xyzw);
+/* ---- weighted pixel filters (pbrt_hip_pixel_filter) ----
+ *  - pbrt_hip_filter_table: host, no device.  The 16 x 16 table of Film::new (film.rs:113-123): out[iy * 16 + ix] = the filter at
+ *    ((ix + 0.5) rx / 16, (iy + 0.5) ry / 16), evaluated in double and rounded to float once (rx, ry: the radii themselves, not 0).
+ *    PBRT_HIP_ERR_INVALID for a record pbrt_hip_scene_create would refuse or radii that are not positive and finite;
+ *  - pbrt_hip_film_from_acc_weighted: pbrt_hip_film_from_acc for the accumulators of a weighted filter -- the fourth channel is the weight
+ *    sum in 2^-24 units and is scaled like the other three.  pbrt_hip_film_from_acc_device knows its scene and converts accordingly. */
+int pbrt_hip_filter_table(const pbrt_hip_pixel_filter *filter, float rx, float ry, float out[256]);
+void pbrt_hip_film_from_acc_weighted(const int64_t *acc, int64_t n_pixels, float *film_xyzw);
 /* host-side geometry of the sharding (no device needed) */
 int64_t pbrt_hip_slab_floats(int32_t xres, int32_t yres, const float crop[4], uint32_t rank, uint32_t world_size);
 /* for every float4 slot of a rank's slab the row-major pixel index inside the cropped film, or -1 */

@@ -136,6 +136,17 @@ int pbrt_hip_blocks_eval_device(int device, uint32_t op, int64_t n, const float 
  * n or a null array. */
 int pbrt_hip_shading_normal_eval_device(int device, int64_t n, const float *in, float *out);
 
+/* ---- weighted pixel filters (pbrt_amd/csrc/filter_weight.inc is the one statement of the arithmetic) ---- */
+/* The footprint and table-index statements of the render kernels' weighted finish over arrays on `device` (two tiny kernels of
+ * kernels_blocks.hip that call the same functions), for radii rx, ry and the cropped window crop = {x0, y0, x1, y1}:
+ *   n_points film points (2 floats each) -> bounds, 4 ints each: x0, y0, x1, y1 of the footprint clipped to the window (x1, y1 exclusive);
+ *   n_pairs (film point, pixel) pairs (2 floats, 2 ints each) -> index: iy * 16 + ix into the filter table, or -1 for a pixel outside the point's
+ *   clipped footprint.
+ * in / out are HOST arrays; either half may be empty (n = 0).  PBRT_HIP_ERR_INVALID for a negative n, a null array or radii that are
+ * not positive and finite. */
+int pbrt_hip_filter_footprint_eval_device(int device, float rx, float ry, const int32_t crop[4], int64_t n_points, const float *points,
+                                          int32_t *bounds, int64_t n_pairs, const float *pair_points, const int32_t *pair_pixels, int32_t *index);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

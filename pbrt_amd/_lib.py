@@ -27,6 +27,11 @@ class Normals(C.Structure):
                 ("pad", C.c_uint32 * 10)]
 
 
+class PixelFilter(C.Structure):
+    """pbrt_hip_pixel_filter: what a slot of the texture table IS when its first word is 3; 64 bytes like Texture"""
+    _fields_ = [("type", C.c_uint32), ("kind", C.c_uint32), ("param", C.c_float * 2), ("pad", C.c_uint32 * 12)]
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_uint32), ("p", C.c_float * 3), ("c", C.c_float * 3), ("pad", C.c_float)]
 
@@ -97,6 +102,9 @@ SYMBOLS = {
     "pbrt_hip_render_acc": (C.c_int, [_vp, C.POINTER(RenderDesc), _pi64, C.POINTER(Stats)]),
     "pbrt_hip_film_from_acc_device": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pbrt_hip_film_from_acc": (None, [_pi64, _i64, _pf]),
+    "pbrt_hip_film_from_acc_weighted": (None, [_pi64, _i64, _pf]),
+    "pbrt_hip_filter_table": (C.c_int, [C.POINTER(PixelFilter), _f, _f, _pf]),
+    "pbrt_hip_filter_footprint_eval_device": (C.c_int, [C.c_int, _f, _f, _pi32, _i64, _pf, _pi32, _i64, _pf, _pi32, _pi32]),
     "pbrt_hip_sobol_matrices": (None, [_pu32]),
     "pbrt_hip_slab_floats": (_i64, [_i32, _i32, _pf, _u32, _u32]),
     "pbrt_hip_slab_pixel_index": (C.c_int, [_i32, _i32, _pf, _u32, _u32, _pi64]),

@@ -9,12 +9,15 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import EnvMap, Light, Material, Normals, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
+from ._lib import EnvMap, Light, Material, Normals, PixelFilter, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
 
 MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
 LIGHT_ENVMAP = 3  # PBRT_HIP_LIGHT_ENVMAP: the infinite light with an environment map
 INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_PATH_MIS = 0, 1, 2  # 2: the path integrator with MIS
+FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_SINC = 1, 2, 3, 4  # PBRT_HIP_FILTER_*: the weighted pixel filters
+FILTER_KINDS = {"triangle": FILTER_TRIANGLE, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL, "sinc": FILTER_SINC}
+FILTER_DEFAULT_PARAMS = {FILTER_TRIANGLE: (0.0, 0.0), FILTER_GAUSSIAN: (2.0, 0.0), FILTER_MITCHELL: (1.0 / 3.0, 1.0 / 3.0), FILTER_SINC: (3.0, 0.0)}  # pbrt-v3's
 FLAG_COUNTERS = 1
 FLAG_WALK_COUNTERS = 2
 SCENE_GPU_BUILD = 1  # pbrt_hip_scene_create_ex flags
@@ -44,7 +47,10 @@ class SceneData:
     (LIGHT_ENVMAP, 0, 0, 0, c rgb) -- c the factor on the texels -- and `envmap` = its (H, W, 3) texels, row 0 = the light's +z, with
     `envmap_world_to_light` = the 3 x 3 rotation; the record travels in a slot appended to the texture table (fill_desc).  Shading normals
     (DESIGN.md 3.18): `tri_n` rows: the normals of a triangle's three corners (n0 xyz, n1 xyz, n2 xyz), world space, any length, zeros = the
-    triangle has none; empty = the scene has none.  Its record travels in a slot of its own behind the checkerboards and the map."""
+    triangle has none; empty = the scene has none.  Its record travels in a slot of its own behind the checkerboards and the map.  A weighted
+    pixel filter: `pixel_filter` = None (the box) or (kind, param0, param1) -- kind a name or number of FILTER_KINDS, the
+    parameters alpha / B, C / tau (omitted ones: pbrt-v3's defaults); its record travels in a slot of its own too, and a render's
+    filter_width is then that filter's radii (0 = the kind's default)."""
     P: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
     idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.uint32))
     mat_id: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint16))
@@ -63,8 +69,11 @@ class SceneData:
     envmap: np.ndarray = field(default_factory=lambda: np.zeros((0, 0, 3), np.float32))
     envmap_world_to_light: np.ndarray = field(default_factory=lambda: np.eye(3, dtype=np.float32))
     tri_n: np.ndarray = field(default_factory=lambda: np.zeros((0, 9), np.float32))
+    pixel_filter: tuple = None
 
     def normalized(self):
+        if self.pixel_filter is not None:
+            self.pixel_filter = pixel_filter_tuple(self.pixel_filter)
         self.P = np.ascontiguousarray(self.P, np.float32).reshape(-1, 3)
         self.idx = np.ascontiguousarray(self.idx, np.uint32).reshape(-1, 3)
         self.mat_id = np.ascontiguousarray(self.mat_id, np.uint16).reshape(-1)
@@ -110,9 +119,10 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
     texs = None
     has_env = sd.envmap.size > 0  # the map's record takes a slot of its own behind the checkerboards (include/pbrt_hip.h pbrt_hip_envmap)
     has_nrm = sd.tri_n.shape[0] > 0  # the normals' record: the last slot (include/pbrt_hip.h pbrt_hip_normals)
-    if len(sd.textures) or has_env or has_nrm:
+    has_flt = sd.pixel_filter is not None  # the pixel filter's record: behind the map's (include/pbrt_hip.h pbrt_hip_pixel_filter)
+    if len(sd.textures) or has_env or has_nrm or has_flt:
         tex_t = tex_t or dict(desc._fields_)["textures"]._type_  # (the Texture class of the caller's own struct mirror)
-        texs = (tex_t * (len(sd.textures) + int(has_env) + int(has_nrm)))()
+        texs = (tex_t * (len(sd.textures) + int(has_env) + int(has_flt) + int(has_nrm)))()
         for i, t in enumerate(sd.textures):
             texs[i].type = int(t[0])
             texs[i].tex1[:] = [float(x) for x in t[1:4]]
@@ -123,12 +133,16 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
             e.world_to_light[:] = [float(x) for x in sd.envmap_world_to_light.reshape(-1)]
             assert C.sizeof(e) == C.sizeof(tex_t)
             C.memmove(C.byref(texs, len(sd.textures) * C.sizeof(tex_t)), C.byref(e), C.sizeof(e))
+        if has_flt:
+            pf = pixel_filter_record(sd.pixel_filter)
+            assert C.sizeof(pf) == C.sizeof(tex_t)
+            C.memmove(C.byref(texs, (len(sd.textures) + int(has_env)) * C.sizeof(tex_t)), C.byref(pf), C.sizeof(pf))
         if has_nrm:
             nr = Normals(type=2, n_tris=sd.tri_n.shape[0], tri_n=_fp(sd.tri_n))
             assert C.sizeof(nr) == C.sizeof(tex_t)
-            C.memmove(C.byref(texs, (len(sd.textures) + int(has_env)) * C.sizeof(tex_t)), C.byref(nr), C.sizeof(nr))
+            C.memmove(C.byref(texs, (len(sd.textures) + int(has_env) + int(has_flt)) * C.sizeof(tex_t)), C.byref(nr), C.sizeof(nr))
         desc.textures = texs
-    desc.n_textures = len(sd.textures) + int(has_env) + int(has_nrm)
+    desc.n_textures = len(sd.textures) + int(has_env) + int(has_flt) + int(has_nrm)
     if sd.tri_uv.shape[0]:
         desc.tri_uv = _fp(sd.tri_uv)
     lights = (light_t * max(len(sd.lights), 1))()
@@ -290,12 +304,62 @@ def quad_build_host_ex(P, idx, tree="default", split_leaves=True):
             "exact_boxes": exact[:nq.value].copy()}
 
 
-def film_from_acc(acc):
-    """pbrt_hip_film_from_acc: (..., 4) int64 accumulators -> (..., 4) float32 film pixels {X, Y, Z, weight}."""
+def film_from_acc(acc, weighted=False):
+    """pbrt_hip_film_from_acc: (..., 4) int64 accumulators -> (..., 4) float32 film pixels {X, Y, Z, weight}.  weighted: the accumulators
+    of a weighted pixel filter, whose fourth is the weight sum in 2^-24 units (pbrt_hip_film_from_acc_weighted)."""
     a = np.ascontiguousarray(acc, np.int64)
     film = np.zeros(a.shape[:-1] + (4,), np.float32)
-    lib().pbrt_hip_film_from_acc(a.ctypes.data_as(C.POINTER(C.c_int64)), a.size // 4, _fp(film))
+    call = lib().pbrt_hip_film_from_acc_weighted if weighted else lib().pbrt_hip_film_from_acc
+    call(a.ctypes.data_as(C.POINTER(C.c_int64)), a.size // 4, _fp(film))
     return film
+
+
+def pixel_filter_tuple(pixel_filter):
+    """(kind number, param0, param1) of a SceneData.pixel_filter: a kind's name or number, or (kind, param0[, param1]); parameters left out
+    are pbrt-v3's defaults"""
+    pf = (pixel_filter,) if isinstance(pixel_filter, (str, int)) else tuple(pixel_filter)
+    kind = FILTER_KINDS[pf[0]] if isinstance(pf[0], str) else int(pf[0])
+    dflt = FILTER_DEFAULT_PARAMS.get(kind, (0.0, 0.0))
+    return (kind,) + tuple(float(pf[1 + k]) if len(pf) > 1 + k else dflt[k] for k in range(2))
+
+
+def pixel_filter_record(pixel_filter):
+    """the pbrt_hip_pixel_filter of a SceneData.pixel_filter (a kind's name or number, or (kind, param0, param1))"""
+    kind, p0, p1 = pixel_filter_tuple(pixel_filter)
+    rec = PixelFilter(type=3, kind=kind)
+    rec.param[:] = [p0, p1]
+    return rec
+
+
+def filter_table(pixel_filter, radius=(0.0, 0.0)):
+    """pbrt_hip_filter_table (host only): the (16, 16) float32 table of weights of a pixel filter -- [iy, ix] = the filter at ((ix + 0.5) rx /
+    16, (iy + 0.5) ry / 16), evaluated in double and rounded once -- for radii `radius` (0 = the kind's default: 2, the sinc 4), DESIGN.md 3.19"""
+    rec = pixel_filter_record(pixel_filter)
+    rx, ry = (float(r) if float(r) != 0.0 else filter_default_radius(rec.kind) for r in radius)
+    out = np.zeros((16, 16), np.float32)
+    check(lib().pbrt_hip_filter_table(C.byref(rec), rx, ry, _fp(out)), "pbrt_hip_filter_table")
+    return out
+
+
+def filter_default_radius(kind):
+    """pbrt-v3's default radius of a weighted filter (both axes): 2, the sinc's 4"""
+    kind = FILTER_KINDS[kind] if isinstance(kind, str) else int(kind)
+    return 4.0 if kind == FILTER_SINC else 2.0
+
+
+def filter_footprint_eval(radius, crop_bounds, points=None, pair_points=None, pair_pixels=None, device=0):
+    """pbrt_hip_filter_footprint_eval_device: csrc/filter_weight.inc over arrays on the device, for radii `radius` and the cropped window
+    crop_bounds = (x0, y0, x1, y1).  points (n, 2) float32 -> bounds (n, 4) int32 {x0, y0, x1, y1} of the clipped footprints; pair_points (m,
+    2) float32 with pair_pixels (m, 2) int32 -> index (m,) int32 into the filter table, -1 outside the footprint.  -> (bounds, index)"""
+    pts = np.ascontiguousarray(np.zeros((0, 2)) if points is None else points, np.float32).reshape(-1, 2)
+    pp = np.ascontiguousarray(np.zeros((0, 2)) if pair_points is None else pair_points, np.float32).reshape(-1, 2)
+    px = np.ascontiguousarray(np.zeros((0, 2)) if pair_pixels is None else pair_pixels, np.int32).reshape(-1, 2)
+    assert len(pp) == len(px)
+    bounds, index = np.zeros((len(pts), 4), np.int32), np.zeros(len(pp), np.int32)
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    check(lib().pbrt_hip_filter_footprint_eval_device(int(device), float(radius[0]), float(radius[1]), (C.c_int32 * 4)(*[int(v) for v in crop_bounds]), len(pts),
+                                                      _fp(pts), i32(bounds), len(pp), _fp(pp), i32(px), i32(index)), "pbrt_hip_filter_footprint_eval_device")
+    return bounds, index
 
 
 def envmap_tables(rgb):
@@ -531,7 +595,8 @@ class Scene:
 
     def render_acc(self, filter_width, **kw):
         """A box filter radius other than 0.5: this rank's fixed-point film accumulators (h, w, 4) int64 {r, g, b, samples}
-        (pbrt_hip_render_acc); accumulators of ranks add exactly, film_from_acc converts.  kw as render."""
+        (pbrt_hip_render_acc); accumulators of ranks add exactly, film_from_acc converts.  A scene with a pixel_filter: at every radius, the
+        fourth accumulator the weight sum in 2^-24 units (film_from_acc(acc, weighted=True)).  kw as render."""
         r = make_render_desc(RenderDesc, filter_width=filter_width, **kw)
         w, h = self.sd.crop_size()
         acc = np.zeros((h, w, 4), np.int64)

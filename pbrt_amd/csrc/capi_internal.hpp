@@ -96,6 +96,10 @@ struct SceneTraits {
   uint32_t env_w = 0, env_h = 0;
   float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
   bool normals = false;  // the texture table held a pbrt_hip_normals record: render_kernel_n renders the scene
+  // the texture table held a pbrt_hip_pixel_filter record: every render of the scene is a wide one.  The record itself, as
+  // the one slot of a table: the scene's own description points at it (bind_scene_filter), which is how film_geom learns of the filter
+  bool has_filter = false;
+  pbrt_hip_texture filter_slot{};
   BuildStats build;
 };
 }  // namespace pbrt_hip
@@ -122,6 +126,11 @@ struct pbrt_hip_scene : pbrt_hip::SceneStream, pbrt_hip::SceneArrays, pbrt_hip::
   pbrt_hip::DevBuf<unsigned long long> d_counters;  // 80: see open()
   pbrt_hip::DevBuf<uint32_t> d_sobol;  // generator matrices of sampler 2 (uploaded at its first use)
   pbrt_hip::DevBuf<uint32_t> d_halton; // per-dimension table of sampler 3 (likewise)
+  // a weighted pixel filter: the 256 weights of the radii of the last render (made on the host at a render with other
+  // radii: pixel_filter.hpp filter_table)
+  pbrt_hip::DevBuf<float> d_filter_table;
+  float filter_table_host[pbrt_hip::kFilterTableFloats] = {};  // (device_types.h: the weights, then 1 / rx and 1 / ry)
+  float filter_table_rx = 0.f, filter_table_ry = 0.f;  // (0: no table yet)
   bool pending = false;
   bool pending_counters = false;
   uint64_t pending_samples = 0;
@@ -142,6 +151,9 @@ namespace pbrt_hip {
 int ensure_canonical(pbrt_hip_scene *s);
 // the array pointers of s->dev from the scene's buffers: the one place that sets them (scene creation, ensure_canonical, clone_scene)
 void bind_scene_arrays(pbrt_hip_scene *s);
+// s->desc's texture table: the scene's own filter slot (SceneTraits::filter_slot) or nothing -- the caller's table is not kept (scene
+// creation, clone_scene)
+void bind_scene_filter(pbrt_hip_scene *s);
 
 // ---- film geometry (capi_render.cpp) ----
 // Film geometry of one render: the cropped window (film.rs:92-101), the sample bounds (film.rs:166-175) and whether the
@@ -156,6 +168,7 @@ struct FilmGeom {
   int32_t crop_h() const { return crop[3] > crop[1] ? crop[3] - crop[1] : 0; }
   size_t crop_px() const { return (size_t)crop_w() * (size_t)crop_h(); }
 };
-// (a filter width of 0 is the default radius 0.5, as in pbrt_hip_render_desc)
+// (a filter width of 0 is the default radius 0.5, as in pbrt_hip_render_desc; a description whose texture table holds a pixel filter's
+// record, DESIGN.md 3.19: 0 is that kind's default radius and the geometry is the wide one at every radius)
 FilmGeom film_geom(const pbrt_hip_scene_desc &d, float filter_xwidth = 0.f, float filter_ywidth = 0.f);
 }  // namespace pbrt_hip

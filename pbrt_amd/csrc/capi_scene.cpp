@@ -20,6 +20,7 @@
 #include "device_types.h"
 #include "envmap.hpp"
 #include "host_math.hpp"
+#include "pixel_filter.hpp"
 #include "quad_nodes.hpp"
 
 using namespace pbrt_hip;
@@ -175,9 +176,19 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
   for (uint32_t i = 0; i < d->n_mats; i++)
     if (kd_textured(d->mats[i]) && is_normals_slot(d->textures, d->mats[i].kd_tex - 1u))
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names the shading normals' record, which is not a texture for Kd");
-  uint32_t n_normals = 0;
+  for (uint32_t i = 0; i < d->n_mats; i++)
+    if (kd_textured(d->mats[i]) && is_filter_slot(d->textures, d->mats[i].kd_tex - 1u))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names the pixel filter's record, which is not a texture for Kd");
+  uint32_t n_normals = 0, n_filters = 0;
   for (uint32_t i = 0; i < d->n_textures; i++) {
     const pbrt_hip_texture &tx = d->textures[i];
+    if (is_filter_slot(d->textures, i)) {  // the pixel filter's record
+      const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": ";
+      if (++n_filters > 1u) return fail(PBRT_HIP_ERR_LIMIT, what + "more than one pixel filter record (type 3)");
+      const int rc = filter_check(filter_slot(d->textures, i), what);
+      if (rc) return rc;
+      continue;
+    }
     if (is_normals_slot(d->textures, i)) {  // the shading normals' record
       const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": shading normals: ";
       if (++n_normals > 1u) return fail(PBRT_HIP_ERR_LIMIT, what + "more than one normals record (type 2)");
@@ -344,7 +355,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
     in->textures.resize(3 * (size_t)d.n_textures);
     for (uint32_t i = 0; i < d.n_textures; i++) {
       const pbrt_hip_texture &tx = d.textures[i];
-      if (is_envmap_slot(d.textures, i) || is_normals_slot(d.textures, i)) continue;  // (an environment map's / the normals' slot: no material names it, its records stay zero)
+      if (is_envmap_slot(d.textures, i) || is_normals_slot(d.textures, i) || is_filter_slot(d.textures, i)) continue;  // (an environment map's / the normals' / the filter's slot: no material names it, its records stay zero)
       in->textures[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
       in->textures[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
       in->textures[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
@@ -459,6 +470,11 @@ void bind_scene_arrays(pbrt_hip_scene *s) {
   D.spheres = s->d_spheres.p;
 }
 
+void bind_scene_filter(pbrt_hip_scene *s) {
+  s->desc.textures = s->has_filter ? &s->filter_slot : nullptr;
+  s->desc.n_textures = s->has_filter ? 1u : 0u;
+}
+
 // The counter flags (PBRT_HIP_FLAG_COUNTERS, counters of pbrt_hip_intersect) count the CANONICAL walk: the oracle's binary
 // tree of DESIGN.md 3.3.  A host-built scene has it; a device-built one gets it here on first use -- vertex / index buffers
 // read back from the device, the host builder (one core, about a second for 1M triangles: a measurement aid, off the
@@ -507,7 +523,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.8 (gfx950; struct sizes of 0.6, as 0.7)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.9 (gfx950; struct sizes of 0.6, as 0.7 and 0.8)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif
@@ -586,7 +602,10 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
     s->desc = *d;
     s->desc.P = nullptr; s->desc.idx = nullptr; s->desc.mat_id = nullptr;
     s->desc.mats = nullptr; s->desc.lights = nullptr; s->desc.spheres = nullptr;
-    s->desc.tri_uv = nullptr; s->desc.textures = nullptr;
+    s->desc.tri_uv = nullptr;
+    pbrt_hip_pixel_filter pf;
+    if ((s->has_filter = find_filter(*d, &pf))) std::memcpy(&s->filter_slot, &pf, sizeof pf);
+    bind_scene_filter(s.get());
     gather_inputs(*d, &in);
     s->n_prims = in.n_prims;
     s->textured = in.textured_tris || in.textured_sph;

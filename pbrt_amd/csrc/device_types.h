@@ -220,7 +220,14 @@ struct RenderParams {
   // shading normals (render_kernel_n): the corner normals of every leaf slot, 3 x float4 {n, 0}, world space, any length
   // (zeros = the triangle has none; a sphere's proxy slot: zeros), read at a shaded triangle hit alone.  At the end, for the reason given above.
   const float4 *tri_n;
+  // a weighted pixel filter (the `if (R.filter_table)` of render_body.inc's WIDE finish): the 16 x 16 table of weights made on
+  // the host (null: the box) with 1 / filter_rx and 1 / filter_ry behind its 256 weights (kFilterTableInvRx, kFilterTableInvRy).  (One
+  // pointer is all the filter adds to the kernel's arguments: every scalar more is a register held through the kernel, and the WIDE
+  // instantiations have none to spare.)  At the end, for the reason given above.
+  const float *filter_table;
 };
+// the device copy of a filter table: the 256 weights, then 1 / rx and 1 / ry
+constexpr uint32_t kFilterTableInvRx = 256u, kFilterTableInvRy = 257u, kFilterTableFloats = 260u;
 // 2^24 fixed-point units per unit of radiance, a component clamped to [0, 2^15]
 constexpr float kFixedOne = 16777216.0f, kFixedMax = 32768.0f;
 
@@ -269,7 +276,11 @@ hipError_t launch_render_n(const DevScene &S, const RenderParams &R, const Rende
 hipError_t launch_pack_nrm(const float *tri_n, const uint32_t *order, uint32_t n_prims, uint32_t n_tris, float4 *out, hipStream_t stream);
 hipError_t launch_shading_normal_eval(int64_t n, const float *in, float *out, hipStream_t stream);
 // fixed-point accumulators -> film pixels {X, Y, Z, weight}
-hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, size_t n_px, hipStream_t stream);
+// (weighted: the accumulators of a weighted pixel filter, whose fourth is the weight sum in 2^-24 units: DESIGN.md 3.19)
+hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, size_t n_px, bool weighted, hipStream_t stream);
+// kernels_blocks.hip: filter_weight.inc over device arrays (pbrt_hip_filter_footprint_eval_device)
+hipError_t launch_filter_footprint_eval(float rx, float ry, const int32_t crop[4], int64_t n_points, const float *points, int32_t *bounds, int64_t n_pairs,
+                                        const float *pair_points, const int32_t *pair_pixels, int32_t *index, hipStream_t stream);
 hipError_t launch_acc_add(unsigned long long *dst, const unsigned long long *src, size_t n, hipStream_t stream);  // dst[i] += src[i]
 hipError_t launch_intersect(const DevScene &S, const RayBatch &B, bool any_hit, uint32_t bvh_depth, hipStream_t stream);
 // (n_prims = n_tris + the spheres, whose records come from the `spheres` table: kernels.hip pack_tris_kernel)

@@ -1,5 +1,5 @@
 // kernel_path.hpp -- what render_body.inc is built from beside the walk: the one-light direct estimate and the environment map's
-// light, the path state and its HBM records, the samplers, and the wide filter's film_add.
+// light, the path state and its HBM records, the samplers, and the wide filters' film_add and film_add_sample.
 #pragma once
 #include "envmap_core.hpp"
 #include "kernel_walk.hpp"
@@ -314,6 +314,36 @@ __device__ __forceinline__ void film_add(unsigned long long *acc, const DevScene
       unsigned long long *a = acc + 4u * ((size_t)(py - S.cy0) * (size_t)(S.cx1 - S.cx0) + (size_t)(px - S.cx0));
       atomicAdd(a, r); atomicAdd(a + 1, g); atomicAdd(a + 2, b); atomicAdd(a + 3, (unsigned long long)n);
     }
+}
+
+
+// ---- weighted pixel filters: the footprint and the table index are filter_weight.inc's ----
+#include "filter_weight.inc"
+// FilmTile::AddSample of ONE sample straight to the film's accumulators: radiance (lr, lg, lb) -- sanitised, clamped to [0, 2^15] per
+// component --, footprint f.  A weighted filter (R.filter_table, wave-uniform): weight w = table[iy * 16 + ix] for every pixel, q = (int64)((w
+// L) 2^24) and (int64)(w 2^24) (the casts truncate toward zero: a negative lobe subtracts).  The box: w = 1 -- the same products -- and the
+// fourth accumulator counts the sample.  ONE loop over the footprint's rows end to end: a second level of divergent control flow costs the
+// scalar registers of its mask, and the WIDE instantiations have none to spare.
+__device__ __forceinline__ void film_add_sample(const RenderParams &R, const DevScene &S, const FilterFootprint &f, float lr, float lg, float lb) {
+  // (1 / rx and 1 / ry ride behind the table's 256 weights -- as kernel arguments they would be two more scalar registers held through the
+  // kernel -- and are read once per sample)
+  float inv_rx = 0.f, inv_ry = 0.f;
+  if (R.filter_table) { inv_rx = R.filter_table[kFilterTableInvRx]; inv_ry = R.filter_table[kFilterTableInvRy]; }
+  int32_t px = f.x0, py = f.x0 < f.x1 ? f.y0 : f.y1;
+#pragma nounroll
+  for (; py < f.y1; px = px + 1 < f.x1 ? px + 1 : f.x0, py += px == f.x0 ? 1 : 0) {
+    float w = 1.0f;
+    unsigned long long qw = 1ull;
+    if (R.filter_table) {
+      w = R.filter_table[filter_axis_index(py, f.dy, inv_ry) * 16 + filter_axis_index(px, f.dx, inv_rx)];
+      qw = (unsigned long long)(long long)(w * kFixedOne);
+    }
+    unsigned long long *a = R.acc + 4u * ((size_t)(py - S.cy0) * (size_t)(S.cx1 - S.cx0) + (size_t)(px - S.cx0));
+    atomicAdd(a, (unsigned long long)(long long)((w * lr) * kFixedOne));
+    atomicAdd(a + 1, (unsigned long long)(long long)((w * lg) * kFixedOne));
+    atomicAdd(a + 2, (unsigned long long)(long long)((w * lb) * kFixedOne));
+    atomicAdd(a + 3, qw);
+  }
 }
 
 }  // namespace

@@ -207,6 +207,22 @@ __global__ void film_from_acc_kernel(const unsigned long long *acc, float4 *film
   film[i] = o;
 }
 
+// the same for a weighted pixel filter's accumulators {r, g, b, weight sum}, all four in 2^-24 units.  A kernel of its own:
+// film_from_acc_kernel keeps its arguments and its machine code.
+__global__ void film_from_acc_weighted_kernel(const unsigned long long *acc, float4 *film, size_t n_px) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_px) return;
+  const float inv = 1.0f / kFixedOne;
+  const V3 sum = {(float)(long long)acc[4 * i] * inv, (float)(long long)acc[4 * i + 1] * inv, (float)(long long)acc[4 * i + 2] * inv};
+  float4 o;
+  const Xyz c = rgb_to_xyz(sum.x, sum.y, sum.z);
+  o.x = c.x;
+  o.y = c.y;
+  o.z = c.z;
+  o.w = (float)(long long)acc[4 * i + 3] * inv;
+  film[i] = o;
+}
+
 }  // namespace
 
 // the fixed-point accumulators of two ranks on one device added (multi_gpu.cpp's loopback exchange; with one rank per device ncclReduce adds them)
@@ -220,9 +236,9 @@ hipError_t launch_acc_add(unsigned long long *dst, const unsigned long long *src
   return hipGetLastError();
 }
 
-hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, size_t n_px, hipStream_t stream) {
+hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, size_t n_px, bool weighted, hipStream_t stream) {
   if (n_px == 0) return hipSuccess;
-  hipLaunchKernelGGL(film_from_acc_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream, acc, film, n_px);
+  hipLaunchKernelGGL(weighted ? film_from_acc_weighted_kernel : film_from_acc_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream, acc, film, n_px);
   return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // polynomials of cephes_poly.hpp, envmap_core.hpp's sincos_0_2pi, kernel_math.hpp's sphere_uv / glass_fresnel / cosine_about /
 // sphere_hit / mis_weight_light / mis_weight_bsdf, kernel_path.hpp's sample_light and the walk's node step and triangle test (kernel_walk.hpp quad_step / walk_inv, quad_nearest.inc, tri_test.inc) with a float64 reference and with the oracle's restatements, element by element, without a render around them.  In a
 // translation unit of its own so that the render and intersect kernels of kernels*.hip keep their names and their machine code.
+// Beside it pbrt_hip_filter_footprint_eval_device: filter_weight.inc's footprint and table index over arrays.
 //
 //   blocks_eval_kernel  one element per thread, 256 threads per workgroup: switches on the op code and calls the PRODUCTION function
 //                       (nothing is restated here); kBlockWidth is how many floats an element reads and writes.
@@ -107,10 +108,78 @@ __global__ void __launch_bounds__(256) blocks_eval_kernel(uint32_t op, int64_t n
   }
 }
 
+// filter_weight.inc over arrays (pbrt_hip_filter_footprint_eval_device): the clipped footprint of film point i ...
+__global__ void __launch_bounds__(256) filter_bounds_kernel(float rx, float ry, int32_t cx0, int32_t cy0, int32_t cx1, int32_t cy1, int64_t n, const float *points,
+                                                            int32_t *bounds) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FilterFootprint f = filter_footprint(points[2 * i], points[2 * i + 1], rx, ry, cx0, cy0, cx1, cy1);
+  bounds[4 * i] = f.x0; bounds[4 * i + 1] = f.y0; bounds[4 * i + 2] = f.x1; bounds[4 * i + 3] = f.y1;
+}
+// ... and the table index of pixel i for film point i, -1 where the pixel is outside the point's clipped footprint
+__global__ void __launch_bounds__(256) filter_index_kernel(float rx, float ry, float inv_rx, float inv_ry, int32_t cx0, int32_t cy0, int32_t cx1, int32_t cy1, int64_t n,
+                                                           const float *points, const int32_t *pixels, int32_t *index) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FilterFootprint f = filter_footprint(points[2 * i], points[2 * i + 1], rx, ry, cx0, cy0, cx1, cy1);
+  const int32_t px = pixels[2 * i], py = pixels[2 * i + 1];
+  const bool inside = px >= f.x0 && px < f.x1 && py >= f.y0 && py < f.y1;
+  index[i] = inside ? filter_axis_index(py, f.dy, inv_ry) * 16 + filter_axis_index(px, f.dx, inv_rx) : -1;
+}
+
 }  // namespace
+
+hipError_t launch_filter_footprint_eval(float rx, float ry, const int32_t crop[4], int64_t n_points, const float *points, int32_t *bounds, int64_t n_pairs,
+                                        const float *pair_points, const int32_t *pair_pixels, int32_t *index, hipStream_t stream) {
+  if (n_points > 0) {
+    hipLaunchKernelGGL(filter_bounds_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, stream, rx, ry, crop[0], crop[1], crop[2], crop[3], n_points,
+                       points, bounds);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (n_pairs > 0) {
+    // (1 / radius as the render's launch forms it: capi_render.cpp)
+    hipLaunchKernelGGL(filter_index_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, rx, ry, 1.0f / rx, 1.0f / ry, crop[0], crop[1], crop[2],
+                       crop[3], n_pairs, pair_points, pair_pixels, index);
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
 }  // namespace pbrt_hip
 
 using namespace pbrt_hip;
+
+extern "C" int pbrt_hip_filter_footprint_eval_device(int device, float rx, float ry, const int32_t crop[4], int64_t n_points, const float *points, int32_t *bounds,
+                                                     int64_t n_pairs, const float *pair_points, const int32_t *pair_pixels, int32_t *index) {
+  if (n_points < 0 || n_pairs < 0 || !crop || (n_points && (!points || !bounds)) || (n_pairs && (!pair_points || !pair_pixels || !index)))
+    return fail(PBRT_HIP_ERR_INVALID, "filter_footprint_eval_device: null argument or negative count");
+  if (!(rx > 0.f) || !(ry > 0.f) || !(rx <= 3.0e38f) || !(ry <= 3.0e38f) || !(1.0f / rx <= 3.0e38f) || !(1.0f / ry <= 3.0e38f))
+    return fail(PBRT_HIP_ERR_INVALID, "filter_footprint_eval_device: the filter radii must be positive and finite");
+  if (n_points == 0 && n_pairs == 0) return PBRT_HIP_OK;
+  return guarded([&]() -> int {
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<float> d_points, d_pair_points;
+    DevBuf<int32_t> d_bounds, d_pair_pixels, d_index;
+    const hipStream_t stream = nullptr;  // the device's default stream
+    if (n_points) {
+      HIP_TRY(d_points.alloc(2 * (size_t)n_points));
+      HIP_TRY(d_bounds.alloc(4 * (size_t)n_points));
+      HIP_TRY(hipMemcpyAsync(d_points.p, points, 8 * (size_t)n_points, hipMemcpyHostToDevice, stream));
+    }
+    if (n_pairs) {
+      HIP_TRY(d_pair_points.alloc(2 * (size_t)n_pairs));
+      HIP_TRY(d_pair_pixels.alloc(2 * (size_t)n_pairs));
+      HIP_TRY(d_index.alloc((size_t)n_pairs));
+      HIP_TRY(hipMemcpyAsync(d_pair_points.p, pair_points, 8 * (size_t)n_pairs, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(d_pair_pixels.p, pair_pixels, 8 * (size_t)n_pairs, hipMemcpyHostToDevice, stream));
+    }
+    HIP_TRY(launch_filter_footprint_eval(rx, ry, crop, n_points, d_points.p, d_bounds.p, n_pairs, d_pair_points.p, d_pair_pixels.p, d_index.p, stream));
+    if (n_points) HIP_TRY(hipMemcpyAsync(bounds, d_bounds.p, 16 * (size_t)n_points, hipMemcpyDeviceToHost, stream));
+    if (n_pairs) HIP_TRY(hipMemcpyAsync(index, d_index.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PBRT_HIP_OK;
+  });
+}
 
 extern "C" int pbrt_hip_blocks_eval_device(int device, uint32_t op, int64_t n, const float *in, float *out) {
   if (op >= PBRT_HIP_BLOCK_COUNT) return fail(PBRT_HIP_ERR_INVALID, "blocks_eval_device: unknown op");

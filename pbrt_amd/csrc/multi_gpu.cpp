@@ -155,6 +155,7 @@ int clone_scene(const pbrt_hip_scene *src, int device, pbrt_hip_scene **out) {
   s->desc = src->desc;
   s->bvh.depth = src->bvh.depth;  // (the host copy of the tree stays with the original: export / info use that one)
   static_cast<SceneTraits &>(*s) = *src;
+  bind_scene_filter(s.get());  // (the pixel filter's record travels with the traits: every GPU makes the table of a render's radii from it)
   int can = 0;
   if (hipDeviceCanAccessPeer(&can, device, src->device) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(src->device, 0);  // (already enabled is fine)
   (void)hipGetLastError();

@@ -310,17 +310,12 @@
             if (WIDE) {
               // FilmTile::AddSample for a box filter of any radius (DESIGN.md 3.11): weight 1 to every pixel of the cropped
               // window within the radius of the sample's film point (kept in the record the default path has its partial
-              // sum in), as 2^-24 fixed point: integer atomics make the sums independent of the order of arrival
+              // sum in), as 2^-24 fixed point: integer atomics make the sums independent of the order of arrival.  A weighted
+              // filter (3.19; wave-uniform: R.filter_table) has the same footprint and a table weight for each of its pixels.
               const float4 fp = rec_load(rec, kRecSum);
-              const float dx = fp.x - 0.5f, dy = fp.y - 0.5f;
-              int32_t x0 = (int32_t)ceilf(dx - R.filter_rx), x1 = (int32_t)floorf(dx + R.filter_rx) + 1;
-              int32_t y0 = (int32_t)ceilf(dy - R.filter_ry), y1 = (int32_t)floorf(dy + R.filter_ry) + 1;
-              x0 = max(x0, S.cx0); x1 = min(x1, S.cx1);
-              y0 = max(y0, S.cy0); y1 = min(y1, S.cy1);
-              unsigned long long ar = (unsigned long long)(long long)(fminf(fmaxf(P.L.x, 0.f), kFixedMax) * kFixedOne);
-              unsigned long long ag = (unsigned long long)(long long)(fminf(fmaxf(P.L.y, 0.f), kFixedMax) * kFixedOne);
-              unsigned long long ab = (unsigned long long)(long long)(fminf(fmaxf(P.L.z, 0.f), kFixedMax) * kFixedOne);
-              uint32_t an = 1u;
+              const FilterFootprint fb = filter_footprint(fp.x, fp.y, R.filter_rx, R.filter_ry, S.cx0, S.cy0, S.cx1, S.cy1);
+              const int32_t x0 = fb.x0, x1 = fb.x1, y0 = fb.y0, y1 = fb.y1;
+              const float lr = fminf(fmaxf(P.L.x, 0.f), kFixedMax), lg = fminf(fmaxf(P.L.y, 0.f), kFixedMax), lb = fminf(fmaxf(P.L.z, 0.f), kFixedMax);
               // Integer sums do not care how they are grouped, and the samples of a chunk -- all in one pixel -- have few
               // distinct footprints: each bound takes one of two neighbouring values as the film point moves through the
               // pixel.  The chunk's samples are therefore added up per footprint in 16 slots of the lane (indexed by the
@@ -339,11 +334,15 @@
               const uint32_t pn = __float_as_uint(a1.z), pkey = __float_as_uint(a1.w);
               P.s++;
               if (sobol) P.rng.state &= 0xffffffffull;
-              if (__builtin_expect(pn != 0u && pkey != key, 0)) {
-                // the slot holds another footprint of this pixel (a bound that takes three values: possible only when
-                // r +- 1/2 lies within rounding of an integer): this sample goes to the film by itself
-                film_add(R.acc, S, x0, x1, y0, y1, ar, ag, ab, 1u);
+              if (R.filter_table != nullptr || __builtin_expect(pn != 0u && pkey != key, 0)) {
+                // a weighted filter: every sample goes to the film by itself, with its pixels' weights.  The box: the slot holds
+                // another footprint of this pixel (a bound that takes three values: possible only when r +- 1/2 lies within
+                // rounding of an integer), and so does this sample, weight 1
+                film_add_sample(R, S, fb, lr, lg, lb);
               } else {
+                unsigned long long ar = (unsigned long long)(long long)(lr * kFixedOne), ag = (unsigned long long)(long long)(lg * kFixedOne),
+                                   ab = (unsigned long long)(long long)(lb * kFixedOne);
+                uint32_t an = 1u;
                 if (pn != 0u) {
                   const float4 a0 = *reinterpret_cast<const float4 *>(sb);         // {r, g}
                   ar += (unsigned long long)__float_as_uint(a0.x) | ((unsigned long long)__float_as_uint(a0.y) << 32);

@@ -1056,9 +1056,22 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
       if (!p.named_params(&name, &ps, api)) return fin(false);
       if (in_options("PixelFilter")) {
         out->filter_name = name;
-        if (name != "box") api.warn("PixelFilter \"" + name + "\": only the box filter is implemented (box.rs:57-61); its radii are used");
-        const float xw = ps.one_float("xwidth", 0.5f), yw = ps.one_float("ywidth", 0.5f);
-        out->filter_radius[0] = xw; out->filter_radius[1] = yw;  // handed to the render desc (radii other than 0.5: DESIGN.md 3.11)
+        // the weighted filters with pbrt-v3's defaults: radii 2 x 2 (the sinc: 4 x 4), alpha 2, B = C = 1/3, tau 3
+        const uint32_t kind = name == "triangle" ? PBRT_HIP_FILTER_TRIANGLE : name == "gaussian" ? PBRT_HIP_FILTER_GAUSSIAN
+                            : name == "mitchell" ? PBRT_HIP_FILTER_MITCHELL : name == "sinc" ? PBRT_HIP_FILTER_SINC : 0u;
+        out->pixel_filter = pbrt_hip_pixel_filter{};  // (a later PixelFilter directive replaces an earlier one)
+        if (kind) {
+          out->pixel_filter.type = PBRT_HIP_TEXTURE_FILTER;
+          out->pixel_filter.kind = kind;
+          if (kind == PBRT_HIP_FILTER_GAUSSIAN) out->pixel_filter.param[0] = ps.one_float("alpha", 2.0f);
+          if (kind == PBRT_HIP_FILTER_MITCHELL) { out->pixel_filter.param[0] = ps.one_float("B", 1.0f / 3.0f); out->pixel_filter.param[1] = ps.one_float("C", 1.0f / 3.0f); }
+          if (kind == PBRT_HIP_FILTER_SINC) out->pixel_filter.param[0] = ps.one_float("tau", 3.0f);
+        } else if (name != "box") {
+          api.warn("PixelFilter \"" + name + "\": only the box, triangle, gaussian, mitchell and sinc filters are implemented; the box filter is used with its radii");
+        }
+        const float dflt = kind == PBRT_HIP_FILTER_SINC ? 4.0f : (kind ? 2.0f : 0.5f);
+        const float xw = ps.one_float("xwidth", dflt), yw = ps.one_float("ywidth", dflt);
+        out->filter_radius[0] = xw; out->filter_radius[1] = yw;  // handed to the render desc (the box, radii other than 0.5: DESIGN.md 3.11)
       }
     } else if (tok == "ReverseOrientation") {
       if (in_world("ReverseOrientation")) api.gs.reverse_orientation = !api.gs.reverse_orientation;
@@ -1166,6 +1179,13 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
     bool textured = false;
     for (uint16_t m : out->mat_id) textured = textured || (out->mats[m].type == PBRT_HIP_MATERIAL_MATTE && out->mats[m].kd_tex != 0u);
     if (!textured) { out->tri_uv.clear(); out->tri_uv.shrink_to_fit(); }
+  }
+  // a weighted pixel filter's record takes a slot of the texture table; a file without one keeps the description it always had
+  if (out->pixel_filter.type == PBRT_HIP_TEXTURE_FILTER) {
+    pbrt_hip_texture slot{};
+    static_assert(sizeof slot == sizeof out->pixel_filter, "the pixel filter's record takes one slot of the texture table");
+    std::memcpy(&slot, &out->pixel_filter, sizeof slot);
+    out->textures.push_back(slot);
   }
   // shading normals travel only when some mesh has them: then their record is the LAST slot of the texture table; a file
   // without them keeps the description it always had

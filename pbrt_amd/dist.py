@@ -109,7 +109,7 @@ def render_sharded(scene, rank, world_size, group=None, **render_kw):
     gather, and return (film on rank 0 or None, stats of the local kernel)."""
     import torch
     sd = scene.sd
-    if is_wide_filter(render_kw.get("filter_width")):
+    if is_wide_filter(render_kw.get("filter_width")) or sd.pixel_filter is not None:  # (a weighted filter, DESIGN.md 3.19: the fixed-point film at every radius)
         w, h = sd.crop_size()
         acc = torch.empty(max(h * w, 1), 4, dtype=torch.int64, device="cuda")  # (render_device zeroes it)
         stream = torch.cuda.current_stream().cuda_stream

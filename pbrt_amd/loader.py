@@ -6,7 +6,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import EnvMap, Normals, RenderDesc, SceneDesc, check, lib
+from ._lib import EnvMap, Normals, PixelFilter, RenderDesc, SceneDesc, check, lib
 from .api import GLASS, SceneData
 
 
@@ -46,7 +46,9 @@ def _collect(h):
         env_slots = [i for i in range(d.n_textures) if d.textures[i].type == 1]
         # (the shading normals' record, DESIGN.md 3.18, is a slot whose first word is 2: it becomes `tri_n`)
         nrm_slots = [i for i in range(d.n_textures) if d.textures[i].type == 2]
-        tex_slots = [i for i in range(d.n_textures) if d.textures[i].type not in (1, 2)]
+        # (the pixel filter's record, DESIGN.md 3.19, is a slot whose first word is 3: it becomes `pixel_filter`)
+        flt_slots = [i for i in range(d.n_textures) if d.textures[i].type == 3]
+        tex_slots = [i for i in range(d.n_textures) if d.textures[i].type not in (1, 2, 3)]
         renum = {0: 0, **{i + 1: k + 1 for k, i in enumerate(tex_slots)}}
         envmap, env_m = np.zeros((0, 0, 3), np.float32), np.eye(3, dtype=np.float32)
         if env_slots:
@@ -57,8 +59,12 @@ def _collect(h):
         if nrm_slots:
             nr = Normals.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[nrm_slots[0]]), C.sizeof(Normals))))
             tri_n = arr(nr.tri_n, 9 * nr.n_tris, np.float32).reshape(-1, 9)
+        pixel_filter = None
+        if flt_slots:
+            pf = PixelFilter.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[flt_slots[0]]), C.sizeof(PixelFilter))))
+            pixel_filter = (int(pf.kind), float(pf.param[0]), float(pf.param[1]))
         sd = SceneData(
-            tri_n=tri_n, envmap=envmap, envmap_world_to_light=env_m,
+            pixel_filter=pixel_filter, tri_n=tri_n, envmap=envmap, envmap_world_to_light=env_m,
             P=arr(d.P, 3 * d.n_verts, np.float32).reshape(-1, 3), idx=arr(d.idx, 3 * d.n_tris, np.uint32).reshape(-1, 3),
             mat_id=arr(d.mat_id, d.n_tris, np.uint16),
             materials=np.array([[d.mats[i].type, *d.mats[i].k, *d.mats[i].le] for i in range(d.n_mats)], np.float32).reshape(-1, 7),

@@ -69,11 +69,46 @@ typedef struct {
  * (s, t) = (su u + du, sv v + dv); tex1 where floor(s) + floor(t) is even, tex2 where odd.  64 bytes. */
 typedef struct {
   uint32_t type;  /* 0 = checkerboard, dimension 2, "uv" mapping; 1 = this slot is the environment-map record below; 2 = the shading
-                     normals' record, pbrt_hip_normals; 3 = the pixel filter's record, pbrt_hip_pixel_filter */
+                     normals' record, pbrt_hip_normals; 3 = the pixel filter's record, pbrt_hip_pixel_filter; 4 = an image texture's
+                     record, pbrt_hip_image_texture */
   float tex1[3], tex2[3];
   float su, sv, du, dv; /* "float uscale" / "vscale" / "udelta" / "vdelta" */
   uint32_t pad[5];
 } pbrt_hip_texture;
+
+/* Texture "name" "spectrum" "imagemap" (the reference stores no texture, api.rs:524-580): pbrt-v3's ImageTexture over a
+ * UVMapping2D without a MIPMap pyramid -- a matte Kd read from an image.  A slot of `textures` whose first word is 4 IS this record -- 64
+ * bytes, read with memcpy like the environment map's; a matte kd_tex = t names it exactly as it names a checkerboard, and the hit's (u, v)
+ * and (s, t) = (su u + du, sv v + dv) are the checkerboard's own.  t = 0 is the BOTTOM row of the image (pbrt-v3): texel row iy counts
+ * from the bottom and is row height - 1 - iy of `rgb`.  All arithmetic in fp32; an index stays a float until it is clamped to [0, W - 1]
+ * (NaN -> 0), so every s has a defined texel.
+ *   filter 0 point     repeat: ix = floor((s - floor(s)) W); clamp, black: ix = floor(s W), clamped; black: 0 outside [0, W - 1]
+ *   filter 1 bilinear  texel centres at (i + 0.5) / W (MIPMap::Lookup at level 0 without ray differentials): repeat reduces s - floor(s)
+ *                      first; sx = s W - 0.5, x0 = floor(sx), the four neighbours weighted (1 - dx, dx) x (1 - dy, dy); repeat wraps a
+ *                      neighbour, clamp clamps it, black gives it weight 0 outside
+ * Refused at scene creation before any device work (the message holds "image"): width or height 0, a NULL `rgb`, a texel that is not finite
+ * or is negative, an unknown wrap / filter, a mapping that is not finite (PBRT_HIP_ERR_INVALID); width or height > 16384, more than 64 image
+ * slots, more than 2^26 texels in all of them (PBRT_HIP_ERR_LIMIT).  A scene with an image-textured material is a textured scene: the
+ * kernels, the refusals (counter flags: PBRT_HIP_ERR_LIMIT) and tri_uv are the checkerboard's.  Glass ignores kd_tex as before. */
+#define PBRT_HIP_TEXTURE_IMAGE 4u
+#define PBRT_HIP_WRAP_REPEAT 0u
+#define PBRT_HIP_WRAP_CLAMP 1u
+#define PBRT_HIP_WRAP_BLACK 2u
+#define PBRT_HIP_TEXFILTER_POINT 0u
+#define PBRT_HIP_TEXFILTER_BILINEAR 1u
+#define PBRT_HIP_IMAGE_MAX_SIZE 16384u        /* width, height */
+#define PBRT_HIP_IMAGE_MAX_SLOTS 64u
+#define PBRT_HIP_IMAGE_MAX_TEXELS (1u << 26)  /* all image slots of a scene together */
+typedef struct {
+  uint32_t type;     /* = 4 */
+  uint32_t width, height;
+  uint32_t wrap;     /* PBRT_HIP_WRAP_*: 0 repeat, 1 clamp, 2 black */
+  const float *rgb;  /* host, 3 x width x height, row-major, row 0 = the first row pbrt_hip_read_image returns (the image's top); copied
+                        during the call */
+  float su, sv, du, dv; /* "float uscale" / "vscale" / "udelta" / "vdelta" */
+  uint32_t filter;   /* PBRT_HIP_TEXFILTER_*: 0 point, 1 bilinear */
+  uint32_t pad[5];
+} pbrt_hip_image_texture;
 
 /* LightSource "infinite" "string mapname" (the reference: src/lights/infinite.rs:52-66 reads the image, multiplies the
  * texels by L x scale and stops at todo!() before its MIPMap and Distribution2D): an environment map in the latitude-longitude
@@ -87,7 +122,7 @@ typedef struct {
  * The light is importance-sampled by pbrt-v3's Distribution2D over luminance x sin theta, from the same (u1, u2) every other light gets.
  * Refused before any device work (the message holds "environment"): width x height > 2^24 (PBRT_HIP_ERR_LIMIT); width or height 0, a NULL
  * `rgb`, a texel that is not finite or is negative, a world_to_light that is not finite or not orthonormal to 1e-4
- * (PBRT_HIP_ERR_INVALID); a matte kd_tex that names such a slot (PBRT_HIP_ERR_INVALID: image textures for Kd do not exist). */
+ * (PBRT_HIP_ERR_INVALID); a matte kd_tex that names such a slot (PBRT_HIP_ERR_INVALID: a texture for Kd is a slot of type 0 or 4). */
 typedef struct {
   uint32_t type;     /* = 1 */
   uint32_t width, height;
@@ -248,9 +283,10 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.9 (gfx950; struct sizes of 0.6, as 0.7 and 0.8)": 0.9 = texture-table slot type 3, the pixel
-                                       filter, inside the same struct sizes; 0.8 = texture-table slot type 2, the shading normals,
-                                       likewise ("as 0.7 and 0.8": tests of the environment map and of the normals look for "0.7" and "0.8"
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.10 (gfx950; struct sizes of 0.6, as 0.7, 0.8 and 0.9)": 0.10 = texture-table slot type 4, the
+                                       image texture, inside the same struct sizes; 0.9 = texture-table slot type 3, the pixel
+                                       filter, likewise; 0.8 = texture-table slot type 2, the shading normals,
+                                       likewise ("as 0.7, 0.8 and 0.9": tests of the environment map, of the normals and of the pixel filter look for "0.7", "0.8" and "0.9"
                                        the way the glass test looks for "0.6"); 0.5 = round 5's ABI (pbrt_hip_scene_desc gained tri_uv / textures / n_textures at its
                                        end, pbrt_hip_material.pad became kd_tex, flags 0 of scene_create_ex = the device builder); 0.6 =
                                        material type 2, glass, inside the same struct sizes; 0.7 = light type 3 and texture-table

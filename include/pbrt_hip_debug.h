@@ -147,6 +147,16 @@ int pbrt_hip_shading_normal_eval_device(int device, int64_t n, const float *in, 
 int pbrt_hip_filter_footprint_eval_device(int device, float rx, float ry, const int32_t crop[4], int64_t n_points, const float *points,
                                           int32_t *bounds, int64_t n_pairs, const float *pair_points, const int32_t *pair_pixels, int32_t *index);
 
+/* ---- image textures for Kd (pbrt_amd/csrc/image_lookup.hpp is the one statement of the arithmetic) ---- */
+/* host only: the lookup of record `which` of `records` (n_records >= 1 records of type 4, checked as pbrt_hip_scene_create checks them and
+ * packed into ONE texel pool as it packs them) at n points: uv = (u, v) pairs, 2 n floats -> rgb, 3 n floats = Kd, the record's mapping
+ * (s, t) = (su u + du, sv v + dv) included. */
+int pbrt_hip_image_lookup_eval_host(const pbrt_hip_image_texture *records, uint32_t n_records, uint32_t which, int64_t n, const float *uv, float *rgb);
+/* the same on `device` (a tiny kernel of kernels_blocks.hip that calls the same header over the uploaded pool): the same bits.
+ * PBRT_HIP_ERR_NO_DEVICE without one. */
+int pbrt_hip_image_lookup_eval_device(int device, const pbrt_hip_image_texture *records, uint32_t n_records, uint32_t which, int64_t n, const float *uv,
+                                      float *rgb);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

@@ -32,6 +32,12 @@ class PixelFilter(C.Structure):
     _fields_ = [("type", C.c_uint32), ("kind", C.c_uint32), ("param", C.c_float * 2), ("pad", C.c_uint32 * 12)]
 
 
+class ImageTexture(C.Structure):
+    """pbrt_hip_image_texture: what a slot of the texture table IS when its first word is 4; 64 bytes like Texture"""
+    _fields_ = [("type", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("wrap", C.c_uint32), ("rgb", C.POINTER(C.c_float)),
+                ("su", C.c_float), ("sv", C.c_float), ("du", C.c_float), ("dv", C.c_float), ("filter", C.c_uint32), ("pad", C.c_uint32 * 5)]
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_uint32), ("p", C.c_float * 3), ("c", C.c_float * 3), ("pad", C.c_float)]
 
@@ -134,6 +140,8 @@ SYMBOLS = {
     "pbrt_hip_envmap_tables": (C.c_int, [_pf, _u32, _u32, _pf, _pf, _pf]),
     "pbrt_hip_envmap_eval_host": (C.c_int, [_pf, _u32, _u32, _pf, _i64, _pf, _pf, _pu32, _pf, _pf]),
     "pbrt_hip_envmap_eval_device": (C.c_int, [_vp, _i64, _pf, _pf, _pu32, _pf, _pf]),
+    "pbrt_hip_image_lookup_eval_host": (C.c_int, [C.POINTER(ImageTexture), _u32, _u32, _i64, _pf, _pf]),
+    "pbrt_hip_image_lookup_eval_device": (C.c_int, [C.c_int, C.POINTER(ImageTexture), _u32, _u32, _i64, _pf, _pf]),
     "pbrt_hip_blocks_eval_device": (C.c_int, [C.c_int, _u32, _i64, _pf, _pf]),
     "pbrt_hip_shading_normal_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
 }

@@ -9,7 +9,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import EnvMap, Light, Material, Normals, PixelFilter, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
+from ._lib import EnvMap, ImageTexture, Light, Material, Normals, PixelFilter, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
 
 MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
@@ -18,6 +18,11 @@ INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_PATH_MIS = 0, 1, 2  # 2: the path
 FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_SINC = 1, 2, 3, 4  # PBRT_HIP_FILTER_*: the weighted pixel filters
 FILTER_KINDS = {"triangle": FILTER_TRIANGLE, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL, "sinc": FILTER_SINC}
 FILTER_DEFAULT_PARAMS = {FILTER_TRIANGLE: (0.0, 0.0), FILTER_GAUSSIAN: (2.0, 0.0), FILTER_MITCHELL: (1.0 / 3.0, 1.0 / 3.0), FILTER_SINC: (3.0, 0.0)}  # pbrt-v3's
+TEXTURE_CHECKER, TEXTURE_IMAGE = 0, 4  # the types of a `textures` row a matte Kd can name; 4: PBRT_HIP_TEXTURE_IMAGE
+WRAP_REPEAT, WRAP_CLAMP, WRAP_BLACK = 0, 1, 2  # PBRT_HIP_WRAP_*
+WRAPS = {"repeat": WRAP_REPEAT, "clamp": WRAP_CLAMP, "black": WRAP_BLACK}
+TEXFILTER_POINT, TEXFILTER_BILINEAR = 0, 1  # PBRT_HIP_TEXFILTER_*
+TEXFILTERS = {"point": TEXFILTER_POINT, "bilinear": TEXFILTER_BILINEAR}
 FLAG_COUNTERS = 1
 FLAG_WALK_COUNTERS = 2
 SCENE_GPU_BUILD = 1  # pbrt_hip_scene_create_ex flags
@@ -50,7 +55,9 @@ class SceneData:
     triangle has none; empty = the scene has none.  Its record travels in a slot of its own behind the checkerboards and the map.  A weighted
     pixel filter: `pixel_filter` = None (the box) or (kind, param0, param1) -- kind a name or number of FILTER_KINDS, the
     parameters alpha / B, C / tau (omitted ones: pbrt-v3's defaults); its record travels in a slot of its own too, and a render's
-    filter_width is then that filter's radii (0 = the kind's default)."""
+    filter_width is then that filter's radii (0 = the kind's default).  Image textures: `images` = a list of (H, W, 3) float32
+    arrays, row 0 = the image's top, and a `textures` row (TEXTURE_IMAGE, image index, wrap, filter, 0, 0, 0, su, sv, du, dv) -- WRAP_*,
+    TEXFILTER_* --, which fill_desc turns into the pbrt_hip_image_texture record of the same slot (image_texture_row makes one)."""
     P: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
     idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.uint32))
     mat_id: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint16))
@@ -70,8 +77,11 @@ class SceneData:
     envmap_world_to_light: np.ndarray = field(default_factory=lambda: np.eye(3, dtype=np.float32))
     tri_n: np.ndarray = field(default_factory=lambda: np.zeros((0, 9), np.float32))
     pixel_filter: tuple = None
+    images: list = field(default_factory=list)
 
     def normalized(self):
+        self.images = [np.ascontiguousarray(im, np.float32) for im in self.images]
+        assert all(im.ndim == 3 and im.shape[2] == 3 for im in self.images)
         if self.pixel_filter is not None:
             self.pixel_filter = pixel_filter_tuple(self.pixel_filter)
         self.P = np.ascontiguousarray(self.P, np.float32).reshape(-1, 3)
@@ -124,6 +134,11 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         tex_t = tex_t or dict(desc._fields_)["textures"]._type_  # (the Texture class of the caller's own struct mirror)
         texs = (tex_t * (len(sd.textures) + int(has_env) + int(has_flt) + int(has_nrm)))()
         for i, t in enumerate(sd.textures):
+            if int(t[0]) == TEXTURE_IMAGE:  # the image's record in the row's own slot: mat_tex numbering does not move
+                rec = image_record(sd.images[int(t[1])], int(t[2]), int(t[3]), t[7:11])
+                assert C.sizeof(rec) == C.sizeof(tex_t)
+                C.memmove(C.byref(texs, i * C.sizeof(tex_t)), C.byref(rec), C.sizeof(rec))
+                continue
             texs[i].type = int(t[0])
             texs[i].tex1[:] = [float(x) for x in t[1:4]]
             texs[i].tex2[:] = [float(x) for x in t[4:7]]
@@ -174,6 +189,39 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
     desc.yres = int(sd.yres)
     desc.crop[:] = [float(x) for x in sd.crop]
     return [mats, lights, spheres, texs, sd]
+
+
+def image_record(image, wrap=WRAP_REPEAT, filter=TEXFILTER_BILINEAR, mapping=(1.0, 1.0, 0.0, 0.0)):
+    """the pbrt_hip_image_texture record of an (H, W, 3) float32 C-contiguous array (row 0 = the image's top), which must outlive its use"""
+    assert image.dtype == np.float32 and image.flags.c_contiguous and image.ndim == 3 and image.shape[2] == 3
+    su, sv, du, dv = (float(x) for x in mapping)
+    return ImageTexture(type=TEXTURE_IMAGE, width=image.shape[1], height=image.shape[0], wrap=WRAPS.get(wrap, wrap), rgb=_fp(image), su=su, sv=sv,
+                        du=du, dv=dv, filter=TEXFILTERS.get(filter, filter))
+
+
+def image_texture_row(image_index, wrap=WRAP_REPEAT, filter=TEXFILTER_BILINEAR, mapping=(1.0, 1.0, 0.0, 0.0)):
+    """a SceneData.textures row that names SceneData.images[image_index]"""
+    return [TEXTURE_IMAGE, image_index, WRAPS.get(wrap, wrap), TEXFILTERS.get(filter, filter), 0, 0, 0, *mapping]
+
+
+def _image_lookup_eval(call, where, images, which, uv):
+    """images: a list of (image, wrap, filter, mapping); uv: (n, 2) -> (n, 3) float32: Kd of record `which` at every (u, v)"""
+    arrays = [np.ascontiguousarray(im[0], np.float32) for im in images]
+    recs = (ImageTexture * len(images))(*[image_record(a, *im[1:]) for a, im in zip(arrays, images)])
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    out = np.zeros((uv.shape[0], 3), np.float32)
+    check(call(recs, len(images), int(which), uv.shape[0], _fp(uv), _fp(out)), where)
+    return out
+
+
+def image_lookup_eval_host(images, which, uv):
+    """pbrt_hip_image_lookup_eval_host: csrc/image_lookup.hpp over arrays on the host (no device needed)"""
+    return _image_lookup_eval(lib().pbrt_hip_image_lookup_eval_host, "pbrt_hip_image_lookup_eval_host", images, which, uv)
+
+
+def image_lookup_eval_device(images, which, uv, device=0):
+    """pbrt_hip_image_lookup_eval_device: the same on the device, over one uploaded texel pool"""
+    return _image_lookup_eval(lambda *a: lib().pbrt_hip_image_lookup_eval_device(int(device), *a), "pbrt_hip_image_lookup_eval_device", images, which, uv)
 
 
 SAMPLERS = {"stratified": 0, "sobol": 1, "sobol_nd": 2, "halton": 3}  # "sobol": the padded (0,2)-sequence sampler (3.10); "sobol_nd": Sobol' proper (3.12); "halton": 3.13

@@ -19,7 +19,7 @@ CLI_PATH = os.path.join(LIB_DIR, "pbrt")  # the C++ command line (csrc/pbrt_main
 # and render_body.inc; they compile side by side.  kernels_blocks.hip holds the debug hook that runs the headers' building blocks over
 # arrays and no render kernel)
 SOURCES = ["kernels.hip", "kernels_x.hip", "kernels_n.hip", "kernels_env.hip", "bvh_gpu.hip", "kernels_blocks.hip", "capi_scene.cpp", "capi_render.cpp", "capi_load.cpp", "multi_gpu.cpp", "bvh_build.cpp", "quad_nodes.cpp", "reinsert_batch.cpp", "imageio.cpp",
-           "scene_parser.cpp", "ply_reader.cpp", "envmap.cpp", "pixel_filter.cpp"]
+           "scene_parser.cpp", "ply_reader.cpp", "envmap.cpp", "pixel_filter.cpp", "image_texture.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -70,6 +70,7 @@ def build_hip(force=False, verbose=False, extra_flags=()):
     deps.append(os.path.join(HERE, "..", "include", "pbrt_hip_debug.h"))
     deps.append(os.path.abspath(__file__))
     if not force and _newer(LIB_PATH, deps):
+        ensure_demo_textures()
         return LIB_PATH
     objs = []
     extra_flags = list(extra_flags) + os.environ.get("PBRT_HIP_EXTRA_FLAGS", "").split()
@@ -96,7 +97,23 @@ def build_hip(force=False, verbose=False, extra_flags=()):
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
+    ensure_demo_textures()
     return LIB_PATH
+
+
+DEMO_TEXTURES = os.path.join(HERE, "..", "scenes", "textures")
+
+
+def ensure_demo_textures():
+    """scenes/textures/planks.png, the image scenes/textured_cornell.pbrt names, is a build product, not a committed file:
+    a generated pattern (scenes.procedural_planks) written by the library's own PNG writer, here, once the library exists."""
+    if os.path.exists(os.path.join(DEMO_TEXTURES, "planks.png")):
+        return
+    root = os.path.dirname(HERE)
+    if root not in sys.path:  # (run as a script, `python pbrt_amd/build.py`, the package is not on the path yet)
+        sys.path.insert(0, root)
+    from pbrt_amd.scenes import write_demo_textures  # (loads the library: host code alone, no device is touched)
+    write_demo_textures(DEMO_TEXTURES)
 
 
 if __name__ == "__main__":

@@ -59,6 +59,8 @@ struct SceneArrays {
   // (3 x float4 {n, 0} per slot); both empty for a scene without them
   DevBuf<float> d_tri_n_in;
   DevBuf<float4> d_tri_n;
+  // image textures for Kd: the texels {r, g, b, 0} of every image slot, back to back; empty for a scene without one
+  DevBuf<float4> d_image_texels;
   // the canonical walk's triangle records and leaf order of a device-built scene (ensure_canonical)
   DevBuf<float4> d_tris_exact;
   DevBuf<uint32_t> d_order_exact;
@@ -73,7 +75,7 @@ struct SceneArrays {
     f(&SceneArrays::d_tri_uv, true); f(&SceneArrays::d_textures, true); f(&SceneArrays::d_glass, true);
     f(&SceneArrays::d_env_texels, true); f(&SceneArrays::d_env_marginal, true); f(&SceneArrays::d_env_conditional, true);
     f(&SceneArrays::d_tri_n_in, false);  // (read by pack_nrm during scene creation and by nothing after it: released there)
-    f(&SceneArrays::d_tri_n, true);
+    f(&SceneArrays::d_tri_n, true); f(&SceneArrays::d_image_texels, true);
     f(&SceneArrays::d_tris_exact, false); f(&SceneArrays::d_order_exact, false);  // (canonical_ready is not copied: a clone makes its own on first use)
   }
   // bytes on the device: pbrt_hip_scene_info's device_bytes
@@ -83,7 +85,7 @@ struct SceneArrays {
     return total;
   }
 };
-static_assert(sizeof(SceneArrays) == 21 * sizeof(DevBuf<float>), "an array of SceneArrays is missing from SceneArrays::for_each");
+static_assert(sizeof(SceneArrays) == 22 * sizeof(DevBuf<float>), "an array of SceneArrays is missing from SceneArrays::for_each");
 
 // What a scene is beside its arrays, its host tree and its description: plain values, which a clone takes in one assignment
 struct SceneTraits {

@@ -265,8 +265,8 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
   HIP_TRY(s->d_stack_overflow.grow((size_t)L.n_workgroups * 64 * L.plan.extra_entries));
   return PBRT_HIP_OK;
 }
-// the scene-owned fields of the kernels' argument block: (u, v) and textures, the glass table, the environment map (null / identity for a
-// scene without them)
+// the scene-owned fields of the kernels' argument block: (u, v) and textures, the glass table, the environment map, the corner normals and
+// the image textures' texel pool (null / identity for a scene without them)
 void scene_render_params(const pbrt_hip_scene *s, RenderParams *R) {
   R->tri_uv = s->d_tri_uv.p;
   R->textures = s->d_textures.p;
@@ -278,6 +278,7 @@ void scene_render_params(const pbrt_hip_scene *s, RenderParams *R) {
   for (int k = 0; k < 9; k++) R->env_m[k] = s->env_m[k];
   for (int k = 0; k < 3; k++) R->env_c[k] = s->env_c[k];
   R->tri_n = s->d_tri_n.p;
+  R->image_texels = s->d_image_texels.p;
 }
 }  // namespace
 

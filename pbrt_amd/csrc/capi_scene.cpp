@@ -20,6 +20,7 @@
 #include "device_types.h"
 #include "envmap.hpp"
 #include "host_math.hpp"
+#include "image_texture.hpp"
 #include "pixel_filter.hpp"
 #include "quad_nodes.hpp"
 
@@ -170,7 +171,7 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
     if (d->mats[i].kd_tex > d->n_textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
     if (d->mats[i].kd_tex && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: textured material but no texture table");
   }
-  for (uint32_t i = 0; i < d->n_mats; i++)  // (image textures for Kd do not exist: a type-1 slot is a light's map)
+  for (uint32_t i = 0; i < d->n_mats; i++)  // (a texture for Kd is a checkerboard, type 0, or an image, type 4: a type-1 slot is a light's map)
     if (kd_textured(d->mats[i]) && is_envmap_slot(d->textures, d->mats[i].kd_tex - 1u))
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names an environment map, which is not a texture for Kd");
   for (uint32_t i = 0; i < d->n_mats; i++)
@@ -179,9 +180,19 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
   for (uint32_t i = 0; i < d->n_mats; i++)
     if (kd_textured(d->mats[i]) && is_filter_slot(d->textures, d->mats[i].kd_tex - 1u))
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names the pixel filter's record, which is not a texture for Kd");
-  uint32_t n_normals = 0, n_filters = 0;
+  uint32_t n_normals = 0, n_filters = 0, n_images = 0;
+  uint64_t image_texels = 0;
   for (uint32_t i = 0; i < d->n_textures; i++) {
     const pbrt_hip_texture &tx = d->textures[i];
+    if (is_image_slot(d->textures, i)) {  // an image texture's record
+      const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": ";
+      const pbrt_hip_image_texture im = image_slot(d->textures, i);
+      int rc = image_check(im, what);
+      if (rc) return rc;
+      image_texels += (uint64_t)im.width * im.height;
+      if ((rc = image_check_totals(++n_images, image_texels, what))) return rc;
+      continue;
+    }
     if (is_filter_slot(d->textures, i)) {  // the pixel filter's record
       const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": ";
       if (++n_filters > 1u) return fail(PBRT_HIP_ERR_LIMIT, what + "more than one pixel filter record (type 3)");
@@ -210,6 +221,11 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
     for (int k = 0; k < 3; k++)
       if (!std::isfinite(tx.tex1[k]) || !std::isfinite(tx.tex2[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture colour is not finite");
   }
+  for (uint32_t i = 0; i < d->n_textures; i++)  // (the images' texels, once every size and the caps have passed)
+    if (is_image_slot(d->textures, i)) {
+      const int rc = image_check_texels(image_slot(d->textures, i), "scene_create: texture slot " + std::to_string(i + 1) + ": ");
+      if (rc) return rc;
+    }
   bool textured = false;  // a triangle whose material's Kd is a texture: its corner (u, v) must be there
   for (uint32_t t = 0; t < d->n_tris && !textured; t++) textured = kd_textured(d->mats[d->mat_id[t]]);
   if (textured) {
@@ -262,6 +278,7 @@ struct SceneInputs {
   std::vector<uint16_t> mat_aug;
   std::vector<float4> lights, mats, spheres, textures;  // the kernels' records: 5, 2, 2 and 3 per light / material / sphere / texture
   std::vector<float4> glass;  // {Kt, eta} per material, when the scene has a glass one; else empty
+  std::vector<float4> image_texels;  // the texel pool of the image textures, when something is textured; else empty
   // an environment-map light: its tables, world_to_light and factor
   bool env = false;
   EnvTables env_tables;
@@ -356,6 +373,10 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
     for (uint32_t i = 0; i < d.n_textures; i++) {
       const pbrt_hip_texture &tx = d.textures[i];
       if (is_envmap_slot(d.textures, i) || is_normals_slot(d.textures, i) || is_filter_slot(d.textures, i)) continue;  // (an environment map's / the normals' / the filter's slot: no material names it, its records stay zero)
+      if (is_image_slot(d.textures, i)) {  // (its texels join the pool, its rows say where)
+        image_pack(image_slot(d.textures, i), &in->image_texels, &in->textures[3 * i]);
+        continue;
+      }
       in->textures[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
       in->textures[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
       in->textures[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
@@ -373,6 +394,7 @@ int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const SceneIn
   HIP_TRY(upload(&s->d_spheres, in.spheres.data(), in.spheres.size(), s->stream));
   HIP_TRY(upload(&s->d_textures, in.textures.data(), in.textures.size(), s->stream));
   HIP_TRY(upload(&s->d_glass, in.glass.data(), in.glass.size(), s->stream));
+  HIP_TRY(upload(&s->d_image_texels, in.image_texels.data(), in.image_texels.size(), s->stream));
   if (in.env) {
     HIP_TRY(upload(&s->d_env_texels, in.env_tables.texels.data(), in.env_tables.texels.size(), s->stream));
     HIP_TRY(upload(&s->d_env_marginal, in.env_tables.marginal.data(), in.env_tables.marginal.size(), s->stream));
@@ -523,7 +545,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.9 (gfx950; struct sizes of 0.6, as 0.7 and 0.8)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.10 (gfx950; struct sizes of 0.6, as 0.7, 0.8 and 0.9)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif

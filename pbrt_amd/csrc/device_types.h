@@ -225,6 +225,10 @@ struct RenderParams {
   // pointer is all the filter adds to the kernel's arguments: every scalar more is a register held through the kernel, and the WIDE
   // instantiations have none to spare.)  At the end, for the reason given above.
   const float *filter_table;
+  // image textures for Kd (the type-4 branch of render_body.inc's TEX block): the texels of every image slot in one pool,
+  // float4 {r, g, b, 0} each -- one aligned 16-byte load per texel --, a slot's first texel at the offset its rows carry (image_lookup.hpp);
+  // null for a scene without an image.  At the end, for the reason given above.
+  const float4 *image_texels;
 };
 // the device copy of a filter table: the 256 weights, then 1 / rx and 1 / ry
 constexpr uint32_t kFilterTableInvRx = 256u, kFilterTableInvRy = 257u, kFilterTableFloats = 260u;
@@ -281,6 +285,8 @@ hipError_t launch_film_from_acc(const unsigned long long *acc, float4 *film, siz
 // kernels_blocks.hip: filter_weight.inc over device arrays (pbrt_hip_filter_footprint_eval_device)
 hipError_t launch_filter_footprint_eval(float rx, float ry, const int32_t crop[4], int64_t n_points, const float *points, int32_t *bounds, int64_t n_pairs,
                                         const float *pair_points, const int32_t *pair_pixels, int32_t *index, hipStream_t stream);
+// kernels_blocks.hip: image_lookup.hpp over device arrays (pbrt_hip_image_lookup_eval_device: the slot's three rows, the pool, n x (u, v) -> n x rgb)
+hipError_t launch_image_lookup_eval(const float4 *rows, const float4 *pool, int64_t n, const float *uv, float *rgb, hipStream_t stream);
 hipError_t launch_acc_add(unsigned long long *dst, const unsigned long long *src, size_t n, hipStream_t stream);  // dst[i] += src[i]
 hipError_t launch_intersect(const DevScene &S, const RayBatch &B, bool any_hit, uint32_t bvh_depth, hipStream_t stream);
 // (n_prims = n_tris + the spheres, whose records come from the `spheres` table: kernels.hip pack_tris_kernel)

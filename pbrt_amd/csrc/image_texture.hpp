@@ -1,0 +1,27 @@
+// image_texture.hpp -- image textures for Kd on the host: the record's place in the texture table, its checks, and the texel
+// pool with the slot's three rows that the kernels read (image_lookup.hpp is the one statement of the lookup's arithmetic).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/pbrt_hip.h"
+
+namespace pbrt_hip {
+
+// the image's record: a slot of the texture table whose first word is 4, read as the environment map's is
+inline bool is_image_slot(const pbrt_hip_texture *textures, uint32_t index) { return textures[index].type == PBRT_HIP_TEXTURE_IMAGE; }
+pbrt_hip_image_texture image_slot(const pbrt_hip_texture *textures, uint32_t index);
+
+// PBRT_HIP_OK, or the refusal of one record (every message holds "image"; `what` prefixes it): everything but the texels ...
+int image_check(const pbrt_hip_image_texture &t, const std::string &what);
+// ... and the texels, finite and >= 0 -- read only once the sizes and image_check_totals have passed for every record of the table
+int image_check_texels(const pbrt_hip_image_texture &t, const std::string &what);
+// the caps over all the image slots of a table: their number and the sum of their texels (PBRT_HIP_ERR_LIMIT)
+int image_check_totals(uint32_t n_slots, uint64_t n_texels, const std::string &what);
+
+// appends the record's texels to `pool` as {r, g, b, 0} in the record's own row order and writes the slot's three rows (image_lookup.hpp encode)
+void image_pack(const pbrt_hip_image_texture &t, std::vector<float4> *pool, float4 rows[3]);
+
+}  // namespace pbrt_hip

@@ -2,6 +2,7 @@
 // light, the path state and its HBM records, the samplers, and the wide filters' film_add and film_add_sample.
 #pragma once
 #include "envmap_core.hpp"
+#include "image_lookup.hpp"
 #include "kernel_walk.hpp"
 
 namespace pbrt_hip {

@@ -2,7 +2,8 @@
 // polynomials of cephes_poly.hpp, envmap_core.hpp's sincos_0_2pi, kernel_math.hpp's sphere_uv / glass_fresnel / cosine_about /
 // sphere_hit / mis_weight_light / mis_weight_bsdf, kernel_path.hpp's sample_light and the walk's node step and triangle test (kernel_walk.hpp quad_step / walk_inv, quad_nearest.inc, tri_test.inc) with a float64 reference and with the oracle's restatements, element by element, without a render around them.  In a
 // translation unit of its own so that the render and intersect kernels of kernels*.hip keep their names and their machine code.
-// Beside it pbrt_hip_filter_footprint_eval_device: filter_weight.inc's footprint and table index over arrays.
+// Beside it pbrt_hip_filter_footprint_eval_device: filter_weight.inc's footprint and table index over arrays, and the kernel of
+// pbrt_hip_image_lookup_eval_device: image_lookup.hpp over arrays.
 //
 //   blocks_eval_kernel  one element per thread, 256 threads per workgroup: switches on the op code and calls the PRODUCTION function
 //                       (nothing is restated here); kBlockWidth is how many floats an element reads and writes.
@@ -127,7 +128,26 @@ __global__ void __launch_bounds__(256) filter_index_kernel(float rx, float ry, f
   index[i] = inside ? filter_axis_index(py, f.dy, inv_ry) * 16 + filter_axis_index(px, f.dx, inv_rx) : -1;
 }
 
+// image_lookup.hpp over arrays (pbrt_hip_image_lookup_eval_device): the slot's three rows, the texel pool, (u, v) -> Kd, the
+// mapping formed as render_body.inc forms it
+__global__ void __launch_bounds__(256) image_lookup_eval_kernel(const float4 *rows, const float4 *pool, int64_t n, const float *uv, float *rgb) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 t0 = rows[0], t1 = rows[1], t2 = rows[2];
+  const float tu = uv[2 * i], tv = uv[2 * i + 1];
+  const float ss = t1.w * tu + t2.y, tt = t2.x * tv + t2.z;
+  float r, g, b;
+  image::lookup(pool, t0, t2.w, ss, tt, &r, &g, &b);
+  rgb[3 * i] = r; rgb[3 * i + 1] = g; rgb[3 * i + 2] = b;
+}
+
 }  // namespace
+
+hipError_t launch_image_lookup_eval(const float4 *rows, const float4 *pool, int64_t n, const float *uv, float *rgb, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(image_lookup_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, rows, pool, n, uv, rgb);
+  return hipGetLastError();
+}
 
 hipError_t launch_filter_footprint_eval(float rx, float ry, const int32_t crop[4], int64_t n_points, const float *points, int32_t *bounds, int64_t n_pairs,
                                         const float *pair_points, const int32_t *pair_pixels, int32_t *index, hipStream_t stream) {

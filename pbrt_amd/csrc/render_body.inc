@@ -194,10 +194,15 @@
                 sphere_uv(ng.x, ng.y, ng.z, &tu, &tv);
               }
               const float ss = t1.w * tu + t2.y, tt = t2.x * tv + t2.z;
-              // the cell's parity taken in FLOAT (an (int) cast of a huge or non-finite s saturates on the GPU and is undefined on the host:
-              // ADVICE r05): f - 2 floor(f / 2) is 0 or 1 exactly while f is an integer below 2^24, 0 beyond (every such float is even), NaN -> tex2
-              const float cf = floorf(ss) + floorf(tt);
-              k = (cf - 2.0f * floorf(0.5f * cf)) == 0.f ? mk(t0.y, t0.z, t0.w) : mk(t1.x, t1.y, t1.z);
+              if (__float_as_uint(t0.x) == image::kSlotType) {
+                // Kd from an image (DESIGN.md 3.20): the slot's rows hold its size, wrap and filter and its place in the texel pool
+                image::lookup(R.image_texels, t0, t2.w, ss, tt, &k.x, &k.y, &k.z);
+              } else {
+                // the cell's parity taken in FLOAT (an (int) cast of a huge or non-finite s saturates on the GPU and is undefined on the host:
+                // ADVICE r05): f - 2 floor(f / 2) is 0 or 1 exactly while f is an integer below 2^24, 0 beyond (every such float is even), NaN -> tex2
+                const float cf = floorf(ss) + floorf(tt);
+                k = (cf - 2.0f * floorf(0.5f * cf)) == 0.f ? mk(t0.y, t0.z, t0.w) : mk(t1.x, t1.y, t1.z);
+              }
             }
             V3 sh_d = {0.f, 0.f, 1.f};
             float sh_tmax = kInf;

@@ -236,7 +236,7 @@ std::string dequote(const std::string &s) { return s.substr(1, s.size() - 2); }
 struct MaterialDef {
   uint32_t type = 0;  // matte
   float k[3] = {0.5f, 0.5f, 0.5f};
-  uint32_t kd_tex = 0;  // 1 + index into LoadedScene::textures when "texture Kd" names a checkerboard
+  uint32_t kd_tex = 0;  // 1 + index into LoadedScene::textures when "texture Kd" names a checkerboard or an image map
   float kt[3] = {1.f, 1.f, 1.f};  // glass (type 2): k = Kr, kt = Kt, eta = the index of refraction
   float eta = 1.5f;
 };
@@ -261,7 +261,7 @@ struct Api {
   std::vector<std::pair<Xform, Xform>> pushed_ctm;
   std::vector<uint32_t> pushed_bits;
   std::map<std::string, std::array<float, 3>> spectrum_textures;
-  std::map<std::string, uint32_t> checker_textures;  // name -> 1 + index into out->textures
+  std::map<std::string, uint32_t> checker_textures;  // name -> 1 + index into out->textures: the checkerboards and the image maps (3.15, 3.20)
   std::map<std::string, MaterialDef> named_materials;
   std::map<std::tuple<uint32_t, float, float, float, float, float, float, uint32_t, float, float, float, float>, uint16_t> material_ids;
   bool camera_set = false;
@@ -347,7 +347,7 @@ struct Api {
     MaterialDef m;
     if (type == "matte") {
       m.type = 0;
-      if (const ParamItem *p = ps.find("Kd", "texture")) {  // a checkerboard keeps its pattern; k = its mean colour (spheres, fallbacks)
+      if (const ParamItem *p = ps.find("Kd", "texture")) {  // a checkerboard / an image map keeps its pattern; k = its mean colour (spheres, fallbacks)
         if (p->strs.size() == 1) {
           auto it = checker_textures.find(p->strs[0]);
           if (it != checker_textures.end()) m.kd_tex = it->second;
@@ -398,10 +398,81 @@ struct Api {
     return id;
   }
 
+  // Texture "name" "spectrum" "imagemap" (pbrt-v3 ImageTexture): the image read through pbrt_hip_read_image (PNG / PFM; a
+  // relative name against the scene file's directory), "bool gamma" (default: true for .png) = pbrt-v3's InverseGammaCorrect, then "float
+  // scale"; with the "uv" mapping it becomes a pbrt_hip_image_texture record that a matte Kd can name, and *mean = the mean texel, which is
+  // what every other parameter gets.  A file that cannot be used: a warning and grey 0.5, never an error.
+  void image_map(const std::string &name, const ParamSet &ps, std::array<float, 3> *mean) {
+    const std::string file = ps.one_string("filename", "");
+    const std::string wrap = ps.one_string("wrap", "repeat"), filter = ps.one_string("filter", "bilinear"), mapping = ps.one_string("mapping", "uv");
+    const float scale = ps.one_float("scale", 1.f);
+    const bool png = file.size() >= 4 && (file.compare(file.size() - 4, 4, ".png") == 0 || file.compare(file.size() - 4, 4, ".PNG") == 0);
+    const bool gamma = ps.one_bool("gamma", png);
+    const bool asked_trilinear = ps.find("trilinear", "bool") != nullptr, asked_aniso = ps.find("maxanisotropy", "float") != nullptr;
+    if (asked_trilinear || asked_aniso)
+      warn("Texture \"" + name + "\" (imagemap): \"trilinear\" / \"maxanisotropy\" are ignored (there is no mip map: the lookup is bilinear or point)");
+    pbrt_hip_image_texture t{};
+    t.type = PBRT_HIP_TEXTURE_IMAGE;
+    t.su = ps.one_float("uscale", 1.f); t.sv = ps.one_float("vscale", 1.f);
+    t.du = ps.one_float("udelta", 0.f); t.dv = ps.one_float("vdelta", 0.f);
+    const std::string path = (file.empty() || file[0] == '/' || cur_dir.empty()) ? file : cur_dir + "/" + file;
+    int32_t w = 0, h = 0;
+    std::vector<float> rgb;
+    bool ok = !file.empty() && pbrt_hip_read_image(path.c_str(), nullptr, &w, &h) == PBRT_HIP_OK && w > 0 && h > 0 && (uint32_t)w <= PBRT_HIP_IMAGE_MAX_SIZE &&
+              (uint32_t)h <= PBRT_HIP_IMAGE_MAX_SIZE && out->image_texels + (uint64_t)w * (uint64_t)h <= PBRT_HIP_IMAGE_MAX_TEXELS;
+    if (ok) {
+      rgb.resize(3 * (size_t)w * (size_t)h);
+      ok = pbrt_hip_read_image(path.c_str(), rgb.data(), &w, &h) == PBRT_HIP_OK;
+    }
+    for (size_t i = 0; ok && i < rgb.size(); i++) {
+      float v = rgb[i];
+      if (gamma) v = v <= 0.04045f ? v * (1.0f / 12.92f) : (float)std::pow(((double)v + 0.055) / 1.055, 2.4);  // pbrt-v3 InverseGammaCorrect, rounded once
+      rgb[i] = v * scale;
+      ok = std::isfinite(rgb[i]) && rgb[i] >= 0.f;
+    }
+    if (!ok) {
+      warn("Texture \"" + name + "\" (imagemap): \"" + file + "\" cannot be used (missing, unreadable, larger than 16384 x 16384 or 2^26 texels in all, or texels that are negative / not finite): replaced by grey 0.5");
+      return;
+    }
+    double sum[3] = {0, 0, 0};
+    for (size_t i = 0; i < rgb.size(); i++) sum[i % 3] += (double)rgb[i];
+    for (int k = 0; k < 3; k++) (*mean)[k] = (float)(sum[k] / ((double)w * (double)h));
+    if (wrap == "repeat") t.wrap = PBRT_HIP_WRAP_REPEAT;
+    else if (wrap == "clamp") t.wrap = PBRT_HIP_WRAP_CLAMP;
+    else if (wrap == "black") t.wrap = PBRT_HIP_WRAP_BLACK;
+    else warn("Texture \"" + name + "\" (imagemap): unknown wrap \"" + wrap + "\", \"repeat\" used");
+    if (filter == "point") t.filter = PBRT_HIP_TEXFILTER_POINT;
+    else {
+      t.filter = PBRT_HIP_TEXFILTER_BILINEAR;
+      if (filter != "bilinear") warn("Texture \"" + name + "\" (imagemap): unknown filter \"" + filter + "\", \"bilinear\" used");
+    }
+    if (mapping != "uv") {
+      warn("Texture \"" + name + "\" (imagemap): only the \"uv\" mapping keeps its image, replaced by the image's mean colour");
+      return;
+    }
+    if (!std::isfinite(t.su) || !std::isfinite(t.sv) || !std::isfinite(t.du) || !std::isfinite(t.dv)) {
+      warn("Texture \"" + name + "\" (imagemap): a mapping that is not finite, replaced by the image's mean colour");
+      return;
+    }
+    if (out->image_rgb.size() >= PBRT_HIP_IMAGE_MAX_SLOTS) {
+      warn("Texture \"" + name + "\" (imagemap): more than 64 image textures, replaced by the image's mean colour");
+      return;
+    }
+    t.width = (uint32_t)w; t.height = (uint32_t)h;
+    out->image_texels += (uint64_t)w * (uint64_t)h;
+    out->image_rgb.emplace_back(std::move(rgb));
+    t.rgb = out->image_rgb.back().data();  // (an inner vector is filled once and keeps its storage when the outer one grows)
+    pbrt_hip_texture slot{};
+    static_assert(sizeof slot == sizeof t, "an image texture takes one slot of the texture table");
+    std::memcpy(&slot, &t, sizeof slot);
+    out->textures.push_back(slot);
+    checker_textures[name] = (uint32_t)out->textures.size();
+  }
+
   // Texture "name" "spectrum" "class" ... (api.rs:524-580 stores nothing; texture.rs is an empty marker).  On this path: a 2-D
   // CHECKERBOARD over the (u, v) mapping keeps its pattern (pbrt-v3 Checkerboard2DTexture, point-sampled: DESIGN.md 3.15) when a
-  // matte material names it as Kd; every spectrum texture is also reduced to one constant colour, which is what a parameter other
-  // than a matte Kd gets.
+  // matte material names it as Kd, and so does an IMAGEMAP (image_map above: DESIGN.md 3.20); every spectrum texture is also reduced to one
+  // constant colour, which is what a parameter other than a matte Kd gets.
   void texture(const std::string &name, const std::string &kind, const std::string &cls, const ParamSet &ps) {
     if (kind != "spectrum" && kind != "color" && kind != "rgb") return;  // float textures: nothing on the path uses them
     std::array<float, 3> c = {0.5f, 0.5f, 0.5f};
@@ -439,6 +510,8 @@ struct Api {
       spectrum(ps, "tex1", a);
       spectrum(ps, "tex2", b);
       c = {a[0] * b[0], a[1] * b[1], a[2] * b[2]};
+    } else if (cls == "imagemap") {
+      image_map(name, ps, &c);
     } else {
       warn("Texture \"" + name + "\" (" + cls + "): not supported, replaced by grey 0.5");
     }

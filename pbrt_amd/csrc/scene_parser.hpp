@@ -67,7 +67,7 @@ struct LoadedScene {
   std::vector<pbrt_hip_material> mats;
   std::vector<pbrt_hip_light> lights;
   std::vector<pbrt_hip_sphere> spheres;
-  std::vector<pbrt_hip_texture> textures;  // checkerboards named by a material's "texture Kd" 
+  std::vector<pbrt_hip_texture> textures;  // checkerboards and image maps named by a material's "texture Kd" 
   std::vector<float> tri_uv;               // 6 per triangle (corner u, v); empty when no material is textured
   // Shading normals: 9 per triangle -- the world-space normals of its three corners, zeros for a triangle of a mesh without
   // them --, EMPTY when no mesh of the file has normals; else the last slot of `textures` is the pbrt_hip_normals record that points into it.
@@ -75,6 +75,10 @@ struct LoadedScene {
   // LightSource "infinite" "string mapname" (DESIGN.md 3.17): the image as read (3 x width x height, row 0 = theta 0).  The slot of
   // `textures` that is its pbrt_hip_envmap record points into it, and the light (type 3) carries that slot's number; at most one.
   std::vector<float> env_rgb;
+  // Texture "imagemap" (DESIGN.md 3.20): the texels of every image map that became a pbrt_hip_image_texture record of `textures`, gamma and
+  // scale applied (3 x width x height each, row 0 = the image's top); the records point into them.  image_texels = their texel count.
+  std::vector<std::vector<float>> image_rgb;
+  uint64_t image_texels = 0;
   // RenderOptions (api.rs:201-249) resolved to values
   float cam_to_world[16];
   float fov = 90.f;

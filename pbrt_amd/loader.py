@@ -6,7 +6,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import EnvMap, Normals, PixelFilter, RenderDesc, SceneDesc, check, lib
+from ._lib import EnvMap, ImageTexture, Normals, PixelFilter, RenderDesc, SceneDesc, check, lib
 from .api import GLASS, SceneData
 
 
@@ -63,8 +63,21 @@ def _collect(h):
         if flt_slots:
             pf = PixelFilter.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[flt_slots[0]]), C.sizeof(PixelFilter))))
             pixel_filter = (int(pf.kind), float(pf.param[0]), float(pf.param[1]))
+        # (an image texture's record, DESIGN.md 3.20, is a slot whose first word is 4: its texels join `images`, and its `textures` row -- in
+        # the slot's own place among the checkerboards -- names them)
+        images = []
+
+        def tex_row(i):
+            t = d.textures[i]
+            if t.type != 4:
+                return [t.type, *t.tex1, *t.tex2, t.su, t.sv, t.du, t.dv]
+            im = ImageTexture.from_buffer_copy(bytes(C.string_at(C.byref(t), C.sizeof(ImageTexture))))
+            images.append(arr(im.rgb, 3 * im.width * im.height, np.float32).reshape(im.height, im.width, 3))
+            return [4, len(images) - 1, im.wrap, im.filter, 0, 0, 0, im.su, im.sv, im.du, im.dv]
+
+        tex_rows = [tex_row(i) for i in tex_slots]
         sd = SceneData(
-            pixel_filter=pixel_filter, tri_n=tri_n, envmap=envmap, envmap_world_to_light=env_m,
+            images=images, pixel_filter=pixel_filter, tri_n=tri_n, envmap=envmap, envmap_world_to_light=env_m,
             P=arr(d.P, 3 * d.n_verts, np.float32).reshape(-1, 3), idx=arr(d.idx, 3 * d.n_tris, np.uint32).reshape(-1, 3),
             mat_id=arr(d.mat_id, d.n_tris, np.uint16),
             materials=np.array([[d.mats[i].type, *d.mats[i].k, *d.mats[i].le] for i in range(d.n_mats)], np.float32).reshape(-1, 7),
@@ -75,8 +88,7 @@ def _collect(h):
             mat_tex=np.array([0 if d.mats[i].type == GLASS else renum[d.mats[i].kd_tex] for i in range(d.n_mats)], np.uint32),
             mat_eta=(np.array([d.mats[i].kd_tex if d.mats[i].type == GLASS else 0x3FC00000 for i in range(d.n_mats)], np.uint32).view(np.float32)
                      if any(d.mats[i].type == GLASS for i in range(d.n_mats)) else np.zeros(0, np.float32)),
-            textures=np.array([[d.textures[i].type, *d.textures[i].tex1, *d.textures[i].tex2, d.textures[i].su, d.textures[i].sv, d.textures[i].du,
-                                d.textures[i].dv] for i in tex_slots], np.float32).reshape(-1, 11),
+            textures=np.array(tex_rows, np.float32).reshape(-1, 11),
             tri_uv=(arr(d.tri_uv, 6 * d.n_tris, np.float32).reshape(-1, 6) if d.tri_uv else np.zeros((0, 6), np.float32))).normalized()
         wbuf = C.create_string_buffer(1 << 16)
         nw = l.pbrt_hip_loaded_warnings(h, wbuf, len(wbuf))

@@ -322,6 +322,64 @@ def envmap_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), sky=None, world_
     ).normalized()
 
 
+def procedural_planks(width=64, height=64):
+    """A generated pattern for the image-texture demos, (height, width, 3) float32 in [0, 1], row 0 = the top: four planks
+    with a darker joint between them, a grain that runs along each, and one knot -- nothing that a constant or a checkerboard could be."""
+    y, x = np.mgrid[0:height, 0:width].astype(np.float64)
+    u, v = (x + 0.5) / width, (y + 0.5) / height
+    plank = np.floor(v * 4.0)
+    grain = 0.5 + 0.5 * np.sin(2.0 * np.pi * (v * 24.0 + 0.35 * np.sin(2.0 * np.pi * (u * 2.0 + plank * 0.37))))
+    tone = 0.55 + 0.12 * np.sin(plank * 2.1 + 0.4) + 0.18 * grain
+    knot = np.exp(-(((u - 0.3) / 0.06) ** 2 + ((v - 0.62) / 0.04) ** 2))
+    tone = tone * (1.0 - 0.6 * knot)
+    joint = np.minimum(v * 4.0 - plank, 1.0 - (v * 4.0 - plank)) < 0.04
+    tone = np.where(joint, 0.18, tone)
+    rgb = np.stack([tone * 0.95, tone * 0.62, tone * 0.34], -1)
+    return np.clip(rgb, 0.0, 1.0).astype(np.float32)
+
+
+def write_demo_textures(directory):
+    """scenes/textures/planks.png, the image scenes/textured_cornell.pbrt names: procedural_planks through the library's own PNG writer (the build calls this,
+    build.py ensure_demo_textures: the file is a build product)"""
+    import os
+
+    from .api import write_image
+    os.makedirs(directory, exist_ok=True)
+    write_image(os.path.join(directory, "planks.png"), procedural_planks())
+
+
+def image_plane_scene(res=256, image=None, wrap="repeat", filter="bilinear", mapping=(3.0, 3.0, 0.0, 0.0)):
+    """A matte plane z = 0 whose Kd is an image under a distant light and a dim sky, seen from above at an angle: the
+    quad's corner (u, v) are (0,0) (1,0) (1,1) (0,1), the image (default: procedural_planks) repeats three times either way."""
+    from .api import image_texture_row
+    image = procedural_planks() if image is None else image
+    v, t = _quad((-4, -4, 0), (4, -4, 0), (4, 4, 0), (-4, 4, 0))
+    return SceneData(
+        P=np.array(v, np.float32), idx=np.array(t, np.uint32), mat_id=np.zeros(2, np.uint16), materials=np.array([_mat(MATTE, (0.5, 0.5, 0.5))], np.float32),
+        lights=np.array([[LIGHT_DISTANT, 0.3, -0.2, 0.9327379, 3.0, 3.0, 3.0], [LIGHT_INFINITE, 0, 0, 0, 0.2, 0.25, 0.3]], np.float32),
+        mat_tex=np.array([1], np.uint32), textures=np.array([image_texture_row(0, wrap, filter, mapping)], np.float32), images=[image],
+        tri_uv=np.array([[0, 0, 1, 0, 1, 1], [0, 0, 1, 1, 0, 1]], np.float32),
+        cam_to_world=_camera((0.5, -6.0, 4.0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=res, yres=res).normalized()
+
+
+def textured_cornell_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), image=None):
+    """cornell_scene with a plank floor and back wall: their Kd is an image (default: procedural_planks as linear texels --
+    what scenes/textured_cornell.pbrt reads back from its PNG but for the 8-bit rounding), repeated twice across each; every quad carries
+    the corner (u, v) (0,0) (1,0) (1,1) (0,1)."""
+    from .api import image_texture_row
+    sd = cornell_scene(xres, yres, crop)
+    if image is None:
+        image = procedural_planks()
+    sd.materials = np.concatenate([sd.materials, [_mat(MATTE, tuple(image.astype(np.float64).mean((0, 1))))]]).astype(np.float32)
+    sd.mat_id = sd.mat_id.copy()
+    sd.mat_id[0:2] = sd.mat_id[4:6] = len(sd.materials) - 1  # floor, back wall
+    sd.mat_tex = np.array([0] * (len(sd.materials) - 1) + [1], np.uint32)
+    sd.textures = np.array([image_texture_row(0, "repeat", "bilinear", (2.0, 2.0, 0.0, 0.0))], np.float32)
+    sd.images = [image]
+    sd.tri_uv = np.tile(np.array([[0, 0, 1, 0, 1, 1], [0, 0, 1, 1, 0, 1]], np.float32), (len(sd.idx) // 2, 1))
+    return sd.normalized()
+
+
 def big_mesh_scene(xres=2048, yres=2048, crop=(0.0, 1.0, 0.0, 1.0), n_tris=12_000_000):
     """The OUT-OF-CACHE workload of bench.py (`--workload big`): the C2 / C3 scene with 12M triangles -- 0.31 GB of
     quantised nodes + 0.58 GB of triangle records, well past the 256 MiB Infinity Cache -- the one regime in which HBM

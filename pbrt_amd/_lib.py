@@ -38,6 +38,23 @@ class ImageTexture(C.Structure):
                 ("su", C.c_float), ("sv", C.c_float), ("du", C.c_float), ("dv", C.c_float), ("filter", C.c_uint32), ("pad", C.c_uint32 * 5)]
 
 
+# the first word of a slot of the texture table: which of the five record classes above the slot IS
+SLOT_CHECKER, SLOT_ENVMAP, SLOT_NORMALS, SLOT_FILTER, SLOT_IMAGE = range(5)
+SLOT_BYTES = C.sizeof(Texture)
+assert all(C.sizeof(cls) == SLOT_BYTES == 64 for cls in (EnvMap, Normals, PixelFilter, ImageTexture))
+
+
+def put_slot(table, i, rec):
+    """record `rec` into slot i of a ctypes array of 64-byte slots (any mirror of pbrt_hip_texture)"""
+    assert C.sizeof(rec) == SLOT_BYTES == C.sizeof(table._type_)
+    C.memmove(C.byref(table, i * SLOT_BYTES), C.byref(rec), SLOT_BYTES)
+
+
+def read_slot(table, i, cls):
+    """slot i of a ctypes array of / pointer to 64-byte slots, read as a `cls`"""
+    return cls.from_buffer_copy(C.string_at(C.byref(table[i]), SLOT_BYTES))
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_uint32), ("p", C.c_float * 3), ("c", C.c_float * 3), ("pad", C.c_float)]
 

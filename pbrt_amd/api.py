@@ -126,38 +126,25 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         if int(m[0]) == GLASS:  # include/pbrt_hip.h: k = Kr, le = Kt, kd_tex = the IEEE-754 bits of eta
             eta = sd.mat_eta[i:i + 1] if len(sd.mat_eta) else np.array([1.5], np.float32)
             mats[i].kd_tex = int(eta.view(np.uint32)[0])
+    # the table: every `textures` row in its own slot (mat_tex numbering does not move), then the records that travel with the scene, each in a
+    # slot of its own -- the map's, the pixel filter's, the normals' (include/pbrt_hip.h pbrt_hip_envmap / _pixel_filter / _normals), in this order
+    records = [image_record(sd.images[int(t[1])], int(t[2]), int(t[3]), t[7:11]) if int(t[0]) == TEXTURE_IMAGE else checker_record(t) for t in sd.textures]
+    has_env = sd.envmap.size > 0
+    if has_env:
+        records.append(EnvMap(type=_lib.SLOT_ENVMAP, width=sd.envmap.shape[1], height=sd.envmap.shape[0], rgb=_fp(sd.envmap),
+                              world_to_light=tuple(float(x) for x in sd.envmap_world_to_light.reshape(-1))))
+    if sd.pixel_filter is not None:
+        records.append(pixel_filter_record(sd.pixel_filter))
+    if sd.tri_n.shape[0]:
+        records.append(Normals(type=_lib.SLOT_NORMALS, n_tris=sd.tri_n.shape[0], tri_n=_fp(sd.tri_n)))
     texs = None
-    has_env = sd.envmap.size > 0  # the map's record takes a slot of its own behind the checkerboards (include/pbrt_hip.h pbrt_hip_envmap)
-    has_nrm = sd.tri_n.shape[0] > 0  # the normals' record: the last slot (include/pbrt_hip.h pbrt_hip_normals)
-    has_flt = sd.pixel_filter is not None  # the pixel filter's record: behind the map's (include/pbrt_hip.h pbrt_hip_pixel_filter)
-    if len(sd.textures) or has_env or has_nrm or has_flt:
+    if records:
         tex_t = tex_t or dict(desc._fields_)["textures"]._type_  # (the Texture class of the caller's own struct mirror)
-        texs = (tex_t * (len(sd.textures) + int(has_env) + int(has_flt) + int(has_nrm)))()
-        for i, t in enumerate(sd.textures):
-            if int(t[0]) == TEXTURE_IMAGE:  # the image's record in the row's own slot: mat_tex numbering does not move
-                rec = image_record(sd.images[int(t[1])], int(t[2]), int(t[3]), t[7:11])
-                assert C.sizeof(rec) == C.sizeof(tex_t)
-                C.memmove(C.byref(texs, i * C.sizeof(tex_t)), C.byref(rec), C.sizeof(rec))
-                continue
-            texs[i].type = int(t[0])
-            texs[i].tex1[:] = [float(x) for x in t[1:4]]
-            texs[i].tex2[:] = [float(x) for x in t[4:7]]
-            texs[i].su, texs[i].sv, texs[i].du, texs[i].dv = (float(x) for x in t[7:11])
-        if has_env:
-            e = EnvMap(type=1, width=sd.envmap.shape[1], height=sd.envmap.shape[0], rgb=_fp(sd.envmap))
-            e.world_to_light[:] = [float(x) for x in sd.envmap_world_to_light.reshape(-1)]
-            assert C.sizeof(e) == C.sizeof(tex_t)
-            C.memmove(C.byref(texs, len(sd.textures) * C.sizeof(tex_t)), C.byref(e), C.sizeof(e))
-        if has_flt:
-            pf = pixel_filter_record(sd.pixel_filter)
-            assert C.sizeof(pf) == C.sizeof(tex_t)
-            C.memmove(C.byref(texs, (len(sd.textures) + int(has_env)) * C.sizeof(tex_t)), C.byref(pf), C.sizeof(pf))
-        if has_nrm:
-            nr = Normals(type=2, n_tris=sd.tri_n.shape[0], tri_n=_fp(sd.tri_n))
-            assert C.sizeof(nr) == C.sizeof(tex_t)
-            C.memmove(C.byref(texs, (len(sd.textures) + int(has_env) + int(has_flt)) * C.sizeof(tex_t)), C.byref(nr), C.sizeof(nr))
+        texs = (tex_t * len(records))()
+        for i, rec in enumerate(records):
+            _lib.put_slot(texs, i, rec)
         desc.textures = texs
-    desc.n_textures = len(sd.textures) + int(has_env) + int(has_flt) + int(has_nrm)
+    desc.n_textures = len(records)
     if sd.tri_uv.shape[0]:
         desc.tri_uv = _fp(sd.tri_uv)
     lights = (light_t * max(len(sd.lights), 1))()
@@ -189,6 +176,12 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
     desc.yres = int(sd.yres)
     desc.crop[:] = [float(x) for x in sd.crop]
     return [mats, lights, spheres, texs, sd]
+
+
+def checker_record(row):
+    """the pbrt_hip_texture record of a SceneData.textures row (type, tex1 rgb, tex2 rgb, su, sv, du, dv)"""
+    su, sv, du, dv = (float(x) for x in row[7:11])
+    return Texture(type=int(row[0]), tex1=tuple(float(x) for x in row[1:4]), tex2=tuple(float(x) for x in row[4:7]), su=su, sv=sv, du=du, dv=dv)
 
 
 def image_record(image, wrap=WRAP_REPEAT, filter=TEXFILTER_BILINEAR, mapping=(1.0, 1.0, 0.0, 0.0)):

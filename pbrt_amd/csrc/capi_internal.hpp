@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <exception>
+#include <optional>
 #include <string>
 
 #include "../../include/pbrt_hip.h"
@@ -87,8 +88,13 @@ struct SceneArrays {
 };
 static_assert(sizeof(SceneArrays) == 22 * sizeof(DevBuf<float>), "an array of SceneArrays is missing from SceneArrays::for_each");
 
-// What a scene is beside its arrays, its host tree and its description: plain values, which a clone takes in one assignment
+struct FilmWindow {  // of a description: all that a finished scene keeps of pbrt_hip_scene_desc beside what went to the device
+  int32_t xres = 0, yres = 0;
+  float crop[4] = {0.f, 1.f, 0.f, 1.f};
+};
+// What a scene is beside its arrays and its host tree: plain values, which a clone takes in one assignment
 struct SceneTraits {
+  FilmWindow window;
   uint32_t n_prims = 0;  // primitives of the tree: dev.n_tris triangles + the spheres
   bool gpu_built = false;  // accelerator built on the device: the canonical tree (counter flags) is made on first use
   uint32_t n_quads_gpu = 0;
@@ -98,10 +104,7 @@ struct SceneTraits {
   uint32_t env_w = 0, env_h = 0;
   float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
   bool normals = false;  // the texture table held a pbrt_hip_normals record: render_kernel_n renders the scene
-  // the texture table held a pbrt_hip_pixel_filter record: every render of the scene is a wide one.  The record itself, as
-  // the one slot of a table: the scene's own description points at it (bind_scene_filter), which is how film_geom learns of the filter
-  bool has_filter = false;
-  pbrt_hip_texture filter_slot{};
+  std::optional<pbrt_hip_pixel_filter> filter;  // the texture table's pixel filter record, if it held one: every render is a wide one
   BuildStats build;
 };
 }  // namespace pbrt_hip
@@ -117,7 +120,6 @@ struct SceneTraits {
 struct pbrt_hip_scene : pbrt_hip::SceneStream, pbrt_hip::SceneArrays, pbrt_hip::SceneTraits {
   int device = 0;
   uint32_t n_cu = 256;  // hipDeviceProp_t::multiProcessorCount of `device`
-  pbrt_hip_scene_desc desc{};  // scalar fields only; pointers are cleared
   pbrt_hip::Bvh bvh;
   pbrt_hip::DevScene dev{};
   // per-render scratch
@@ -153,9 +155,6 @@ namespace pbrt_hip {
 int ensure_canonical(pbrt_hip_scene *s);
 // the array pointers of s->dev from the scene's buffers: the one place that sets them (scene creation, ensure_canonical, clone_scene)
 void bind_scene_arrays(pbrt_hip_scene *s);
-// s->desc's texture table: the scene's own filter slot (SceneTraits::filter_slot) or nothing -- the caller's table is not kept (scene
-// creation, clone_scene)
-void bind_scene_filter(pbrt_hip_scene *s);
 
 // ---- film geometry (capi_render.cpp) ----
 // Film geometry of one render: the cropped window (film.rs:92-101), the sample bounds (film.rs:166-175) and whether the
@@ -170,7 +169,7 @@ struct FilmGeom {
   int32_t crop_h() const { return crop[3] > crop[1] ? crop[3] - crop[1] : 0; }
   size_t crop_px() const { return (size_t)crop_w() * (size_t)crop_h(); }
 };
-// (a filter width of 0 is the default radius 0.5, as in pbrt_hip_render_desc; a description whose texture table holds a pixel filter's
-// record, DESIGN.md 3.19: 0 is that kind's default radius and the geometry is the wide one at every radius)
-FilmGeom film_geom(const pbrt_hip_scene_desc &d, float filter_xwidth = 0.f, float filter_ywidth = 0.f);
+// (a filter width of 0 is the default radius 0.5; under a pixel filter's record, DESIGN.md 3.19 -- `filter`, NULL: the box --, it is that
+// kind's default radius, and the geometry is the wide one at every radius)
+FilmGeom film_geom(const FilmWindow &w, const pbrt_hip_pixel_filter *filter = nullptr, float filter_xwidth = 0.f, float filter_ywidth = 0.f);
 }  // namespace pbrt_hip

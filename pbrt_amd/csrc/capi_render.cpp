@@ -34,18 +34,17 @@ void sample_bounds(const int32_t c[4], float rx, float ry, int32_t sb[4]) {
 }
 }  // namespace
 
-FilmGeom film_geom(const pbrt_hip_scene_desc &d, float filter_xwidth, float filter_ywidth) {
+FilmGeom film_geom(const FilmWindow &w, const pbrt_hip_pixel_filter *filter, float filter_xwidth, float filter_ywidth) {
   FilmGeom g;
   g.rx = filter_radius(filter_xwidth);
   g.ry = filter_radius(filter_ywidth);
   g.wide = filter_is_wide(g.rx, g.ry);
-  pbrt_hip_pixel_filter pf;
-  if (find_filter(d, &pf)) {  // a weighted filter: its kind's default radii, and the fixed-point film at every radius
-    g.rx = filter_radius_of(pf, filter_xwidth);
-    g.ry = filter_radius_of(pf, filter_ywidth);
+  if (filter) {  // a weighted filter: its kind's default radii, and the fixed-point film at every radius
+    g.rx = filter_radius_of(*filter, filter_xwidth);
+    g.ry = filter_radius_of(*filter, filter_ywidth);
     g.wide = true;
   }
-  film_cropped_bounds(d.xres, d.yres, d.crop, g.crop);
+  film_cropped_bounds(w.xres, w.yres, w.crop, g.crop);
   g.pad_x = g.pad_y = 0;
   for (int k = 0; k < 4; k++) g.sb[k] = g.crop[k];
   if (g.wide) {
@@ -63,9 +62,9 @@ FilmGeom film_geom(const pbrt_hip_scene_desc &d, float filter_xwidth, float filt
 
 namespace {
 
-FilmGeom film_geom(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r) { return pbrt_hip::film_geom(s->desc, r->filter_xwidth, r->filter_ywidth); }
-// the scene's pixel filter record (s->has_filter)
-pbrt_hip_pixel_filter scene_filter(const pbrt_hip_scene *s) { return filter_slot(&s->filter_slot, 0); }
+FilmGeom film_geom(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
+  return pbrt_hip::film_geom(s->window, s->filter ? &*s->filter : nullptr, r->filter_xwidth, r->filter_ywidth);
+}
 // number of 64x64 super-tiles a rank owns, and the grid of super-tiles
 struct Shard {
   int32_t w, h;
@@ -148,8 +147,8 @@ int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
   if (r->max_depth > PBRT_HIP_MAX_DEPTH) return fail(PBRT_HIP_ERR_LIMIT, "render: maxdepth above 1023");
   // box filter radii, box.rs:57-61 (0 = the default 0.5): any positive radius up to 16 pixels; a weighted filter's likewise (0 = its
   // kind's default)
-  const float fx = s->has_filter ? filter_radius_of(scene_filter(s), r->filter_xwidth) : filter_radius(r->filter_xwidth);
-  const float fy = s->has_filter ? filter_radius_of(scene_filter(s), r->filter_ywidth) : filter_radius(r->filter_ywidth);
+  const float fx = s->filter ? filter_radius_of(*s->filter, r->filter_xwidth) : filter_radius(r->filter_xwidth);
+  const float fy = s->filter ? filter_radius_of(*s->filter, r->filter_ywidth) : filter_radius(r->filter_ywidth);
   if (!(fx > 0.f) || !(fy > 0.f) || !std::isfinite(fx) || !std::isfinite(fy)) return fail(PBRT_HIP_ERR_INVALID, "render: the filter radii must be positive");
   if (fx > 16.f || fy > 16.f) return fail(PBRT_HIP_ERR_LIMIT, "render: filter radius above 16 pixels");
   // the combinations of switches the library does not build
@@ -163,11 +162,11 @@ int check_render_desc(const pbrt_hip_scene *s, const pbrt_hip_render_desc *r) {
     const uint64_t foot = (uint64_t)(2 * (int)std::ceil(fx) + 1) * (uint64_t)(2 * (int)std::ceil(fy) + 1);
     if ((uint64_t)r->spp_x * (uint64_t)r->spp_y * foot > (1ull << 24))
       return fail(PBRT_HIP_ERR_LIMIT, "render: samples per pixel x filter footprint above 2^24 (the fixed-point film's accumulators could wrap)");
-    if (s->has_filter) {
+    if (s->filter) {
       // 3.19: a sample adds at most |w| x 2^39 units, so the same rule with the table's largest weight in the product (a triangle filter
       // of radius 16 has weights up to 240.25, which count as 241); the kernel's 1 / radius must be a number
       if (!std::isfinite(1.0f / fx) || !std::isfinite(1.0f / fy)) return fail(PBRT_HIP_ERR_INVALID, "render: the filter radii must be positive");
-      const pbrt_hip_pixel_filter pf = scene_filter(s);
+      const pbrt_hip_pixel_filter &pf = *s->filter;
       float table[256], wmax = 0.f;
       filter_table(pf, fx, fy, table);
       for (float w : table) wmax = std::max(wmax, std::fabs(w));
@@ -252,7 +251,7 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
   // the stride: 26 MB at most, and one layout for every instantiation); with another box filter radius 16 x 2 x 64 more
   // behind them (kWideSlotFloat4: a chunk's sums per footprint)
   HIP_TRY(s->d_lane_state.grow((size_t)L.n_workgroups * (L.variant.wide ? 320 + 2048 : 320)));
-  if (s->has_filter) HIP_TRY(s->d_filter_table.grow(kFilterTableFloats));  // a weighted filter: its 256 weights and the two inverse radii
+  if (s->filter) HIP_TRY(s->d_filter_table.grow(kFilterTableFloats));  // a weighted filter: its 256 weights and the two inverse radii
   if (!L.variant.wide) {
     const size_t need = (size_t)L.pass_tiles * 4096u * (1u << L.chunk_shift);  // one float4 per item of a pass
     // (C3 1.07 GB in one pass; C4's 4096^2 x 16 chunks on one GPU: 3 passes over 1.43 GB; the buffer follows the frame: released when a
@@ -377,7 +376,7 @@ int pbrt_hip_render_device(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, voi
     RenderParams R;
     R.sx0 = fg.sb[0]; R.sy0 = fg.sb[1]; R.sw = sh.w; R.sh = sh.h;
     R.seq_x0 = fg.sb[0] + fg.pad_x; R.seq_y0 = fg.sb[1] + fg.pad_y;
-    R.seq_w = (uint32_t)(s->desc.xres + 2 * fg.pad_x); R.seq_h = (uint32_t)(s->desc.yres + 2 * fg.pad_y);
+    R.seq_w = (uint32_t)(s->window.xres + 2 * fg.pad_x); R.seq_h = (uint32_t)(s->window.yres + 2 * fg.pad_y);
     R.max_lum = r->max_sample_luminance > 0.f ? r->max_sample_luminance : std::numeric_limits<float>::infinity();
     R.filter_rx = fg.rx; R.filter_ry = fg.ry;
     R.acc = fg.wide ? (unsigned long long *)d_slab : nullptr;
@@ -422,10 +421,10 @@ int pbrt_hip_render_device(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, voi
     R.partials = fg.wide ? nullptr : s->d_partials.p;
     R.stack_overflow = s->d_stack_overflow.p;
     R.stack_overflow_entries = L.plan.extra_entries;
-    if (s->has_filter) {  // the table of this render's radii (the host copy lives in the scene: the copy is asynchronous)
+    if (s->filter) {  // the table of this render's radii (the host copy lives in the scene: the copy is asynchronous)
       if (s->filter_table_rx != fg.rx || s->filter_table_ry != fg.ry) {
         HIP_TRY(hipStreamSynchronize(st));  // (an earlier copy from the host table may still be queued on this stream)
-        filter_table(scene_filter(s), fg.rx, fg.ry, s->filter_table_host);
+        filter_table(*s->filter, fg.rx, fg.ry, s->filter_table_host);
         s->filter_table_host[kFilterTableInvRx] = 1.0f / fg.rx;
         s->filter_table_host[kFilterTableInvRy] = 1.0f / fg.ry;
         s->filter_table_rx = fg.rx; s->filter_table_ry = fg.ry;
@@ -491,7 +490,7 @@ int pbrt_hip_film_assemble_device(const pbrt_hip_scene *s, const void *d_slab, u
                                   void *d_film, void *stream) {
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "film_assemble: null argument");
   if (world == 0 || rank >= world) return fail(PBRT_HIP_ERR_INVALID, "film_assemble: rank must be < world_size");
-  const Shard sh = make_shard(s->desc.xres, s->desc.yres, s->desc.crop, rank, world);
+  const Shard sh = make_shard(s->window.xres, s->window.yres, s->window.crop, rank, world);
   if (sh.w <= 0 || sh.h <= 0) return PBRT_HIP_OK;  // (an empty crop window: a film of no pixels, which a caller may well hold in a NULL buffer)
   if (!d_film) return fail(PBRT_HIP_ERR_INVALID, "film_assemble: null argument");
   HIP_TRY(hipSetDevice(s->device));
@@ -540,12 +539,12 @@ int64_t pbrt_hip_render_buffer_bytes(const pbrt_hip_scene *s, const pbrt_hip_ren
 
 int pbrt_hip_film_from_acc_device(const pbrt_hip_scene *s, const void *d_acc, void *d_film, void *stream) {
   if (!s) return fail(PBRT_HIP_ERR_INVALID, "film_from_acc: null argument");
-  const size_t n_px = film_geom(s->desc).crop_px();
+  const size_t n_px = film_geom(s->window).crop_px();
   if (!n_px) return PBRT_HIP_OK;  // (an empty crop window)
   if (!d_film) return fail(PBRT_HIP_ERR_INVALID, "film_from_acc: null argument");
   if (n_px && !d_acc) return fail(PBRT_HIP_ERR_INVALID, "film_from_acc: null accumulators");
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(launch_film_from_acc((const unsigned long long *)d_acc, (float4 *)d_film, n_px, s->has_filter, (hipStream_t)stream));
+  HIP_TRY(launch_film_from_acc((const unsigned long long *)d_acc, (float4 *)d_film, n_px, s->filter.has_value(), (hipStream_t)stream));
   return PBRT_HIP_OK;
 }
 

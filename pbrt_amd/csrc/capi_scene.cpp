@@ -23,6 +23,7 @@
 #include "image_texture.hpp"
 #include "pixel_filter.hpp"
 #include "quad_nodes.hpp"
+#include "texture_table.hpp"
 
 using namespace pbrt_hip;
 
@@ -91,32 +92,31 @@ int build_canonical(pbrt_hip_scene *s, const float *P, const uint32_t *idx, uint
 // request (PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE, or PBRT_HIP_BUILDER=host in the environment when the caller left the choice open).
 enum class Builder { kHost, kHostOptimized, kGpu, kGpuPlain };
 
-// a material whose Kd is a texture
-bool kd_textured(const pbrt_hip_material &m) { return m.kd_tex != 0u && m.type == 0u; }
 // the 1-based texture-table number an environment-map light carries as the bits of its `pad`
 uint32_t light_env_slot(const pbrt_hip_light &l) { uint32_t u; std::memcpy(&u, &l.pad, 4); return u; }
 // a glass material's index of refraction: the float whose bits ride in kd_tex
 float glass_eta(const pbrt_hip_material &m) { float e; std::memcpy(&e, &m.kd_tex, 4); return e; }
-// the shading normals' record: a slot of the texture table whose first word is 2, read as the environment map's is
-bool is_normals_slot(const pbrt_hip_texture *textures, uint32_t index) { return textures[index].type == PBRT_HIP_TEXTURE_NORMALS; }
-pbrt_hip_normals normals_slot(const pbrt_hip_texture *textures, uint32_t index) {
-  static_assert(sizeof(pbrt_hip_normals) == sizeof(pbrt_hip_texture), "a pbrt_hip_normals is one slot of the texture table");
-  pbrt_hip_normals n;
-  std::memcpy(&n, textures + index, sizeof(n));
-  return n;
-}
-// the table's normals record into *out; false: the table holds none (check_scene_desc has refused a second one)
-bool find_normals(const pbrt_hip_scene_desc &d, pbrt_hip_normals *out) {
-  for (uint32_t i = 0; i < d.n_textures && d.textures; i++)
-    if (is_normals_slot(d.textures, i)) { *out = normals_slot(d.textures, i); return true; }
-  return false;
-}
 // glass is an interface between index 1 and eta: eta = 1 (index-matched: nothing reflects, nothing bends) is legal; 16 is four times
 // the densest real dielectric and keeps eta^2 and 1 / eta^2 -- the radiance scale of a refraction -- far from fp32's ends
 constexpr float kGlassEtaMin = 1.0f, kGlassEtaMax = 16.0f;
 
-// Every refusal that depends on the description alone, before any HIP call, and the builder that `flags` (and PBRT_HIP_BUILDER) ask for.
-int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *builder) {
+// ---- check_scene_desc in stages: every refusal that depends on the description alone, before any HIP call.  Which of two faults is
+// reported is part of the behaviour, so a concern whose refusals lie apart in that order has a stage for each part: the lights' and the
+// materials' values early and their kinds last, the spheres' material ids and boxes apart from the mesh (check_scene_desc, below, is the order;
+// tests/test_scene_refusals_host.py holds every message and pairs of faults across the stages) ----
+
+// the camera and the crop window
+int check_view(const pbrt_hip_scene_desc *d) {
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(d->cam_to_world[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: camera matrix is not finite");
+  if (!(d->fov > 0.f && d->fov < 180.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: fov must lie in (0, 180) degrees");
+  for (int k = 0; k < 4; k++)  // Film "cropwindow": fractions of the film (film.rs:92-101 multiplies and rounds them up: a NaN or 1e30 there is an int overflow)
+    if (!(d->crop[k] >= 0.f && d->crop[k] <= 1.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: crop window values must lie in [0, 1]");
+  return PBRT_HIP_OK;
+}
+
+// the film's size, the mesh and the spheres: arrays, counts, indices, finite coordinates
+int check_mesh(const pbrt_hip_scene_desc *d) {
   if (d->xres <= 0 || d->yres <= 0) return fail(PBRT_HIP_ERR_INVALID, "scene_create: resolution must be positive");
   if (d->n_tris && (!d->P || !d->idx || !d->mat_id)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: missing mesh arrays");
   if ((d->n_tris || d->n_spheres) && (!d->mats || d->n_mats == 0)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: no materials");
@@ -137,13 +137,47 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
     if (!std::isfinite(sp.c[0]) || !std::isfinite(sp.c[1]) || !std::isfinite(sp.c[2]) || !std::isfinite(sp.r) || !(sp.r > 0.f))
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere centre / radius must be finite and the radius positive");
   }
-  // (a NaN in a light's position or in a colour travels into ray directions and throughputs: a ray that is not a number is pruned by
-  // nothing and walks the whole tree -- minutes per frame on a large scene -- before its sample is dropped as NaN)
+  return PBRT_HIP_OK;
+}
+// ... the spheres' material ids (after it, mats[mat_id[t]] and mats[spheres[s].mat] are there) ...
+int check_sphere_materials(const pbrt_hip_scene_desc *d) {
+  for (uint32_t s = 0; s < d->n_spheres; s++)
+    if (d->spheres[s].mat >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere material id out of range");
+  return PBRT_HIP_OK;
+}
+// ... and their boxes
+int check_sphere_boxes(const pbrt_hip_scene_desc *d) {
+  for (uint32_t s = 0; s < d->n_spheres; s++)  // (a finite centre and radius can still make an infinite box)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(d->spheres[s].c[k] - d->spheres[s].r) || !std::isfinite(d->spheres[s].c[k] + d->spheres[s].r))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: a sphere's bounding box is not finite");
+  return PBRT_HIP_OK;
+}
+
+// (a NaN in a light's position or in a colour travels into ray directions and throughputs: a ray that is not a number is pruned by
+// nothing and walks the whole tree -- minutes per frame on a large scene -- before its sample is dropped as NaN)
+int check_light_values(const pbrt_hip_scene_desc *d) {
   if (d->n_lights && !d->lights) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_lights > 0 but no light table");
   for (uint32_t i = 0; i < d->n_lights; i++)
     for (int k = 0; k < 3; k++)
       if (!std::isfinite(d->lights[i].p[k]) || !std::isfinite(d->lights[i].c[k]))
         return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": position / direction / colour is not finite");
+  return PBRT_HIP_OK;
+}
+int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
+  for (uint32_t i = 0; i < d->n_lights; i++)
+    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+  uint32_t n_env = 0;
+  for (uint32_t i = 0; i < d->n_lights; i++) {  // an environment-map light names a type-1 slot of the texture table; one per scene
+    if (d->lights[i].type != PBRT_HIP_LIGHT_ENVMAP) continue;
+    if (table.named(light_env_slot(d->lights[i])) != SlotKind::kEnvmap)
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": an environment-map light (type 3) must name a type-1 slot of the texture table in `pad`");
+    if (++n_env > 1u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than one environment-map light (type 3)");
+  }
+  return PBRT_HIP_OK;
+}
+
+int check_material_values(const pbrt_hip_scene_desc *d) {
   for (uint32_t i = 0; i < d->n_mats; i++)
     for (int k = 0; k < 3; k++)
       if (d->mats[i].type != PBRT_HIP_MATERIAL_GLASS && (!std::isfinite(d->mats[i].k[k]) || !std::isfinite(d->mats[i].le[k])))
@@ -158,108 +192,113 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
     if (!std::isfinite(eta) || !(eta >= kGlassEtaMin && eta <= kGlassEtaMax))
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": glass eta (the float in kd_tex) must be finite and lie in [1, 16]");
   }
-  for (int k = 0; k < 16; k++)
-    if (!std::isfinite(d->cam_to_world[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: camera matrix is not finite");
-  if (!(d->fov > 0.f && d->fov < 180.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: fov must lie in (0, 180) degrees");
-  for (int k = 0; k < 4; k++)  // Film "cropwindow": fractions of the film (film.rs:92-101 multiplies and rounds them up: a NaN or 1e30 there is an int overflow)
-    if (!(d->crop[k] >= 0.f && d->crop[k] <= 1.f)) return fail(PBRT_HIP_ERR_INVALID, "scene_create: crop window values must lie in [0, 1]");
-  for (uint32_t s = 0; s < d->n_spheres; s++)
-    if (d->spheres[s].mat >= d->n_mats) return fail(PBRT_HIP_ERR_INVALID, "scene_create: sphere material id out of range");
-  if (d->n_textures && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_textures > 0 but no texture table");
+  return PBRT_HIP_OK;
+}
+// what the materials' kd_tex name
+int check_kd_tex(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   for (uint32_t i = 0; i < d->n_mats; i++) {
     if (d->mats[i].type == PBRT_HIP_MATERIAL_GLASS) continue;  // (kd_tex holds eta)
-    if (d->mats[i].kd_tex > d->n_textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
-    if (d->mats[i].kd_tex && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: textured material but no texture table");
+    if (table.named(d->mats[i].kd_tex) == SlotKind::kOutOfRange) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
   }
-  for (uint32_t i = 0; i < d->n_mats; i++)  // (a texture for Kd is a checkerboard, type 0, or an image, type 4: a type-1 slot is a light's map)
-    if (kd_textured(d->mats[i]) && is_envmap_slot(d->textures, d->mats[i].kd_tex - 1u))
-      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names an environment map, which is not a texture for Kd");
+  for (uint32_t i = 0; i < d->n_mats; i++) {  // (a texture for Kd is a checkerboard or an image; a slot of no known kind is check_table's to refuse)
+    if (!kd_textured(d->mats[i])) continue;
+    const char *names = nullptr;
+    switch (table.named(d->mats[i].kd_tex)) {
+      case SlotKind::kEnvmap: names = "an environment map"; break;
+      case SlotKind::kNormals: names = "the shading normals' record"; break;
+      case SlotKind::kFilter: names = "the pixel filter's record"; break;
+      default: break;
+    }
+    if (names) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names " + names + ", which is not a texture for Kd");
+  }
+  return PBRT_HIP_OK;
+}
+int check_material_kinds(const pbrt_hip_scene_desc *d) {
   for (uint32_t i = 0; i < d->n_mats; i++)
-    if (kd_textured(d->mats[i]) && is_normals_slot(d->textures, d->mats[i].kd_tex - 1u))
-      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names the shading normals' record, which is not a texture for Kd");
-  for (uint32_t i = 0; i < d->n_mats; i++)
-    if (kd_textured(d->mats[i]) && is_filter_slot(d->textures, d->mats[i].kd_tex - 1u))
-      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names the pixel filter's record, which is not a texture for Kd");
+    if (d->mats[i].type > PBRT_HIP_MATERIAL_GLASS) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
+  return PBRT_HIP_OK;
+}
+
+// the records of the texture table in slot order, then the images' texels, then the (u, v) that textured triangles need
+int check_table(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   uint32_t n_normals = 0, n_filters = 0, n_images = 0;
   uint64_t image_texels = 0;
-  for (uint32_t i = 0; i < d->n_textures; i++) {
-    const pbrt_hip_texture &tx = d->textures[i];
-    if (is_image_slot(d->textures, i)) {  // an image texture's record
-      const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": ";
-      const pbrt_hip_image_texture im = image_slot(d->textures, i);
-      int rc = image_check(im, what);
-      if (rc) return rc;
-      image_texels += (uint64_t)im.width * im.height;
-      if ((rc = image_check_totals(++n_images, image_texels, what))) return rc;
-      continue;
+  for (uint32_t i = 0; i < table.kinds.size(); i++) {
+    const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": ";
+    int rc = PBRT_HIP_OK;
+    switch (table.kinds[i]) {
+      case SlotKind::kImage: {
+        const pbrt_hip_image_texture &im = table.images[n_images].rec;
+        if ((rc = image_check(im, what))) return rc;
+        image_texels += (uint64_t)im.width * im.height;
+        rc = image_check_totals(++n_images, image_texels, what);
+        break;
+      }
+      case SlotKind::kFilter:
+        if (++n_filters > 1u) return fail(PBRT_HIP_ERR_LIMIT, what + "more than one pixel filter record (type 3)");
+        rc = filter_check(*table.filter, what);
+        break;
+      case SlotKind::kNormals: {
+        if (++n_normals > 1u) return fail(PBRT_HIP_ERR_LIMIT, what + "shading normals: more than one normals record (type 2)");
+        const pbrt_hip_normals &nr = *table.normals;
+        if (nr.n_tris != d->n_tris) return fail(PBRT_HIP_ERR_INVALID, what + "shading normals: n_tris is " + std::to_string(nr.n_tris) + ", the description has " + std::to_string(d->n_tris) + " triangles");
+        if (!nr.tri_n) return fail(PBRT_HIP_ERR_INVALID, what + "shading normals: tri_n is NULL");
+        for (size_t k = 0; k < 9 * (size_t)nr.n_tris; k++)
+          if (!std::isfinite(nr.tri_n[k])) return fail(PBRT_HIP_ERR_INVALID, what + "shading normals: component " + std::to_string(k % 9) + " of triangle " + std::to_string(k / 9) + " is not finite");
+        break;
+      }
+      case SlotKind::kEnvmap:
+        rc = envmap_check(read_slot<pbrt_hip_envmap>(table.slots, i), what);
+        break;
+      case SlotKind::kChecker: {
+        const pbrt_hip_texture tx = read_slot<pbrt_hip_texture>(table.slots, i);
+        if (!std::isfinite(tx.su) || !std::isfinite(tx.sv) || !std::isfinite(tx.du) || !std::isfinite(tx.dv))
+          return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture mapping is not finite");
+        for (int k = 0; k < 3; k++)
+          if (!std::isfinite(tx.tex1[k]) || !std::isfinite(tx.tex2[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture colour is not finite");
+        break;
+      }
+      default: return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown texture type");
     }
-    if (is_filter_slot(d->textures, i)) {  // the pixel filter's record
-      const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": ";
-      if (++n_filters > 1u) return fail(PBRT_HIP_ERR_LIMIT, what + "more than one pixel filter record (type 3)");
-      const int rc = filter_check(filter_slot(d->textures, i), what);
-      if (rc) return rc;
-      continue;
-    }
-    if (is_normals_slot(d->textures, i)) {  // the shading normals' record
-      const std::string what = "scene_create: texture slot " + std::to_string(i + 1) + ": shading normals: ";
-      if (++n_normals > 1u) return fail(PBRT_HIP_ERR_LIMIT, what + "more than one normals record (type 2)");
-      const pbrt_hip_normals nr = normals_slot(d->textures, i);
-      if (nr.n_tris != d->n_tris) return fail(PBRT_HIP_ERR_INVALID, what + "n_tris is " + std::to_string(nr.n_tris) + ", the description has " + std::to_string(d->n_tris) + " triangles");
-      if (!nr.tri_n) return fail(PBRT_HIP_ERR_INVALID, what + "tri_n is NULL");
-      for (size_t k = 0; k < 9 * (size_t)nr.n_tris; k++)
-        if (!std::isfinite(nr.tri_n[k])) return fail(PBRT_HIP_ERR_INVALID, what + "component " + std::to_string(k % 9) + " of triangle " + std::to_string(k / 9) + " is not finite");
-      continue;
-    }
-    if (is_envmap_slot(d->textures, i)) {  // an environment map's record
-      const int rc = envmap_check(envmap_slot(d->textures, i), "scene_create: texture slot " + std::to_string(i + 1) + ": ");
-      if (rc) return rc;
-      continue;
-    }
-    if (tx.type != 0u) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown texture type");
-    if (!std::isfinite(tx.su) || !std::isfinite(tx.sv) || !std::isfinite(tx.du) || !std::isfinite(tx.dv))
-      return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture mapping is not finite");
-    for (int k = 0; k < 3; k++)
-      if (!std::isfinite(tx.tex1[k]) || !std::isfinite(tx.tex2[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture colour is not finite");
+    if (rc) return rc;
   }
-  for (uint32_t i = 0; i < d->n_textures; i++)  // (the images' texels, once every size and the caps have passed)
-    if (is_image_slot(d->textures, i)) {
-      const int rc = image_check_texels(image_slot(d->textures, i), "scene_create: texture slot " + std::to_string(i + 1) + ": ");
-      if (rc) return rc;
-    }
-  bool textured = false;  // a triangle whose material's Kd is a texture: its corner (u, v) must be there
-  for (uint32_t t = 0; t < d->n_tris && !textured; t++) textured = kd_textured(d->mats[d->mat_id[t]]);
-  if (textured) {
+  for (const TextureTable::Image &im : table.images) {  // (the images' texels, once every size and the caps have passed)
+    const int rc = image_check_texels(im.rec, "scene_create: texture slot " + std::to_string(im.slot + 1) + ": ");
+    if (rc) return rc;
+  }
+  if (table.textured_tris) {
     if (!d->tri_uv) return fail(PBRT_HIP_ERR_INVALID, "scene_create: a triangle's material is textured but tri_uv is NULL");
     for (size_t i = 0; i < 6 * (size_t)d->n_tris; i++)
       if (!std::isfinite(d->tri_uv[i])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: tri_uv is not finite");
   }
+  return PBRT_HIP_OK;
+}
+
+// the builder that `flags` (and PBRT_HIP_BUILDER) ask for
+int check_flags(uint32_t flags, Builder *builder) {
   if (flags & ~(PBRT_HIP_SCENE_GPU_BUILD | PBRT_HIP_SCENE_OPTIMIZED_TREE | PBRT_HIP_SCENE_PLAIN_TREE | PBRT_HIP_SCENE_HOST_BUILD))
     return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown flag");
   const bool want_host = (flags & (PBRT_HIP_SCENE_HOST_BUILD | PBRT_HIP_SCENE_OPTIMIZED_TREE)) != 0u;
   const bool want_gpu = (flags & (PBRT_HIP_SCENE_GPU_BUILD | PBRT_HIP_SCENE_PLAIN_TREE)) != 0u;
   if (want_host && want_gpu)
     return fail(PBRT_HIP_ERR_INVALID, "scene_create: PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE are host builds, not combined with PBRT_HIP_SCENE_GPU_BUILD / _PLAIN_TREE");
-  for (uint32_t s = 0; s < d->n_spheres; s++)  // (a finite centre and radius can still make an infinite box)
-    for (int k = 0; k < 3; k++)
-      if (!std::isfinite(d->spheres[s].c[k] - d->spheres[s].r) || !std::isfinite(d->spheres[s].c[k] + d->spheres[s].r))
-        return fail(PBRT_HIP_ERR_INVALID, "scene_create: a sphere's bounding box is not finite");
-  for (uint32_t i = 0; i < d->n_lights; i++)
-    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
-  uint32_t n_env = 0;
-  for (uint32_t i = 0; i < d->n_lights; i++) {  // an environment-map light names a type-1 slot of the texture table; one per scene
-    if (d->lights[i].type != PBRT_HIP_LIGHT_ENVMAP) continue;
-    const uint32_t t = light_env_slot(d->lights[i]);
-    if (t == 0u || t > d->n_textures || !d->textures || !is_envmap_slot(d->textures, t - 1u))
-      return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": an environment-map light (type 3) must name a type-1 slot of the texture table in `pad`");
-    if (++n_env > 1u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than one environment-map light (type 3)");
-  }
-  for (uint32_t i = 0; i < d->n_mats; i++)
-    if (d->mats[i].type > PBRT_HIP_MATERIAL_GLASS) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
   const char *env = want_host || want_gpu ? nullptr : std::getenv("PBRT_HIP_BUILDER");
   if (flags & PBRT_HIP_SCENE_OPTIMIZED_TREE) *builder = Builder::kHostOptimized;
   else if ((flags & PBRT_HIP_SCENE_HOST_BUILD) || (env && std::strcmp(env, "host") == 0)) *builder = Builder::kHost;
   else *builder = (flags & PBRT_HIP_SCENE_PLAIN_TREE) ? Builder::kGpuPlain : Builder::kGpu;  // (PBRT_HIP_SCENE_PLAIN_TREE alone qualifies the default)
   return PBRT_HIP_OK;
+}
+
+// The stages in their order; the description's table is decoded once the indices it goes by are known to be sound (*table: what
+// gather_inputs and upload_inputs go by)
+int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *builder, TextureTable *table) {
+  int rc;
+  if ((rc = check_mesh(d)) || (rc = check_light_values(d)) || (rc = check_material_values(d)) || (rc = check_view(d)) || (rc = check_sphere_materials(d))) return rc;
+  if (d->n_textures && !d->textures) return fail(PBRT_HIP_ERR_INVALID, "scene_create: n_textures > 0 but no texture table");
+  *table = decode_texture_table(*d);
+  if ((rc = check_kd_tex(d, *table)) || (rc = check_table(d, *table)) || (rc = check_flags(flags, builder)) || (rc = check_sphere_boxes(d))) return rc;
+  if ((rc = check_light_kinds(d, *table))) return rc;
+  return check_material_kinds(d);
 }
 
 // What a checked description puts on the device, assembled on the host.
@@ -286,10 +325,8 @@ struct SceneInputs {
   float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
   float le_inf[3] = {0.f, 0.f, 0.f};
   bool has_inf = false;
-  bool textured_tris = false;  // a triangle whose material's Kd is a texture: its corner (u, v) go up too
-  bool textured_sph = false;   // a sphere whose material's Kd is one: (u, v) from its own parametrisation (kernel_math.hpp sphere_uv)
 };
-void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
+void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, SceneInputs *in) {
   auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
   in->P = d.P; in->idx = d.idx; in->mat = d.mat_id;
   in->n_verts = d.n_verts;
@@ -324,7 +361,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
       in->has_inf = true;
     }
     if (l.type == PBRT_HIP_LIGHT_ENVMAP) {
-      const pbrt_hip_envmap e = envmap_slot(d.textures, light_env_slot(l) - 1u);
+      const pbrt_hip_envmap e = *table.envmap(light_env_slot(l));
       in->env = true;
       in->env_w = e.width; in->env_h = e.height;
       for (int k = 0; k < 9; k++) in->env_m[k] = e.world_to_light[k];
@@ -365,27 +402,23 @@ void gather_inputs(const pbrt_hip_scene_desc &d, SceneInputs *in) {
     const pbrt_hip_sphere &sp = d.spheres[i];
     in->spheres[2 * i] = make_float4(sp.c[0], sp.c[1], sp.c[2], sp.r);
     in->spheres[2 * i + 1] = make_float4(as_f(sp.mat), 0, 0, 0);
-    in->textured_sph = in->textured_sph || kd_textured(d.mats[sp.mat]);
   }
-  for (uint32_t t = 0; t < d.n_tris && !in->textured_tris; t++) in->textured_tris = kd_textured(d.mats[d.mat_id[t]]);
-  if (in->textured_tris || in->textured_sph) {  // (the texture table goes up only when something is textured)
-    in->textures.resize(3 * (size_t)d.n_textures);
-    for (uint32_t i = 0; i < d.n_textures; i++) {
-      const pbrt_hip_texture &tx = d.textures[i];
-      if (is_envmap_slot(d.textures, i) || is_normals_slot(d.textures, i) || is_filter_slot(d.textures, i)) continue;  // (an environment map's / the normals' / the filter's slot: no material names it, its records stay zero)
-      if (is_image_slot(d.textures, i)) {  // (its texels join the pool, its rows say where)
-        image_pack(image_slot(d.textures, i), &in->image_texels, &in->textures[3 * i]);
-        continue;
-      }
+  if (table.textured_tris || table.textured_sph) {  // (the texture table goes up only when something is textured)
+    in->textures.resize(3 * table.kinds.size());  // (an environment map's / the normals' / the filter's slot: no material names it, its rows stay zero)
+    for (uint32_t i = 0; i < table.kinds.size(); i++) {
+      if (table.kinds[i] != SlotKind::kChecker) continue;
+      const pbrt_hip_texture tx = read_slot<pbrt_hip_texture>(table.slots, i);
       in->textures[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
       in->textures[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
       in->textures[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
     }
+    for (const TextureTable::Image &im : table.images)  // (its texels join the pool, its rows say where)
+      image_pack(im.rec, &in->image_texels, &in->textures[3 * (size_t)im.slot]);
   }
 }
 
 // The inputs into the scene's arrays (asynchronously: `in` outlives the stream's synchronisation) and the counts of s->dev they make
-int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const SceneInputs &in) {
+int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const TextureTable &table, const SceneInputs &in) {
   HIP_TRY(upload(&s->d_P, in.P, 3 * (size_t)in.n_verts, s->stream));
   HIP_TRY(upload(&s->d_idx, in.idx, 3 * (size_t)in.n_prims, s->stream));
   HIP_TRY(upload(&s->d_mat_id, in.mat, in.n_prims, s->stream));
@@ -404,10 +437,9 @@ int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const SceneIn
     for (int k = 0; k < 9; k++) s->env_m[k] = in.env_m[k];
     for (int k = 0; k < 3; k++) s->env_c[k] = in.env_c[k];
   }
-  if (in.textured_tris) HIP_TRY(upload(&s->d_tri_uv_in, d.tri_uv, 6 * (size_t)d.n_tris, s->stream));
-  pbrt_hip_normals nr;
-  if (find_normals(d, &nr)) {  // (the caller's array: it outlives the call, and the stream is synchronised before the call returns)
-    HIP_TRY(upload(&s->d_tri_n_in, nr.tri_n, 9 * (size_t)d.n_tris, s->stream));
+  if (table.textured_tris) HIP_TRY(upload(&s->d_tri_uv_in, d.tri_uv, 6 * (size_t)d.n_tris, s->stream));
+  if (table.normals) {  // (the caller's array: it outlives the call, and the stream is synchronised before the call returns)
+    HIP_TRY(upload(&s->d_tri_n_in, table.normals->tri_n, 9 * (size_t)d.n_tris, s->stream));
     s->normals = in.n_prims > 0;  // (a scene without a primitive has no hit to shade and no leaf slot to hold a normal)
   }
   DevScene &D = s->dev;
@@ -490,11 +522,6 @@ void bind_scene_arrays(pbrt_hip_scene *s) {
   D.mats = s->d_mats.p;
   D.lights = s->d_lights.p;
   D.spheres = s->d_spheres.p;
-}
-
-void bind_scene_filter(pbrt_hip_scene *s) {
-  s->desc.textures = s->has_filter ? &s->filter_slot : nullptr;
-  s->desc.n_textures = s->has_filter ? 1u : 0u;
 }
 
 // The counter flags (PBRT_HIP_FLAG_COUNTERS, counters of pbrt_hip_intersect) count the CANONICAL walk: the oracle's binary
@@ -611,7 +638,8 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
   *out = nullptr;
   return guarded([&]() -> int {
     Builder builder;
-    int rc = check_scene_desc(d, flags, &builder);
+    TextureTable table;
+    int rc = check_scene_desc(d, flags, &builder, &table);
     if (rc) return rc;
     int ndev = pbrt_hip_device_count();
     if (ndev <= 0) return fail(PBRT_HIP_ERR_NO_DEVICE, "scene_create: no HIP device (there is no CPU fallback)");
@@ -621,19 +649,14 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
     SceneInputs in;  // (declared before the scene: freed after it, on every exit)
     std::unique_ptr<pbrt_hip_scene> s(new pbrt_hip_scene());
     if ((rc = s->open(device))) return rc;
-    s->desc = *d;
-    s->desc.P = nullptr; s->desc.idx = nullptr; s->desc.mat_id = nullptr;
-    s->desc.mats = nullptr; s->desc.lights = nullptr; s->desc.spheres = nullptr;
-    s->desc.tri_uv = nullptr;
-    pbrt_hip_pixel_filter pf;
-    if ((s->has_filter = find_filter(*d, &pf))) std::memcpy(&s->filter_slot, &pf, sizeof pf);
-    bind_scene_filter(s.get());
-    gather_inputs(*d, &in);
+    s->window = {d->xres, d->yres, {d->crop[0], d->crop[1], d->crop[2], d->crop[3]}};
+    s->filter = table.filter;
+    gather_inputs(*d, table, &in);
     s->n_prims = in.n_prims;
-    s->textured = in.textured_tris || in.textured_sph;
+    s->textured = table.textured_tris || table.textured_sph;
     s->glass = !in.glass.empty();
-    if ((rc = upload_inputs(s.get(), *d, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
-    if (in.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
+    if ((rc = upload_inputs(s.get(), *d, table, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
+    if (table.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
       HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));
       HIP_TRY(launch_pack_uv(s->d_tri_uv_in.p, s->d_order.p, in.n_prims, d->n_tris, s->d_tri_uv.p, s->stream));
     }

@@ -11,13 +11,6 @@
 
 namespace pbrt_hip {
 
-pbrt_hip_envmap envmap_slot(const pbrt_hip_texture *textures, uint32_t index) {
-  static_assert(sizeof(pbrt_hip_envmap) == sizeof(pbrt_hip_texture) && sizeof(pbrt_hip_envmap) == 64, "an environment map takes one slot of the texture table");
-  pbrt_hip_envmap e;
-  std::memcpy(&e, textures + index, sizeof e);
-  return e;
-}
-
 int envmap_check_image(const float *rgb, uint32_t w, uint32_t h, const std::string &what) {
   if (w == 0 || h == 0) return fail(PBRT_HIP_ERR_INVALID, what + "environment map: width and height must be >= 1");
   if ((uint64_t)w * h > (1ull << 24)) return fail(PBRT_HIP_ERR_LIMIT, what + "environment map: more than 2^24 texels");

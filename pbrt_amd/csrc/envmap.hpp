@@ -11,10 +11,6 @@
 
 namespace pbrt_hip {
 
-// the slot `index` (0-based) of a texture table read as the record it is when its first word is 1 (the table's element type is 4-aligned)
-pbrt_hip_envmap envmap_slot(const pbrt_hip_texture *textures, uint32_t index);
-inline bool is_envmap_slot(const pbrt_hip_texture *textures, uint32_t index) { return textures[index].type == 1u; }
-
 // Every refusal of the record (include/pbrt_hip.h): 0, or the status with the message set; `what` prefixes it
 int envmap_check(const pbrt_hip_envmap &e, const std::string &what);
 int envmap_check_image(const float *rgb, uint32_t width, uint32_t height, const std::string &what);

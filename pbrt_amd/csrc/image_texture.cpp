@@ -9,13 +9,6 @@
 
 namespace pbrt_hip {
 
-pbrt_hip_image_texture image_slot(const pbrt_hip_texture *textures, uint32_t index) {
-  static_assert(sizeof(pbrt_hip_image_texture) == sizeof(pbrt_hip_texture) && sizeof(pbrt_hip_image_texture) == 64, "an image texture takes one slot of the texture table");
-  pbrt_hip_image_texture t;
-  std::memcpy(&t, textures + index, sizeof t);
-  return t;
-}
-
 int image_check(const pbrt_hip_image_texture &t, const std::string &what) {
   if (t.width == 0 || t.height == 0) return fail(PBRT_HIP_ERR_INVALID, what + "image texture: width and height must be >= 1");
   if (t.width > PBRT_HIP_IMAGE_MAX_SIZE || t.height > PBRT_HIP_IMAGE_MAX_SIZE)

@@ -1,5 +1,5 @@
-// image_texture.hpp -- image textures for Kd on the host: the record's place in the texture table, its checks, and the texel
-// pool with the slot's three rows that the kernels read (image_lookup.hpp is the one statement of the lookup's arithmetic).
+// image_texture.hpp -- image textures for Kd on the host: the record's checks, and the texel pool with the slot's three
+// rows that the kernels read (image_lookup.hpp is the one statement of the lookup's arithmetic).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,10 +9,6 @@
 #include "../../include/pbrt_hip.h"
 
 namespace pbrt_hip {
-
-// the image's record: a slot of the texture table whose first word is 4, read as the environment map's is
-inline bool is_image_slot(const pbrt_hip_texture *textures, uint32_t index) { return textures[index].type == PBRT_HIP_TEXTURE_IMAGE; }
-pbrt_hip_image_texture image_slot(const pbrt_hip_texture *textures, uint32_t index);
 
 // PBRT_HIP_OK, or the refusal of one record (every message holds "image"; `what` prefixes it): everything but the texels ...
 int image_check(const pbrt_hip_image_texture &t, const std::string &what);

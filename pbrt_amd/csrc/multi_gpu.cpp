@@ -152,10 +152,8 @@ int clone_scene(const pbrt_hip_scene *src, int device, pbrt_hip_scene **out) {
   std::unique_ptr<pbrt_hip_scene> s(new pbrt_hip_scene());
   const int rc = s->open(device);
   if (rc) return rc;
-  s->desc = src->desc;
   s->bvh.depth = src->bvh.depth;  // (the host copy of the tree stays with the original: export / info use that one)
-  static_cast<SceneTraits &>(*s) = *src;
-  bind_scene_filter(s.get());  // (the pixel filter's record travels with the traits: every GPU makes the table of a render's radii from it)
+  static_cast<SceneTraits &>(*s) = *src;  // (the film window and the pixel filter's record with them: every GPU makes the table of a render's radii from it)
   int can = 0;
   if (hipDeviceCanAccessPeer(&can, device, src->device) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(src->device, 0);  // (already enabled is fine)
   (void)hipGetLastError();
@@ -176,7 +174,7 @@ int multi_create(const pbrt_hip_scene_desc *d, int n_gpus, uint32_t flags, pbrt_
   const int ndev = pbrt_hip_device_count();
   if (ndev <= 0) return fail(PBRT_HIP_ERR_NO_DEVICE, "multi_create: no HIP device (there is no CPU fallback)");
   if (d->xres <= 0 || d->yres <= 0) return fail(PBRT_HIP_ERR_INVALID, "multi_create: resolution must be positive");
-  const FilmGeom fg = film_geom(*d);
+  const FilmGeom fg = film_geom(FilmWindow{d->xres, d->yres, {d->crop[0], d->crop[1], d->crop[2], d->crop[3]}});  // (the cropped window: no filter moves it)
   const int32_t w = fg.crop_w(), h = fg.crop_h();
   if (n_gpus <= 0) {
     // all visible devices -- but no more than there are 64x64 super-tiles to deal out (a 64x64 film on eight GPUs would
@@ -249,7 +247,8 @@ int ensure_buffers(pbrt_hip_multi *m, size_t count, bool gather) {
 int multi_render(pbrt_hip_multi *m, const pbrt_hip_render_desc *r, float *film, pbrt_hip_stats *per_gpu) {
   if (m->broken) return fail(PBRT_HIP_ERR_INTERNAL, "multi_render: an earlier collective failed and the communicators were aborted; create a new handle");
   const int n = m->n;
-  const bool wide = film_geom(m->scenes[0]->desc, r->filter_xwidth, r->filter_ywidth).wide;  // accumulators of the whole window, summed instead of gathered
+  const pbrt_hip_scene *s0 = m->scenes[0];
+  const bool wide = film_geom(s0->window, s0->filter ? &*s0->filter : nullptr, r->filter_xwidth, r->filter_ywidth).wide;  // accumulators of the whole window, summed instead of gathered
   const size_t per_gpu_f4 = wide ? 2 * m->n_px : m->max_slab;
   int code = ensure_buffers(m, per_gpu_f4, !wide);
   if (code) return code;

@@ -1,27 +1,11 @@
-// pixel_filter.hpp -- the weighted pixel filters on the host: the record's place in the texture table, its checks, the
-// kinds' default radii and the 16 x 16 table the render kernels read (pixel_filter.cpp).  Plain C++, nothing of HIP.
+// pixel_filter.hpp -- the weighted pixel filters on the host: the record's checks, the kinds' default radii and the
+// 16 x 16 table the render kernels read (pixel_filter.cpp).  Plain C++, nothing of HIP.
 #pragma once
-#include <cstring>
 #include <string>
 
 #include "../../include/pbrt_hip.h"
 
 namespace pbrt_hip {
-
-// the filter's record: a slot of the texture table whose first word is 3, read as the environment map's is
-inline bool is_filter_slot(const pbrt_hip_texture *textures, uint32_t index) { return textures[index].type == PBRT_HIP_TEXTURE_FILTER; }
-inline pbrt_hip_pixel_filter filter_slot(const pbrt_hip_texture *textures, uint32_t index) {
-  static_assert(sizeof(pbrt_hip_pixel_filter) == sizeof(pbrt_hip_texture), "a pbrt_hip_pixel_filter is one slot of the texture table");
-  pbrt_hip_pixel_filter f;
-  std::memcpy(&f, textures + index, sizeof(f));
-  return f;
-}
-// the table's filter record into *out; false: the table holds none (scene creation has refused a second one)
-inline bool find_filter(const pbrt_hip_scene_desc &d, pbrt_hip_pixel_filter *out) {
-  for (uint32_t i = 0; i < d.n_textures && d.textures; i++)
-    if (is_filter_slot(d.textures, i)) { *out = filter_slot(d.textures, i); return true; }
-  return false;
-}
 
 // PBRT_HIP_OK, or the refusal of a record (`what` prefixes the message, which holds "filter")
 int filter_check(const pbrt_hip_pixel_filter &f, const std::string &what);

@@ -14,6 +14,7 @@
 #include "envmap.hpp"
 #include "host_math.hpp"
 #include "ply_reader.hpp"
+#include "texture_table.hpp"
 
 namespace pbrt_hip {
 
@@ -412,7 +413,6 @@ struct Api {
     if (asked_trilinear || asked_aniso)
       warn("Texture \"" + name + "\" (imagemap): \"trilinear\" / \"maxanisotropy\" are ignored (there is no mip map: the lookup is bilinear or point)");
     pbrt_hip_image_texture t{};
-    t.type = PBRT_HIP_TEXTURE_IMAGE;
     t.su = ps.one_float("uscale", 1.f); t.sv = ps.one_float("vscale", 1.f);
     t.du = ps.one_float("udelta", 0.f); t.dv = ps.one_float("vdelta", 0.f);
     const std::string path = (file.empty() || file[0] == '/' || cur_dir.empty()) ? file : cur_dir + "/" + file;
@@ -462,10 +462,7 @@ struct Api {
     out->image_texels += (uint64_t)w * (uint64_t)h;
     out->image_rgb.emplace_back(std::move(rgb));
     t.rgb = out->image_rgb.back().data();  // (an inner vector is filled once and keeps its storage when the outer one grows)
-    pbrt_hip_texture slot{};
-    static_assert(sizeof slot == sizeof t, "an image texture takes one slot of the texture table");
-    std::memcpy(&slot, &t, sizeof slot);
-    out->textures.push_back(slot);
+    out->textures.push_back(write_slot(t));
     checker_textures[name] = (uint32_t)out->textures.size();
   }
 
@@ -729,7 +726,7 @@ struct Api {
     // world_to_light = the rotation of the CTM, inverted.  A CTM that is a rotation gives its inverse's 3 x 3 as it stands; one that scales
     // or shears: a warning, and the rotation that Gram-Schmidt leaves of the light's axes (x kept, y made orthogonal to it, z completing them)
     pbrt_hip_envmap e{};
-    e.type = 1u; e.width = (uint32_t)w; e.height = (uint32_t)h;
+    e.width = (uint32_t)w; e.height = (uint32_t)h;
     const float *m = ctm[0].m, *mi = ctm[0].inv;
     for (int i = 0; i < 3; i++)
       for (int j = 0; j < 3; j++) e.world_to_light[3 * i + j] = mi[4 * i + j];
@@ -751,10 +748,7 @@ struct Api {
     }
     out->env_rgb.swap(rgb);
     e.rgb = out->env_rgb.data();  // (filled once: the vector is not touched again)
-    pbrt_hip_texture slot{};
-    static_assert(sizeof slot == sizeof e, "an environment map takes one slot of the texture table");
-    std::memcpy(&slot, &e, sizeof slot);
-    out->textures.push_back(slot);
+    out->textures.push_back(write_slot(e));
     const uint32_t number = (uint32_t)out->textures.size();  // 1-based
     l->type = PBRT_HIP_LIGHT_ENVMAP;
     std::memcpy(&l->pad, &number, 4);
@@ -1254,25 +1248,16 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
     if (!textured) { out->tri_uv.clear(); out->tri_uv.shrink_to_fit(); }
   }
   // a weighted pixel filter's record takes a slot of the texture table; a file without one keeps the description it always had
-  if (out->pixel_filter.type == PBRT_HIP_TEXTURE_FILTER) {
-    pbrt_hip_texture slot{};
-    static_assert(sizeof slot == sizeof out->pixel_filter, "the pixel filter's record takes one slot of the texture table");
-    std::memcpy(&slot, &out->pixel_filter, sizeof slot);
-    out->textures.push_back(slot);
-  }
+  if (out->pixel_filter.type == PBRT_HIP_TEXTURE_FILTER) out->textures.push_back(write_slot(out->pixel_filter));
   // shading normals travel only when some mesh has them: then their record is the LAST slot of the texture table; a file
   // without them keeps the description it always had
   if (!api.any_normals) {
     out->tri_n.clear(); out->tri_n.shrink_to_fit();
   } else {
     pbrt_hip_normals nr{};
-    nr.type = PBRT_HIP_TEXTURE_NORMALS;
     nr.n_tris = (uint32_t)out->mat_id.size();
     nr.tri_n = out->tri_n.data();  // (the vector is not touched again)
-    pbrt_hip_texture slot{};
-    static_assert(sizeof slot == sizeof nr, "the normals' record takes one slot of the texture table");
-    std::memcpy(&slot, &nr, sizeof slot);
-    out->textures.push_back(slot);
+    out->textures.push_back(write_slot(nr));
   }
   if (!api.camera_set) mat_identity(out->cam_to_world);
   // (round 6: spheres are primitives of the BVH like triangles -- the warning that hundreds of them cost every ray a loop is gone; what

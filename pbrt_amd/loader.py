@@ -6,7 +6,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import EnvMap, ImageTexture, Normals, PixelFilter, RenderDesc, SceneDesc, check, lib
+from ._lib import (SLOT_ENVMAP, SLOT_FILTER, SLOT_IMAGE, SLOT_NORMALS, EnvMap, ImageTexture, Normals, PixelFilter, RenderDesc, SceneDesc, check, lib,
+                   read_slot)
 from .api import GLASS, SceneData
 
 
@@ -40,40 +41,33 @@ def _collect(h):
         def arr(ptr, n, dt):
             return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt).copy() if n else np.zeros(0, dt)
 
-        # an environment map's record sits in a slot of the texture table whose first word is 1: it becomes SceneData's
-        # `envmap`, the other slots stay the checkerboards -- numbered as they are while the map's slot is the last one, as the parser leaves
-        # it unless a texture is declared after the light (such a scene's texture numbers are remapped here)
-        env_slots = [i for i in range(d.n_textures) if d.textures[i].type == 1]
-        # (the shading normals' record, DESIGN.md 3.18, is a slot whose first word is 2: it becomes `tri_n`)
-        nrm_slots = [i for i in range(d.n_textures) if d.textures[i].type == 2]
-        # (the pixel filter's record, DESIGN.md 3.19, is a slot whose first word is 3: it becomes `pixel_filter`)
-        flt_slots = [i for i in range(d.n_textures) if d.textures[i].type == 3]
-        tex_slots = [i for i in range(d.n_textures) if d.textures[i].type not in (1, 2, 3)]
+        # The texture table, classified once by the slots' first words.  The map's record becomes SceneData's `envmap`, the
+        # normals' (3.18) `tri_n`, the pixel filter's (3.19) `pixel_filter`; every other slot stays a `textures` row -- numbered as it is while
+        # the records' slots come last, as the parser leaves them unless a texture is declared after the light (such a scene's texture numbers
+        # are remapped here).  An image's texels (3.20) join `images`, and its row -- in the slot's own place -- names them.
+        slots = {}
+        for i in range(d.n_textures):
+            slots.setdefault(d.textures[i].type, []).append(i)
+
+        def first(kind, cls):
+            return read_slot(d.textures, slots[kind][0], cls) if kind in slots else None
+
+        tex_slots = sorted(i for kind, at in slots.items() if kind not in (SLOT_ENVMAP, SLOT_NORMALS, SLOT_FILTER) for i in at)
         renum = {0: 0, **{i + 1: k + 1 for k, i in enumerate(tex_slots)}}
-        envmap, env_m = np.zeros((0, 0, 3), np.float32), np.eye(3, dtype=np.float32)
-        if env_slots:
-            e = EnvMap.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[env_slots[0]]), C.sizeof(EnvMap))))
-            envmap = arr(e.rgb, 3 * e.width * e.height, np.float32).reshape(e.height, e.width, 3)
-            env_m = np.array(list(e.world_to_light), np.float32).reshape(3, 3)
-        tri_n = np.zeros((0, 9), np.float32)
-        if nrm_slots:
-            nr = Normals.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[nrm_slots[0]]), C.sizeof(Normals))))
-            tri_n = arr(nr.tri_n, 9 * nr.n_tris, np.float32).reshape(-1, 9)
-        pixel_filter = None
-        if flt_slots:
-            pf = PixelFilter.from_buffer_copy(bytes(C.string_at(C.byref(d.textures[flt_slots[0]]), C.sizeof(PixelFilter))))
-            pixel_filter = (int(pf.kind), float(pf.param[0]), float(pf.param[1]))
-        # (an image texture's record, DESIGN.md 3.20, is a slot whose first word is 4: its texels join `images`, and its `textures` row -- in
-        # the slot's own place among the checkerboards -- names them)
+        e, nr, pf = first(SLOT_ENVMAP, EnvMap), first(SLOT_NORMALS, Normals), first(SLOT_FILTER, PixelFilter)
+        envmap = arr(e.rgb, 3 * e.width * e.height, np.float32).reshape(e.height, e.width, 3) if e else np.zeros((0, 0, 3), np.float32)
+        env_m = np.array(list(e.world_to_light), np.float32).reshape(3, 3) if e else np.eye(3, dtype=np.float32)
+        tri_n = arr(nr.tri_n, 9 * nr.n_tris, np.float32).reshape(-1, 9) if nr else np.zeros((0, 9), np.float32)
+        pixel_filter = (int(pf.kind), float(pf.param[0]), float(pf.param[1])) if pf else None
         images = []
 
         def tex_row(i):
-            t = d.textures[i]
-            if t.type != 4:
+            if i not in slots.get(SLOT_IMAGE, ()):
+                t = d.textures[i]
                 return [t.type, *t.tex1, *t.tex2, t.su, t.sv, t.du, t.dv]
-            im = ImageTexture.from_buffer_copy(bytes(C.string_at(C.byref(t), C.sizeof(ImageTexture))))
+            im = read_slot(d.textures, i, ImageTexture)
             images.append(arr(im.rgb, 3 * im.width * im.height, np.float32).reshape(im.height, im.width, 3))
-            return [4, len(images) - 1, im.wrap, im.filter, 0, 0, 0, im.su, im.sv, im.du, im.dv]
+            return [SLOT_IMAGE, len(images) - 1, im.wrap, im.filter, 0, 0, 0, im.su, im.sv, im.du, im.dv]
 
         tex_rows = [tex_row(i) for i in tex_slots]
         sd = SceneData(

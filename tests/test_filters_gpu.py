@@ -110,6 +110,21 @@ def test_ranks_add_and_conversions_agree(shared, gpu):
     assert np.array_equal(film.view(np.uint32), host.view(np.uint32))
 
 
+def test_clones_carry_the_filter(gpu, monkeypatch):
+    """A weighted filter through pbrt_hip_multi_*: rank 1 renders from a CLONE of the scene, which has the filter's record from the original.
+    The whole 72 x 40 film is two super-tiles, one per rank; the ranks' integer accumulators add exactly, so the film is the single scene's
+    bit for bit -- at the kind's default radii and at radii of the render's own."""
+    monkeypatch.setenv("PBRT_HIP_MULTI_LOOPBACK", "1")
+    sd = dataclasses.replace(small_scene()[0], xres=72, yres=40, crop=(0.0, 1.0, 0.0, 1.0), pixel_filter="gaussian").normalized()
+    kw = dict(spp=(2, 2), max_depth=DEPTH, seed=SEED)
+    with gpu.Scene(sd, device=0) as one, gpu.MultiScene(sd, 2) as two:
+        for extra in ({}, {"filter_width": (1.0, 3.0)}):
+            want, _ = one.render(**kw, **extra)
+            got, per_rank = two.render(**kw, **extra)
+            assert len(per_rank) == 2 and all(st["samples"] > 0 for st in per_rank), per_rank
+            assert np.abs(want[..., :3]).sum() > 0 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), extra
+
+
 # ---- 8. the hook ----
 def _adversarial_points(rng, cb, rx, ry, n):
     """film points where a bound or an index can flip: integers and half-integers +- 1 ulp, points with d +- r within an ulp of an integer,

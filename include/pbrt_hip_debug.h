@@ -65,6 +65,52 @@ int pbrt_hip_quad_build_host_ex(const float *P, uint32_t n_verts, const uint32_t
                                 uint32_t tree, uint32_t *quads, uint32_t cap_nodes, uint32_t *n_quads, uint32_t *stack_need,
                                 uint32_t *order, float *root_box, uint32_t *n_refs, float *exact_boxes);
 
+/* ---- the device tree builder between its stages (pbrt_amd/csrc/bvh_gpu.hip) ---- */
+/* A binary tree of n one-triangle leaves in the device builder's form: interior nodes [0, n - 1), the root 0; child = 2 (n - 1) words, an
+ * interior node or 0x80000000 | leaf slot; parent_internal (n - 1 words; the root's: 0xffffffff) and parent_leaf (n words, by slot); boxes =
+ * six floats (lo xyz, hi xyz) per node, the leaf of slot k following the interior nodes as node (n - 1) + k; order = leaf slot -> triangle.
+ * The LINK form re-insertion works on (pbrt_amd/csrc/reinsert_core.hpp): nodes [0, 2 n - 1) numbered as in `boxes`, par (2 n - 1 words; the
+ * root's: 0xffffffff), kid (2 (n - 1) words), boxes as above.
+ * The arrays of HOST memory the device hook fills, each of which may be NULL, and the scalars it sets: */
+typedef struct pbrt_hip_build_stages {
+  uint32_t *morton_keys;  /* n: as morton_kernel wrote them, before the sort */
+  uint32_t *built_child, *built_parent_internal, *built_parent_leaf;  /* the tree after stage 1 (sah_build) */
+  float *built_boxes;
+  uint32_t *built_order;
+  uint32_t *links_par, *links_kid;  /* the link form after the passes of stage 2, before the child order (written when reinsert_ran) */
+  float *links_boxes;
+  uint32_t *opt_child, *opt_parent_internal, *opt_parent_leaf;  /* the tree stage 3 collapses (= built where stage 2 did not run) */
+  float *opt_boxes;
+  uint32_t *opt_order;
+  float *dp_F, *dp_Fl, *dp_G;  /* written when dp_ran: F[(4 node + k - 1) 3 + d - 1] of the n - 1 interior nodes, Fl[3 slot + d - 1], G[node] */
+  uint32_t *quads;             /* 16 words per quad node, quad_capacity nodes of room */
+  uint32_t quad_capacity;
+  uint32_t reinsert_ran, passes, moves, undone;  /* stage 2: whether it ran (flag set, tree at or above the threshold), passes kept, moves applied */
+  uint64_t visits;                               /* nodes its searches looked at, over all passes */
+  double cost_before, cost_after;                /* pbrt_hip_scene_optimize_cost's sums */
+  uint32_t dp_ran, n_quads, stack_need;
+} pbrt_hip_build_stages;
+#define PBRT_HIP_BUILD_STAGES_REINSERT 1u
+/* Uploads the soup to `device`, runs the builder a scene is built with (gpu_build_quads; flags: PBRT_HIP_BUILD_STAGES_REINSERT = with stage 2,
+ * as the default scene) with an observer that copies the tree to the host after every stage, and returns the copies.  No scene, no kernel
+ * of its own.  PBRT_HIP_ERR_INVALID for a null P / idx / out, n_tris < 2, a vertex index >= n_verts, a vertex that is not finite. */
+int pbrt_hip_gpu_build_stages_device(int device, const float *P, uint32_t n_verts, const uint32_t *idx, uint32_t n_tris, uint32_t flags,
+                                     pbrt_hip_build_stages *out);
+/* host only: stage 2 on a GIVEN tree -- child / boxes / order as above -> the link form after reinsert_batch_links with the default
+ * ReinsertBatchParams (the device loop's passes, pbrt_amd/csrc/reinsert_batch.cpp), child order included.  stats (8 words): passes run (an
+ * undone one included), visits, searches that found a move, moves applied, most visits of one search, undone, the summed area before and
+ * after in fixed point, units of 2^-*fixed_exp (ri_cost_kernel's sums); *valid = LinkTree::valid of the result.  Outputs may be NULL.
+ * PBRT_HIP_ERR_INVALID for a null input, n_tris < 2, a box that is not finite, a triangle id >= n_tris, a child word out of range or words
+ * that do not form one tree. */
+int pbrt_hip_reinsert_links_host(uint32_t n_tris, const uint32_t *child, const float *boxes, const uint32_t *order, uint32_t *par, uint32_t *kid,
+                                 float *links_boxes, uint64_t *stats, int32_t *fixed_exp, uint32_t *valid);
+/* host only: stage 3 on a GIVEN tree -- quad_nodes.cpp's collapse with the rule forced; a leaf child's slot is the tree's own.  Refusals as above,
+ * and an unknown rule; PBRT_HIP_ERR_LIMIT when cap_nodes is too small. */
+#define PBRT_HIP_COLLAPSE_GREEDY 1u
+#define PBRT_HIP_COLLAPSE_DP 2u
+int pbrt_hip_collapse_host(uint32_t n_tris, const uint32_t *child, const float *boxes, const uint32_t *order, uint32_t rule, uint32_t *quads,
+                           uint32_t cap_nodes, uint32_t *n_quads, uint32_t *stack_need);
+
 /* ---- samplers: the reference holds the Sobol' generator matrices (sobolmatrices.rs:81) and no sampler ---- */
 /* host only: the generator matrices sampler 2 uses -- 128 dimensions x 32 columns, rows 0 .. 127 of the reference's
  * SOBOL_MATRICES32 (sobolmatrices.rs:81), the first 32 of its 52 columns -- for tests of that claim */

@@ -55,6 +55,17 @@ def read_slot(table, i, cls):
     return cls.from_buffer_copy(C.string_at(C.byref(table[i]), SLOT_BYTES))
 
 
+class BuildStages(C.Structure):
+    """pbrt_hip_build_stages (include/pbrt_hip_debug.h): the host arrays pbrt_hip_gpu_build_stages_device fills, and its scalars"""
+    _u, _fl = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+    _fields_ = [("morton_keys", _u), ("built_child", _u), ("built_parent_internal", _u), ("built_parent_leaf", _u), ("built_boxes", _fl),
+                ("built_order", _u), ("links_par", _u), ("links_kid", _u), ("links_boxes", _fl), ("opt_child", _u), ("opt_parent_internal", _u),
+                ("opt_parent_leaf", _u), ("opt_boxes", _fl), ("opt_order", _u), ("dp_F", _fl), ("dp_Fl", _fl), ("dp_G", _fl), ("quads", _u),
+                ("quad_capacity", C.c_uint32), ("reinsert_ran", C.c_uint32), ("passes", C.c_uint32), ("moves", C.c_uint32), ("undone", C.c_uint32),
+                ("visits", C.c_uint64), ("cost_before", C.c_double), ("cost_after", C.c_double), ("dp_ran", C.c_uint32), ("n_quads", C.c_uint32),
+                ("stack_need", C.c_uint32)]
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_uint32), ("p", C.c_float * 3), ("c", C.c_float * 3), ("pad", C.c_float)]
 
@@ -116,6 +127,9 @@ SYMBOLS = {
     "pbrt_hip_bvh_build_host": (C.c_int, [_pf, _u32, _pu32, _u32, _pu32, _pu32, _pu32, _pu32]),
     "pbrt_hip_quad_build_host": (C.c_int, [_pf, _u32, _pu32, _u32, C.c_int, _pu32, _u32, _pu32, _pu32]),
     "pbrt_hip_quad_build_host_ex": (C.c_int, [_pf, _u32, _pu32, _u32, C.c_int, _u32, _pu32, _u32, _pu32, _pu32, _pu32, _pf, _pu32, _pf]),
+    "pbrt_hip_gpu_build_stages_device": (C.c_int, [C.c_int, _pf, _u32, _pu32, _u32, _u32, C.POINTER(BuildStages)]),
+    "pbrt_hip_reinsert_links_host": (C.c_int, [_u32, _pu32, _pf, _pu32, _pu32, _pu32, _pf, _pu64, _pi32, _pu32]),
+    "pbrt_hip_collapse_host": (C.c_int, [_u32, _pu32, _pf, _pu32, _u32, _pu32, _u32, _pu32, _pu32]),
     "pbrt_hip_render": (C.c_int, [_vp, C.POINTER(RenderDesc), _pf, C.POINTER(Stats)]),
     "pbrt_hip_render_device": (C.c_int, [_vp, C.POINTER(RenderDesc), _vp, _vp]),
     "pbrt_hip_render_prepare": (C.c_int, [_vp, C.POINTER(RenderDesc)]),

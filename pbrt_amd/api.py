@@ -345,6 +345,71 @@ def quad_build_host_ex(P, idx, tree="default", split_leaves=True):
             "exact_boxes": exact[:nq.value].copy()}
 
 
+def _stage_tree_args(child, boxes, order):
+    child = np.ascontiguousarray(child, np.uint32).reshape(-1)
+    boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1)
+    order = np.ascontiguousarray(order, np.uint32).reshape(-1)
+    n = order.size
+    if n < 1 or child.size != 2 * (n - 1) or boxes.size != 6 * (2 * n - 1):
+        raise ValueError("a tree of n leaves has 2 (n - 1) child words, 6 (2 n - 1) box floats and n order words")
+    return n, child, boxes, order
+
+
+def gpu_build_stages(P, idx, reinsert=True, device=0):
+    """pbrt_hip_gpu_build_stages_device: the device tree builder run on a triangle soup with an observer between its stages ->
+    dict(morton_keys; built / optimised = dict(child[n - 1, 2], parent_internal, parent_leaf, boxes[2 n - 1, 6], order); links = dict(par, kid[n - 1, 2],
+    boxes) or None where stage 2 did not run; reinsert = its counts, or None; dp = dict(F[n - 1, 4, 3], Fl[n, 3], G) or None; quads[n_quads, 16],
+    stack_need)"""
+    P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(idx, np.uint32).reshape(-1, 3)
+    n = max(idx.shape[0], 2)
+    u, f = (lambda *s: np.zeros(s, np.uint32)), (lambda *s: np.zeros(s, np.float32))
+    tree = lambda: {"child": u(n - 1, 2), "parent_internal": u(n - 1), "parent_leaf": u(n), "boxes": f(2 * n - 1, 6), "order": u(n)}
+    keys, built, opt = u(n), tree(), tree()
+    links = {"par": u(2 * n - 1), "kid": u(n - 1, 2), "boxes": f(2 * n - 1, 6)}
+    dp = {"F": f(n - 1, 4, 3), "Fl": f(n, 3), "G": f(n - 1)}
+    quads = u(n, 16)
+    st = _lib.BuildStages(morton_keys=_u32p(keys), links_par=_u32p(links["par"]), links_kid=_u32p(links["kid"]), links_boxes=_fp(links["boxes"]),
+                          dp_F=_fp(dp["F"]), dp_Fl=_fp(dp["Fl"]), dp_G=_fp(dp["G"]), quads=_u32p(quads), quad_capacity=n)
+    for name, t in (("built", built), ("opt", opt)):
+        for k, a in t.items():
+            setattr(st, f"{name}_{k}", _fp(a) if k == "boxes" else _u32p(a))
+    check(lib().pbrt_hip_gpu_build_stages_device(device, _fp(P), P.shape[0], _u32p(idx), idx.shape[0], 1 if reinsert else 0, C.byref(st)),
+          "pbrt_hip_gpu_build_stages_device")
+    ran = bool(st.reinsert_ran)
+    return {"morton_keys": keys, "built": built, "optimised": opt, "links": links if ran else None,
+            "reinsert": {"passes": st.passes, "moves": st.moves, "undone": st.undone, "visits": st.visits, "cost_before": st.cost_before,
+                         "cost_after": st.cost_after} if ran else None,
+            "dp": dp if st.dp_ran else None, "quads": quads[:st.n_quads].copy(), "stack_need": st.stack_need}
+
+
+def reinsert_links_host(child, boxes, order):
+    """pbrt_hip_reinsert_links_host (no device): stage 2 of the device builder run on the host on the binary tree child / boxes / order ->
+    dict(par, kid[n - 1, 2], boxes[2 n - 1, 6], passes, visits, found, applied, max_visits, undone, fixed_before, fixed_after, fixed_exp, valid)"""
+    n, child, boxes, order = _stage_tree_args(child, boxes, order)
+    par, kid, bx = np.zeros(2 * n - 1, np.uint32), np.zeros((n - 1, 2), np.uint32), np.zeros((2 * n - 1, 6), np.float32)
+    stats = np.zeros(8, np.uint64)
+    e, valid = C.c_int32(), C.c_uint32()
+    check(lib().pbrt_hip_reinsert_links_host(n, _u32p(child), _fp(boxes), _u32p(order), _u32p(par), _u32p(kid), _fp(bx),
+                                             stats.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(e), C.byref(valid)), "pbrt_hip_reinsert_links_host")
+    out = {"par": par, "kid": kid, "boxes": bx, "fixed_exp": e.value, "valid": bool(valid.value)}
+    out.update(zip(("passes", "visits", "found", "applied", "max_visits", "undone", "fixed_before", "fixed_after"), (int(v) for v in stats)))
+    return out
+
+
+COLLAPSE_RULES = {"greedy": 1, "dp": 2}
+
+
+def collapse_host(child, boxes, order, rule):
+    """pbrt_hip_collapse_host (no device): stage 3 on the binary tree child / boxes / order, `rule` "dp" or "greedy" -> (quads[n, 16], stack_need)"""
+    n, child, boxes, order = _stage_tree_args(child, boxes, order)
+    quads = np.zeros((n, 16), np.uint32)
+    nq, need = C.c_uint32(), C.c_uint32()
+    check(lib().pbrt_hip_collapse_host(n, _u32p(child), _fp(boxes), _u32p(order), COLLAPSE_RULES[rule], _u32p(quads), n, C.byref(nq), C.byref(need)),
+          "pbrt_hip_collapse_host")
+    return quads[:nq.value].copy(), need.value
+
+
 def film_from_acc(acc, weighted=False):
     """pbrt_hip_film_from_acc: (..., 4) int64 accumulators -> (..., 4) float32 film pixels {X, Y, Z, weight}.  weighted: the accumulators
     of a weighted pixel filter, whose fourth is the weight sum in 2^-24 units (pbrt_hip_film_from_acc_weighted)."""

@@ -26,6 +26,7 @@
 #include <rocprim/device/device_radix_sort.hpp>  // (rocPRIM directly: hipCUB is its CUDA-compatibility face)
 #include <rocprim/device/device_scan.hpp>
 
+#include "build_stages.hpp"
 #include "dev_buf.hpp"
 #include "device_types.h"
 #include "quad_encode.hpp"
@@ -747,8 +748,25 @@ struct BinaryTree {
   }
 };
 
+// ---- the observer (build_stages.hpp): copies to the host on the build's stream, for tests that look between the stages ----
+template <class T, class U>
+hipError_t copy_to_host(std::vector<T> &out, const U *d_src, size_t count, hipStream_t stream) {
+  static_assert(sizeof(U) % sizeof(T) == 0, "whole elements");
+  out.resize(count * (sizeof(U) / sizeof(T)));
+  if (count) GB_TRY(hipMemcpyAsync(out.data(), d_src, count * sizeof(U), hipMemcpyDeviceToHost, stream));
+  return hipStreamSynchronize(stream);
+}
+hipError_t copy_tree_to_host(StageTree &out, const BinaryTree &t, const uint32_t *d_order, hipStream_t stream) {
+  const size_t n = (size_t)t.n;
+  GB_TRY(copy_to_host(out.child, t.child.p, 2 * (n - 1), stream));
+  GB_TRY(copy_to_host(out.parent_internal, t.parent_internal.p, n - 1, stream));
+  GB_TRY(copy_to_host(out.parent_leaf, t.parent_leaf.p, n, stream));
+  GB_TRY(copy_to_host(out.boxes, t.boxes.p, kBoxWords * (2 * n - 1), stream));  // (a box's three 64-bit words are six floats)
+  return copy_to_host(out.order, d_order, n, stream);
+}
+
 // Stage 1: Morton keys, the radix sort, and the level-synchronous binned SAH build over the sorted triangles.  Fills `t` and d_order.
-hipError_t sah_build(const float *d_P, const uint32_t *d_idx, BinaryTree &t, uint32_t *d_order, hipStream_t stream) {
+hipError_t sah_build(const float *d_P, const uint32_t *d_idx, BinaryTree &t, uint32_t *d_order, hipStream_t stream, GpuBuildStages *obs) {
   const int n = t.n;
   const uint32_t n_tris = (uint32_t)n;
   const dim3 block(256), grid_t((n_tris + 255u) / 256u);
@@ -830,6 +848,10 @@ hipError_t sah_build(const float *d_P, const uint32_t *d_idx, BinaryTree &t, uin
     GB_TRY(hipGetLastError());
     GB_TRY(hipStreamSynchronize(stream));  // (the scratch above is freed when this block ends)
   }
+  if (obs) {  // (the sort read keys and wrote keys_out: keys is still what morton_kernel left)
+    GB_TRY(copy_to_host(obs->morton_keys, keys.p, (size_t)n, stream));
+    GB_TRY(copy_tree_to_host(obs->built, t, d_order, stream));
+  }
   return hipSuccess;
 }
 
@@ -864,7 +886,7 @@ ReinsertKnobs read_reinsert_knobs() {
 // Passes of search / lock / check / apply / refit until a pass moves fewer than one node in 1024, `passes` at most, or the
 // searches have looked at more than kVisitBudget nodes per node of the tree in total (a mesh of coincident boxes, where
 // nothing prunes a search, costs a bounded amount).  The host reads two numbers per pass.
-hipError_t reinsert(BinaryTree &t, uint32_t *d_order, ReinsertStats &st, hipStream_t stream) {
+hipError_t reinsert(BinaryTree &t, uint32_t *d_order, ReinsertStats &st, hipStream_t stream, GpuBuildStages *obs) {
   const ReinsertKnobs knobs = read_reinsert_knobs();
   const int n = t.n;
   if ((uint32_t)n < knobs.min_tris || n < 8 || knobs.passes <= 0) return hipSuccess;
@@ -935,6 +957,16 @@ hipError_t reinsert(BinaryTree &t, uint32_t *d_order, ReinsertStats &st, hipStre
     if (reins::stop_after_pass(knobs.stop, applied, h_stats[0], n_nodes)) break;
   }
   st.cost_after = (double)cost * cost_unit;
+  if (obs) {  // the link form as the passes left it (the timing fields are set below)
+    obs->reinsert_ran = true;
+    GB_TRY(copy_to_host(obs->par, par.p, n_nodes, stream));
+    GB_TRY(copy_to_host(obs->kid, kid.p, 2 * (size_t)n_int, stream));
+    GB_TRY(copy_to_host(obs->bx, t.boxes.p, kBoxWords * (size_t)n_nodes, stream));
+    obs->reinsert = st;
+    obs->reinsert.passes = (uint32_t)done;
+    obs->reinsert.moves = (uint32_t)std::min<unsigned long long>(h_stats[2], 0xffffffffull);
+    obs->visits = h_stats[0];
+  }
   // child order, leaf counts, leaves renumbered in depth-first order, and back to the builder's arrays
   hipLaunchKernelGGL(ri_order_kernel, grid_i, block, 0, stream, rt);
   GB_TRY(zero_on_device(t.visits.p, (size_t)n, stream));
@@ -965,7 +997,7 @@ struct CollapseResult {
 };
 // Writes d_quads and `out`.  `done` is recorded behind the last read-back, so that the synchronisation which brings the results
 // home completes the caller's timing too.
-hipError_t collapse(const BinaryTree &t, uint4 *d_quads, hipEvent_t done, CollapseResult &out, hipStream_t stream) {
+hipError_t collapse(const BinaryTree &t, uint4 *d_quads, hipEvent_t done, CollapseResult &out, hipStream_t stream, GpuBuildStages *obs) {
   const int n = t.n;
   DevBuf<CollapseItem> q0, q1;
   DevBuf<uint32_t> counters, level_counts;
@@ -1023,13 +1055,24 @@ hipError_t collapse(const BinaryTree &t, uint4 *d_quads, hipEvent_t done, Collap
   out.n_quads = h_counters[0];
   out.stack_need = h_counters[1];
   out.levels = levels;
+  if (obs) {
+    obs->dp_ran = use_dp;
+    if (use_dp) {
+      GB_TRY(copy_to_host(obs->F, dpF.p, kDpFWords * ((size_t)n - 1), stream));
+      GB_TRY(copy_to_host(obs->Fl, dpFl.p, kDpFlWords * (size_t)n, stream));
+      GB_TRY(copy_to_host(obs->G, dpG.p, (size_t)n - 1, stream));
+    }
+    GB_TRY(copy_to_host(obs->quads, d_quads, 4 * (size_t)out.n_quads, stream));
+    obs->n_quads = out.n_quads;
+    obs->stack_need = out.stack_need;
+  }
   return hipSuccess;
 }
 
 }  // namespace
 
 hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_tris, uint32_t *d_order, uint4 *d_quads,
-                           uint32_t quad_capacity, uint32_t flags, GpuBuildInfo *info, hipStream_t stream) {
+                           uint32_t quad_capacity, uint32_t flags, GpuBuildInfo *info, hipStream_t stream, GpuBuildStages *stages) {
   if (n_tris < 2u || n_tris > 0x7fffffffu) return hipErrorInvalidValue;  // (the caller builds trees of fewer than two triangles on the host)
   if (quad_capacity + 1u < n_tris) return hipErrorInvalidValue;  // a quad per interior node of the binary tree at most
   BinaryTree tree;
@@ -1037,11 +1080,12 @@ hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_t
   Events ev;
   GB_TRY(ev.create());
   GB_TRY(hipEventRecord(ev.a, stream));
-  GB_TRY(sah_build(d_P, d_idx, tree, d_order, stream));
+  GB_TRY(sah_build(d_P, d_idx, tree, d_order, stream, stages));
   info->reinsert = ReinsertStats{};
-  if (flags & kGpuBuildReinsert) GB_TRY(reinsert(tree, d_order, info->reinsert, stream));
+  if (flags & kGpuBuildReinsert) GB_TRY(reinsert(tree, d_order, info->reinsert, stream, stages));
+  if (stages) GB_TRY(copy_tree_to_host(stages->optimised, tree, d_order, stream));
   CollapseResult c{};
-  GB_TRY(collapse(tree, d_quads, ev.b, c, stream));
+  GB_TRY(collapse(tree, d_quads, ev.b, c, stream, stages));
   GB_TRY(hipEventElapsedTime(&info->build_ms, ev.a, ev.b));
   info->n_quads = c.n_quads;
   info->stack_need = c.stack_need;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/pbrt_hip.h"
+#include "build_stages.hpp"
 #include "bvh_build.hpp"
 #include "capi_internal.hpp"
 #include "device_types.h"
@@ -550,6 +551,30 @@ int ensure_canonical(pbrt_hip_scene *s) {
 }
 }  // namespace pbrt_hip
 
+// ---- the device tree builder between its stages, and the host's runs of stages 2 and 3 on a given tree (build_stages.hpp) ----
+namespace {
+template <class T>
+void copy_out(T *dst, const std::vector<T> &src) {
+  if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
+}
+void copy_tree_out(const StageTree &t, uint32_t *child, uint32_t *parent_internal, uint32_t *parent_leaf, float *boxes, uint32_t *order) {
+  copy_out(child, t.child); copy_out(parent_internal, t.parent_internal); copy_out(parent_leaf, t.parent_leaf);
+  copy_out(boxes, t.boxes); copy_out(order, t.order);
+}
+// a binary tree handed in as child words / boxes / leaf order: the refusals the two host hooks share (the words themselves:
+// link_tree_of_child_words)
+int check_stage_tree(const char *who, uint32_t n_tris, const uint32_t *child, const float *boxes, const uint32_t *order) {
+  const std::string w = who;
+  if (!child || !boxes || !order) return fail(PBRT_HIP_ERR_INVALID, w + ": null argument");
+  if (n_tris < 2u || n_tris > 0x7fffffffu) return fail(PBRT_HIP_ERR_INVALID, w + ": fewer than two triangles (or more than 2^31 - 1)");
+  for (size_t i = 0; i < 6 * (2 * (size_t)n_tris - 1); i++)
+    if (!std::isfinite(boxes[i])) return fail(PBRT_HIP_ERR_INVALID, w + ": a box is not finite");
+  for (uint32_t k = 0; k < n_tris; k++)
+    if (order[k] >= n_tris) return fail(PBRT_HIP_ERR_INVALID, w + ": a triangle id of the leaf order is out of range");
+  return PBRT_HIP_OK;
+}
+}  // namespace
+
 int pbrt_hip_scene::open(int on_device) {
   device = on_device;
   HIP_TRY(hipSetDevice(device));
@@ -624,6 +649,94 @@ int pbrt_hip_quad_build_host_ex(const float *P, uint32_t n_verts, const uint32_t
       if (*n_quads > cap_nodes) return fail(PBRT_HIP_ERR_LIMIT, "quad_build_host: output too small");
       if (!q.q.empty()) std::memcpy(quads, q.q.data(), q.q.size() * 16);
       if (exact_boxes && !q.exact.empty()) std::memcpy(exact_boxes, q.exact.data(), q.exact.size() * 4);
+    }
+    return PBRT_HIP_OK;
+  });
+}
+
+int pbrt_hip_gpu_build_stages_device(int device, const float *P, uint32_t n_verts, const uint32_t *idx, uint32_t n_tris, uint32_t flags,
+                                     pbrt_hip_build_stages *out) {
+  return guarded([&]() -> int {
+    if (!P || !idx || !out) return fail(PBRT_HIP_ERR_INVALID, "gpu_build_stages: null argument");
+    if (n_tris < 2u || n_tris > 0x7fffffffu) return fail(PBRT_HIP_ERR_INVALID, "gpu_build_stages: fewer than two triangles (or more than 2^31 - 1)");
+    if (flags & ~PBRT_HIP_BUILD_STAGES_REINSERT) return fail(PBRT_HIP_ERR_INVALID, "gpu_build_stages: unknown flag");
+    for (size_t i = 0; i < 3 * (size_t)n_tris; i++)
+      if (idx[i] >= n_verts) return fail(PBRT_HIP_ERR_INVALID, "gpu_build_stages: vertex index out of range");
+    if (first_non_finite_vertex(P, idx, n_tris) >= 0) return fail(PBRT_HIP_ERR_INVALID, "gpu_build_stages: a vertex is not finite");
+    const int ndev = pbrt_hip_device_count();
+    if (ndev <= 0) return fail(PBRT_HIP_ERR_NO_DEVICE, "gpu_build_stages: no HIP device (there is no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(PBRT_HIP_ERR_INVALID, "gpu_build_stages: device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    const hipStream_t stream = nullptr;  // (the device's default stream, as the other hooks)
+    DevBuf<float> d_P;
+    DevBuf<uint32_t> d_idx, d_order;
+    DevBuf<uint4> d_quads;
+    HIP_TRY(upload(&d_P, P, 3 * (size_t)n_verts, stream));
+    HIP_TRY(upload(&d_idx, idx, 3 * (size_t)n_tris, stream));
+    HIP_TRY(d_order.alloc(n_tris));
+    HIP_TRY(d_quads.alloc(4 * (size_t)n_tris));
+    GpuBuildInfo gb{};
+    GpuBuildStages st;
+    HIP_TRY(gpu_build_quads(d_P.p, d_idx.p, n_tris, d_order.p, d_quads.p, n_tris, (flags & PBRT_HIP_BUILD_STAGES_REINSERT) ? kGpuBuildReinsert : 0u, &gb,
+                            stream, &st));
+    copy_out(out->morton_keys, st.morton_keys);
+    copy_tree_out(st.built, out->built_child, out->built_parent_internal, out->built_parent_leaf, out->built_boxes, out->built_order);
+    copy_out(out->links_par, st.par); copy_out(out->links_kid, st.kid); copy_out(out->links_boxes, st.bx);
+    copy_tree_out(st.optimised, out->opt_child, out->opt_parent_internal, out->opt_parent_leaf, out->opt_boxes, out->opt_order);
+    copy_out(out->dp_F, st.F); copy_out(out->dp_Fl, st.Fl); copy_out(out->dp_G, st.G);
+    out->reinsert_ran = st.reinsert_ran ? 1u : 0u;
+    out->passes = st.reinsert.passes; out->moves = st.reinsert.moves; out->undone = st.reinsert.undone;
+    out->visits = st.visits;
+    out->cost_before = st.reinsert.cost_before; out->cost_after = st.reinsert.cost_after;
+    out->dp_ran = st.dp_ran ? 1u : 0u;
+    out->n_quads = st.n_quads; out->stack_need = st.stack_need;
+    if (out->quads) {
+      if (st.n_quads > out->quad_capacity) return fail(PBRT_HIP_ERR_LIMIT, "gpu_build_stages: output too small");
+      copy_out(out->quads, st.quads);
+    }
+    return PBRT_HIP_OK;
+  });
+}
+
+int pbrt_hip_reinsert_links_host(uint32_t n_tris, const uint32_t *child, const float *boxes, const uint32_t *order, uint32_t *par, uint32_t *kid,
+                                 float *links_boxes, uint64_t *stats, int32_t *fixed_exp, uint32_t *valid) {
+  return guarded([&]() -> int {
+    const int rc = check_stage_tree("reinsert_links_host", n_tris, child, boxes, order);
+    if (rc) return rc;
+    LinkTree lt;
+    std::string why;
+    if (!link_tree_of_child_words(n_tris, child, boxes, &lt, &why)) return fail(PBRT_HIP_ERR_INVALID, "reinsert_links_host: " + why);
+    ReinsertBatchStats st;
+    reinsert_batch_links(&lt, ReinsertBatchParams{}, &st);
+    copy_out(par, lt.par);
+    copy_out(kid, lt.kid);
+    if (links_boxes) std::memcpy(links_boxes, lt.bx.data(), lt.bx.size() * sizeof(lt.bx[0]));  // (three 64-bit words = six floats)
+    if (stats) {
+      const uint64_t s[8] = {st.passes, st.visits, st.found, st.applied, st.max_visits, st.undone, st.fixed_before, st.fixed_after};
+      std::memcpy(stats, s, sizeof(s));
+    }
+    if (fixed_exp) *fixed_exp = st.fixed_exp;
+    if (valid) *valid = lt.valid() ? 1u : 0u;
+    return PBRT_HIP_OK;
+  });
+}
+
+int pbrt_hip_collapse_host(uint32_t n_tris, const uint32_t *child, const float *boxes, const uint32_t *order, uint32_t rule, uint32_t *quads,
+                           uint32_t cap_nodes, uint32_t *n_quads, uint32_t *stack_need) {
+  return guarded([&]() -> int {
+    const int rc = check_stage_tree("collapse_host", n_tris, child, boxes, order);
+    if (rc) return rc;
+    if (!n_quads || !stack_need) return fail(PBRT_HIP_ERR_INVALID, "collapse_host: null argument");
+    if (rule != PBRT_HIP_COLLAPSE_GREEDY && rule != PBRT_HIP_COLLAPSE_DP) return fail(PBRT_HIP_ERR_INVALID, "collapse_host: unknown rule");
+    QuadNodes q;
+    std::string why;
+    if (!collapse_child_words(n_tris, child, boxes, rule == PBRT_HIP_COLLAPSE_DP ? kCollapseDp : kCollapseGreedy, &q, &why))
+      return fail(PBRT_HIP_ERR_INVALID, "collapse_host: " + why);
+    *n_quads = (uint32_t)(q.q.size() / 4);
+    *stack_need = q.stack_need;
+    if (quads) {
+      if (*n_quads > cap_nodes) return fail(PBRT_HIP_ERR_LIMIT, "collapse_host: output too small");
+      std::memcpy(quads, q.q.data(), q.q.size() * 16);
     }
     return PBRT_HIP_OK;
   });

@@ -313,8 +313,9 @@ struct GpuBuildInfo {
   ReinsertStats reinsert;
 };
 constexpr uint32_t kGpuBuildReinsert = 1u;  // flags of gpu_build_quads: optimise the binary tree by re-insertion before the collapse
+struct GpuBuildStages;  // build_stages.hpp: host copies of the tree between the stages (null on every production path)
 hipError_t gpu_build_quads(const float *d_P, const uint32_t *d_idx, uint32_t n_tris, uint32_t *d_order, uint4 *d_quads,
-                           uint32_t quad_capacity, uint32_t flags, GpuBuildInfo *info, hipStream_t stream);
+                           uint32_t quad_capacity, uint32_t flags, GpuBuildInfo *info, hipStream_t stream, GpuBuildStages *stages = nullptr);
 hipError_t launch_assemble(const float4 *slab, float4 *film, int32_t w, int32_t h, uint32_t rank, uint32_t world,
                            uint32_t n_local_super, hipStream_t stream);
 

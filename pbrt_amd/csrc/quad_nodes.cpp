@@ -8,6 +8,7 @@
 #include <cstring>
 #include <limits>
 
+#include "build_stages.hpp"
 #include "quad_encode.hpp"
 
 namespace pbrt_hip {
@@ -263,6 +264,40 @@ void make_quad_nodes_as(const RefBvh &b, const uint32_t *slot_of_ref, bool split
     const int nk = count_of(b.nodes[it.node]) ? qb.leaf_children(it.node, kids) : qb.choose_children(it.node, how, kids);
     qb.emit(it, kids, nk);
   }
+}
+
+// (build_stages.hpp) the collapse above over a tree in the device builder's form: flattened depth-first, reference r = leaf slot r
+bool collapse_child_words(uint32_t n_tris, const uint32_t *child, const float *boxes, Collapse how, QuadNodes *out, std::string *why) {
+  LinkTree lt;  // (checks every word, and that the words form one tree)
+  if (!link_tree_of_child_words(n_tris, child, boxes, &lt, why)) return false;
+  const uint32_t n_int = n_tris - 1u;
+  RefBvh rb;
+  rb.ref_tri.resize(n_tris);
+  rb.ref_lo.resize(3 * (size_t)n_tris);
+  rb.ref_hi.resize(3 * (size_t)n_tris);
+  for (uint32_t r = 0; r < n_tris; r++) {
+    rb.ref_tri[r] = r;
+    for (int a = 0; a < 3; a++) { rb.ref_lo[3 * (size_t)r + a] = boxes[6 * (size_t)(n_int + r) + a]; rb.ref_hi[3 * (size_t)r + a] = boxes[6 * (size_t)(n_int + r) + 3 + a]; }
+  }
+  rb.nodes.reserve(2 * (size_t)n_tris);
+  struct It { uint32_t node; int patch; };
+  std::vector<It> st = {{0u, -1}};
+  while (!st.empty()) {
+    const It it = st.back();
+    st.pop_back();
+    const int me = (int)rb.nodes.size();
+    if (it.patch >= 0) rb.nodes[it.patch].offset = (uint32_t)me;
+    BvhNode b{};
+    for (int a = 0; a < 3; a++) { b.lo[a] = boxes[6 * (size_t)it.node + a]; b.hi[a] = boxes[6 * (size_t)it.node + 3 + a]; }
+    if (it.node >= n_int) { b.offset = it.node - n_int; b.count_axis = 1u; }
+    rb.nodes.push_back(b);
+    if (it.node < n_int) {
+      st.push_back({lt.kid[2 * (size_t)it.node + 1], me});  // second child: patched when reached
+      st.push_back({lt.kid[2 * (size_t)it.node], -1});      // first child: the next node
+    }
+  }
+  make_quad_nodes_as(rb, nullptr, /*split_leaves=*/false, how, out);
+  return true;
 }
 
 // A-B aid (PBRT_HIP_QUAD_LAYOUT=pre|pre_big behind the debug switch): renumber the quad nodes in depth-first PRE-order, so

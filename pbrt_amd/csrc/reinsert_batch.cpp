@@ -5,6 +5,8 @@
 // the same tree from the same input.  Nothing here is on the product's render path: the product optimises on the device.
 #include "reinsert_batch.hpp"
 
+#include "build_stages.hpp"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -152,6 +154,43 @@ void link_tree_of(const RefBvh &rb, LinkTree *out) {
   }
 }
 
+// (build_stages.hpp) the device's own conversion, ri_links_kernel of bvh_gpu.hip, with every word checked first
+bool link_tree_of_child_words(uint32_t n_tris, const uint32_t *child, const float *boxes, LinkTree *out, std::string *why) {
+  auto bad = [&](const char *m) { if (why) *why = m; return false; };
+  if (n_tris < 2u || n_tris > 0x7fffffffu) return bad("fewer than two triangles");
+  const uint32_t n_int = n_tris - 1u, n_nodes = 2u * n_int + 1u;
+  out->n_int = n_int;
+  out->par.assign(n_nodes, kNone);
+  out->kid.assign(2 * (size_t)n_int, kNone);
+  out->bx.assign(3 * (size_t)n_nodes, 0ull);
+  for (uint32_t i = 0; i < n_int; i++)
+    for (int k = 0; k < 2; k++) {
+      const uint32_t c = child[2 * (size_t)i + k], slot = c & ~kLeafRef;
+      if ((c & kLeafRef) ? slot >= n_tris : c >= n_int) return bad("a child word is out of range");
+      const uint32_t id = (c & kLeafRef) ? n_int + slot : c;
+      if (id == 0u || out->par[id] != kNone) return bad("a node is the child of two nodes, or the root of one");
+      out->kid[2 * (size_t)i + k] = id;
+      out->par[id] = i;
+    }
+  // (2 n - 2 child words, all different and none the root: every other node has one parent; what is left to rule out is a cycle)
+  std::vector<uint32_t> st = {0u};
+  size_t reached = 0;
+  while (!st.empty()) {
+    const uint32_t i = st.back();
+    st.pop_back();
+    reached++;
+    if (i < n_int) { st.push_back(out->kid[2 * (size_t)i]); st.push_back(out->kid[2 * (size_t)i + 1]); }
+  }
+  if (reached != n_nodes) return bad("not every node is reachable from the root");
+  reins::Tree t{n_int, out->par.data(), out->kid.data(), out->bx.data()};
+  for (uint32_t i = 0; i < n_nodes; i++) {
+    reins::Box b;
+    for (int a = 0; a < 3; a++) { b.lo[a] = boxes[6 * (size_t)i + a]; b.hi[a] = boxes[6 * (size_t)i + 3 + a]; }
+    reins::store_box(t, i, b);
+  }
+  return true;
+}
+
 void ref_bvh_of(const LinkTree &lt, const RefBvh &refs, RefBvh *out) {
   RefBvh o;
   const uint32_t n_int = lt.n_int;
@@ -243,8 +282,8 @@ void reinsert_batch_links(LinkTree *lt, const ReinsertBatchParams &prm, Reinsert
     return;
   }
   // the summed area of the interior nodes as the device reduces it: exact integers (units of 2^-se of reinsert_core.hpp's find_move)
+  int se = 0;  // (the root's box is the union of the leaves' boxes: no pass changes it, nor the scale)
   auto fixed_cost = [&]() {
-    int se = 0;
     (void)frexpf(reins::area(reins::load_box(t, 0u)), &se);
     se = 40 - se;
     se = se > 100 ? 100 : (se < -100 ? -100 : se);
@@ -254,7 +293,11 @@ void reinsert_batch_links(LinkTree *lt, const ReinsertBatchParams &prm, Reinsert
     return sum;
   };
   unsigned long long cost = fixed_cost();
-  if (stats) stats->cost_before = stats->cost_after = lt->cost();
+  if (stats) {
+    stats->cost_before = stats->cost_after = lt->cost();
+    stats->fixed_before = stats->fixed_after = cost;
+    stats->fixed_exp = se;
+  }
   uint64_t visits_total = 0;
   for (int pass = 0; pass < prm.passes; pass++) {
     const std::vector<uint32_t> par_b = lt->par, kid_b = lt->kid;  // (a pass that raises the cost is undone)
@@ -314,7 +357,7 @@ void reinsert_batch_links(LinkTree *lt, const ReinsertBatchParams &prm, Reinsert
       break;
     }
     cost = cost_now;
-    if (stats) { stats->applied += applied; stats->cost_after = lt->cost(); }
+    if (stats) { stats->applied += applied; stats->cost_after = lt->cost(); stats->fixed_after = cost; }
     if (mu == 1 && reins::stop_after_pass(prm.stop, applied, visits_total, n_nodes)) break;
   }
   for (uint32_t i = 0; i < n_int; i++) reins::order_children(t, i);

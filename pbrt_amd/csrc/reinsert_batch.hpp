@@ -30,6 +30,9 @@ struct ReinsertBatchStats {
   uint64_t passes = 0, visits = 0, found = 0, applied = 0, max_visits = 0;
   uint64_t undone = 0;          // 1: the last pass raised the summed area and was undone
   double cost_before = 0, cost_after = 0;  // summed half surface area of the interior nodes
+  // the same two sums as the device reduces them (bvh_gpu.hip ri_cost_kernel): exact integers in units of 2^-fixed_exp
+  uint64_t fixed_before = 0, fixed_after = 0;
+  int32_t fixed_exp = 0;
 };
 
 // `rb`: every leaf holds one reference

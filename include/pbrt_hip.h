@@ -42,6 +42,7 @@ typedef enum {
 #define PBRT_HIP_MATERIAL_MATTE 0u
 #define PBRT_HIP_MATERIAL_MIRROR 1u
 #define PBRT_HIP_MATERIAL_GLASS 2u
+#define PBRT_HIP_MATERIAL_PLASTIC 3u
 /* Material "matte" / "mirror" / "glass" (scene files name them: scenes/check-sphere.pbrt:21,29; the
  * reference only has the TODO at api.rs:255-269).  32 bytes.
  * GLASS (type 2) is pbrt-v3's GlassMaterial with zero roughness: one FresnelSpecular lobe, an interface between index 1
@@ -52,13 +53,22 @@ typedef enum {
  * sample chooses reflection (probability F, the Fresnel reflectance; weight Kr) or refraction (1 - F; weight Kt eta_i^2 / eta_t^2:
  * radiance transport); also under Integrator "directlighting", where pbrt-v3 follows both branches and this path follows the one
  * chosen (same expectation).  Every interface crossed costs one bounce of max_depth.  A glass primitive occludes shadow rays (as in
- * pbrt-v3: no caustics by light sampling).  Not with the counter flags (PBRT_HIP_ERR_LIMIT). */
+ * pbrt-v3: no caustics by light sampling).  Not with the counter flags (PBRT_HIP_ERR_LIMIT).
+ * PLASTIC (type 3) is pbrt-v3's PlasticMaterial: a Lambertian base Kd / pi plus a Trowbridge-Reitz microfacet reflection of
+ * isotropic width alpha with the Fresnel term of a dielectric of index 1.5 against 1.  It reuses the record the way glass does:
+ *   k = Kd, le = Ks (a plastic surface does not emit), kd_tex = the IEEE-754 bits of the float alpha.
+ * Kd, Ks finite and >= 0, alpha finite and in [1e-3, 1] (PBRT_HIP_ERR_INVALID otherwise, the message holds "plastic"; a type-3 record whose
+ * le and kd_tex are all zero -- nothing of plastic in it -- is refused as "unknown material type", as every type-3 record was until 0.10).  A plastic vertex
+ * draws what a matte one draws, in the same order; its lobe is about the GEOMETRIC normal.  Rendered for every integrator, sampler and
+ * filter, with spheres, textures on other materials, glass; NOT in a scene whose texture table holds an environment map (slot type 1) or
+ * shading normals (slot type 2): pbrt_hip_scene_create refuses the pair with PBRT_HIP_ERR_LIMIT (the message holds "plastic").  Not with
+ * the counter flags (PBRT_HIP_ERR_LIMIT at render, as for glass). */
 typedef struct {
-  uint32_t type; /* PBRT_HIP_MATERIAL_*: 0 = matte (Lambertian, k = Kd), 1 = mirror (perfect specular, k = Kr), 2 = glass (above) */
+  uint32_t type; /* PBRT_HIP_MATERIAL_*: 0 = matte (Lambertian, k = Kd), 1 = mirror (perfect specular, k = Kr), 2 = glass, 3 = plastic (above) */
   float k[3];
   float le[3]; /* emitted radiance; non-zero turns every triangle using it into an area light
-                  (replaces api.rs:476-478 area_light_source -> todo!()).  GLASS: Kt */
-  uint32_t kd_tex; /* GLASS: the bits of the float eta.  Matte only: 0 = Kd is k; t > 0 = Kd is textures[t - 1] evaluated at the hit's (u, v): a triangle's corner (u, v)
+                  (replaces api.rs:476-478 area_light_source -> todo!()).  GLASS: Kt.  PLASTIC: Ks */
+  uint32_t kd_tex; /* GLASS: the bits of the float eta.  PLASTIC: the bits of the float alpha.  Matte only: 0 = Kd is k; t > 0 = Kd is textures[t - 1] evaluated at the hit's (u, v): a triangle's corner (u, v)
                       (tri_uv) interpolated like the hit point; a SPHERE's own (u, v) = (phi / 2 pi, 1 - theta / pi) with phi = atan2(n.y, n.x)
                       in [0, 2 pi), theta = acos(n.z) of the unit normal n about the WORLD's z axis (pbrt-v3 Sphere::Intersect for an
                       unrotated sphere: a sphere here is a centre and a radius, its CTM's rotation is not carried -- the parser warns) */
@@ -283,7 +293,8 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.10 (gfx950; struct sizes of 0.6, as 0.7, 0.8 and 0.9)": 0.10 = texture-table slot type 4, the
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.11 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9 and 0.10)": 0.11 = material type 3, plastic, inside
+                                       the same struct sizes; 0.10 = texture-table slot type 4, the
                                        image texture, inside the same struct sizes; 0.9 = texture-table slot type 3, the pixel
                                        filter, likewise; 0.8 = texture-table slot type 2, the shading normals,
                                        likewise ("as 0.7, 0.8 and 0.9": tests of the environment map, of the normals and of the pixel filter look for "0.7", "0.8" and "0.9"

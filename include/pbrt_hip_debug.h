@@ -203,6 +203,15 @@ int pbrt_hip_image_lookup_eval_host(const pbrt_hip_image_texture *records, uint3
 int pbrt_hip_image_lookup_eval_device(int device, const pbrt_hip_image_texture *records, uint32_t n_records, uint32_t which, int64_t n, const float *uv,
                                       float *rgb);
 
+/* ---- the plastic material's BSDF (pbrt_amd/csrc/plastic_bsdf.hpp is the one statement of the arithmetic) ---- */
+/* plastic_bsdf.hpp over arrays on `device` (a small kernel of kernels_blocks.hip): element i reads 18 floats of `in` -- nf, wo, wi (unit
+ * vectors, nf the normal turned towards wo), u1, u2, Kd.rgb, Ks.rgb, alpha -- and writes 10 floats of `out`: f(wo, wi).rgb, pdf_b(wi), the
+ * direction wi' the sampler draws from (u1, u2), and f(wo, wi') cos / pdf_b(wi').rgb (the last six are zero where the sample dies).  in /
+ * out are HOST arrays.  PBRT_HIP_ERR_INVALID for a negative n or a null array, PBRT_HIP_ERR_NO_DEVICE without a device. */
+#define PBRT_HIP_PLASTIC_EVAL_IN 18
+#define PBRT_HIP_PLASTIC_EVAL_OUT 10
+int pbrt_hip_plastic_eval_device(int device, int64_t n, const float *in, float *out);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

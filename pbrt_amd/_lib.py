@@ -174,6 +174,7 @@ SYMBOLS = {
     "pbrt_hip_image_lookup_eval_host": (C.c_int, [C.POINTER(ImageTexture), _u32, _u32, _i64, _pf, _pf]),
     "pbrt_hip_image_lookup_eval_device": (C.c_int, [C.c_int, C.POINTER(ImageTexture), _u32, _u32, _i64, _pf, _pf]),
     "pbrt_hip_blocks_eval_device": (C.c_int, [C.c_int, _u32, _i64, _pf, _pf]),
+    "pbrt_hip_plastic_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
     "pbrt_hip_shading_normal_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
 }
 

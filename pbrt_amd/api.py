@@ -12,6 +12,7 @@ from . import _lib
 from ._lib import EnvMap, ImageTexture, Light, Material, Normals, PixelFilter, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
 
 MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
+PLASTIC = 3  # PBRT_HIP_MATERIAL_PLASTIC: DESIGN.md 3.21
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
 LIGHT_ENVMAP = 3  # PBRT_HIP_LIGHT_ENVMAP: the infinite light with an environment map
 INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_PATH_MIS = 0, 1, 2  # 2: the path integrator with MIS
@@ -48,7 +49,8 @@ class SceneData:
     0 or 1 + the row of `textures` that is material i's Kd, `textures` rows: (type 0 = checkerboard, tex1 rgb, tex2 rgb, su, sv, du,
     dv), `tri_uv` rows: (u0, v0, u1, v1, u2, v2) per triangle (needed when a triangle's material is textured).  Glass:
     a `materials` row (GLASS, Kr rgb, Kt rgb) -- a glass surface does not emit -- and `mat_eta[i]` = its index of refraction (an empty
-    `mat_eta` = 1.5 for every glass row; the entries of other rows are not read).  An environment map: a `lights` row
+    `mat_eta` = 1.5 for every glass row; the entries of other rows are not read).  Plastic: a `materials` row (PLASTIC, Kd rgb,
+    Ks rgb) and `mat_eta[i]` = its alpha, the float that rides where glass keeps eta (plastic_material makes the pair).  An environment map: a `lights` row
     (LIGHT_ENVMAP, 0, 0, 0, c rgb) -- c the factor on the texels -- and `envmap` = its (H, W, 3) texels, row 0 = the light's +z, with
     `envmap_world_to_light` = the 3 x 3 rotation; the record travels in a slot appended to the texture table (fill_desc).  Shading normals
     (DESIGN.md 3.18): `tri_n` rows: the normals of a triangle's three corners (n0 xyz, n1 xyz, n2 xyz), world space, any length, zeros = the
@@ -126,6 +128,8 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         if int(m[0]) == GLASS:  # include/pbrt_hip.h: k = Kr, le = Kt, kd_tex = the IEEE-754 bits of eta
             eta = sd.mat_eta[i:i + 1] if len(sd.mat_eta) else np.array([1.5], np.float32)
             mats[i].kd_tex = int(eta.view(np.uint32)[0])
+        if int(m[0]) == PLASTIC:  # k = Kd, le = Ks, kd_tex = the IEEE-754 bits of alpha
+            mats[i].kd_tex = int(sd.mat_eta[i:i + 1].view(np.uint32)[0]) if len(sd.mat_eta) else 0  # (no alpha given: 0, which scene creation refuses)
     # the table: every `textures` row in its own slot (mat_tex numbering does not move), then the records that travel with the scene, each in a
     # slot of its own -- the map's, the pixel filter's, the normals' (include/pbrt_hip.h pbrt_hip_envmap / _pixel_filter / _normals), in this order
     records = [image_record(sd.images[int(t[1])], int(t[2]), int(t[3]), t[7:11]) if int(t[0]) == TEXTURE_IMAGE else checker_record(t) for t in sd.textures]
@@ -176,6 +180,33 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
     desc.yres = int(sd.yres)
     desc.crop[:] = [float(x) for x in sd.crop]
     return [mats, lights, spheres, texs, sd]
+
+
+def roughness_to_alpha(roughness, remap=True):
+    """alpha of a plastic material as the scene parser forms it: the float32 roughness through pbrt-v3's RoughnessToAlpha
+    polynomial in double (remap), rounded to float32 and clamped to [1e-3, 1]"""
+    import math
+    r = float(np.float32(roughness))
+    a = r
+    if remap:
+        x = math.log(max(r, 1e-3))
+        a = 1.62142 + 0.819955 * x + 0.1734 * x * x + 0.0171201 * x * x * x + 0.000640711 * x * x * x * x
+    a = np.float32(a)
+    return np.float32(min(max(a, np.float32(1e-3)), np.float32(1.0))) if a == a else np.float32(1e-3)
+
+
+def plastic_material(kd=(0.25, 0.25, 0.25), ks=(0.25, 0.25, 0.25), roughness=0.1, remap=True):
+    """-> (the `materials` row (PLASTIC, Kd, Ks), alpha for `mat_eta`) of Material "plastic" with these parameters (pbrt-v3's defaults)"""
+    return [PLASTIC, *kd, *ks], roughness_to_alpha(roughness, remap)
+
+
+def plastic_eval_device(x, device=0):
+    """pbrt_hip_plastic_eval_device: csrc/plastic_bsdf.hpp over arrays on the device.  x (n, 18): nf, wo, wi, u1, u2, Kd, Ks, alpha ->
+    (n, 10) float32: f(wo, wi), pdf_b(wi), the sampled wi', f(wo, wi') cos / pdf_b(wi')"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 18)
+    out = np.zeros((x.shape[0], 10), np.float32)
+    check(lib().pbrt_hip_plastic_eval_device(int(device), x.shape[0], _fp(x), _fp(out)), "pbrt_hip_plastic_eval_device")
+    return out
 
 
 def checker_record(row):

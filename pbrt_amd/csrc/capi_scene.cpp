@@ -100,6 +100,12 @@ float glass_eta(const pbrt_hip_material &m) { float e; std::memcpy(&e, &m.kd_tex
 // glass is an interface between index 1 and eta: eta = 1 (index-matched: nothing reflects, nothing bends) is legal; 16 is four times
 // the densest real dielectric and keeps eta^2 and 1 / eta^2 -- the radiance scale of a refraction -- far from fp32's ends
 constexpr float kGlassEtaMin = 1.0f, kGlassEtaMax = 16.0f;
+// a plastic material's alpha rides in kd_tex the same way: the microfacet lobe's width, within [1e-3, 1] -- below, D's
+// peak 1 / (pi alpha^2) leaves fp32's comfortable range; above, pbrt-v3's roughness remap never goes
+float plastic_alpha(const pbrt_hip_material &m) { return glass_eta(m); }
+constexpr float kPlasticAlphaMin = 1e-3f, kPlasticAlphaMax = 1.0f;
+// the materials that reuse `le` and `kd_tex` for parameters of their own: they do not emit and name no texture
+bool reuses_le(const pbrt_hip_material &m) { return m.type == PBRT_HIP_MATERIAL_GLASS || m.type == PBRT_HIP_MATERIAL_PLASTIC; }
 
 // ---- check_scene_desc in stages: every refusal that depends on the description alone, before any HIP call.  Which of two faults is
 // reported is part of the behaviour, so a concern whose refusals lie apart in that order has a stage for each part: the lights' and the
@@ -181,7 +187,7 @@ int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
 int check_material_values(const pbrt_hip_scene_desc *d) {
   for (uint32_t i = 0; i < d->n_mats; i++)
     for (int k = 0; k < 3; k++)
-      if (d->mats[i].type != PBRT_HIP_MATERIAL_GLASS && (!std::isfinite(d->mats[i].k[k]) || !std::isfinite(d->mats[i].le[k])))
+      if (!reuses_le(d->mats[i]) && (!std::isfinite(d->mats[i].k[k]) || !std::isfinite(d->mats[i].le[k])))
         return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": colour / emission is not finite");
   for (uint32_t i = 0; i < d->n_mats; i++) {  // glass: k = Kr, le = Kt, kd_tex = the bits of eta
     const pbrt_hip_material &m = d->mats[i];
@@ -198,7 +204,7 @@ int check_material_values(const pbrt_hip_scene_desc *d) {
 // what the materials' kd_tex name
 int check_kd_tex(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   for (uint32_t i = 0; i < d->n_mats; i++) {
-    if (d->mats[i].type == PBRT_HIP_MATERIAL_GLASS) continue;  // (kd_tex holds eta)
+    if (reuses_le(d->mats[i])) continue;  // (kd_tex holds eta / alpha)
     if (table.named(d->mats[i].kd_tex) == SlotKind::kOutOfRange) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material texture number out of range");
   }
   for (uint32_t i = 0; i < d->n_mats; i++) {  // (a texture for Kd is a checkerboard or an image; a slot of no known kind is check_table's to refuse)
@@ -216,7 +222,35 @@ int check_kd_tex(const pbrt_hip_scene_desc *d, const TextureTable &table) {
 }
 int check_material_kinds(const pbrt_hip_scene_desc *d) {
   for (uint32_t i = 0; i < d->n_mats; i++)
-    if (d->mats[i].type > PBRT_HIP_MATERIAL_GLASS) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
+    if (d->mats[i].type > PBRT_HIP_MATERIAL_PLASTIC) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
+  // (a plastic record is checked HERE, where its kind is recognised -- the place a type-3 record was refused as unknown before there was
+  // plastic --, so that every fault that used to win against it still does)
+  for (uint32_t i = 0; i < d->n_mats; i++) {  // plastic: k = Kd, le = Ks, kd_tex = the bits of alpha
+    const pbrt_hip_material &m = d->mats[i];
+    if (m.type != PBRT_HIP_MATERIAL_PLASTIC) continue;
+    // Until 0.10 type 3 was no material at all.  A type-3 record that carries NOTHING of plastic -- no Ks and no alpha word: the words a
+    // matte record leaves zero -- is what a caller of that ABI wrote, and keeps the refusal it always had, word for word
+    if (m.kd_tex == 0u && m.le[0] == 0.f && m.le[1] == 0.f && m.le[2] == 0.f) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(m.k[k]) || !std::isfinite(m.le[k]) || !(m.k[k] >= 0.f) || !(m.le[k] >= 0.f))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": plastic Kd / Ks must be finite and >= 0");
+    const float alpha = plastic_alpha(m);
+    if (!std::isfinite(alpha) || !(alpha >= kPlasticAlphaMin && alpha <= kPlasticAlphaMax))  // (the message names both readings of the record)
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": plastic alpha (the float in kd_tex) must be finite and lie in [1e-3, 1]; "
+                  "type 3 is plastic since 0.11, to a caller that meant anything else it is an unknown material type");
+  }
+  return PBRT_HIP_OK;
+}
+// plastic is rendered by the GLS instantiations of render_kernel_x alone: the families that render an environment map or
+// shading normals do not carry its branch, and the scene is refused here, not at render time
+int check_plastic_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
+  bool plastic = false;
+  for (uint32_t i = 0; i < d->n_mats && !plastic; i++) plastic = d->mats[i].type == PBRT_HIP_MATERIAL_PLASTIC;
+  if (!plastic) return PBRT_HIP_OK;
+  for (const SlotKind kind : table.kinds) {
+    if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a plastic material is not available in a scene with an environment map");
+    if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a plastic material is not available in a scene with shading normals");
+  }
   return PBRT_HIP_OK;
 }
 
@@ -299,7 +333,8 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
   *table = decode_texture_table(*d);
   if ((rc = check_kd_tex(d, *table)) || (rc = check_table(d, *table)) || (rc = check_flags(flags, builder)) || (rc = check_sphere_boxes(d))) return rc;
   if ((rc = check_light_kinds(d, *table))) return rc;
-  return check_material_kinds(d);
+  if ((rc = check_material_kinds(d))) return rc;
+  return check_plastic_family(d, *table);
 }
 
 // What a checked description puts on the device, assembled on the host.
@@ -372,7 +407,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, Scen
   }
   for (uint32_t t = 0; t < d.n_tris; t++) {
     const pbrt_hip_material &m = d.mats[d.mat_id[t]];
-    if (m.type == PBRT_HIP_MATERIAL_GLASS) continue;  // (its le is Kt: glass does not emit)
+    if (reuses_le(m)) continue;  // (its le is Kt / Ks: glass and plastic do not emit)
     if (!(m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) continue;
     F3 p[3];
     for (int v = 0; v < 3; v++) {
@@ -396,6 +431,11 @@ void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, Scen
       in->mats[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (in->glass.empty()) in->glass.assign(d.n_mats, make_float4(0.f, 0.f, 0.f, 1.f));
       in->glass[i] = make_float4(m.le[0], m.le[1], m.le[2], glass_eta(m));
+    }
+    if (m.type == PBRT_HIP_MATERIAL_PLASTIC) {  // the same table carries {Ks, alpha}: no emission, no texture word
+      in->mats[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (in->glass.empty()) in->glass.assign(d.n_mats, make_float4(0.f, 0.f, 0.f, 1.f));
+      in->glass[i] = make_float4(m.le[0], m.le[1], m.le[2], plastic_alpha(m));
     }
   }
   in->spheres.resize(2 * (size_t)d.n_spheres);
@@ -597,7 +637,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.10 (gfx950; struct sizes of 0.6, as 0.7, 0.8 and 0.9)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.11 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9 and 0.10)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif

@@ -4,6 +4,7 @@
 #include "envmap_core.hpp"
 #include "image_lookup.hpp"
 #include "kernel_walk.hpp"
+#include "plastic_bsdf.hpp"
 
 namespace pbrt_hip {
 namespace {
@@ -72,6 +73,70 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
       scale = scale * mis_weight_light(pl, pbl);
     }
     Ld = (f * lc) * scale;
+    tmax = dist * kShadowShrink;
+    return true;
+  }
+}
+
+// sample_light's sibling for a BSDF that is not Lambertian (the plastic material; called under PLS alone, so that
+// sample_light and the instantiations built from it keep their machine code): the same light from the same (u1, u2), WITHOUT a BSDF
+// factor and without a MIS weight -- Lg = Li cos_i nL / pdf_l, the caller multiplies by f(wo, wi) -- and pl = the density that MIS
+// compares with the BSDF's for wi (light picked with 1 / nL), 0 for the point and the distant light.  The operations are sample_light's.
+__device__ __forceinline__ bool sample_light_general(const DevScene &S, uint32_t li, V3 po, V3 nf, float u1, float u2, float nLf, V3 &Lg, V3 &wi,
+                                                     float &tmax, float &pl) {
+  const float4 l0 = S.lights[5 * li];
+  const float4 l3 = S.lights[5 * li + 3];
+  const uint32_t type = __float_as_uint(l0.x);
+  const V3 p0 = {l0.y, l0.z, l0.w};
+  const V3 lc = xyz(l3);
+  pl = 0.f;
+  if (type == 0u) {
+    V3 dv = p0 - po;
+    float dist2 = dot(dv, dv);
+    if (!(dist2 > 0.f)) return false;
+    float dist = sqrtf(dist2);
+    wi = dv / dist;
+    float cs = dot(wi, nf);
+    if (!(cs > 0.f)) return false;
+    Lg = lc * ((cs / dist2) * nLf);
+    tmax = dist * kShadowShrink;
+    return true;
+  } else if (type == 1u) {
+    wi = p0;
+    float cs = dot(wi, nf);
+    if (!(cs > 0.f)) return false;
+    Lg = lc * (cs * nLf);
+    tmax = kInf;
+    return true;
+  } else if (type == 2u) {
+    // the constant infinite light: a cosine-sampled direction, pdf_l = cos_i / pi, so Lg = Le pi nL
+    float z = cosine_about(nf, u1, u2, wi);
+    if (z == 0.f) return false;
+    Lg = (lc * envmap::kPi) * nLf;
+    pl = (z * kInvPi) / nLf;
+    tmax = kInf;
+    return true;
+  } else {
+    // an emissive triangle (device type 3; the environment map's type 4 never arrives: a scene with plastic and a map is refused)
+    const float4 l1 = S.lights[5 * li + 1];
+    const float4 l2 = S.lights[5 * li + 2];
+    const float4 l4 = S.lights[5 * li + 4];
+    float su0 = sqrtf(u1);
+    float b0 = 1.0f - su0;
+    float b1 = u2 * su0;
+    float b2 = (1.0f - b0) - b1;
+    V3 pt = (p0 * b0 + xyz(l1) * b1) + xyz(l2) * b2;
+    V3 dv = pt - po;
+    float dist2 = dot(dv, dv);
+    if (!(dist2 > 0.f)) return false;
+    float dist = sqrtf(dist2);
+    wi = dv / dist;
+    float cs = dot(wi, nf);
+    if (!(cs > 0.f)) return false;
+    float cl = -dot(wi, xyz(l4));
+    if (!(cl > 0.f)) return false;
+    Lg = lc * ((((cs * cl) * l1.w) / dist2) * nLf);
+    pl = (dist2 / (cl * l1.w)) / nLf;
     tmax = dist * kShadowShrink;
     return true;
   }

@@ -43,6 +43,8 @@ __global__ void __launch_bounds__(64, (COUNT ? 1 : render_waves_per_simd(RenderF
   constexpr bool LREC = kLdsPathRecords && STACK != 0 && render_default_path(default_variant(SPH, COUNT, EXACT, WIDE, SND));
   (void)MIS;
   (void)GLS;
+  constexpr bool PLS = false;  // (the plastic material, DESIGN.md 3.21: the GLS instantiations of render_kernel_x alone)
+  (void)PLS;
   (void)ENV;
 #include "render_body.inc"
 }

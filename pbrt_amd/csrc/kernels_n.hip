@@ -24,6 +24,8 @@ namespace {
 template <bool SPH, int STACK, bool MIS, bool TEX, bool SND, bool ENV>
 __global__ void __launch_bounds__(64, render_waves_per_simd(RenderFamily::kN, SPH, true)) render_kernel_n(const DevScene S, const RenderParams R) {
   constexpr bool COUNT = false, EXACT = false, WIDE = false, GLS = true, NRM = true;
+  constexpr bool PLS = false;  // (no plastic beside shading normals: pbrt_hip_scene_create refuses the pair)
+  (void)PLS;
   constexpr bool LREC = false;  // (path records in LDS: the default path alone, kernels.hip render_kernel)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
 #include "render_body.inc"

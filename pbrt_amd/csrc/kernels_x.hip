@@ -8,7 +8,7 @@ namespace {
 
 // The variants of the path that BASELINE's configs do not use, in a kernel of their own name so that render_kernel's instantiations keep
 // theirs (and their machine code): MIS = multiple importance sampling of the direct-light estimate, TEX = materials
-// whose Kd is a checkerboard texture (3.15), GLS = glass materials (3.16) -- and every combination of the three with the table samplers
+// whose Kd is a checkerboard texture (3.15), GLS = glass materials (3.16) and, in the same instantiations, plastic ones (3.21) -- and every combination of the three with the table samplers
 // (SND: 3.12, 3.13) and a box filter radius other than 0.5 (WIDE: 3.11), which render_kernel instantiates one at a time.  No counters.
 // (The GLS instantiations get the spheres' register budget -- render_variant.hpp --: a spill costs every scene more than glass scenes
 // lose in occupancy.)
@@ -18,6 +18,8 @@ __global__ void __launch_bounds__(64, render_waves_per_simd(RenderFamily::kX, SP
   constexpr bool LREC = false;  // (path records in LDS: the default path alone, kernels.hip render_kernel)
   constexpr int STEPS = PBRT_STEPS_PER_CHECK;
   (void)ENV;
+  constexpr bool PLS = GLS;  // the plastic material rides in the GLS instantiations, a run-time branch on the type word
+  (void)PLS;
 #include "render_body.inc"
 }
 

@@ -1,5 +1,5 @@
 // render_body.inc -- the body of every family of render kernels (render_variant.hpp), included once in each family's kernel unit: they are the
-// same program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, ENV, NRM, LREC in scope -- template
+// same program text, with the compile-time constants SPH, COUNT, EXACT, STACK, STEPS, WIDE, SND, MIS, TEX, GLS, PLS, ENV, NRM, LREC in scope -- template
 // arguments where the family has the switch, constants where it does not.  (A shared __device__
 // function would be the tidy way to say this; the text is included instead because wrapping the body in a function -- forceinline or
 // not -- perturbs the register allocation of the production instantiation, whose machine code the committed counter profiles are
@@ -117,7 +117,7 @@
             }
             m0 = S.mats[2 * mid];
             m1 = S.mats[2 * mid + 1];
-            if (GLS && __float_as_uint(m0.x) == 2u) gl = R.glass[mid];
+            if (GLS && (__float_as_uint(m0.x) == 2u || (PLS && __float_as_uint(m0.x) == 3u))) gl = R.glass[mid];  // (PLS: {Ks, alpha} of a plastic material, 3.21)
           }
           if (P.bounces == 0 || P.specular) {
             if (hit) {
@@ -261,6 +261,45 @@
                 else { P.beta = P.beta * k; P.specular = false; }
                 // MIS: the pending light sample and, beside it, the density the bounce ray was drawn with (read where it lands)
                 if (MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, z * kInvPi));
+              }
+            } else if (PLS && __float_as_uint(m0.x) == 3u) {
+              // plastic (DESIGN.md 3.21; plastic_bsdf.hpp): k = Kd, gl = {Ks, alpha}.  The requests of a matte vertex in their order -- the
+              // pick, the light's pair, the bounce's pair --; the light sample carries f(wo, wi) in the Lambertian factor's place and, with
+              // MIS, the weight against THIS BSDF's density; the bounce keeps its density beside the pending light sample as matte does
+              const V3 ks = mk(gl.x, gl.y, gl.z);
+              if (nL > 0u) {
+                const float xi = sample_1d<SND>(P, sobol, spp_mask, R.sobol_mat, halton);
+                float u1, u2;
+                sample_2d<SND>(P, sobol, spp_mask, u1, u2, R.sobol_mat, halton);
+                uint32_t li = (uint32_t)(xi * nLf);
+                li = min(li, nL - 1u);
+                V3 Lg;
+                float pl;
+                if (sample_light_general(S, li, po, nf, u1, u2, nLf, Lg, sh_d, sh_tmax, pl)) {
+                  V3 f;
+                  float pbl;
+                  plastic::eval(nf, wo, sh_d, k, ks, gl.w, f, pbl);
+                  V3 Ld = f * Lg;
+                  if (MIS && pl > 0.f) {
+                    // (the constant infinite light keeps 3.14's constant pair of weights, 1 / (1 + nL^2) here and nL^2 / (nL^2 + 1) where a
+                    // bounce ray escapes: the escape does not know the vertex it left, and the pair sums to one whatever the BSDF)
+                    Ld = Ld * (__float_as_uint(S.lights[5 * li].x) == 2u ? 1.0f / (1.0f + nLf * nLf) : mis_weight_light(pl, pbl));
+                  }
+                  need_shadow = true;
+                  lpend = P.beta * Ld;
+                  if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
+                }
+              }
+              if (direct_only) {
+                alive = false;
+              } else {
+                float u1, u2;
+                sample_2d<SND>(P, sobol, spp_mask, u1, u2, R.sobol_mat, halton);
+                V3 wgt;
+                float pb;
+                if (!plastic::sample_f(nf, wo, u1, u2, k, ks, gl.w, P.wi_next, wgt, pb)) alive = false;
+                else { P.beta = P.beta * wgt; P.specular = false; }
+                if (MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, pb));
               }
             } else {  // mirror
               const float c = dot(wo, nsh);

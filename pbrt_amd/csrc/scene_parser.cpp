@@ -239,7 +239,7 @@ struct MaterialDef {
   float k[3] = {0.5f, 0.5f, 0.5f};
   uint32_t kd_tex = 0;  // 1 + index into LoadedScene::textures when "texture Kd" names a checkerboard or an image map
   float kt[3] = {1.f, 1.f, 1.f};  // glass (type 2): k = Kr, kt = Kt, eta = the index of refraction
-  float eta = 1.5f;
+  float eta = 1.5f;               // plastic (type 3): k = Kd, kt = Ks, eta = alpha -- the record's words, as the ABI reuses them
 };
 struct GraphicsState {  // api.rs:251-289
   MaterialDef material;
@@ -373,6 +373,29 @@ struct Api {
           warn(std::string("Material \"glass\": \"") + rough + "\" is ignored (smooth glass is rendered)");
       if (ps.find("bumpmap", "texture", "float")) warn("Material \"glass\": \"bumpmap\" is ignored (smooth glass is rendered)");
       if (ps.find("remaproughness", "bool")) warn("Material \"glass\": \"remaproughness\" is ignored (smooth glass is rendered)");
+    } else if (type == "plastic") {
+      // pbrt-v3 PlasticMaterial: Kd, Ks (default 0.25), "float roughness" (default 0.1), "bool remaproughness" (default
+      // true); alpha = the remapped roughness, in double, rounded to float and clamped to what pbrt_hip_scene_create takes.  A texture given
+      // as Kd / Ks is reduced to its constant colour, as every parameter but a matte Kd is; a roughness texture to the default.
+      m.type = PBRT_HIP_MATERIAL_PLASTIC;
+      m.k[0] = m.k[1] = m.k[2] = 0.25f;
+      m.kt[0] = m.kt[1] = m.kt[2] = 0.25f;
+      spectrum(ps, "Kd", m.k);
+      spectrum(ps, "Ks", m.kt);
+      if (ps.find("roughness", "texture")) warn("Material \"plastic\": a \"roughness\" texture is not supported, the default roughness 0.1 is used");
+      const double rough = ps.one_float("roughness", 0.1f);
+      double a = rough;
+      if (ps.one_bool("remaproughness", true)) {  // pbrt-v3 TrowbridgeReitzDistribution::RoughnessToAlpha
+        const double x = std::log(std::max(rough, 1e-3));
+        a = 1.62142 + 0.819955 * x + 0.1734 * x * x + 0.0171201 * x * x * x + 0.000640711 * x * x * x * x;
+      }
+      float alpha = (float)a;
+      if (!(alpha >= 1e-3f && alpha <= 1.0f)) {  // (a NaN goes to the lower end)
+        alpha = alpha > 1.0f ? 1.0f : 1e-3f;
+        warn("Material \"plastic\": the roughness gives alpha " + std::to_string(a) + ", clamped to " + (alpha == 1.0f ? "1" : "1e-3") + " (alpha lies in [1e-3, 1])");
+      }
+      m.eta = alpha;
+      if (ps.find("bumpmap", "texture", "float")) warn("Material \"plastic\": \"bumpmap\" is ignored (no bump mapping on this path)");
     } else {
       warn("Material \"" + type + "\" is not supported by this path: using matte Kd 0.5");
     }
@@ -380,7 +403,7 @@ struct Api {
   }
 
   uint16_t material_id(const MaterialDef &m, const float le[3]) {
-    const bool glass = m.type == PBRT_HIP_MATERIAL_GLASS;  // (the others keep the key they had: Kt = eta = 0)
+    const bool glass = m.type == PBRT_HIP_MATERIAL_GLASS || m.type == PBRT_HIP_MATERIAL_PLASTIC;  // (the others keep the key they had: Kt = eta = 0; plastic: Ks, alpha)
     auto key = std::make_tuple(m.type, m.k[0], m.k[1], m.k[2], le[0], le[1], le[2], m.kd_tex, glass ? m.kt[0] : 0.f, glass ? m.kt[1] : 0.f,
                                glass ? m.kt[2] : 0.f, glass ? m.eta : 0.f);
     auto it = material_ids.find(key);
@@ -389,7 +412,7 @@ struct Api {
     pm.type = m.type;
     pm.kd_tex = m.kd_tex;
     for (int i = 0; i < 3; i++) { pm.k[i] = m.k[i]; pm.le[i] = le[i]; }
-    if (glass) {  // include/pbrt_hip.h: le = Kt, kd_tex = the bits of eta
+    if (glass) {  // include/pbrt_hip.h: le = Kt, kd_tex = the bits of eta (plastic: le = Ks, kd_tex = the bits of alpha)
       for (int i = 0; i < 3; i++) pm.le[i] = m.kt[i];
       std::memcpy(&pm.kd_tex, &m.eta, 4);
     }
@@ -571,6 +594,11 @@ struct Api {
     if (shape_mat.type == PBRT_HIP_MATERIAL_GLASS && (le[0] > 0.f || le[1] > 0.f || le[2] > 0.f)) {
       // a glass material has no room for emission (its `le` is Kt): the shape emits, its surface is black matte
       warn("Material \"glass\" under an AreaLightSource: the shape emits and is rendered as black matte");
+      shape_mat = MaterialDef();
+      shape_mat.k[0] = shape_mat.k[1] = shape_mat.k[2] = 0.f;
+    }
+    if (shape_mat.type == PBRT_HIP_MATERIAL_PLASTIC && (le[0] > 0.f || le[1] > 0.f || le[2] > 0.f)) {  // (its `le` is Ks: as glass)
+      warn("Material \"plastic\" under an AreaLightSource: the shape emits and is rendered as black matte");
       shape_mat = MaterialDef();
       shape_mat.k[0] = shape_mat.k[1] = shape_mat.k[2] = 0.f;
     }
@@ -1251,6 +1279,14 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
   if (out->pixel_filter.type == PBRT_HIP_TEXTURE_FILTER) out->textures.push_back(write_slot(out->pixel_filter));
   // shading normals travel only when some mesh has them: then their record is the LAST slot of the texture table; a file
   // without them keeps the description it always had
+  if (api.any_normals) {  // (plastic reflects about the geometric normal, and a scene with plastic takes no normals record: DESIGN.md 3.21)
+    bool plastic = false;
+    for (const pbrt_hip_material &m : out->mats) plastic = plastic || m.type == PBRT_HIP_MATERIAL_PLASTIC;
+    if (plastic) {
+      api.warn("a scene with a \"plastic\" material: the meshes' normals \"N\" are ignored (every mesh renders flat)");
+      api.any_normals = false;
+    }
+  }
   if (!api.any_normals) {
     out->tri_n.clear(); out->tri_n.shrink_to_fit();
   } else {

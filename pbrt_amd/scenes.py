@@ -6,13 +6,14 @@
   random_mesh_scene   C2 / C3: N random triangles in a box with a ceiling area light
   cornell_scene       C4: Cornell-style box
   glass_sphere_scene  a glass sphere and a glass cube in a Cornell-style box (= scenes/glass_sphere.pbrt)
+  plastic_scene       a plastic floor and two plastic spheres in a Cornell-style box (= scenes/plastic_spheres.pbrt)
   envmap_scene        a matte ground, a glass and a mirror sphere under an environment map (= scenes/envmap_spheres.pbrt)
   icosphere_scene     C1 with its sphere tessellated, with or without shading normals
   smooth_mesh_scene   two octahedra with per-vertex normals over a flat ground (= scenes/smooth_mesh.pbrt)
 """
 import numpy as np
 
-from .api import GLASS, LIGHT_DISTANT, LIGHT_ENVMAP, LIGHT_INFINITE, LIGHT_POINT, MATTE, MIRROR, SceneData, look_at
+from .api import GLASS, PLASTIC, roughness_to_alpha, LIGHT_DISTANT, LIGHT_ENVMAP, LIGHT_INFINITE, LIGHT_POINT, MATTE, MIRROR, SceneData, look_at
 
 MESH_SEED = 0x5EED0001
 
@@ -275,6 +276,47 @@ def glass_sphere_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), glass=True
         P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
         materials=np.array(mats, np.float32), mat_eta=np.array(eta, np.float32),
         spheres=np.array([[0.4, -0.2, -0.45, 0.35, BALL]], np.float32),
+        cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
+    ).normalized()
+
+
+def plastic_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), plastic=True, light_scale=1.0, roughness=(0.2, 0.05, 0.4)):
+    """The plastic material's scene, array for array what scenes/plastic_spheres.pbrt loads to: the Cornell-style box
+    [-1, 1]^3 open towards the camera with a grey PLASTIC floor (roughness 0.2), white ceiling and back wall, red left and green right walls, a
+    1 x 1 ceiling emitter with Le (10, 9, 7), and two plastic spheres of radius 0.35 standing on the floor: a blue one of roughness 0.05 and an
+    orange one of roughness 0.4 (remapped roughnesses, pbrt-v3's default).  `plastic=False`: the same scene with every plastic material
+    replaced by matte of the same Kd (a scene of matte materials alone).  `light_scale`: the emitter's side (its radiance grows by 1 /
+    light_scale^2: the same power); `roughness`: of the floor and the two spheres."""
+    FLOOR, WHITE, RED, GREEN, LIGHT, BLUE, ORANGE = range(7)  # (numbered in the order the scene file's shapes first use them)
+    le = tuple(np.float32(v) / np.float32(light_scale * light_scale) for v in (10, 9, 7))
+    mats = [_mat(PLASTIC, (0.4, 0.4, 0.4), (0.3, 0.3, 0.3)), _mat(MATTE, (0.73, 0.73, 0.73)), _mat(MATTE, (0.65, 0.05, 0.05)), _mat(MATTE, (0.12, 0.45, 0.15)),
+            _mat(MATTE, (0, 0, 0), le), _mat(PLASTIC, (0.1, 0.2, 0.6), (0.3, 0.3, 0.3)), _mat(PLASTIC, (0.6, 0.3, 0.05), (0.25, 0.25, 0.25))]  # a plastic row: (PLASTIC, Kd, Ks)
+    alpha = [1.5] * 7  # (mat_eta: the float beside a row; what a row that is neither glass nor plastic carries is not read)
+    for m, r in zip((FLOOR, BLUE, ORANGE), roughness):
+        alpha[m] = roughness_to_alpha(r)
+    if not plastic:
+        for m in (FLOOR, BLUE, ORANGE):
+            mats[m] = _mat(MATTE, mats[m][1:4])
+    V, I, M = [], [], []
+
+    def add(q, m):
+        base = len(V)
+        v, t = _quad(*q)
+        V.extend(v)
+        I.extend([[base + a for a in tri] for tri in t])
+        M.extend([m, m])
+
+    h = 0.5 * light_scale
+    add(((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1)), FLOOR)  # floor
+    add(((-1, -1, 1), (-1, 1, 1), (1, 1, 1), (1, -1, 1)), WHITE)      # ceiling
+    add(((-1, 1, -1), (1, 1, -1), (1, 1, 1), (-1, 1, 1)), WHITE)      # back wall (y = +1)
+    add(((-1, -1, -1), (-1, 1, -1), (-1, 1, 1), (-1, -1, 1)), RED)    # left
+    add(((1, -1, -1), (1, -1, 1), (1, 1, 1), (1, 1, -1)), GREEN)      # right
+    add(((-h, -h, 0.999), (-h, h, 0.999), (h, h, 0.999), (h, -h, 0.999)), LIGHT)  # normal -z
+    return SceneData(
+        P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
+        materials=np.array(mats, np.float32), mat_eta=np.array(alpha if plastic else [], np.float32),
+        spheres=np.array([[-0.45, 0.15, -0.65, 0.35, BLUE], [0.45, -0.2, -0.65, 0.35, ORANGE]], np.float32),
         cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
     ).normalized()
 

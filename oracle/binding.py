@@ -22,6 +22,12 @@ class Texture(C.Structure):
                 ("du", C.c_float), ("dv", C.c_float), ("pad", C.c_uint32 * 5)]
 
 
+class ImageTexture(C.Structure):
+    """orc_image_texture: the 64 bytes of a slot whose first word is 4"""
+    _fields_ = [("type", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("wrap", C.c_uint32), ("rgb", C.POINTER(C.c_float)),
+                ("su", C.c_float), ("sv", C.c_float), ("du", C.c_float), ("dv", C.c_float), ("filter", C.c_uint32), ("pad", C.c_uint32 * 5)]
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_uint32), ("p", C.c_float * 3), ("c", C.c_float * 3), ("pad", C.c_float)]
 
@@ -123,7 +129,12 @@ def lib(native=False):
         l.orc_envmap_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int64] + [C.c_void_p] * 5
         l.orc_blocks_eval.restype = C.c_int
         l.orc_blocks_eval.argtypes = [C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
-        l.orc_quad_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
+        for n in ("orc_shading_normal_eval", "orc_plastic_eval"):
+            getattr(l, n).restype = C.c_int
+            getattr(l, n).argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
+        l.orc_image_lookup_eval.restype = C.c_int
+        l.orc_image_lookup_eval.argtypes = [C.POINTER(ImageTexture), C.c_uint32, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
+        l.orc_quad_walk.argtypes =[C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
         _libs[native] = l
     return _libs[native]
 
@@ -328,7 +339,9 @@ class OracleScene:
         self.h = self.l.orc_scene_create(C.byref(desc))
         del keep
         if not self.h:
-            raise ValueError("orc_scene_create: a scene the oracle does not know (material type > 2, light type > 3, a map light without its map slot, a matte Kd from a map slot)")
+            raise ValueError("orc_scene_create: a scene the oracle does not render (a material type above 3, a light type above 3, a map light "
+                             "without its map slot, an unknown slot type, the pixel filter's slot, a second normals slot or one whose n_tris is "
+                             "not the scene's, a matte Kd from a slot of type 1, 2 or 3, plastic beside a map or normals)")
 
     def close(self):
         if getattr(self, "h", None):
@@ -453,6 +466,41 @@ def blocks_eval(op, x):
     out = np.zeros((len(x), w_out), np.float32)
     if lib().orc_blocks_eval(code, len(x), _p(x), _p(out)) != 0:
         raise ValueError("orc_blocks_eval: bad argument")
+    return out
+
+
+def shading_normal_eval(x):
+    """orc_shading_normal_eval.  x (n, 17): n0, n1, n2, ng, b1, b2, wo -> (n, 4) float32: nsf, fell_back"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 17)
+    out = np.zeros((len(x), 4), np.float32)
+    if lib().orc_shading_normal_eval(len(x), _p(x), _p(out)) != 0:
+        raise ValueError("orc_shading_normal_eval: bad argument")
+    return out
+
+
+def plastic_eval(x):
+    """orc_plastic_eval.  x (n, 18): nf, wo, wi, u1, u2, Kd, Ks, alpha -> (n, 10) float32: f(wo, wi), pdf_b(wi), the sampled
+    wi', f(wo, wi') cos / pdf_b(wi')"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 18)
+    out = np.zeros((len(x), 10), np.float32)
+    if lib().orc_plastic_eval(len(x), _p(x), _p(out)) != 0:
+        raise ValueError("orc_plastic_eval: bad argument")
+    return out
+
+
+def image_lookup_eval(images, which, uv):
+    """orc_image_lookup_eval (DESIGN.md 3.20).  images: a list of (image (H, W, 3), wrap, filter, (su, sv, du, dv)), packed into one pool;
+    uv (n, 2) -> (n, 3) float32: Kd of record `which`"""
+    arrays = [np.ascontiguousarray(im[0], np.float32) for im in images]
+    recs = (ImageTexture * len(images))()
+    for r, a, im in zip(recs, arrays, images):
+        r.type, r.width, r.height, r.wrap, r.filter = 4, a.shape[1], a.shape[0], int(im[1]), int(im[2])
+        r.rgb = a.ctypes.data_as(C.POINTER(C.c_float))
+        r.su, r.sv, r.du, r.dv = (float(v) for v in im[3])
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    out = np.zeros((len(uv), 3), np.float32)
+    if lib().orc_image_lookup_eval(recs, len(images), int(which), len(uv), _p(uv), _p(out)) != 0:
+        raise ValueError("orc_image_lookup_eval: bad argument")
     return out
 
 

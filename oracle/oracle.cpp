@@ -285,6 +285,18 @@ static inline void concentric_sample_disk(float u1, float u2, float *dx, float *
   }
 }
 
+// the two tangents of the frame about n (pbrt-v3 CoordinateSystem)
+static inline void coordinate_system(Vec3 n, Vec3 *v2, Vec3 *v3_) {
+  if (std::fabs(n.x) > std::fabs(n.y)) {
+    float l = std::sqrt(n.x * n.x + n.z * n.z);
+    *v2 = {-n.z / l, 0.f, n.x / l};
+  } else {
+    float l = std::sqrt(n.y * n.y + n.z * n.z);
+    *v2 = {0.f, n.z / l, -n.y / l};
+  }
+  *v3_ = cross(n, *v2);
+}
+
 // cosine-weighted direction about n (pbrt-v3 CosineSampleHemisphere + CoordinateSystem);
 // returns the local z (= cos theta); z == 0 means pdf == 0
 static inline float cosine_sample_about(Vec3 n, float u1, float u2, Vec3 *wi) {
@@ -292,17 +304,69 @@ static inline float cosine_sample_about(Vec3 n, float u1, float u2, Vec3 *wi) {
   concentric_sample_disk(u1, u2, &dx, &dy);
   float zz = (1.0f - dx * dx) - dy * dy;
   float z = std::sqrt(zz > 0.f ? zz : 0.f);
-  Vec3 v2;
-  if (std::fabs(n.x) > std::fabs(n.y)) {
-    float l = std::sqrt(n.x * n.x + n.z * n.z);
-    v2 = {-n.z / l, 0.f, n.x / l};
-  } else {
-    float l = std::sqrt(n.y * n.y + n.z * n.z);
-    v2 = {0.f, n.z / l, -n.y / l};
-  }
-  Vec3 v3_ = cross(n, v2);
+  Vec3 v2, v3_;
+  coordinate_system(n, &v2, &v3_);
   *wi = (v2 * dx + v3_ * dy) + n * z;
   return z;
+}
+
+// -------- the plastic material, restated from the spec's text: a Lambertian base Kd / pi plus one Trowbridge-Reitz lobe of
+// width alpha with the Fresnel term of a dielectric of index 1.5 against 1.  nf = the geometric normal turned towards wo. --------
+static inline float plastic_lambda(float cs, float a2) {
+  const float c2 = cs * cs;
+  return 0.5f * (std::sqrt(1.0f + a2 * (std::fmax(0.f, 1.0f - c2) / c2)) - 1.0f);
+}
+// f(wo, wi) and the density the sampler below has for wi; both zero where cos_i <= 0, cos_o <= 0, wo + wi = 0 or wo . wh <= 0
+static inline void plastic_eval(Vec3 nf, Vec3 wo, Vec3 wi, Vec3 kd, Vec3 ks, float alpha, Vec3 *f, float *pdf) {
+  *f = v3(0.f, 0.f, 0.f);
+  *pdf = 0.f;
+  const float cos_o = dot(wo, nf), cos_i = dot(wi, nf);
+  if (!(cos_i > 0.f) || !(cos_o > 0.f)) return;
+  const Vec3 sum = wo + wi;
+  const float len2 = dot(sum, sum);
+  if (!(len2 > 0.f)) return;
+  const Vec3 wh = sum / std::sqrt(len2);
+  const float c = dot(wh, nf), oh = dot(wo, wh);
+  if (!(oh > 0.f)) return;
+  const float a2 = alpha * alpha;
+  const float e = (c * c) * (a2 - 1.0f) + 1.0f;
+  const float D = a2 / (kPi * (e * e));
+  const float G = 1.0f / ((1.0f + plastic_lambda(cos_o, a2)) + plastic_lambda(cos_i, a2));
+  float F, ct;
+  const float ih = std::fabs(dot(wi, wh));
+  glass_fresnel(ih < 1.0f ? ih : 1.0f, 1.0f / 1.5f, &F, &ct);
+  const float spec = ((D * G) * F) / ((4.0f * cos_o) * cos_i);
+  *f = kd * kInvPi + ks * spec;
+  *pdf = 0.5f * (cos_i * kInvPi) + 0.5f * ((D * c) / (4.0f * oh));
+}
+// One bounce from the pair a matte bounce draws: u1 < 1/2 the cosine lobe about nf, else a half vector from D cos theta and wo mirrored
+// about it.  false: the sample dies (wo . wh <= 0, cos_i <= 0 or pdf_b = 0); else *weight = f cos_i / pdf_b and *pdf = pdf_b
+static inline bool plastic_sample_f(Vec3 nf, Vec3 wo, float u1, float u2, Vec3 kd, Vec3 ks, float alpha, Vec3 *wi, Vec3 *weight, float *pdf) {
+  const float one_minus_eps = 1.0f - std::numeric_limits<float>::epsilon();
+  *weight = v3(0.f, 0.f, 0.f);
+  *pdf = 0.f;
+  if (u1 < 0.5f) {
+    const float u = std::fmin(2.0f * u1, one_minus_eps);
+    if (cosine_sample_about(nf, u, u2, wi) == 0.f) return false;
+  } else {
+    const float u = std::fmin(2.0f * u1 - 1.0f, one_minus_eps);
+    const float tan2 = ((alpha * alpha) * u) / (1.0f - u);
+    const float cos_t = 1.0f / std::sqrt(1.0f + tan2);
+    const float sin_t = std::sqrt(std::fmax(0.f, 1.0f - cos_t * cos_t));
+    float sin_p, cos_p;
+    sincos_octants(kTwoPi * u2, &sin_p, &cos_p);
+    Vec3 v2, v3_;
+    coordinate_system(nf, &v2, &v3_);
+    const Vec3 wh = (v2 * (sin_t * cos_p) + v3_ * (sin_t * sin_p)) + nf * cos_t;
+    const float oh = dot(wo, wh);
+    if (!(oh > 0.f)) return false;
+    *wi = -wo + wh * (2.0f * oh);
+  }
+  Vec3 f;
+  plastic_eval(nf, wo, *wi, kd, ks, alpha, &f, pdf);
+  if (!(*pdf > 0.f)) return false;
+  *weight = f * (dot(*wi, nf) / *pdf);
+  return true;
 }
 
 struct RayStats {
@@ -403,6 +467,16 @@ class PathIntegrator {
       if (!hit || bounces >= max_depth_) break;
       Vec3 nf = dot(ng, wo) < 0.f ? -ng : ng;
       Vec3 po = p + nf * kSpawnEps;
+      // a triangle's corner normals, interpolated like the hit point, give nsf, which takes nf's place where matte and mirror
+      // scatter; `smooth` = the triangle had a usable normal (else nsf is nf bit for bit and nothing below differs).  Spheres keep theirs.
+      Vec3 nsf = nf;
+      bool smooth = false;
+      if (!scene.tri_n.empty() && h.prim < scene.n_tris()) {
+        const float *q = &scene.tri_n[9 * (size_t)h.prim];
+        bool fell_back;
+        nsf = shading_normal(v3(q[0], q[1], q[2]), v3(q[3], q[4], q[5]), v3(q[6], q[7], q[8]), ng, h.b1, h.b2, wo, &fell_back);
+        smooth = !fell_back;
+      }
       Vec3 k = v3(m->k[0], m->k[1], m->k[2]);
       if (m->type == 0 && m->kd_tex != 0u && (h.prim >= scene.n_tris() || !scene.tri_uv.empty())) {
         // Kd from a texture (pbrt-v3 Checkerboard2DTexture over UVMapping2D, aamode none): the corner (u, v) of the
@@ -418,10 +492,18 @@ class PathIntegrator {
         } else {
           sphere_uv(ng.x, ng.y, ng.z, &u, &v);
         }
-        const float ss = tx.su * u + tx.du, tt = tx.sv * v + tx.dv;
-        // (the parity in float on both sides: an (int) cast of a huge s is undefined here and saturates on the GPU)
-        const float cf = std::floor(ss) + std::floor(tt);
-        k = (cf - 2.0f * std::floor(0.5f * cf)) == 0.f ? v3(tx.tex1[0], tx.tex1[1], tx.tex1[2]) : v3(tx.tex2[0], tx.tex2[1], tx.tex2[2]);
+        const ImageSlot &im = scene.images[m->kd_tex - 1u];
+        if (im.W != 0u) {
+          // Kd from an image: the same (u, v), the record's own mapping in the same statement
+          const float *mp = &scene.image_mapping[4 * (size_t)(m->kd_tex - 1u)];
+          const float ss = mp[0] * u + mp[2], tt = mp[1] * v + mp[3];
+          k = image_lookup(scene.image_pool.data(), im, ss, tt);
+        } else {
+          const float ss = tx.su * u + tx.du, tt = tx.sv * v + tx.dv;
+          // (the parity in float on both sides: an (int) cast of a huge s is undefined here and saturates on the GPU)
+          const float cf = std::floor(ss) + std::floor(tt);
+          k = (cf - 2.0f * std::floor(0.5f * cf)) == 0.f ? v3(tx.tex1[0], tx.tex1[1], tx.tex1[2]) : v3(tx.tex2[0], tx.tex2[1], tx.tex2[2]);
+        }
       }
       Vec3 wi;
       Vec3 leave = po;  // where the next ray starts
@@ -458,7 +540,9 @@ class PathIntegrator {
           Vec3 Ld;
           Ray sh;
           const LightRec &lt = scene.lights[li];
-          if (lt.type == 4 ? sample_env_light(po, nf, k, u1, u2, nLf, &Ld, &sh) : sample_light(lt, po, nf, k, u1, u2, nLf, &Ld, &sh, mis_)) {
+          // (3.18: the light is sampled about nsf, and counts only if it also arrives on the geometric front side)
+          if ((lt.type == 4 ? sample_env_light(po, nsf, k, u1, u2, nLf, &Ld, &sh) : sample_light(lt, po, nsf, k, u1, u2, nLf, &Ld, &sh, mis_)) &&
+              (!smooth || dot(sh.d, nf) > 0.f)) {
             st.shadow++;
             const bool occ = scene.IntersectP(sh, &st.c);
             if (g_debug_li) { uint32_t a; std::memcpy(&a, &Ld.x, 4); std::fprintf(stderr, "ORC   light %u Ld %08x occluded %d tmax %a\n", li, a, (int)occ, sh.tmax); }
@@ -468,20 +552,60 @@ class PathIntegrator {
         if (direct_only_) break;
         float u1, u2;
         sampler.Get2D(&u1, &u2);
-        float z = cosine_sample_about(nf, u1, u2, &wi);
+        float z = cosine_sample_about(nsf, u1, u2, &wi);
         if (g_debug_li) {
           float dx, dy; concentric_sample_disk(u1, u2, &dx, &dy);
           std::fprintf(stderr, "ORC   cos u1 %a u2 %a dx %a dy %a z %a nf %a %a %a wi %a %a %a\n", u1, u2, dx, dy, z, nf.x, nf.y, nf.z, wi.x, wi.y, wi.z);
         }
         if (z == 0.f) break;
+        if (smooth && !(dot(wi, nf) > 0.f)) break;  // 3.18: the lobe reflects to the geometric front side only
         beta = beta * k;
         specular = false;
         pb = z * kInvPi;
-      } else {  // mirror
-        float c = dot(wo, nf);
-        wi = -wo + nf * (2.0f * c);
+      } else if (m->type == 3) {
+        // plastic: k = Kd, le = Ks, kd_tex = the bits of alpha; about the GEOMETRIC normal.  The requests of a matte vertex in
+        // their order: the pick, the light's pair, the bounce's pair.  Ld = f(wo, wi) Lg; under MIS an emissive triangle's sample is weighted
+        // against THIS BSDF's density for wi, the constant infinite light keeps 3.14's constant pair 1 / (1 + nL^2) | nL^2 / (nL^2 + 1)
+        const Vec3 ks = v3(m->le[0], m->le[1], m->le[2]);
+        float alpha;
+        std::memcpy(&alpha, &m->kd_tex, 4);
+        if (nL > 0) {
+          float xi = sampler.Get1D();
+          float u1, u2;
+          sampler.Get2D(&u1, &u2);
+          uint32_t li = (uint32_t)(xi * nLf);
+          if (li > nL - 1) li = nL - 1;
+          const LightRec &lt = scene.lights[li];
+          Vec3 Lg;
+          Ray sh;
+          float pl;
+          if (sample_light_general(lt, po, nf, u1, u2, nLf, &Lg, &sh, &pl)) {
+            Vec3 f;
+            float pbl;
+            plastic_eval(nf, wo, sh.d, k, ks, alpha, &f, &pbl);
+            Vec3 Ld = f * Lg;
+            if (mis_ && pl > 0.f) Ld = Ld * (lt.type == 2 ? 1.0f / (1.0f + nLf * nLf) : mis_weight_light(pl, pbl));
+            st.shadow++;
+            const bool occ = scene.IntersectP(sh, &st.c);
+            if (g_debug_li) { uint32_t a; std::memcpy(&a, &Ld.x, 4); std::fprintf(stderr, "ORC   plastic light %u Ld %08x occluded %d tmax %a\n", li, a, (int)occ, sh.tmax); }
+            if (!occ) L = L + beta * Ld;
+          }
+        }
+        if (direct_only_) break;
+        float u1, u2;
+        sampler.Get2D(&u1, &u2);
+        Vec3 weight;
+        float pdf_b;
+        if (!plastic_sample_f(nf, wo, u1, u2, k, ks, alpha, &wi, &weight, &pdf_b)) break;  // a dead sample ends the path
+        beta = beta * weight;
+        specular = false;
+        pb = pdf_b;  // what an emitter the bounce ray runs into is weighted with
+      } else {  // mirror (3.18: about nsf; the path ends where the reflection leaves through the geometric back face)
+        float c = dot(wo, nsf);
+        wi = -wo + nsf * (2.0f * c);
         beta = beta * k;
         specular = true;
+        if (smooth && !(dot(wi, nf) > 0.f)) break;
       }
       if (beta.x == 0.f && beta.y == 0.f && beta.z == 0.f) break;
       ray.o = leave;
@@ -497,8 +621,66 @@ class PathIntegrator {
     return L;
   }
 
-  // what a surface emits: a glass material's `le` words hold Kt -- glass does not emit
-  static Vec3 emitted(const orc_material &m) { return m.type == 2 ? v3(0.f, 0.f, 0.f) : v3(m.le[0], m.le[1], m.le[2]); }
+  // what a surface emits: a glass material's `le` words hold Kt, a plastic one's Ks (3.21) -- neither emits
+  static Vec3 emitted(const orc_material &m) { return m.type >= 2 ? v3(0.f, 0.f, 0.f) : v3(m.le[0], m.le[1], m.le[2]); }
+
+  // The general light sample of 3.21: the light of sample_light from the same (u1, u2) WITHOUT a BSDF factor and without a MIS weight --
+  // Lg = Li cos_i nL / pdf_l, the caller multiplies by f(wo, wi) -- and *pl = the density MIS compares with the BSDF's for wi (the light
+  // picked with 1 / nL); 0 for the point and the distant light.  The operations are sample_light's.
+  static bool sample_light_general(const LightRec &l, Vec3 po, Vec3 nf, float u1, float u2, float nLf, Vec3 *Lg, Ray *sh, float *pl) {
+    sh->o = po;
+    *pl = 0.f;
+    if (l.type == 0) {  // point
+      Vec3 dv = l.p0 - po;
+      float dist2 = dot(dv, dv);
+      if (!(dist2 > 0.f)) return false;
+      float dist = std::sqrt(dist2);
+      Vec3 wi = dv / dist;
+      float cs = dot(wi, nf);
+      if (!(cs > 0.f)) return false;
+      *Lg = l.c * ((cs / dist2) * nLf);
+      sh->d = wi;
+      sh->tmax = dist * kShadowShrink;
+      return true;
+    } else if (l.type == 1) {  // distant
+      Vec3 wi = l.p0;
+      float cs = dot(wi, nf);
+      if (!(cs > 0.f)) return false;
+      *Lg = l.c * (cs * nLf);
+      sh->d = wi;
+      sh->tmax = kInf;
+      return true;
+    } else if (l.type == 2) {  // constant infinite: wi cosine-sampled, pdf_l = cos_i / pi, so Lg = Le pi nL
+      Vec3 wi;
+      float z = cosine_sample_about(nf, u1, u2, &wi);
+      if (z == 0.f) return false;
+      *Lg = (l.c * kPi) * nLf;
+      *pl = (z * kInvPi) / nLf;
+      sh->d = wi;
+      sh->tmax = kInf;
+      return true;
+    } else {  // emissive triangle (the map, type 4, never arrives: plastic beside a map is refused)
+      float su0 = std::sqrt(u1);
+      float b0 = 1.0f - su0;
+      float b1 = u2 * su0;
+      float b2 = (1.0f - b0) - b1;
+      Vec3 pt = (l.p0 * b0 + l.p1 * b1) + l.p2 * b2;
+      Vec3 dv = pt - po;
+      float dist2 = dot(dv, dv);
+      if (!(dist2 > 0.f)) return false;
+      float dist = std::sqrt(dist2);
+      Vec3 wi = dv / dist;
+      float cs = dot(wi, nf);
+      if (!(cs > 0.f)) return false;
+      float cl = -dot(wi, l.n);
+      if (!(cl > 0.f)) return false;
+      *Lg = l.c * ((((cs * cl) * l.area) / dist2) * nLf);
+      *pl = (dist2 / (cl * l.area)) / nLf;
+      sh->d = wi;
+      sh->tmax = dist * kShadowShrink;
+      return true;
+    }
+  }
 
   // Le(d) = c * the texel direction d looks at (point-sampled); *pdf = the density over solid angle with which the map's
   // light sample draws d
@@ -856,11 +1038,36 @@ static uint32_t slot_type(const orc_scene_desc *d, uint32_t slot) {  // slot: 0-
   return t;
 }
 // what the oracle does not know it refuses (NULL from orc_scene_create), so that no test gets a film of something else
+static_assert(sizeof(orc_image_texture) == 64 && sizeof(orc_normals) == 64, "an image or normals record takes one slot of the texture table");
 static bool scene_is_known(const orc_scene_desc *d) {
+  // the table: checkerboards (0), the map (1), ONE normals record for all the scene's triangles (2), images (4, 3.20).  The
+  // pixel filter's record (3, 3.19) is refused: the weighted filters are held to the oracle through its radiances, never through its film
+  uint32_t n_normals = 0;
+  bool has_map_slot = false;
+  for (uint32_t i = 0; i < d->n_textures; i++) {
+    const uint32_t t = slot_type(d, i);
+    if (t == 3u || t > 4u) return false;
+    if (t == 1u) has_map_slot = true;
+    if (t == 2u) {
+      orc_normals r;
+      std::memcpy(&r, (const char *)d->textures + 64 * (size_t)i, sizeof r);
+      if (++n_normals > 1u || r.n_tris != d->n_tris || !r.tri_n) return false;
+    }
+    if (t == 4u) {
+      orc_image_texture r;
+      std::memcpy(&r, (const char *)d->textures + 64 * (size_t)i, sizeof r);
+      if (r.width == 0u || r.height == 0u || !r.rgb || r.wrap > 2u || r.filter > 1u) return false;
+    }
+  }
   for (uint32_t i = 0; i < d->n_mats; i++) {
     const orc_material &m = d->mats[i];
-    if (m.type > 2u) return false;
-    if (m.type == 0u && m.kd_tex != 0u && m.kd_tex <= d->n_textures && slot_type(d, m.kd_tex - 1u) == 1u) return false;  // Kd from a map slot
+    if (m.type > 3u) return false;
+    if (m.type == 3u && (has_map_slot || n_normals != 0u)) return false;  // plastic beside a map or normals: no kernel renders it (3.21)
+    if (m.type == 0u && m.kd_tex != 0u) {  // Kd from a slot: a checkerboard or an image
+      if (m.kd_tex > d->n_textures) return false;
+      const uint32_t t = slot_type(d, m.kd_tex - 1u);
+      if (t != 0u && t != 4u) return false;
+    }
   }
   uint32_t n_maps = 0;
   for (uint32_t i = 0; i < d->n_lights; i++) {
@@ -890,6 +1097,26 @@ orc_scene *orc_scene_create(const orc_scene_desc *d) {
   if (d->n_spheres) s.spheres.assign(d->spheres, d->spheres + d->n_spheres);
   if (d->n_textures) s.textures.assign(d->textures, d->textures + d->n_textures);
   if (d->tri_uv) s.tri_uv.assign(d->tri_uv, d->tri_uv + 6 * (size_t)d->n_tris);
+  // the records that ride in the table: the images' texels into one pool in slot order (3.20), the corner normals (3.18)
+  s.images.resize(d->n_textures);
+  s.image_mapping.assign(4 * (size_t)d->n_textures, 0.f);
+  for (uint32_t i = 0; i < d->n_textures; i++) {
+    const char *slot = (const char *)d->textures + 64 * (size_t)i;
+    if (slot_type(d, i) == 4u) {
+      orc_image_texture r;
+      std::memcpy(&r, slot, sizeof r);
+      ImageSlot &im = s.images[i];
+      im.W = r.width; im.H = r.height; im.wrap = r.wrap; im.filter = r.filter;
+      im.first = s.image_pool.size() / 3;
+      s.image_pool.insert(s.image_pool.end(), r.rgb, r.rgb + 3 * (size_t)r.width * r.height);
+      const float mp[4] = {r.su, r.sv, r.du, r.dv};
+      std::memcpy(&s.image_mapping[4 * (size_t)i], mp, sizeof mp);
+    } else if (slot_type(d, i) == 2u) {
+      orc_normals r;
+      std::memcpy(&r, slot, sizeof r);
+      s.tri_n.assign(r.tri_n, r.tri_n + 9 * (size_t)r.n_tris);
+    }
+  }
   // light list: explicit lights in order, then every emissive triangle in index order
   for (uint32_t i = 0; i < d->n_lights; i++) {
     LightRec l{};
@@ -914,7 +1141,7 @@ orc_scene *orc_scene_create(const orc_scene_desc *d) {
   }
   for (uint32_t t = 0; t < d->n_tris; t++) {
     const orc_material &m = s.mats[s.mat_id[t]];
-    if (m.type != 2 && (m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) {  // (a glass material's le words are Kt: not a light)
+    if (m.type < 2 && (m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) {  // (a glass material's le words are Kt, a plastic one's Ks: not a light)
       LightRec l{};
       l.type = 3;
       s.tri_verts(t, &l.p0, &l.p1, &l.p2);
@@ -1034,6 +1261,55 @@ int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out) {
         break;
       }
     }
+  }
+  return 0;
+}
+// Normals, plastic and images over arrays, in the layouts of the product's hooks (tests)
+int orc_shading_normal_eval(int64_t n, const float *in, float *out) {
+  if (n < 0 || !in || !out) return -1;
+  for (int64_t i = 0; i < n; i++) {
+    const float *x = in + 17 * i;
+    bool fell_back;
+    const Vec3 nsf = shading_normal(v3(x[0], x[1], x[2]), v3(x[3], x[4], x[5]), v3(x[6], x[7], x[8]), v3(x[9], x[10], x[11]), x[12], x[13],
+                                    v3(x[14], x[15], x[16]), &fell_back);
+    out[4 * i] = nsf.x; out[4 * i + 1] = nsf.y; out[4 * i + 2] = nsf.z;
+    out[4 * i + 3] = fell_back ? 1.0f : 0.f;
+  }
+  return 0;
+}
+int orc_plastic_eval(int64_t n, const float *in, float *out) {
+  if (n < 0 || !in || !out) return -1;
+  for (int64_t i = 0; i < n; i++) {
+    const float *x = in + 18 * i;
+    float *y = out + 10 * i;
+    const Vec3 nf = v3(x[0], x[1], x[2]), wo = v3(x[3], x[4], x[5]), wi = v3(x[6], x[7], x[8]);
+    const Vec3 kd = v3(x[11], x[12], x[13]), ks = v3(x[14], x[15], x[16]);
+    Vec3 f, ws = v3(0.f, 0.f, 0.f), weight;
+    float pdf, pdf_s;
+    plastic_eval(nf, wo, wi, kd, ks, x[17], &f, &pdf);
+    y[0] = f.x; y[1] = f.y; y[2] = f.z; y[3] = pdf;
+    if (!plastic_sample_f(nf, wo, x[9], x[10], kd, ks, x[17], &ws, &weight, &pdf_s)) ws = weight = v3(0.f, 0.f, 0.f);
+    y[4] = ws.x; y[5] = ws.y; y[6] = ws.z;
+    y[7] = weight.x; y[8] = weight.y; y[9] = weight.z;
+  }
+  return 0;
+}
+int orc_image_lookup_eval(const orc_image_texture *records, uint32_t n_records, uint32_t which, int64_t n, const float *uv, float *rgb) {
+  if (!records || n_records == 0u || which >= n_records || n < 0 || (n && (!uv || !rgb))) return -1;
+  std::vector<float> pool;
+  std::vector<ImageSlot> slots(n_records);
+  for (uint32_t i = 0; i < n_records; i++) {
+    const orc_image_texture &r = records[i];
+    if (r.type != 4u || r.width == 0u || r.height == 0u || !r.rgb || r.wrap > 2u || r.filter > 1u) return -1;
+    slots[i].W = r.width; slots[i].H = r.height; slots[i].wrap = r.wrap; slots[i].filter = r.filter;
+    slots[i].first = pool.size() / 3;
+    pool.insert(pool.end(), r.rgb, r.rgb + 3 * (size_t)r.width * r.height);
+  }
+  const orc_image_texture &r = records[which];
+  for (int64_t i = 0; i < n; i++) {
+    const float ss = r.su * uv[2 * i] + r.du, tt = r.sv * uv[2 * i + 1] + r.dv;
+    const Vec3 c = image_lookup(pool.data(), slots[which], ss, tt);
+    rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
   }
   return 0;
 }

@@ -370,4 +370,66 @@ static inline float env_sample_continuous(const float *cdf, uint32_t n, float u,
   return ((float)k + place) / (float)n;
 }
 
+// ---- the shading normal of a triangle hit, restated from the spec's text: the corner normals interpolated in the order of
+// the hit point, the fallback to ng for a sum that is zero or not finite, the unit normal turned to ng's side (ng stays the winding's
+// normal), then the flip that makes nf.  *fell_back: the result is +-ng bit for bit and nothing of 3.18's extra rules applies. ----
+static inline Vec3 shading_normal(Vec3 n0, Vec3 n1, Vec3 n2, Vec3 ng, float b1, float b2, Vec3 wo, bool *fell_back) {
+  const float w = (1.0f - b1) - b2;
+  const Vec3 n = (n0 * w + n1 * b1) + n2 * b2;
+  const float l2 = dot(n, n);
+  *fell_back = !(l2 > 0.f) || !std::isfinite(l2);
+  Vec3 ns = ng;
+  if (!*fell_back) {
+    ns = n / std::sqrt(l2);
+    if (dot(ns, ng) < 0.f) ns = -ns;
+  }
+  return dot(ng, wo) < 0.f ? -ns : ns;
+}
+
+// ---- Kd from an image, restated from the spec's text.  texels: 3 floats per texel, row-major, row 0 = the image's TOP;
+// t = 0 is the BOTTOM row: texel row iy counted from the bottom is row H - 1 - iy.  An index stays a float until it is clamped. ----
+struct ImageSlot {
+  uint32_t W = 0, H = 0, wrap = 0, filter = 0;  // wrap: 0 repeat, 1 clamp, 2 black; filter: 0 point, 1 bilinear
+  size_t first = 0;                             // the slot's first texel in the scene's pool
+};
+// (uint32_t)min(max(xf, 0), nf - 1): the maximum first, so that a NaN becomes 0 and the cast never sees a value outside [0, n - 1]
+static inline uint32_t image_index(float xf, float nf) { return (uint32_t)std::fmin(std::fmax(xf, 0.f), nf - 1.0f); }
+static inline bool image_inside(float xf, float nf) { return xf >= 0.f && xf <= nf - 1.0f; }
+static inline Vec3 image_lookup(const float *pool, const ImageSlot &im, float s, float t) {
+  const float Wf = (float)im.W, Hf = (float)im.H;
+  const float *img = pool + 3 * im.first;
+  auto texel = [&](uint32_t ix, uint32_t iy) {  // iy from the bottom
+    const float *c = img + 3 * ((size_t)(im.H - 1u - iy) * im.W + ix);
+    return v3(c[0], c[1], c[2]);
+  };
+  if (im.filter == 0u) {
+    const float xf = im.wrap == 0u ? std::floor((s - std::floor(s)) * Wf) : std::floor(s * Wf);
+    const float yf = im.wrap == 0u ? std::floor((t - std::floor(t)) * Hf) : std::floor(t * Hf);
+    if (im.wrap == 2u && !(image_inside(xf, Wf) && image_inside(yf, Hf))) return v3(0.f, 0.f, 0.f);  // tested before the clamp: a NaN is black
+    return texel(image_index(xf, Wf), image_index(yf, Hf));
+  }
+  // bilinear: texel centres at (i + 0.5) / W, from the UNREDUCED s
+  const float sx = s * Wf - 0.5f, sy = t * Hf - 0.5f;
+  const float x0 = std::floor(sx), y0 = std::floor(sy);
+  const float dx = std::fmin(std::fmax(sx - x0, 0.f), 1.0f), dy = std::fmin(std::fmax(sy - y0, 0.f), 1.0f);
+  // a neighbour's index and weight along one axis: repeat wraps it (pbrt-v3's Mod), black gives it weight 0 outside, then the clamp
+  auto neighbour = [&](float c, float w, float nf, uint32_t *idx) {
+    if (im.wrap == 0u) c = c - nf * std::floor(c / nf);
+    if (im.wrap == 2u && !image_inside(c, nf)) w = 0.f;
+    *idx = image_index(c, nf);
+    return w;
+  };
+  Vec3 acc = v3(0.f, 0.f, 0.f);
+  for (int j = 0; j < 2; j++) {  // j outer, i inner
+    uint32_t iy;
+    const float wy = neighbour(j ? y0 + 1.0f : y0, j ? dy : 1.0f - dy, Hf, &iy);
+    for (int i = 0; i < 2; i++) {
+      uint32_t ix;
+      const float wx = neighbour(i ? x0 + 1.0f : x0, i ? dx : 1.0f - dx, Wf, &ix);
+      acc = acc + texel(ix, iy) * (wx * wy);
+    }
+  }
+  return acc;
+}
+
 }  // namespace orc

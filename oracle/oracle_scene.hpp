@@ -162,6 +162,10 @@ class Scene {
   std::vector<orc_material> mats;
   std::vector<orc_texture> textures;
   std::vector<float> tri_uv;          // 6 per triangle (corner u, v), or empty
+  std::vector<ImageSlot> images;      // one per slot of `textures` (W = 0 where the slot is no image) ...
+  std::vector<float> image_mapping;   // ... its su, sv, du, dv (4 per slot: an image record keeps them elsewhere than a checkerboard does) ...
+  std::vector<float> image_pool;      // ... and the texels of all of them, back to back, 3 floats per texel
+  std::vector<float> tri_n;           // 9 per triangle (the corners' normals), or empty
   std::vector<orc_sphere> spheres;
   std::vector<LightRec> lights;
   Vec3 le_infinite{0, 0, 0};

@@ -29,21 +29,45 @@ extern "C" {
  * include/pbrt_hip.h's pbrt_hip_scene_desc so a test can hand both the same bytes,
  * but declared independently. */
 typedef struct {
-  uint32_t type;  /* 0 = matte, 1 = mirror, 2 = glass; anything else: orc_scene_create returns NULL */
-  float k[3];     /* Kd (matte) or Kr (mirror, glass) */
-  float le[3];    /* emitted radiance (one-sided, along the geometric normal); glass: Kt -- a glass surface does not emit */
-  uint32_t kd_tex; /* matte: 0 = Kd is k, t > 0 = textures[t - 1] at the hit's (u, v) on triangles (the slot must be a
-                      checkerboard, not a map: NULL).  glass: the IEEE-754 bits of the float eta */
+  uint32_t type;  /* 0 = matte, 1 = mirror, 2 = glass, 3 = plastic (3.21); anything else: orc_scene_create returns NULL */
+  float k[3];     /* Kd (matte, plastic) or Kr (mirror, glass) */
+  float le[3];    /* emitted radiance (one-sided, along the geometric normal); glass: Kt, plastic: Ks -- neither surface emits */
+  uint32_t kd_tex; /* matte: 0 = Kd is k, t > 0 = textures[t - 1] at the hit's (u, v) (the slot must be a checkerboard
+                      or an image -- a slot of type 1, 2 or 3: NULL).  glass: the IEEE-754 bits of the float eta.  plastic: those of alpha */
 } orc_material;
 
 typedef struct {
   uint32_t type;  /* 0 = checkerboard 2D over (u, v): pbrt-v3 Checkerboard2DTexture, aamode none.  A slot whose first word is 1 is not
                      this struct but the 64-byte record of an environment map (type = 1, width, height, reserved,
-                     const float *rgb, float world_to_light[9], pad), which the oracle reads with memcpy into a struct of its own */
+                     const float *rgb, float world_to_light[9], pad), which the oracle reads with memcpy into a struct of its own; likewise
+                     2 = the shading normals' record (orc_normals below) and 4 = an image texture's (orc_image_texture,
+                     3.20).  3, the pixel filter's record (3.19), and anything above 4: orc_scene_create returns NULL */
   float tex1[3], tex2[3];
   float su, sv, du, dv;
   uint32_t pad[5];
 } orc_texture;
+
+/* The 64 bytes of a slot whose first word is 4, declared here independently of the product's header: Kd from an image,
+ * point or bilinear lookup, three wrap modes; t = 0 is the image's BOTTOM row, row 0 of rgb its top */
+typedef struct {
+  uint32_t type;  /* = 4 */
+  uint32_t width, height;
+  uint32_t wrap;     /* 0 repeat, 1 clamp, 2 black */
+  const float *rgb;  /* 3 * width * height, row-major */
+  float su, sv, du, dv;
+  uint32_t filter;   /* 0 point, 1 bilinear */
+  uint32_t pad[5];
+} orc_image_texture;
+
+/* The 64 bytes of a slot whose first word is 2: the normals of every triangle's three corners, world space, any length;
+ * all zero = "this triangle has none" */
+typedef struct {
+  uint32_t type;        /* = 2 */
+  uint32_t n_tris;      /* the description's n_tris, or NULL */
+  uint32_t reserved[2];
+  const float *tri_n;   /* 9 * n_tris */
+  uint32_t pad[10];
+} orc_normals;
 
 typedef struct {
   uint32_t type;  /* 0 point, 1 distant, 2 infinite(constant), 3 infinite with an environment map; above: NULL */
@@ -136,8 +160,11 @@ float orc_gamma_correct(float v);
 uint8_t orc_to_byte(float v);
 
 /* ---- scene / BVH / rays ---- */
-/* NULL for what the oracle does not know: a material type above 2, a light type above 3, a type-3 light that names no map slot (or a
- * second one), a matte kd_tex that names a map slot */
+/* NULL for what the oracle does not render: a material type above 3, a light type above 3, a type-3 light that names no map slot (or a
+ * second one), a slot of an unknown type (above 4) or the pixel filter's (type 3: the weighted filters are compared through accumulators of
+ * the oracle's radiances, no test hands the oracle the record), a second normals slot or one whose n_tris is not the scene's (or without
+ * its array), an image slot without texels or with an unknown wrap or filter, a matte kd_tex that names a slot of type 1, 2 or 3 (or none
+ * at all), a plastic material (type 3) beside a map slot or a normals slot -- what the product refuses too */
 orc_scene *orc_scene_create(const orc_scene_desc *desc);
 void orc_scene_destroy(orc_scene *s);
 uint32_t orc_bvh_node_count(const orc_scene *s);
@@ -171,6 +198,16 @@ enum { ORC_BLOCK_SIN = 0, ORC_BLOCK_COS, ORC_BLOCK_ATAN_POS, ORC_BLOCK_ACOS, ORC
        ORC_BLOCK_COSINE_ABOUT, ORC_BLOCK_SPHERE_HIT, ORC_BLOCK_QUAD_STEP, ORC_BLOCK_QUAD_STEP_PK, ORC_BLOCK_TRI_HIT,
        ORC_BLOCK_MIS_W_LIGHT, ORC_BLOCK_MIS_W_BSDF, ORC_BLOCK_LIGHT, ORC_BLOCK_COUNT };
 int orc_blocks_eval(uint32_t op, int64_t n, const float *in, float *out);
+/* ---- normals, plastic and images over arrays, each in the layout of the product's hook of the same name (pbrt_hip_shading_normal_eval_device,
+ * pbrt_hip_plastic_eval_device, pbrt_hip_image_lookup_eval_host); 0, or -1 for a bad argument ---- */
+/* in (17): the corner normals n0 n1 n2, ng, b1, b2, wo -> out (4): nsf, fell_back (0 or 1) -- DESIGN.md 3.18 */
+int orc_shading_normal_eval(int64_t n, const float *in, float *out);
+/* in (18): nf, wo, wi, u1, u2, Kd, Ks, alpha -> out (10): f(wo, wi), pdf_b(wi), the sampled wi', f(wo, wi') cos / pdf_b(wi') (the last six zero
+ * where the sample dies) -- DESIGN.md 3.21 */
+int orc_plastic_eval(int64_t n, const float *in, float *out);
+/* the lookup of record `which` of n_records image records, packed into ONE texel pool as a scene packs them, at n (u, v) pairs -> 3 n floats,
+ * the record's mapping included -- DESIGN.md 3.20 */
+int orc_image_lookup_eval(const orc_image_texture *records, uint32_t n_records, uint32_t which, int64_t n, const float *uv, float *rgb);
 /* one element of QUAD_STEP (quad_walk.cpp; what orc_blocks_eval calls): x = 24 floats, y = 6 */
 void orc_quad_step_eval(const float *x, float *y);
 /* camera ray for film point (fx, fy) */

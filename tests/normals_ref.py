@@ -1,5 +1,5 @@
 """Float64 references of the shading normals for tests/test_normals_host.py and tests/test_normals_gpu.py.  Nothing below
-shares a line with the library or the oracle (which knows nothing of normals): the normal's statement in float64 with its first-order error
+shares a line with the library or the oracle (whose own restatement tests/test_oracle_normals_plastic_images.py holds to this): the normal's statement in float64 with its first-order error
 bounds, closed forms of the lit plane, the clipped cosine lobe and the mirror, the camera of DESIGN.md 3.2 in float64, and the scenes the GPU
 tests build.  Every bound is derived from the roundings the kernel states (fp32, fixed operation order, no contraction) -- none is taken
 from the outputs under test.

@@ -125,9 +125,9 @@ def test_2x2_point_images_render_the_checkerboard_film(gpu, oracle, case):
     sd = make()
     isd = ref.with_checkers_as_images(sd)
     assert len(isd.images) == len(sd.textures) >= 1 and (isd.textures[:, 0] == 4).all() and np.array_equal(isd.mat_tex, sd.mat_tex)
-    # (the oracle has neither the weighted filters nor the shading normals: there the checkerboard scene's HIP film, which
-    # tests/test_filters_gpu.py and tests/test_normals_gpu.py hold to their own restatements, is the reference)
-    want = _render(oracle.OracleScene(sd), how, kw) if sd.pixel_filter is None and len(sd.tri_n) == 0 else None
+    # (the oracle is not handed the weighted filters' record: there the checkerboard scene's HIP film, which tests/test_filters_gpu.py
+    # holds to its own restatement, is the reference)
+    want = _render(oracle.OracleScene(sd), how, kw) if sd.pixel_filter is None else None
     with gpu.Scene(sd, builder=builder) as sc:
         checker = _render(sc, how, kw)
         if case.startswith("deep"):  # the overflow variant of the walk's stack, or the case does not reach the instantiations it is there for
@@ -141,6 +141,7 @@ def test_2x2_point_images_render_the_checkerboard_film(gpu, oracle, case):
         if want is not None:
             assert_bit_equal(checker, want, f"{case}: the checkerboard scene against the oracle")
             assert_bit_equal(image, want, f"{case}: the 2 x 2 images against the oracle's film of the checkerboards")
+            assert_bit_equal(image, oracle.OracleScene(isd).render(**kw)[0], f"{case}: the 2 x 2 images against the oracle's film of the images")
     else:
         assert want is None or np.array_equal(checker, want), f"{case}: the checkerboard scene against the oracle (accumulators)"
         assert np.array_equal(image, checker) and np.abs(image[..., 3]).sum() > 0, f"{case}: the 2 x 2 images against the checkerboards (accumulators)"
@@ -186,7 +187,7 @@ def _plane_with_image(image, wrap, filt, mapping, res=64):
 
 def _plane_uv(oracle, res, offsets):
     """(u, v) of the plane under the rays through pixel + offset, for every pixel: (len(offsets), res, res, 2), float64"""
-    o_sc = oracle.OracleScene(lit_plane_scene("distant", res)[0])  # (the camera alone: the oracle is never shown an image)
+    o_sc = oracle.OracleScene(lit_plane_scene("distant", res)[0])  # (the camera alone: these closed forms do not go through the oracle's image lookup)
     out = np.zeros((len(offsets), res, res, 2))
     for k, (ox, oy) in enumerate(offsets):
         for py in range(res):

@@ -1,5 +1,5 @@
-"""Shading normals on the GPU.  The oracle knows nothing of normals, so it is asked only for scenes WITHOUT the record (or
-with normals that change nothing but rounding); everything else is held to tests/normals_ref.py: the hook against float64 with first-order
+"""Shading normals on the GPU.  What stood before the oracle learnt normals (tests/test_normals_plastic_parity_gpu.py
+holds the films to it word for word), held to tests/normals_ref.py: the hook against float64 with first-order
 bounds, closed forms (one normal for a whole plane, the clipped cosine lobe, the mirror), the leaf-order gather triangle by triangle, the
 tessellated sphere against C1's analytic image, and the library against itself (runs, shards, render_multi, scene file = arrays)."""
 import ctypes as C
@@ -82,7 +82,7 @@ PLANE_CASES = {
 
 
 @pytest.mark.parametrize("case", list(PLANE_CASES))
-def test_one_normal_for_the_whole_plane(gpu, case):
+def test_one_normal_for_the_whole_plane(gpu, oracle, case):
     n_star, wl = PLANE_CASES[case]
     sd, _ = lit_plane_scene("distant", 16)
     sd.lights[0, 1:4] = wl
@@ -95,9 +95,12 @@ def test_one_normal_for_the_whole_plane(gpu, case):
     lit = wl32[2] > 0 and n_unit @ wl32 > 0
     want = nr.lambert_distant(sd.materials[0, 1:4], (3.0, 2.0, 1.0), n_unit, wl32) if lit else np.zeros(3)
     assert lit == ("hemisphere" not in case)
+    o = oracle.OracleScene(sd)
     with gpu.Scene(sd) as sc:
         for kw in SETTINGS:
-            rgb = _rgb(sc.render(spp=(2, 2), seed=9, **kw)[0])
+            film = sc.render(spp=(2, 2), seed=9, **kw)[0]
+            assert_bit_equal(film, o.render(spp=(2, 2), seed=9, **kw)[0], f"{case} {kw}: against the oracle")  # (beside the closed form: word for word)
+            rgb = _rgb(film)
             if lit:
                 assert np.allclose(rgb, want, **BAR), (case, kw, rgb.min((0, 1)), rgb.max((0, 1)), want)
             else:

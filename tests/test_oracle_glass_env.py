@@ -243,8 +243,8 @@ def test_oracle_refuses_what_it_does_not_know():
     assert _create(sd)
 
     def mat_type(desc):
-        desc.mats[0].type = 3
-    assert not _create(sd, mat_type)  # a material type above 2
+        desc.mats[0].type = 4
+    assert not _create(sd, mat_type)  # a material type the oracle does not know (3 is plastic now: tests/test_oracle_normals_plastic_images.py)
 
     def light_type(desc):
         desc.lights[0].type = 4

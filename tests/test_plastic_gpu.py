@@ -51,7 +51,7 @@ def _plane_scene(res, eye, lights, kd=(0.3, 0.4, 0.5), ks=(0.5, 0.4, 0.3), rough
 
 
 @pytest.mark.parametrize("sampler", SAMPLERS)
-def test_one_bounce_frames_match_the_reference(gpu, sampler):
+def test_one_bounce_frames_match_the_reference(gpu, oracle, sampler):
     """A plastic quad under one point light, and under one distant light, direct lighting, 4 spp: nothing is random but the film points.
     The bar is the one the twin's fixed cases are held to (tests/test_oracle_glass_env.py, tests/test_normals_gpu.py): weights equal, 99 %
     of the pixels within 1e-4 per channel, PSNR >= 90 dB."""
@@ -61,6 +61,7 @@ def test_one_bounce_frames_match_the_reference(gpu, sampler):
         kw = dict(integrator=INTEGRATOR_DIRECT, max_depth=5, spp=(2, 2), seed=11, sampler=sampler)
         with gpu.Scene(sd) as sc:
             film = sc.render(**kw)[0]
+        assert_bit_equal(film, oracle.OracleScene(sd).render(**kw)[0], f"{name} light, {sampler}: against the oracle")
         ps, share, weights = twin_agreement(_ref(sd, **kw), film)
         print(f"{name} light, {sampler}: PSNR {ps:.1f} dB, {100 * share:.2f} % of the pixels within 1e-4")
         assert film[..., 1].mean() > 0.05
@@ -79,10 +80,11 @@ def plastic_box():
 
 
 @pytest.mark.parametrize("case", PATH_CASES, ids=lambda c: "-".join(f"{k}={v}" for k, v in c.items()))
-def test_whole_paths_match_the_reference(gpu, plastic_box, case):
+def test_whole_paths_match_the_reference(gpu, oracle, plastic_box, case):
     kw = dict(case, max_depth=5, spp=(4, 4), seed=5)
     with gpu.Scene(plastic_box) as sc:
         film = sc.render(**kw)[0]
+    assert_bit_equal(film, oracle.OracleScene(plastic_box).render(**kw)[0], f"plastic_scene vs the oracle, {kw}")  # (and, beside the bar below, word for word)
     ok, ps, off = meets_random_scene_bar(_ref(plastic_box, **kw), film, kw)
     print(f"{case}: PSNR {ps:.1f} dB, {off} of {32 * 32} pixels off at 1e-4")
     assert ok, (case, ps, off)

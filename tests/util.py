@@ -736,6 +736,94 @@ def random_glass_env_case(seed, cap=True):
     return dataclasses.replace(sd, **rep).normalized(), kw
 
 
+def random_corner_normals(sd, seed):
+    """(n_tris, 9) float32 corner normals for the parity tests of DESIGN.md 3.18, from a generator of their own: most within 60 degrees of
+    the winding's normal ng and scaled 10^-3 .. 10^3 per corner; a tenth of the triangles all zero ("none": shaded flat), a tenth with one
+    zero corner, a tenth on the far side of ng (the flip to ng's side applies)"""
+    import normals_ref as nr
+    rng = np.random.default_rng(93_000 + seed)
+    n = len(sd.idx)
+    if n == 0:
+        return np.zeros((0, 9), np.float32)
+    P = sd.P.astype(np.float64)[sd.idx.astype(np.int64)]
+    ng = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    ln = np.linalg.norm(ng, axis=1, keepdims=True)
+    ng = np.where(ln > 0, ng / np.where(ln > 0, ln, 1.0), np.array([[0.0, 0.0, 1.0]]))  # (a triangle that fp32 collapsed: any axis)
+    kind = rng.permutation(n) % 10  # 0: all zero, 1: one zero corner, 2: the far side
+    axis = np.where((kind == 2)[:, None], -ng, ng)
+    nc = np.stack([nr._cone(rng, axis, 60.0) * 10.0 ** rng.uniform(-3, 3, (n, 1)) for _ in range(3)], 1)
+    nc[kind == 0] = 0.0
+    one = np.flatnonzero(kind == 1)
+    nc[one, rng.integers(0, 3, len(one))] = 0.0
+    return nc.reshape(n, 9).astype(np.float32)
+
+
+def random_images_for_checkers(sd, seed):
+    """the scene with its checkerboards replaced, slot by slot, by random images of 1 .. 17 texels a side under a random
+    filter and wrap, the checkerboard's own mapping kept"""
+    import dataclasses
+    from pbrt_amd import api
+    rng = np.random.default_rng(94_000 + seed)
+    images, rows = [], []
+    for t in sd.textures:
+        assert int(t[0]) == 0
+        h, w = int(rng.choice([1, 2, 3, 5, 17])), int(rng.choice([1, 2, 4, 8, 17]))
+        rows.append(api.image_texture_row(len(images), int(rng.integers(0, 3)), int(rng.integers(0, 2)), tuple(float(x) for x in t[7:11])))
+        images.append(rng.uniform(0.05, 0.95, (h, w, 3)).astype(np.float32))
+    return dataclasses.replace(sd, textures=np.array(rows, np.float32).reshape(-1, 11), images=images).normalized()
+
+
+def random_normals_plastic_case(seed, feature, cap=True):
+    """random_glass_env_case's sibling for shading normals, plastic (3.21) and image textures (3.20): that case -- None where
+    it is None -- changed by generators of their own.  feature "normals": random_corner_normals on every triangle, and no wide filter (the
+    combination the product refuses); the map, the glass and the textures stay.  feature "plastic": materials that do not emit become
+    plastic with probability 0.5 each (alpha of 1e-3, 0.05, 0.4618 or 1; one in ten with Ks = 0, one in ten with Kd = 0),
+    and where none of the used ones was turned the most used one is; the map and its light are REMOVED and no normals are added -- plastic
+    never stands beside a map or beside normals, which the product and the oracle refuse.  Either feature: on every other seed the
+    checkerboards become random images."""
+    import dataclasses
+    from pbrt_amd import LIGHT_ENVMAP, PLASTIC
+    assert feature in ("normals", "plastic")
+    case = random_glass_env_case(seed, cap)
+    if case is None:
+        return None
+    sd, kw = case
+    kw = dict(kw)
+    if feature == "normals":
+        sd = dataclasses.replace(sd, tri_n=random_corner_normals(sd, seed)).normalized()
+        kw.pop("filter_width", None)
+    else:
+        g = np.random.default_rng(95_000 + seed)
+        mats, eta = sd.materials.copy(), sd.mat_eta.copy() if len(sd.mat_eta) else np.full(len(sd.materials), 1.5, np.float32)
+        n = len(mats)
+        draws = [(g.random(), float(g.choice([1e-3, 0.05, 0.4618, 1.0])), g.uniform(0.05, 0.9, 3), g.uniform(0.05, 0.9, 3), g.random()) for _ in range(n)]
+        can = ~((mats[:, 0] == 0) & (mats[:, 4:7] > 0).any(1))  # (glass may turn too: half of it stays beside the plastic)
+        used = np.bincount(np.concatenate([sd.mat_id.astype(np.int64), sd.spheres[:, 4].astype(np.int64)]), minlength=n)[:n]
+        turn = np.array([d[0] < 0.5 for d in draws]) & can
+        if not (turn & (used > 0)).any() and (used * can).max(initial=0) > 0:
+            turn[int(np.argmax(used * can))] = True
+        for i in np.flatnonzero(turn):
+            _, alpha, kd, ks, z = draws[i]
+            if z < 0.1:
+                ks = np.zeros(3)
+            elif z < 0.2:
+                kd = np.zeros(3)
+            mats[i] = [PLASTIC, *kd, *ks]
+            eta[i] = alpha
+        lights = sd.lights[sd.lights[:, 0] != LIGHT_ENVMAP]
+        sd = dataclasses.replace(sd, materials=mats, mat_eta=eta.astype(np.float32), mat_tex=np.where(turn, 0, sd.mat_tex).astype(np.uint32), lights=lights,
+                                 envmap=np.zeros((0, 0, 3), np.float32)).normalized()
+        assert not case_holds_map(sd) and len(sd.tri_n) == 0
+    if seed % 2 and len(sd.textures):
+        sd = random_images_for_checkers(sd, seed)
+    return sd, kw
+
+
+def case_holds_plastic(sd):
+    m = np.concatenate([sd.mat_id.astype(np.int64), sd.spheres[:, 4].astype(np.int64)])
+    return bool(len(m)) and bool((sd.materials[m, 0] == 3).any())
+
+
 def case_holds_glass(sd):
     """a primitive of the scene is glass"""
     m = np.concatenate([sd.mat_id.astype(np.int64), sd.spheres[:, 4].astype(np.int64)])

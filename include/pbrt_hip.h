@@ -80,7 +80,7 @@ typedef struct {
 typedef struct {
   uint32_t type;  /* 0 = checkerboard, dimension 2, "uv" mapping; 1 = this slot is the environment-map record below; 2 = the shading
                      normals' record, pbrt_hip_normals; 3 = the pixel filter's record, pbrt_hip_pixel_filter; 4 = an image texture's
-                     record, pbrt_hip_image_texture */
+                     record, pbrt_hip_image_texture; 6 = a spot light's cone, pbrt_hip_spot_cone */
   float tex1[3], tex2[3];
   float su, sv, du, dv; /* "float uscale" / "vscale" / "udelta" / "vdelta" */
   uint32_t pad[5];
@@ -201,11 +201,33 @@ typedef struct {
  * exist for every integrator and sampler, with and without spheres, textures and glass, and NOT for: a box filter radius other than
  * 0.5, the counter flags (both PBRT_HIP_ERR_LIMIT at render, the message names the combination). */
 #define PBRT_HIP_LIGHT_ENVMAP 3u
+/* LightSource "spot" (pbrt-v3's SpotLight): type 5 -- 4 stays an unknown light type --, a point light at p with intensity c
+ * = I inside a cone with a smooth edge.  The 32-byte record cannot hold the cone, so `pad` = the BITS of the 1-based number of a type-6 slot
+ * of `textures` -- a pbrt_hip_spot_cone record, named the way the environment map's light names its map --: a unit axis that points AWAY from the light and
+ * two cosines cos_total <= cos_start.  For a shading point with unit direction wi towards the light, ct = -(wi . axis):
+ *   falloff = 0 where ct < cos_total, 1 where ct >= cos_start, else ((ct - cos_total) / (cos_start - cos_total))^4
+ * and the light is the point light times that falloff; cos_total = cos_start is a hard edge.  A delta light: MIS weight 1, never hit by a
+ * ray.  Several spot lights may share a cone slot.  Refused at scene creation before any device work (PBRT_HIP_ERR_INVALID, the message
+ * holds "spot"): a type-5 light whose `pad` names no type-6 slot; an axis that is not finite or whose squared length is off 1 by more than
+ * 1e-4; a cosine that is not finite or lies outside [-1, 1]; cos_total > cos_start; a matte kd_tex that names a cone slot.  A scene with a
+ * spot light is rendered by the kernels that render glass and plastic (the GLS instantiations of render_kernel_x), for every integrator,
+ * sampler and filter; NOT in a scene whose texture table holds an environment map (slot type 1) or shading normals (slot type 2):
+ * pbrt_hip_scene_create refuses the pair with PBRT_HIP_ERR_LIMIT (the message holds "spot").  Not with the counter flags
+ * (PBRT_HIP_ERR_LIMIT at render, as for glass). */
+#define PBRT_HIP_LIGHT_SPOT 5u
+#define PBRT_HIP_TEXTURE_SPOT 6u /* (slot types 5 and 7 stay unknown texture types) */
 typedef struct {
-  uint32_t type; /* 0 point, 1 distant, 2 infinite with constant radiance, 3 infinite with an environment map */
-  float p[3];    /* point: position; distant: unit direction TOWARDS the light */
-  float c[3];    /* point: intensity I; distant / infinite: radiance L; 3: the factor on the texels */
-  float pad;     /* 3: the bits of the texture-table number (1-based) of the pbrt_hip_envmap */
+  uint32_t type;   /* = 6 */
+  float axis[3];   /* unit, world space, from the light into the cone */
+  float cos_total; /* cosine of the cone's half angle: no light outside */
+  float cos_start; /* cosine of the angle at which the falloff starts: full intensity inside; >= cos_total */
+  uint32_t pad[10];
+} pbrt_hip_spot_cone;
+typedef struct {
+  uint32_t type; /* 0 point, 1 distant, 2 infinite with constant radiance, 3 infinite with an environment map, 5 spot */
+  float p[3];    /* point, spot: position; distant: unit direction TOWARDS the light */
+  float c[3];    /* point, spot: intensity I; distant / infinite: radiance L; 3: the factor on the texels */
+  float pad;     /* 3: the bits of the texture-table number (1-based) of the pbrt_hip_envmap; 5: of the pbrt_hip_spot_cone */
 } pbrt_hip_light;
 
 /* Shape "sphere" (check-sphere.pbrt:22), world space.  A primitive of the BVH like a triangle (primitive number n_tris + index, which is

@@ -212,6 +212,15 @@ int pbrt_hip_image_lookup_eval_device(int device, const pbrt_hip_image_texture *
 #define PBRT_HIP_PLASTIC_EVAL_OUT 10
 int pbrt_hip_plastic_eval_device(int device, int64_t n, const float *in, float *out);
 
+/* ---- the spot light's sample (pbrt_amd/csrc/spot_light.hpp is the one statement of the arithmetic) ---- */
+/* spot_light.hpp over arrays on `device` (a small kernel of kernels_blocks.hip): element i reads 15 floats of `in` -- the shading point po,
+ * its normal nf, the light's position p, the cone's axis, cos_total, cos_start, nL (the scene's light count as a float) -- and writes 7
+ * floats of `out`: ok (1 or 0), wi.xyz, tmax, the falloff, and scale = ((cos / dist^2) nL) falloff (the last six are zero where ok is).
+ * in / out are HOST arrays.  PBRT_HIP_ERR_INVALID for a negative n or a null array, PBRT_HIP_ERR_NO_DEVICE without a device. */
+#define PBRT_HIP_SPOT_EVAL_IN 15
+#define PBRT_HIP_SPOT_EVAL_OUT 7
+int pbrt_hip_spot_eval_device(int device, int64_t n, const float *in, float *out);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

@@ -38,10 +38,16 @@ class ImageTexture(C.Structure):
                 ("su", C.c_float), ("sv", C.c_float), ("du", C.c_float), ("dv", C.c_float), ("filter", C.c_uint32), ("pad", C.c_uint32 * 5)]
 
 
-# the first word of a slot of the texture table: which of the five record classes above the slot IS
+class SpotCone(C.Structure):
+    """pbrt_hip_spot_cone: what a slot of the texture table IS when its first word is 6; 64 bytes like Texture"""
+    _fields_ = [("type", C.c_uint32), ("axis", C.c_float * 3), ("cos_total", C.c_float), ("cos_start", C.c_float), ("pad", C.c_uint32 * 10)]
+
+
+# the first word of a slot of the texture table: which of the six record classes above the slot IS (5 is no record)
 SLOT_CHECKER, SLOT_ENVMAP, SLOT_NORMALS, SLOT_FILTER, SLOT_IMAGE = range(5)
+SLOT_SPOT = 6
 SLOT_BYTES = C.sizeof(Texture)
-assert all(C.sizeof(cls) == SLOT_BYTES == 64 for cls in (EnvMap, Normals, PixelFilter, ImageTexture))
+assert all(C.sizeof(cls) == SLOT_BYTES == 64 for cls in (EnvMap, Normals, PixelFilter, ImageTexture, SpotCone))
 
 
 def put_slot(table, i, rec):
@@ -175,6 +181,7 @@ SYMBOLS = {
     "pbrt_hip_image_lookup_eval_device": (C.c_int, [C.c_int, C.POINTER(ImageTexture), _u32, _u32, _i64, _pf, _pf]),
     "pbrt_hip_blocks_eval_device": (C.c_int, [C.c_int, _u32, _i64, _pf, _pf]),
     "pbrt_hip_plastic_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
+    "pbrt_hip_spot_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
     "pbrt_hip_shading_normal_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
 }
 

@@ -9,12 +9,13 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import EnvMap, ImageTexture, Light, Material, Normals, PixelFilter, RenderDesc, SceneDesc, Sphere, Stats, Texture, check, lib
+from ._lib import EnvMap, ImageTexture, Light, Material, Normals, PixelFilter, RenderDesc, SceneDesc, Sphere, SpotCone, Stats, Texture, check, lib
 
 MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
 PLASTIC = 3  # PBRT_HIP_MATERIAL_PLASTIC: DESIGN.md 3.21
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
 LIGHT_ENVMAP = 3  # PBRT_HIP_LIGHT_ENVMAP: the infinite light with an environment map
+LIGHT_SPOT = 5  # PBRT_HIP_LIGHT_SPOT: a point light inside a cone with a smooth edge; 4 is no light type
 INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_PATH_MIS = 0, 1, 2  # 2: the path integrator with MIS
 FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_SINC = 1, 2, 3, 4  # PBRT_HIP_FILTER_*: the weighted pixel filters
 FILTER_KINDS = {"triangle": FILTER_TRIANGLE, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL, "sinc": FILTER_SINC}
@@ -59,7 +60,10 @@ class SceneData:
     parameters alpha / B, C / tau (omitted ones: pbrt-v3's defaults); its record travels in a slot of its own too, and a render's
     filter_width is then that filter's radii (0 = the kind's default).  Image textures: `images` = a list of (H, W, 3) float32
     arrays, row 0 = the image's top, and a `textures` row (TEXTURE_IMAGE, image index, wrap, filter, 0, 0, 0, su, sv, du, dv) -- WRAP_*,
-    TEXFILTER_* --, which fill_desc turns into the pbrt_hip_image_texture record of the same slot (image_texture_row makes one)."""
+    TEXFILTER_* --, which fill_desc turns into the pbrt_hip_image_texture record of the same slot (image_texture_row makes one).  Spot lights
+    (DESIGN.md 3.22): a `lights` row (LIGHT_SPOT, position, I rgb) and `spot_cones` rows (axis xyz -- unit, from the light into the cone --,
+    cos_total, cos_start), the k-th row the cone of the k-th LIGHT_SPOT row (spot_light makes the pair); each cone travels in a slot of its own
+    behind the filter's and before the normals'."""
     P: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
     idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.uint32))
     mat_id: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint16))
@@ -80,6 +84,7 @@ class SceneData:
     tri_n: np.ndarray = field(default_factory=lambda: np.zeros((0, 9), np.float32))
     pixel_filter: tuple = None
     images: list = field(default_factory=list)
+    spot_cones: np.ndarray = field(default_factory=lambda: np.zeros((0, 5), np.float32))
 
     def normalized(self):
         self.images = [np.ascontiguousarray(im, np.float32) for im in self.images]
@@ -107,6 +112,7 @@ class SceneData:
         assert self.envmap.ndim == 3 and self.envmap.shape[2] == 3
         self.envmap_world_to_light = np.ascontiguousarray(self.envmap_world_to_light, np.float32).reshape(3, 3)
         self.tri_n = np.ascontiguousarray(self.tri_n, np.float32).reshape(-1, 9)
+        self.spot_cones = np.ascontiguousarray(self.spot_cones, np.float32).reshape(-1, 5)
         assert self.idx.shape[0] == self.mat_id.shape[0] and self.tri_uv.shape[0] in (0, self.idx.shape[0])
         assert self.tri_n.shape[0] in (0, self.idx.shape[0])
         return self
@@ -131,7 +137,8 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         if int(m[0]) == PLASTIC:  # k = Kd, le = Ks, kd_tex = the IEEE-754 bits of alpha
             mats[i].kd_tex = int(sd.mat_eta[i:i + 1].view(np.uint32)[0]) if len(sd.mat_eta) else 0  # (no alpha given: 0, which scene creation refuses)
     # the table: every `textures` row in its own slot (mat_tex numbering does not move), then the records that travel with the scene, each in a
-    # slot of its own -- the map's, the pixel filter's, the normals' (include/pbrt_hip.h pbrt_hip_envmap / _pixel_filter / _normals), in this order
+    # slot of its own -- the map's, the pixel filter's, the spot lights' cones, the normals' (include/pbrt_hip.h pbrt_hip_envmap / _pixel_filter /
+    # _spot_cone / _normals), in this order
     records = [image_record(sd.images[int(t[1])], int(t[2]), int(t[3]), t[7:11]) if int(t[0]) == TEXTURE_IMAGE else checker_record(t) for t in sd.textures]
     has_env = sd.envmap.size > 0
     if has_env:
@@ -139,6 +146,9 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
                               world_to_light=tuple(float(x) for x in sd.envmap_world_to_light.reshape(-1))))
     if sd.pixel_filter is not None:
         records.append(pixel_filter_record(sd.pixel_filter))
+    first_cone = len(records)  # (0-based slot of cone 0)
+    for c in sd.spot_cones:
+        records.append(SpotCone(type=_lib.SLOT_SPOT, axis=tuple(float(x) for x in c[0:3]), cos_total=float(c[3]), cos_start=float(c[4])))
     if sd.tri_n.shape[0]:
         records.append(Normals(type=_lib.SLOT_NORMALS, n_tris=sd.tri_n.shape[0], tri_n=_fp(sd.tri_n)))
     texs = None
@@ -152,12 +162,16 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
     if sd.tri_uv.shape[0]:
         desc.tri_uv = _fp(sd.tri_uv)
     lights = (light_t * max(len(sd.lights), 1))()
+    n_spot = 0
     for i, l in enumerate(sd.lights):
         lights[i].type = int(l[0])
         lights[i].p[:] = [float(x) for x in l[1:4]]
         lights[i].c[:] = [float(x) for x in l[4:7]]
         if int(l[0]) == LIGHT_ENVMAP:  # `pad` = the bits of the 1-based number of the map's slot (0: the scene holds no map -- refused)
             lights[i].pad = float(np.array([len(sd.textures) + 1 if has_env else 0], np.uint32).view(np.float32)[0])
+        if int(l[0]) == LIGHT_SPOT:  # `pad` = the bits of the 1-based number of its cone's slot (0: `spot_cones` has no row for it -- refused)
+            lights[i].pad = float(np.array([first_cone + n_spot + 1 if n_spot < len(sd.spot_cones) else 0], np.uint32).view(np.float32)[0])
+            n_spot += 1
     spheres = (sphere_t * max(len(sd.spheres), 1))()
     for i, s in enumerate(sd.spheres):
         spheres[i].c[:] = [float(x) for x in s[0:3]]
@@ -198,6 +212,28 @@ def roughness_to_alpha(roughness, remap=True):
 def plastic_material(kd=(0.25, 0.25, 0.25), ks=(0.25, 0.25, 0.25), roughness=0.1, remap=True):
     """-> (the `materials` row (PLASTIC, Kd, Ks), alpha for `mat_eta`) of Material "plastic" with these parameters (pbrt-v3's defaults)"""
     return [PLASTIC, *kd, *ks], roughness_to_alpha(roughness, remap)
+
+
+def spot_light(p, to, I=(1.0, 1.0, 1.0), coneangle=30.0, conedeltaangle=5.0):
+    """-> (the `lights` row (LIGHT_SPOT, p, I), the `spot_cones` row) of LightSource "spot" at `p` aimed at `to` (pbrt-v3's defaults), as the
+    scene parser forms them under an identity CTM: the axis normalised in double and rounded, the cosines from the float32
+    angles in double and rounded"""
+    import math
+    p32, to32 = np.asarray(p, np.float32), np.asarray(to, np.float32)
+    d = to32.astype(np.float64) - p32.astype(np.float64)
+    axis = (d / math.sqrt(float((d * d).sum()))).astype(np.float32)
+    cone, delta = float(np.float32(coneangle)), float(np.float32(conedeltaangle))
+    cos_total, cos_start = np.float32(math.cos(math.radians(cone))), np.float32(math.cos(math.radians(cone - delta)))
+    return [LIGHT_SPOT, *p32, *I], [*axis, cos_total, max(cos_start, cos_total)]
+
+
+def spot_eval_device(x, device=0):
+    """pbrt_hip_spot_eval_device: csrc/spot_light.hpp over arrays on the device.  x (n, 15): po, nf, p, axis, cos_total, cos_start, nL ->
+    (n, 7) float32: ok, wi, tmax, the falloff, scale = ((cos / dist^2) nL) falloff; zeros behind ok = 0"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 15)
+    out = np.zeros((x.shape[0], 7), np.float32)
+    check(lib().pbrt_hip_spot_eval_device(int(device), x.shape[0], _fp(x), _fp(out)), "pbrt_hip_spot_eval_device")
+    return out
 
 
 def plastic_eval_device(x, device=0):

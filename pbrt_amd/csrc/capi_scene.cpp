@@ -93,7 +93,8 @@ int build_canonical(pbrt_hip_scene *s, const float *P, const uint32_t *idx, uint
 // request (PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE, or PBRT_HIP_BUILDER=host in the environment when the caller left the choice open).
 enum class Builder { kHost, kHostOptimized, kGpu, kGpuPlain };
 
-// the 1-based texture-table number an environment-map light carries as the bits of its `pad`
+// the 1-based texture-table number an environment-map light carries as the bits of its `pad`; a spot light names its cone's
+// slot the same way (3.22)
 uint32_t light_env_slot(const pbrt_hip_light &l) { uint32_t u; std::memcpy(&u, &l.pad, 4); return u; }
 // a glass material's index of refraction: the float whose bits ride in kd_tex
 float glass_eta(const pbrt_hip_material &m) { float e; std::memcpy(&e, &m.kd_tex, 4); return e; }
@@ -104,6 +105,8 @@ constexpr float kGlassEtaMin = 1.0f, kGlassEtaMax = 16.0f;
 // peak 1 / (pi alpha^2) leaves fp32's comfortable range; above, pbrt-v3's roughness remap never goes
 float plastic_alpha(const pbrt_hip_material &m) { return glass_eta(m); }
 constexpr float kPlasticAlphaMin = 1e-3f, kPlasticAlphaMax = 1.0f;
+// how far a spot cone's axis may be from unit length, as a squared length
+constexpr float kSpotAxisTolerance = 1e-4f;
 // the materials that reuse `le` and `kd_tex` for parameters of their own: they do not emit and name no texture
 bool reuses_le(const pbrt_hip_material &m) { return m.type == PBRT_HIP_MATERIAL_GLASS || m.type == PBRT_HIP_MATERIAL_PLASTIC; }
 
@@ -171,9 +174,36 @@ int check_light_values(const pbrt_hip_scene_desc *d) {
         return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": position / direction / colour is not finite");
   return PBRT_HIP_OK;
 }
+// a spot light's cone: a unit axis and two cosines, cos_total <= cos_start
+int check_spot_cone(const pbrt_hip_spot_cone &c, const std::string &what) {
+  float len2 = 0.f;
+  for (int k = 0; k < 3; k++) {
+    if (!std::isfinite(c.axis[k])) return fail(PBRT_HIP_ERR_INVALID, what + "a spot light's axis is not finite");
+    len2 += c.axis[k] * c.axis[k];
+  }
+  if (!(std::fabs(len2 - 1.0f) <= kSpotAxisTolerance)) return fail(PBRT_HIP_ERR_INVALID, what + "a spot light's axis must be a unit vector (squared length within 1e-4 of 1)");
+  if (!std::isfinite(c.cos_total) || !std::isfinite(c.cos_start) || !(c.cos_total >= -1.f && c.cos_total <= 1.f) || !(c.cos_start >= -1.f && c.cos_start <= 1.f))
+    return fail(PBRT_HIP_ERR_INVALID, what + "a spot light's cos_total / cos_start must be finite and lie in [-1, 1]");
+  if (c.cos_total > c.cos_start) return fail(PBRT_HIP_ERR_INVALID, what + "a spot light's cos_total must not exceed cos_start (the falloff starts inside the cone)");
+  return PBRT_HIP_OK;
+}
 int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   for (uint32_t i = 0; i < d->n_lights; i++)
-    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP && d->lights[i].type != PBRT_HIP_LIGHT_SPOT) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+  // (a spot light and its cone are checked HERE, where the light's kind is recognised -- the place a type-5 light was refused as unknown
+  // before there were spot lights --, so that every fault that used to win against it still does)
+  for (uint32_t i = 0; i < d->n_lights; i++) {
+    if (d->lights[i].type != PBRT_HIP_LIGHT_SPOT) continue;
+    const std::string what = "scene_create: light " + std::to_string(i) + ": ";
+    const pbrt_hip_spot_cone *cone = table.cone(light_env_slot(d->lights[i]));
+    if (!cone) return fail(PBRT_HIP_ERR_INVALID, what + "a spot light (type 5) must name a type-6 slot of the texture table, its cone, in `pad`");
+    const int rc = check_spot_cone(*cone, what);
+    if (rc) return rc;
+  }
+  for (const TextureTable::Cone &c : table.cones) {  // (a cone no light names is held to the same rules)
+    const int rc = check_spot_cone(c.rec, "scene_create: texture slot " + std::to_string(c.slot + 1) + ": ");
+    if (rc) return rc;
+  }
   uint32_t n_env = 0;
   for (uint32_t i = 0; i < d->n_lights; i++) {  // an environment-map light names a type-1 slot of the texture table; one per scene
     if (d->lights[i].type != PBRT_HIP_LIGHT_ENVMAP) continue;
@@ -214,6 +244,7 @@ int check_kd_tex(const pbrt_hip_scene_desc *d, const TextureTable &table) {
       case SlotKind::kEnvmap: names = "an environment map"; break;
       case SlotKind::kNormals: names = "the shading normals' record"; break;
       case SlotKind::kFilter: names = "the pixel filter's record"; break;
+      case SlotKind::kSpot: names = "a spot light's cone"; break;
       default: break;
     }
     if (names) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names " + names + ", which is not a texture for Kd");
@@ -250,6 +281,17 @@ int check_plastic_family(const pbrt_hip_scene_desc *d, const TextureTable &table
   for (const SlotKind kind : table.kinds) {
     if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a plastic material is not available in a scene with an environment map");
     if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a plastic material is not available in a scene with shading normals");
+  }
+  return PBRT_HIP_OK;
+}
+// a spot light is sampled under PLS alone: the same families, the same refusal
+int check_spot_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
+  bool spot = false;
+  for (uint32_t i = 0; i < d->n_lights && !spot; i++) spot = d->lights[i].type == PBRT_HIP_LIGHT_SPOT;
+  if (!spot) return PBRT_HIP_OK;
+  for (const SlotKind kind : table.kinds) {
+    if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a spot light is not available in a scene with an environment map");
+    if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a spot light is not available in a scene with shading normals");
   }
   return PBRT_HIP_OK;
 }
@@ -293,6 +335,7 @@ int check_table(const pbrt_hip_scene_desc *d, const TextureTable &table) {
           if (!std::isfinite(tx.tex1[k]) || !std::isfinite(tx.tex2[k])) return fail(PBRT_HIP_ERR_INVALID, "scene_create: texture colour is not finite");
         break;
       }
+      case SlotKind::kSpot: break;  // (a cone is checked with the lights, check_light_kinds)
       default: return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown texture type");
     }
     if (rc) return rc;
@@ -334,7 +377,8 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
   if ((rc = check_kd_tex(d, *table)) || (rc = check_table(d, *table)) || (rc = check_flags(flags, builder)) || (rc = check_sphere_boxes(d))) return rc;
   if ((rc = check_light_kinds(d, *table))) return rc;
   if ((rc = check_material_kinds(d))) return rc;
-  return check_plastic_family(d, *table);
+  if ((rc = check_plastic_family(d, *table))) return rc;
+  return check_spot_family(d, *table);
 }
 
 // What a checked description puts on the device, assembled on the host.
@@ -361,6 +405,7 @@ struct SceneInputs {
   float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
   float le_inf[3] = {0.f, 0.f, 0.f};
   bool has_inf = false;
+  bool has_spot = false;  // a spot light: the scene needs the GLS instantiations
 };
 void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, SceneInputs *in) {
   auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
@@ -386,10 +431,18 @@ void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, Scen
   // light table: explicit lights, then every emissive triangle in index order
   for (uint32_t i = 0; i < d.n_lights; i++) {
     const pbrt_hip_light &l = d.lights[i];
-    // (type 3 of the boundary, the environment map, is 4 in this table: 3 is an emissive triangle here -- kernel_path.hpp kDevLightEnv)
+    // (type 3 of the boundary, the environment map, is 4 in this table: 3 is an emissive triangle here -- kernel_path.hpp kDevLightEnv;
+    // a spot light keeps its 5, kDevLightSpot, with the cone in the rows a point light leaves free: DESIGN.md 3.22)
     in->lights.push_back(make_float4(as_f(l.type == PBRT_HIP_LIGHT_ENVMAP ? 4u : l.type), l.p[0], l.p[1], l.p[2]));
-    in->lights.push_back(make_float4(0, 0, 0, 0));
-    in->lights.push_back(make_float4(0, 0, 0, 0));
+    if (l.type == PBRT_HIP_LIGHT_SPOT) {
+      const pbrt_hip_spot_cone &c = *table.cone(light_env_slot(l));
+      in->lights.push_back(make_float4(c.axis[0], c.axis[1], c.axis[2], c.cos_total));
+      in->lights.push_back(make_float4(c.cos_start, 0, 0, 0));
+      in->has_spot = true;
+    } else {
+      in->lights.push_back(make_float4(0, 0, 0, 0));
+      in->lights.push_back(make_float4(0, 0, 0, 0));
+    }
     in->lights.push_back(make_float4(l.c[0], l.c[1], l.c[2], 0));
     in->lights.push_back(make_float4(0, 0, 0, 0));
     if (l.type == 2) {
@@ -807,7 +860,7 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
     gather_inputs(*d, table, &in);
     s->n_prims = in.n_prims;
     s->textured = table.textured_tris || table.textured_sph;
-    s->glass = !in.glass.empty();
+    s->glass = !in.glass.empty() || in.has_spot;  // (a spot light is sampled under PLS, in the GLS instantiations: DESIGN.md 3.22)
     if ((rc = upload_inputs(s.get(), *d, table, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
     if (table.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
       HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));

@@ -5,9 +5,14 @@
 #include "image_lookup.hpp"
 #include "kernel_walk.hpp"
 #include "plastic_bsdf.hpp"
+#include "spot_light.hpp"
 
 namespace pbrt_hip {
 namespace {
+
+// the light table's type word of a spot light: position in row 0, {axis, cos_total} in row 1, cos_start in row 2, I in
+// row 3 (capi_scene.cpp gather_inputs).  sample_light below knows nothing of it: a spot light is taken BEFORE that chain, under PLS
+constexpr uint32_t kDevLightSpot = 5u;
 
 // One light of UniformSampleOneLight.  false: geometry rules the light out.
 // mis: the estimate weighted with the power heuristic pl^2 / (pl^2 + pb^2), pl = this strategy's density for the
@@ -78,6 +83,21 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
   }
 }
 
+// A spot light at a matte vertex (spot_light.hpp): sample_light's outputs for light li, which the caller has found to be of
+// type kDevLightSpot.  Called under PLS alone -- the GLS instantiations of render_kernel_x --, so that sample_light and the instantiations
+// built from it keep their machine code.  A delta light: no MIS weight.
+__device__ __forceinline__ bool sample_light_spot(const DevScene &S, uint32_t li, V3 po, V3 nf, V3 kd, float nLf, V3 &Ld, V3 &wi, float &tmax) {
+  const float4 l0 = S.lights[5 * li];
+  const float4 l1 = S.lights[5 * li + 1];
+  const float4 l2 = S.lights[5 * li + 2];
+  const float4 l3 = S.lights[5 * li + 3];
+  const V3 f = kd * kInvPi;
+  float fall, scale;
+  if (!spot::sample(po, nf, mk(l0.y, l0.z, l0.w), xyz(l1), l1.w, l2.x, nLf, wi, tmax, fall, scale)) return false;
+  Ld = (f * xyz(l3)) * scale;
+  return true;
+}
+
 // sample_light's sibling for a BSDF that is not Lambertian (the plastic material; called under PLS alone, so that
 // sample_light and the instantiations built from it keep their machine code): the same light from the same (u1, u2), WITHOUT a BSDF
 // factor and without a MIS weight -- Lg = Li cos_i nL / pdf_l, the caller multiplies by f(wo, wi) -- and pl = the density that MIS
@@ -115,6 +135,14 @@ __device__ __forceinline__ bool sample_light_general(const DevScene &S, uint32_t
     Lg = (lc * envmap::kPi) * nLf;
     pl = (z * kInvPi) / nLf;
     tmax = kInf;
+    return true;
+  } else if (type == kDevLightSpot) {
+    // a spot light: the point light with the cone's falloff, a delta light like it (pl stays 0)
+    const float4 l1 = S.lights[5 * li + 1];
+    const float4 l2 = S.lights[5 * li + 2];
+    float fall, scale;
+    if (!spot::sample(po, nf, p0, xyz(l1), l1.w, l2.x, nLf, wi, tmax, fall, scale)) return false;
+    Lg = lc * scale;
     return true;
   } else {
     // an emissive triangle (device type 3; the environment map's type 4 never arrives: a scene with plastic and a map is refused)

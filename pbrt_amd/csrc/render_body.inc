@@ -243,6 +243,13 @@
                     if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
                   }
                 } else
+                if (PLS && __float_as_uint(S.lights[5 * li].x) == kDevLightSpot) {  // a spot light (3.22): taken before sample_light's chain, which does not know it
+                  if (sample_light_spot(S, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)) {
+                    need_shadow = true;
+                    lpend = P.beta * Ld;
+                    if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
+                  }
+                } else
                 if (sample_light(S, li, po, nsh, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS) && (!(NRM && smooth) || dot(sh_d, nf) > 0.f)) {
                   need_shadow = true;
                   lpend = P.beta * Ld;

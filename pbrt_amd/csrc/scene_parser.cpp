@@ -283,6 +283,9 @@ struct Api {
   bool warned_object_light = false;
   bool any_normals = false;           // some mesh of the file carried normals: the scene gets a pbrt_hip_normals record
   bool warned_glass_normals = false;  // (said once per file)
+  // LightSource "spot" (DESIGN.md 3.22): the cones, in the order of their lights.  A spot light's `pad` holds its cone's 1-based place HERE
+  // until the file has been read; parse_scene then appends the cones to the texture table and writes the slots' numbers
+  std::vector<pbrt_hip_spot_cone> spot_cones;
   // instancing multiplies geometry (instances x the object's triangles): a bound on what a small file can ask for (the tests lower it)
   const size_t kMaxSceneTriangles = [] {
     const char *on = std::getenv("PBRT_HIP_DEBUG_KNOBS"), *v = std::getenv("PBRT_HIP_MAX_SCENE_TRIANGLES");
@@ -816,8 +819,72 @@ struct Api {
       // warning and the constant L x scale (infinite.rs:56-58)
       const std::string map = ps.one_string("mapname", "");
       if (!map.empty()) environment_map(map, &l);
+    } else if (name == "spot") {
+      // DESIGN.md 3.22 (pbrt-v3 CreateSpotLight): the position through the CTM as a point, the axis to - from as a vector, the two cosines
+      // from the angles in double.  The cone is evaluated in WORLD space; pbrt-v3 evaluates it in light space, and the two agree for a CTM
+      // that is a similarity
+      float I[3] = {1, 1, 1}, from[3] = {0, 0, 0}, to[3] = {0, 0, 1}, p[3];
+      spectrum(ps, "I", I);
+      ps.point3("from", from);
+      ps.point3("to", to);
+      float cone = ps.one_float("coneangle", 30.f), delta = ps.one_float("conedeltaangle", 5.f);
+      if (cone > 180.f) {
+        warn("LightSource \"spot\": coneangle " + std::to_string(cone) + " lies outside (0, 180], clamped to 180");
+        cone = 180.f;
+      } else if (!(cone > 0.f)) {  // (the interval is open at 0: there is no nearest value, the default stands in)
+        warn("LightSource \"spot\": coneangle " + std::to_string(cone) + " lies outside (0, 180], clamped to the default 30");
+        cone = 30.f;
+      }
+      if (!(delta >= 0.f && delta <= cone)) {
+        const float c = delta > cone ? cone : 0.f;
+        warn("LightSource \"spot\": conedeltaangle " + std::to_string(delta) + " lies outside [0, coneangle], clamped to " + std::to_string(c));
+        delta = c;
+      }
+      // (in double from the float CTM and rounded once: the position and the axis are within an ulp of the exact products)
+      const float *cm = ctm[0].m;
+      double d[3], w[3], hw = (double)cm[12] * from[0] + (double)cm[13] * from[1] + (double)cm[14] * from[2] + (double)cm[15];
+      if (!(hw != 0.0)) hw = 1.0;
+      for (int i = 0; i < 3; i++) d[i] = (double)to[i] - (double)from[i];
+      for (int i = 0; i < 3; i++) {
+        p[i] = (float)(((double)cm[4 * i] * from[0] + (double)cm[4 * i + 1] * from[1] + (double)cm[4 * i + 2] * from[2] + (double)cm[4 * i + 3]) / hw);
+        w[i] = (double)cm[4 * i] * d[0] + (double)cm[4 * i + 1] * d[1] + (double)cm[4 * i + 2] * d[2];
+      }
+      const double len = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+      if (!(len > 0.0) || !std::isfinite(len)) {
+        warn("LightSource \"spot\": \"from\" and \"to\" are the same point (or the axis is not finite): the light has no direction and is skipped");
+        report_unused("LightSource", ps);
+        return;
+      }
+      {  // the CTM's linear part: a similarity has orthogonal columns of equal length (to 1e-4, relative)
+        const float *m = ctm[0].m;
+        double col[3][3], n2[3], worst = 0.0;
+        for (int j = 0; j < 3; j++) {
+          for (int i = 0; i < 3; i++) col[j][i] = m[4 * i + j];
+          n2[j] = col[j][0] * col[j][0] + col[j][1] * col[j][1] + col[j][2] * col[j][2];
+        }
+        const double s2 = (n2[0] + n2[1] + n2[2]) / 3.0;
+        for (int j = 0; j < 3; j++) {
+          worst = std::max(worst, std::fabs(std::sqrt(n2[j]) - std::sqrt(s2)) / std::sqrt(s2));
+          const int k = (j + 1) % 3;
+          worst = std::max(worst, std::fabs(col[j][0] * col[k][0] + col[j][1] * col[k][1] + col[j][2] * col[k][2]) / s2);
+        }
+        if (!(worst <= 1e-4))
+          warn("LightSource \"spot\": the transformation scales unevenly or shears; the cone is evaluated in world space about the transformed axis, "
+               "where pbrt-v3 evaluates it in the light's own space (the two agree for rotations, translations and uniform scales)");
+      }
+      pbrt_hip_spot_cone c{};
+      for (int i = 0; i < 3; i++) c.axis[i] = (float)(w[i] / len);
+      const double rad = 3.14159265358979323846 / 180.0;
+      c.cos_total = (float)std::cos((double)cone * rad);
+      c.cos_start = (float)std::cos(((double)cone - (double)delta) * rad);
+      if (c.cos_total > c.cos_start) c.cos_start = c.cos_total;  // (delta = 0: the same double either way; kept for a libm that is not monotone)
+      spot_cones.push_back(c);
+      const uint32_t pending = (uint32_t)spot_cones.size();  // (1-based, into spot_cones: parse_scene turns it into the slot's number)
+      l.type = PBRT_HIP_LIGHT_SPOT;
+      std::memcpy(&l.pad, &pending, 4);
+      for (int i = 0; i < 3; i++) { l.p[i] = p[i]; l.c[i] = I[i] * scale[i]; }
     } else {
-      warn("light_source: light type '" + name + "' unknown.");  // api.rs:692 (spot, goniometric, projection: not on this path either)
+      warn("light_source: light type '" + name + "' unknown.");  // api.rs:692 (goniometric, projection: not on this path either)
       return;
     }
     out->lights.push_back(l);
@@ -1277,6 +1344,32 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
   }
   // a weighted pixel filter's record takes a slot of the texture table; a file without one keeps the description it always had
   if (out->pixel_filter.type == PBRT_HIP_TEXTURE_FILTER) out->textures.push_back(write_slot(out->pixel_filter));
+  // the spot lights' cones are appended behind every slot a material or the map's light names -- no number moves -- and
+  // before the normals' record, which stays last.  A scene with an environment map is rendered by a family without the spot branch, and
+  // scene creation refuses the pair: the file's spot lights are dropped, and said so, so that a loaded file is one scene creation takes
+  if (!api.spot_cones.empty() && !out->env_rgb.empty()) {
+    api.warn("a scene with an environment map (\"mapname\"): its " + std::to_string(api.spot_cones.size()) + " spot light(s) are ignored");
+    std::vector<pbrt_hip_light> kept;
+    for (const pbrt_hip_light &l : out->lights)
+      if (l.type != PBRT_HIP_LIGHT_SPOT) kept.push_back(l);
+    out->lights.swap(kept);
+    api.spot_cones.clear();
+  }
+  if (!api.spot_cones.empty()) {
+    const uint32_t first = (uint32_t)out->textures.size();  // (0-based slot of cone 0)
+    for (const pbrt_hip_spot_cone &c : api.spot_cones) out->textures.push_back(write_slot(c));
+    for (pbrt_hip_light &l : out->lights) {
+      if (l.type != PBRT_HIP_LIGHT_SPOT) continue;
+      uint32_t number;
+      std::memcpy(&number, &l.pad, 4);
+      number += first;
+      std::memcpy(&l.pad, &number, 4);
+    }
+    if (api.any_normals) {  // (the same family rule as plastic's, below)
+      api.warn("a scene with a \"spot\" light: the meshes' normals \"N\" are ignored (every mesh renders flat)");
+      api.any_normals = false;
+    }
+  }
   // shading normals travel only when some mesh has them: then their record is the LAST slot of the texture table; a file
   // without them keeps the description it always had
   if (api.any_normals) {  // (plastic reflects about the geometric normal, and a scene with plastic takes no normals record: DESIGN.md 3.21)

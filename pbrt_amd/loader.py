@@ -6,9 +6,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (SLOT_ENVMAP, SLOT_FILTER, SLOT_IMAGE, SLOT_NORMALS, EnvMap, ImageTexture, Normals, PixelFilter, RenderDesc, SceneDesc, check, lib,
-                   read_slot)
-from .api import GLASS, PLASTIC, SceneData
+from ._lib import (SLOT_ENVMAP, SLOT_FILTER, SLOT_IMAGE, SLOT_NORMALS, SLOT_SPOT, EnvMap, ImageTexture, Normals, PixelFilter, RenderDesc, SceneDesc,
+                   SpotCone, check, lib, read_slot)
+from .api import GLASS, LIGHT_SPOT, PLASTIC, SceneData
 
 
 @dataclass
@@ -52,7 +52,7 @@ def _collect(h):
         def first(kind, cls):
             return read_slot(d.textures, slots[kind][0], cls) if kind in slots else None
 
-        tex_slots = sorted(i for kind, at in slots.items() if kind not in (SLOT_ENVMAP, SLOT_NORMALS, SLOT_FILTER) for i in at)
+        tex_slots = sorted(i for kind, at in slots.items() if kind not in (SLOT_ENVMAP, SLOT_NORMALS, SLOT_FILTER, SLOT_SPOT) for i in at)
         renum = {0: 0, **{i + 1: k + 1 for k, i in enumerate(tex_slots)}}
         e, nr, pf = first(SLOT_ENVMAP, EnvMap), first(SLOT_NORMALS, Normals), first(SLOT_FILTER, PixelFilter)
         envmap = arr(e.rgb, 3 * e.width * e.height, np.float32).reshape(e.height, e.width, 3) if e else np.zeros((0, 0, 3), np.float32)
@@ -70,7 +70,14 @@ def _collect(h):
             return [SLOT_IMAGE, len(images) - 1, im.wrap, im.filter, 0, 0, 0, im.su, im.sv, im.du, im.dv]
 
         tex_rows = [tex_row(i) for i in tex_slots]
+        # a spot light's `pad` holds the bits of its cone's slot number: the cones in the order of their lights
+        cones = []
+        for i in range(d.n_lights):
+            if d.lights[i].type == LIGHT_SPOT:
+                c = read_slot(d.textures, int(np.array([d.lights[i].pad], np.float32).view(np.uint32)[0]) - 1, SpotCone)
+                cones.append([*c.axis, c.cos_total, c.cos_start])
         sd = SceneData(
+            spot_cones=np.array(cones, np.float32).reshape(-1, 5),
             images=images, pixel_filter=pixel_filter, tri_n=tri_n, envmap=envmap, envmap_world_to_light=env_m,
             P=arr(d.P, 3 * d.n_verts, np.float32).reshape(-1, 3), idx=arr(d.idx, 3 * d.n_tris, np.uint32).reshape(-1, 3),
             mat_id=arr(d.mat_id, d.n_tris, np.uint16),

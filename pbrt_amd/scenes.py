@@ -7,6 +7,7 @@
   cornell_scene       C4: Cornell-style box
   glass_sphere_scene  a glass sphere and a glass cube in a Cornell-style box (= scenes/glass_sphere.pbrt)
   plastic_scene       a plastic floor and two plastic spheres in a Cornell-style box (= scenes/plastic_spheres.pbrt)
+  spot_scene          a plastic and a matte sphere in a Cornell-style box lit by two spot lights (= scenes/spot_cornell.pbrt)
   envmap_scene        a matte ground, a glass and a mirror sphere under an environment map (= scenes/envmap_spheres.pbrt)
   icosphere_scene     C1 with its sphere tessellated, with or without shading normals
   smooth_mesh_scene   two octahedra with per-vertex normals over a flat ground (= scenes/smooth_mesh.pbrt)
@@ -316,6 +317,41 @@ def plastic_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), plastic=True, l
     return SceneData(
         P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
         materials=np.array(mats, np.float32), mat_eta=np.array(alpha if plastic else [], np.float32),
+        spheres=np.array([[-0.45, 0.15, -0.65, 0.35, BLUE], [0.45, -0.2, -0.65, 0.35, ORANGE]], np.float32),
+        cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
+    ).normalized()
+
+
+def spot_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0)):
+    """The spot light's scene, array for array what scenes/spot_cornell.pbrt loads to: the Cornell-style box [-1, 1]^3 open
+    towards the camera (white floor / ceiling / back wall, red left and green right walls) WITHOUT a ceiling emitter, a blue plastic sphere
+    and an orange matte sphere of radius 0.35 standing on the floor, and two spot lights under the ceiling: a warm one of half angle 35
+    degrees (the falloff over the outer 10) aimed at the floor in front of the matte sphere, and a cool one of half angle 20 degrees (the
+    outer 6) aimed at the plastic sphere -- so a matte vertex and a plastic vertex both sample a spot light."""
+    from .api import plastic_material, spot_light
+    WHITE, RED, GREEN, BLUE, ORANGE = range(5)  # (numbered in the order the scene file's shapes first use them)
+    blue, alpha = plastic_material((0.1, 0.2, 0.6), (0.3, 0.3, 0.3), 0.1)
+    mats = [_mat(MATTE, (0.73, 0.73, 0.73)), _mat(MATTE, (0.65, 0.05, 0.05)), _mat(MATTE, (0.12, 0.45, 0.15)), blue, _mat(MATTE, (0.6, 0.3, 0.05))]
+    V, I, M = [], [], []
+
+    def add(q, m):
+        base = len(V)
+        v, t = _quad(*q)
+        V.extend(v)
+        I.extend([[base + a for a in tri] for tri in t])
+        M.extend([m, m])
+
+    add(((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1)), WHITE)  # floor
+    add(((-1, -1, 1), (-1, 1, 1), (1, 1, 1), (1, -1, 1)), WHITE)      # ceiling
+    add(((-1, 1, -1), (1, 1, -1), (1, 1, 1), (-1, 1, 1)), WHITE)      # back wall (y = +1)
+    add(((-1, -1, -1), (-1, 1, -1), (-1, 1, 1), (-1, -1, 1)), RED)    # left
+    add(((1, -1, -1), (1, -1, 1), (1, 1, 1), (1, 1, -1)), GREEN)      # right
+    lights, cones = zip(spot_light((0.5, -0.3, 0.95), (0.4, -0.45, -1.0), (6.0, 5.5, 4.5), 35.0, 10.0),
+                        spot_light((-0.7, -0.6, 0.9), (-0.45, 0.15, -0.65), (5.0, 5.0, 6.0), 20.0, 6.0))
+    return SceneData(
+        P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
+        materials=np.array(mats, np.float32), mat_eta=np.array([1.5, 1.5, 1.5, alpha, 1.5], np.float32),
+        lights=np.array(lights, np.float32), spot_cones=np.array(cones, np.float32),
         spheres=np.array([[-0.45, 0.15, -0.65, 0.35, BLUE], [0.45, -0.2, -0.65, 0.35, ORANGE]], np.float32),
         cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
     ).normalized()

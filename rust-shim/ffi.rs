@@ -24,6 +24,10 @@ pub const LIGHT_ENVMAP: u32 = 3;
 // pbrt_hip_envmap: what a slot of `textures` IS when its first word is 1 -- 64 bytes like HipTexture; copy it into the slot with ptr::copy_nonoverlapping
 // (HipTexture is 4-aligned, this record holds a pointer).  rgb: 3 * width * height floats, row 0 = the light's +z, copied during scene_create
 #[repr(C)] pub struct HipEnvMap   { pub kind: u32 /* = 1 */, pub width: u32, pub height: u32, pub reserved: u32, pub rgb: *const f32, pub world_to_light: [f32; 9], pub pad: u32 }
+// kind == LIGHT_SPOT (5): p = the position, c = I * scale; pad = f32::from_bits(n), n = the 1-based number of the slot of `textures` that
+// holds the light's cone, a pbrt_hip_spot_cone (first word 6): a unit axis from the light into the cone, cos_total <= cos_start
+pub const LIGHT_SPOT: u32 = 5;
+#[repr(C)] pub struct HipSpotCone { pub kind: u32 /* = 6 */, pub axis: [f32; 3], pub cos_total: f32, pub cos_start: f32, pub pad: [u32; 10] }
 #[repr(C)] pub struct HipSphere   { pub c: [f32; 3], pub r: f32, pub mat: u32, pub pad: [u32; 3] }
 #[repr(C)] pub struct HipSceneDesc {
     pub p: *const f32, pub idx: *const u32, pub mat_id: *const u16,

@@ -80,7 +80,8 @@ typedef struct {
 typedef struct {
   uint32_t type;  /* 0 = checkerboard, dimension 2, "uv" mapping; 1 = this slot is the environment-map record below; 2 = the shading
                      normals' record, pbrt_hip_normals; 3 = the pixel filter's record, pbrt_hip_pixel_filter; 4 = an image texture's
-                     record, pbrt_hip_image_texture; 6 = a spot light's cone, pbrt_hip_spot_cone */
+                     record, pbrt_hip_image_texture; 6 = a spot light's cone, pbrt_hip_spot_cone; 8 = a mapped light's record,
+                     pbrt_hip_light_map */
   float tex1[3], tex2[3];
   float su, sv, du, dv; /* "float uscale" / "vscale" / "udelta" / "vdelta" */
   uint32_t pad[5];
@@ -223,11 +224,46 @@ typedef struct {
   float cos_start; /* cosine of the angle at which the falloff starts: full intensity inside; >= cos_total */
   uint32_t pad[10];
 } pbrt_hip_spot_cone;
+/* LightSource "projection" / "goniometric" (pbrt-v3's ProjectionLight and GonioPhotometricLight): type 6 -- 4 and 7 stay
+ * unknown light types --, a point light at p with intensity c = I, multiplied by an image looked up in the direction from the light to
+ * the shaded point.  `pad` = the BITS of the 1-based number of a type-8 slot of `textures`, a pbrt_hip_light_map record:
+ *   kind            0 projection, 1 goniometric
+ *   image           the 1-based number of a type-4 slot (pbrt_hip_image_texture): its texels, wrap and filter serve the light; its su sv du dv
+ *                   are ignored.  A material may name the same slot
+ *   world_to_light  a row-major rotation, as pbrt_hip_envmap has it
+ *   inv_tan, sx, sy projection: 1 / tan(fov / 2) and the half extents of the screen window; goniometric: all three 0
+ * With wi the unit direction from the shaded point towards the light, d = -wi and w = world_to_light d:
+ *   projection   (the light looks along its +z) no light unless w.z > 1e-3; px = (w.x / w.z) inv_tan, py = (w.y / w.z) inv_tan; no light
+ *                unless -sx <= px <= sx and -sy <= py <= sy; (s, t) = ((px + sx) / (2 sx), (py + sy) / (2 sy))
+ *   goniometric  (the light's +y is the pole, pbrt-v3's swap of y and z) theta = acos(clamp(w.y, -1, 1)), phi = atan2(w.z, w.x) in
+ *                [0, 2 pi); (s, t) = (phi / 2 pi, 1 - theta / pi)
+ * and the light is the point light times the image at (s, t), t = 0 the image's BOTTOM row: the file's top row is the light's +y of a
+ * projection and the +y pole of a goniometric map (a deliberate choice: DESIGN.md 3.23).  No sample where all three channels are 0.  A delta
+ * light: MIS weight 1, never hit by a ray.  Several lights may share a record.  Refused at scene creation before any device work
+ * (PBRT_HIP_ERR_INVALID, the message holds "light map"): a type-6 light whose `pad` names no type-8 slot; a kind other than 0 or 1; an
+ * `image` that names no type-4 slot; a world_to_light that is not finite or off orthonormal by more than 1e-4; projection: inv_tan, sx or
+ * sy not finite or not > 0; goniometric: any of the three not 0; a matte kd_tex that names a type-8 slot.  A record no light names is held
+ * to the same rules.  Rendered by the kernels that render glass, plastic and spot lights (the GLS instantiations of render_kernel_x), for
+ * every integrator, sampler and filter; NOT in a scene whose texture table holds an environment map (slot type 1) or shading normals (slot
+ * type 2): PBRT_HIP_ERR_LIMIT (the message holds "light map").  Not with the counter flags (PBRT_HIP_ERR_LIMIT at render, as for glass). */
+#define PBRT_HIP_LIGHT_MAPPED 6u
+#define PBRT_HIP_TEXTURE_LIGHT_MAP 8u /* (slot types 5 and 7 stay unknown texture types) */
+#define PBRT_HIP_LIGHT_MAP_PROJECTION 0u
+#define PBRT_HIP_LIGHT_MAP_GONIOMETRIC 1u
 typedef struct {
-  uint32_t type; /* 0 point, 1 distant, 2 infinite with constant radiance, 3 infinite with an environment map, 5 spot */
-  float p[3];    /* point, spot: position; distant: unit direction TOWARDS the light */
-  float c[3];    /* point, spot: intensity I; distant / infinite: radiance L; 3: the factor on the texels */
-  float pad;     /* 3: the bits of the texture-table number (1-based) of the pbrt_hip_envmap; 5: of the pbrt_hip_spot_cone */
+  uint32_t type;  /* = 8 */
+  uint32_t kind;  /* PBRT_HIP_LIGHT_MAP_* */
+  uint32_t image; /* 1-based number of a type-4 slot */
+  float world_to_light[9];
+  float inv_tan, sx, sy;
+  uint32_t pad[1];
+} pbrt_hip_light_map;
+typedef struct {
+  uint32_t type; /* 0 point, 1 distant, 2 infinite with constant radiance, 3 infinite with an environment map, 5 spot, 6 mapped */
+  float p[3];    /* point, spot, mapped: position; distant: unit direction TOWARDS the light */
+  float c[3];    /* point, spot, mapped: intensity I; distant / infinite: radiance L; 3: the factor on the texels */
+  float pad;     /* 3: the bits of the texture-table number (1-based) of the pbrt_hip_envmap; 5: of the pbrt_hip_spot_cone; 6: of the
+                    pbrt_hip_light_map */
 } pbrt_hip_light;
 
 /* Shape "sphere" (check-sphere.pbrt:22), world space.  A primitive of the BVH like a triangle (primitive number n_tris + index, which is
@@ -315,7 +351,8 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.11 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9 and 0.10)": 0.11 = material type 3, plastic, inside
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.12 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10 and 0.11)": 0.12 = light type 6, a mapped light, and
+                                       texture-table slot type 8, its record, inside the same struct sizes; 0.11 = material type 3, plastic, inside
                                        the same struct sizes; 0.10 = texture-table slot type 4, the
                                        image texture, inside the same struct sizes; 0.9 = texture-table slot type 3, the pixel
                                        filter, likewise; 0.8 = texture-table slot type 2, the shading normals,

@@ -221,6 +221,16 @@ int pbrt_hip_plastic_eval_device(int device, int64_t n, const float *in, float *
 #define PBRT_HIP_SPOT_EVAL_OUT 7
 int pbrt_hip_spot_eval_device(int device, int64_t n, const float *in, float *out);
 
+/* ---- a mapped light's sample (pbrt_amd/csrc/light_map.hpp is the one statement of the arithmetic) ---- */
+/* light_map.hpp over arrays on `device` (a small kernel of kernels_blocks.hip) for ONE light-map record and the image it reads (the
+ * record's own `image` number is not used): element i reads 10 floats of `in` -- the shading point po, its normal nf, the light's position
+ * p, nL (the scene's light count as a float) -- and writes 11 floats of `out`: ok (1 or 0), wi.xyz, tmax, scale = (cos / dist^2) nL, the
+ * image coordinates s, t, and the image's rgb there (the last ten are zero where ok is).  in / out are HOST arrays.  Both records are checked
+ * as scene creation checks them (PBRT_HIP_ERR_INVALID / _LIMIT); PBRT_HIP_ERR_INVALID for a negative n or a null pointer. */
+#define PBRT_HIP_LIGHT_MAP_EVAL_IN 10
+#define PBRT_HIP_LIGHT_MAP_EVAL_OUT 11
+int pbrt_hip_light_map_eval_device(int device, const pbrt_hip_image_texture *image, const pbrt_hip_light_map *map, int64_t n, const float *in, float *out);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

@@ -43,11 +43,18 @@ class SpotCone(C.Structure):
     _fields_ = [("type", C.c_uint32), ("axis", C.c_float * 3), ("cos_total", C.c_float), ("cos_start", C.c_float), ("pad", C.c_uint32 * 10)]
 
 
-# the first word of a slot of the texture table: which of the six record classes above the slot IS (5 is no record)
+class LightMap(C.Structure):
+    """pbrt_hip_light_map: what a slot of the texture table IS when its first word is 8; 64 bytes like Texture"""
+    _fields_ = [("type", C.c_uint32), ("kind", C.c_uint32), ("image", C.c_uint32), ("world_to_light", C.c_float * 9), ("inv_tan", C.c_float), ("sx", C.c_float),
+                ("sy", C.c_float), ("pad", C.c_uint32 * 1)]
+
+
+# the first word of a slot of the texture table: which of the seven record classes above the slot IS (5 and 7 are no record)
 SLOT_CHECKER, SLOT_ENVMAP, SLOT_NORMALS, SLOT_FILTER, SLOT_IMAGE = range(5)
 SLOT_SPOT = 6
+SLOT_LIGHT_MAP = 8
 SLOT_BYTES = C.sizeof(Texture)
-assert all(C.sizeof(cls) == SLOT_BYTES == 64 for cls in (EnvMap, Normals, PixelFilter, ImageTexture, SpotCone))
+assert all(C.sizeof(cls) == SLOT_BYTES == 64 for cls in (EnvMap, Normals, PixelFilter, ImageTexture, SpotCone, LightMap))
 
 
 def put_slot(table, i, rec):
@@ -182,6 +189,7 @@ SYMBOLS = {
     "pbrt_hip_blocks_eval_device": (C.c_int, [C.c_int, _u32, _i64, _pf, _pf]),
     "pbrt_hip_plastic_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
     "pbrt_hip_spot_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
+    "pbrt_hip_light_map_eval_device": (C.c_int, [C.c_int, C.POINTER(ImageTexture), C.POINTER(LightMap), _i64, _pf, _pf]),
     "pbrt_hip_shading_normal_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
 }
 

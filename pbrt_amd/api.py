@@ -9,13 +9,15 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import EnvMap, ImageTexture, Light, Material, Normals, PixelFilter, RenderDesc, SceneDesc, Sphere, SpotCone, Stats, Texture, check, lib
+from ._lib import EnvMap, ImageTexture, Light, LightMap, Material, Normals, PixelFilter, RenderDesc, SceneDesc, Sphere, SpotCone, Stats, Texture, check, lib
 
 MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
 PLASTIC = 3  # PBRT_HIP_MATERIAL_PLASTIC: DESIGN.md 3.21
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
 LIGHT_ENVMAP = 3  # PBRT_HIP_LIGHT_ENVMAP: the infinite light with an environment map
 LIGHT_SPOT = 5  # PBRT_HIP_LIGHT_SPOT: a point light inside a cone with a smooth edge; 4 is no light type
+LIGHT_MAPPED = 6  # PBRT_HIP_LIGHT_MAPPED: a point light times an image looked up in the direction from the light; 7 is no light type
+LIGHT_MAP_PROJECTION, LIGHT_MAP_GONIOMETRIC = 0, 1  # PBRT_HIP_LIGHT_MAP_*: a light map's kind
 INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_PATH_MIS = 0, 1, 2  # 2: the path integrator with MIS
 FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_SINC = 1, 2, 3, 4  # PBRT_HIP_FILTER_*: the weighted pixel filters
 FILTER_KINDS = {"triangle": FILTER_TRIANGLE, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL, "sinc": FILTER_SINC}
@@ -63,7 +65,10 @@ class SceneData:
     TEXFILTER_* --, which fill_desc turns into the pbrt_hip_image_texture record of the same slot (image_texture_row makes one).  Spot lights
     (DESIGN.md 3.22): a `lights` row (LIGHT_SPOT, position, I rgb) and `spot_cones` rows (axis xyz -- unit, from the light into the cone --,
     cos_total, cos_start), the k-th row the cone of the k-th LIGHT_SPOT row (spot_light makes the pair); each cone travels in a slot of its own
-    behind the filter's and before the normals'."""
+    behind the filter's and before the normals'.  Mapped lights: a `lights` row (LIGHT_MAPPED, position, I rgb) and `light_maps`
+    rows of 14 (kind, the 1-based number of a TEXTURE_IMAGE row of `textures`, world_to_light[9] row-major, inv_tan, sx, sy), the k-th row the
+    record of the k-th LIGHT_MAPPED row (projection_light / goniometric_light make the pair); each record travels in a slot of its own behind
+    the cones."""
     P: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
     idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.uint32))
     mat_id: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint16))
@@ -85,6 +90,7 @@ class SceneData:
     pixel_filter: tuple = None
     images: list = field(default_factory=list)
     spot_cones: np.ndarray = field(default_factory=lambda: np.zeros((0, 5), np.float32))
+    light_maps: np.ndarray = field(default_factory=lambda: np.zeros((0, 14), np.float32))
 
     def normalized(self):
         self.images = [np.ascontiguousarray(im, np.float32) for im in self.images]
@@ -113,6 +119,7 @@ class SceneData:
         self.envmap_world_to_light = np.ascontiguousarray(self.envmap_world_to_light, np.float32).reshape(3, 3)
         self.tri_n = np.ascontiguousarray(self.tri_n, np.float32).reshape(-1, 9)
         self.spot_cones = np.ascontiguousarray(self.spot_cones, np.float32).reshape(-1, 5)
+        self.light_maps = np.ascontiguousarray(self.light_maps, np.float32).reshape(-1, 14)
         assert self.idx.shape[0] == self.mat_id.shape[0] and self.tri_uv.shape[0] in (0, self.idx.shape[0])
         assert self.tri_n.shape[0] in (0, self.idx.shape[0])
         return self
@@ -137,8 +144,8 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         if int(m[0]) == PLASTIC:  # k = Kd, le = Ks, kd_tex = the IEEE-754 bits of alpha
             mats[i].kd_tex = int(sd.mat_eta[i:i + 1].view(np.uint32)[0]) if len(sd.mat_eta) else 0  # (no alpha given: 0, which scene creation refuses)
     # the table: every `textures` row in its own slot (mat_tex numbering does not move), then the records that travel with the scene, each in a
-    # slot of its own -- the map's, the pixel filter's, the spot lights' cones, the normals' (include/pbrt_hip.h pbrt_hip_envmap / _pixel_filter /
-    # _spot_cone / _normals), in this order
+    # slot of its own -- the map's, the pixel filter's, the spot lights' cones, the mapped lights' records, the normals' (include/pbrt_hip.h
+    # pbrt_hip_envmap / _pixel_filter / _spot_cone / _light_map / _normals), in this order
     records = [image_record(sd.images[int(t[1])], int(t[2]), int(t[3]), t[7:11]) if int(t[0]) == TEXTURE_IMAGE else checker_record(t) for t in sd.textures]
     has_env = sd.envmap.size > 0
     if has_env:
@@ -149,6 +156,10 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
     first_cone = len(records)  # (0-based slot of cone 0)
     for c in sd.spot_cones:
         records.append(SpotCone(type=_lib.SLOT_SPOT, axis=tuple(float(x) for x in c[0:3]), cos_total=float(c[3]), cos_start=float(c[4])))
+    first_map = len(records)  # (0-based slot of light map 0)
+    for m in sd.light_maps:
+        records.append(LightMap(type=_lib.SLOT_LIGHT_MAP, kind=int(m[0]), image=int(m[1]), world_to_light=tuple(float(x) for x in m[2:11]), inv_tan=float(m[11]),
+                                sx=float(m[12]), sy=float(m[13])))
     if sd.tri_n.shape[0]:
         records.append(Normals(type=_lib.SLOT_NORMALS, n_tris=sd.tri_n.shape[0], tri_n=_fp(sd.tri_n)))
     texs = None
@@ -162,7 +173,7 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
     if sd.tri_uv.shape[0]:
         desc.tri_uv = _fp(sd.tri_uv)
     lights = (light_t * max(len(sd.lights), 1))()
-    n_spot = 0
+    n_spot = n_mapped = 0
     for i, l in enumerate(sd.lights):
         lights[i].type = int(l[0])
         lights[i].p[:] = [float(x) for x in l[1:4]]
@@ -172,6 +183,9 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         if int(l[0]) == LIGHT_SPOT:  # `pad` = the bits of the 1-based number of its cone's slot (0: `spot_cones` has no row for it -- refused)
             lights[i].pad = float(np.array([first_cone + n_spot + 1 if n_spot < len(sd.spot_cones) else 0], np.uint32).view(np.float32)[0])
             n_spot += 1
+        if int(l[0]) == LIGHT_MAPPED:  # likewise, of its record's slot
+            lights[i].pad = float(np.array([first_map + n_mapped + 1 if n_mapped < len(sd.light_maps) else 0], np.uint32).view(np.float32)[0])
+            n_mapped += 1
     spheres = (sphere_t * max(len(sd.spheres), 1))()
     for i, s in enumerate(sd.spheres):
         spheres[i].c[:] = [float(x) for x in s[0:3]]
@@ -225,6 +239,48 @@ def spot_light(p, to, I=(1.0, 1.0, 1.0), coneangle=30.0, conedeltaangle=5.0):
     cone, delta = float(np.float32(coneangle)), float(np.float32(conedeltaangle))
     cos_total, cos_start = np.float32(math.cos(math.radians(cone))), np.float32(math.cos(math.radians(cone - delta)))
     return [LIGHT_SPOT, *p32, *I], [*axis, cos_total, max(cos_start, cos_total)]
+
+
+def _rotation9(world_to_light):
+    m = np.asarray(world_to_light, np.float32).reshape(-1)
+    assert m.shape == (9,)
+    return [float(x) for x in m]
+
+
+def projection_light(p, image, I=(1.0, 1.0, 1.0), fov=45.0, aspect=1.0, world_to_light=np.eye(3)):
+    """-> (the `lights` row (LIGHT_MAPPED, p, I), the `light_maps` row) of LightSource "projection" at `p` as the scene parser
+    forms them: `image` = the 1-based number of the TEXTURE_IMAGE row of `textures` it projects (the parser's: bilinear, wrap clamp), `aspect` =
+    that image's width / height, inv_tan = 1 / tan(fov / 2) from the float32 angle in double and rounded, the screen window pbrt-v3's.  The
+    light looks along the +z of its own frame with +y up; world_to_light is a rotation, row-major."""
+    import math
+    f = float(np.float32(fov))
+    if not (0.0 < f < 180.0):
+        f = 45.0
+    a = np.float32(aspect)
+    sx, sy = (a, np.float32(1.0)) if a > 1.0 else (np.float32(1.0), np.float32(1.0) / a)
+    return ([LIGHT_MAPPED, *np.asarray(p, np.float32), *I],
+            [LIGHT_MAP_PROJECTION, int(image), *_rotation9(world_to_light), np.float32(1.0 / math.tan(f * (math.pi / 360.0))), sx, sy])
+
+
+def goniometric_light(p, image, I=(1.0, 1.0, 1.0), world_to_light=np.eye(3)):
+    """-> (the `lights` row (LIGHT_MAPPED, p, I), the `light_maps` row) of LightSource "goniometric" at `p`: `image` = the
+    1-based number of the TEXTURE_IMAGE row of `textures` that is its latitude-longitude map (the parser's: bilinear, wrap repeat); the pole
+    is the +y of the light's own frame"""
+    return [LIGHT_MAPPED, *np.asarray(p, np.float32), *I], [LIGHT_MAP_GONIOMETRIC, int(image), *_rotation9(world_to_light), 0.0, 0.0, 0.0]
+
+
+def light_map_eval_device(x, image, light_map, wrap=WRAP_CLAMP, filter=TEXFILTER_BILINEAR, device=0):
+    """pbrt_hip_light_map_eval_device: csrc/light_map.hpp over arrays on the device.  x (n, 10): po, nf, p, nL; image (H, W, 3) float32 with
+    row 0 = its top, read with `wrap` and `filter`; light_map = a `light_maps` row (its image number is not used) -> (n, 11) float32: ok, wi,
+    tmax, scale = (cos / dist^2) nL, s, t, rgb; zeros behind ok = 0"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 10)
+    out = np.zeros((x.shape[0], 11), np.float32)
+    im = np.ascontiguousarray(image, np.float32)
+    rec = image_record(im, int(wrap), int(filter), (1.0, 1.0, 0.0, 0.0))
+    m = np.asarray(light_map, np.float32).reshape(14)
+    lm = LightMap(type=_lib.SLOT_LIGHT_MAP, kind=int(m[0]), image=1, world_to_light=tuple(float(v) for v in m[2:11]), inv_tan=float(m[11]), sx=float(m[12]), sy=float(m[13]))
+    check(lib().pbrt_hip_light_map_eval_device(int(device), C.byref(rec), C.byref(lm), x.shape[0], _fp(x), _fp(out)), "pbrt_hip_light_map_eval_device")
+    return out
 
 
 def spot_eval_device(x, device=0):

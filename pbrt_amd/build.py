@@ -106,8 +106,9 @@ DEMO_TEXTURES = os.path.join(HERE, "..", "scenes", "textures")
 
 def ensure_demo_textures():
     """scenes/textures/planks.png, the image scenes/textured_cornell.pbrt names, is a build product, not a committed file:
-    a generated pattern (scenes.procedural_planks) written by the library's own PNG writer, here, once the library exists."""
-    if os.path.exists(os.path.join(DEMO_TEXTURES, "planks.png")):
+    a generated pattern (scenes.procedural_planks) written by the library's own PNG writer, here, once the library exists.  So are
+    slide.png and gonio.pfm, the images of scenes/projector_cornell.pbrt."""
+    if all(os.path.exists(os.path.join(DEMO_TEXTURES, f)) for f in ("planks.png", "slide.png", "gonio.pfm")):
         return
     root = os.path.dirname(HERE)
     if root not in sys.path:  # (run as a script, `python pbrt_amd/build.py`, the package is not on the path yet)

@@ -187,9 +187,17 @@ int check_spot_cone(const pbrt_hip_spot_cone &c, const std::string &what) {
   if (c.cos_total > c.cos_start) return fail(PBRT_HIP_ERR_INVALID, what + "a spot light's cos_total must not exceed cos_start (the falloff starts inside the cone)");
   return PBRT_HIP_OK;
 }
+// a mapped light's record: light_map_check's rules, and an `image` that names an image texture's slot
+int check_light_map(const pbrt_hip_light_map &m, const TextureTable &table, const std::string &what) {
+  const int rc = light_map_check(m, what);
+  if (rc) return rc;
+  if (table.named(m.image) != SlotKind::kImage) return fail(PBRT_HIP_ERR_INVALID, what + "light map: `image` must name a type-4 slot of the texture table (1-based)");
+  return PBRT_HIP_OK;
+}
 int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   for (uint32_t i = 0; i < d->n_lights; i++)
-    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP && d->lights[i].type != PBRT_HIP_LIGHT_SPOT) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP && d->lights[i].type != PBRT_HIP_LIGHT_SPOT && d->lights[i].type != PBRT_HIP_LIGHT_MAPPED)
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
   // (a spot light and its cone are checked HERE, where the light's kind is recognised -- the place a type-5 light was refused as unknown
   // before there were spot lights --, so that every fault that used to win against it still does)
   for (uint32_t i = 0; i < d->n_lights; i++) {
@@ -202,6 +210,19 @@ int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   }
   for (const TextureTable::Cone &c : table.cones) {  // (a cone no light names is held to the same rules)
     const int rc = check_spot_cone(c.rec, "scene_create: texture slot " + std::to_string(c.slot + 1) + ": ");
+    if (rc) return rc;
+  }
+  // (a mapped light and its record likewise: DESIGN.md 3.23)
+  for (uint32_t i = 0; i < d->n_lights; i++) {
+    if (d->lights[i].type != PBRT_HIP_LIGHT_MAPPED) continue;
+    const std::string what = "scene_create: light " + std::to_string(i) + ": ";
+    const pbrt_hip_light_map *map = table.light_map(light_env_slot(d->lights[i]));
+    if (!map) return fail(PBRT_HIP_ERR_INVALID, what + "a mapped light (type 6) must name a type-8 slot of the texture table, its light map, in `pad`");
+    const int rc = check_light_map(*map, table, what);
+    if (rc) return rc;
+  }
+  for (const TextureTable::LightMap &m : table.light_maps) {  // (a record no light names is held to the same rules)
+    const int rc = check_light_map(m.rec, table, "scene_create: texture slot " + std::to_string(m.slot + 1) + ": ");
     if (rc) return rc;
   }
   uint32_t n_env = 0;
@@ -245,6 +266,7 @@ int check_kd_tex(const pbrt_hip_scene_desc *d, const TextureTable &table) {
       case SlotKind::kNormals: names = "the shading normals' record"; break;
       case SlotKind::kFilter: names = "the pixel filter's record"; break;
       case SlotKind::kSpot: names = "a spot light's cone"; break;
+      case SlotKind::kLightMap: names = "a light map's record"; break;
       default: break;
     }
     if (names) return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": kd_tex names " + names + ", which is not a texture for Kd");
@@ -295,6 +317,17 @@ int check_spot_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   }
   return PBRT_HIP_OK;
 }
+// a mapped light is sampled under PLS alone too
+int check_light_map_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
+  bool mapped = false;
+  for (uint32_t i = 0; i < d->n_lights && !mapped; i++) mapped = d->lights[i].type == PBRT_HIP_LIGHT_MAPPED;
+  if (!mapped) return PBRT_HIP_OK;
+  for (const SlotKind kind : table.kinds) {
+    if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a light map (a projection or goniometric light) is not available in a scene with an environment map");
+    if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a light map (a projection or goniometric light) is not available in a scene with shading normals");
+  }
+  return PBRT_HIP_OK;
+}
 
 // the records of the texture table in slot order, then the images' texels, then the (u, v) that textured triangles need
 int check_table(const pbrt_hip_scene_desc *d, const TextureTable &table) {
@@ -336,6 +369,7 @@ int check_table(const pbrt_hip_scene_desc *d, const TextureTable &table) {
         break;
       }
       case SlotKind::kSpot: break;  // (a cone is checked with the lights, check_light_kinds)
+      case SlotKind::kLightMap: break;  // (likewise)
       default: return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown texture type");
     }
     if (rc) return rc;
@@ -378,7 +412,8 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
   if ((rc = check_light_kinds(d, *table))) return rc;
   if ((rc = check_material_kinds(d))) return rc;
   if ((rc = check_plastic_family(d, *table))) return rc;
-  return check_spot_family(d, *table);
+  if ((rc = check_spot_family(d, *table))) return rc;
+  return check_light_map_family(d, *table);
 }
 
 // What a checked description puts on the device, assembled on the host.
@@ -397,7 +432,7 @@ struct SceneInputs {
   std::vector<uint16_t> mat_aug;
   std::vector<float4> lights, mats, spheres, textures;  // the kernels' records: 5, 2, 2 and 3 per light / material / sphere / texture
   std::vector<float4> glass;  // {Kt, eta} per material, when the scene has a glass one; else empty
-  std::vector<float4> image_texels;  // the texel pool of the image textures, when something is textured; else empty
+  std::vector<float4> image_texels;  // the texel pool of the image textures, when something is textured or a mapped light reads an image (3.23); else empty
   // an environment-map light: its tables, world_to_light and factor
   bool env = false;
   EnvTables env_tables;
@@ -406,6 +441,7 @@ struct SceneInputs {
   float le_inf[3] = {0.f, 0.f, 0.f};
   bool has_inf = false;
   bool has_spot = false;  // a spot light: the scene needs the GLS instantiations
+  bool has_mapped = false;  // a mapped light: likewise, and the texture rows and the texel pool go up for its image
 };
 void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, SceneInputs *in) {
   auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
@@ -432,8 +468,21 @@ void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, Scen
   for (uint32_t i = 0; i < d.n_lights; i++) {
     const pbrt_hip_light &l = d.lights[i];
     // (type 3 of the boundary, the environment map, is 4 in this table: 3 is an emissive triangle here -- kernel_path.hpp kDevLightEnv;
-    // a spot light keeps its 5, kDevLightSpot, with the cone in the rows a point light leaves free: DESIGN.md 3.22)
-    in->lights.push_back(make_float4(as_f(l.type == PBRT_HIP_LIGHT_ENVMAP ? 4u : l.type), l.p[0], l.p[1], l.p[2]));
+    // a spot light keeps its 5, kDevLightSpot, with the cone in the rows a point light leaves free: DESIGN.md 3.22; a mapped light is 6,
+    // kDevLightProjection, or 7, kDevLightGonio, by its record's kind, with {a row of world_to_light, inv_tan / sx / sy} in rows 1, 2 and 4 and
+    // the bits of its image slot's 0-based number in row 3's w: 3.23)
+    const pbrt_hip_light_map *map = l.type == PBRT_HIP_LIGHT_MAPPED ? table.light_map(light_env_slot(l)) : nullptr;
+    const uint32_t dev_type = l.type == PBRT_HIP_LIGHT_ENVMAP ? 4u : (map ? 6u + map->kind : l.type);
+    in->lights.push_back(make_float4(as_f(dev_type), l.p[0], l.p[1], l.p[2]));
+    if (map) {
+      const float *m = map->world_to_light;
+      in->lights.push_back(make_float4(m[0], m[1], m[2], map->inv_tan));
+      in->lights.push_back(make_float4(m[3], m[4], m[5], map->sx));
+      in->lights.push_back(make_float4(l.c[0], l.c[1], l.c[2], as_f(map->image - 1u)));
+      in->lights.push_back(make_float4(m[6], m[7], m[8], map->sy));
+      in->has_mapped = true;
+      continue;
+    }
     if (l.type == PBRT_HIP_LIGHT_SPOT) {
       const pbrt_hip_spot_cone &c = *table.cone(light_env_slot(l));
       in->lights.push_back(make_float4(c.axis[0], c.axis[1], c.axis[2], c.cos_total));
@@ -497,8 +546,8 @@ void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, Scen
     in->spheres[2 * i] = make_float4(sp.c[0], sp.c[1], sp.c[2], sp.r);
     in->spheres[2 * i + 1] = make_float4(as_f(sp.mat), 0, 0, 0);
   }
-  if (table.textured_tris || table.textured_sph) {  // (the texture table goes up only when something is textured)
-    in->textures.resize(3 * table.kinds.size());  // (an environment map's / the normals' / the filter's slot: no material names it, its rows stay zero)
+  if (table.textured_tris || table.textured_sph || in->has_mapped) {  // (the texture table goes up only when something is textured, or a mapped light reads an image)
+    in->textures.resize(3 * table.kinds.size());  // (an environment map's / the normals' / the filter's / a cone's / a light map's slot: nothing on the device reads it, its rows stay zero)
     for (uint32_t i = 0; i < table.kinds.size(); i++) {
       if (table.kinds[i] != SlotKind::kChecker) continue;
       const pbrt_hip_texture tx = read_slot<pbrt_hip_texture>(table.slots, i);
@@ -690,7 +739,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.11 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9 and 0.10)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.12 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10 and 0.11)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif
@@ -860,7 +909,7 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
     gather_inputs(*d, table, &in);
     s->n_prims = in.n_prims;
     s->textured = table.textured_tris || table.textured_sph;
-    s->glass = !in.glass.empty() || in.has_spot;  // (a spot light is sampled under PLS, in the GLS instantiations: DESIGN.md 3.22)
+    s->glass = !in.glass.empty() || in.has_spot || in.has_mapped;  // (a spot and a mapped light are sampled under PLS, in the GLS instantiations: DESIGN.md 3.22, 3.23)
     if ((rc = upload_inputs(s.get(), *d, table, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
     if (table.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
       HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));

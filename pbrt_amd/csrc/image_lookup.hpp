@@ -1,5 +1,5 @@
 // image_lookup.hpp -- Kd from an image, written once for the device (render_body.inc's TEX block in kernels_x.hip,
-// kernels_env.hip and kernels_n.hip, and the debug hook's kernel in kernels_blocks.hip) and for the host (image_texture.cpp:
+// kernels_env.hip and kernels_n.hip, the mapped lights' image of light_map.hpp (3.23), and the debug hook's kernel in kernels_blocks.hip) and for the host (image_texture.cpp:
 // pbrt_hip_image_lookup_eval_host, what the CPU tests run), in the manner of envmap_core.hpp: fp32, one fixed order of operations, built
 // with -ffp-contract=off, no call into libm / ocml beyond floorf / fminf / fmaxf, which are exact.
 //

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "capi_internal.hpp"
+#include "envmap.hpp"
 #include "image_lookup.hpp"
 
 namespace pbrt_hip {
@@ -40,6 +41,22 @@ void image_pack(const pbrt_hip_image_texture &t, std::vector<float4> *pool, floa
   pool->resize(first + n);
   for (size_t i = 0; i < n; i++) (*pool)[first + i] = make_float4(t.rgb[3 * i], t.rgb[3 * i + 1], t.rgb[3 * i + 2], 0.f);
   image::encode(t.width, t.height, t.wrap, t.filter, t.su, t.sv, t.du, t.dv, (uint32_t)first, &rows[0], &rows[1], &rows[2]);
+}
+
+int light_map_check(const pbrt_hip_light_map &m, const std::string &what) {
+  if (m.kind > PBRT_HIP_LIGHT_MAP_GONIOMETRIC) return fail(PBRT_HIP_ERR_INVALID, what + "light map: unknown kind (0 projection, 1 goniometric)");
+  for (int k = 0; k < 9; k++)
+    if (!std::isfinite(m.world_to_light[k])) return fail(PBRT_HIP_ERR_INVALID, what + "light map: world_to_light is not finite");
+  if (envmap_orthonormal_error(m.world_to_light) > kEnvOrthonormalTolerance)
+    return fail(PBRT_HIP_ERR_INVALID, what + "light map: world_to_light is not orthonormal to 1e-4 (a rotation is expected)");
+  const float window[3] = {m.inv_tan, m.sx, m.sy};
+  for (int k = 0; k < 3; k++) {
+    if (m.kind == PBRT_HIP_LIGHT_MAP_PROJECTION && (!std::isfinite(window[k]) || !(window[k] > 0.f)))
+      return fail(PBRT_HIP_ERR_INVALID, what + "light map: a projection's inv_tan, sx and sy must be finite and > 0");
+    if (m.kind == PBRT_HIP_LIGHT_MAP_GONIOMETRIC && !(window[k] == 0.f))
+      return fail(PBRT_HIP_ERR_INVALID, what + "light map: a goniometric record's inv_tan, sx and sy must be 0");
+  }
+  return PBRT_HIP_OK;
 }
 
 namespace {

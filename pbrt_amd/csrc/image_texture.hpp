@@ -20,4 +20,8 @@ int image_check_totals(uint32_t n_slots, uint64_t n_texels, const std::string &w
 // appends the record's texels to `pool` as {r, g, b, 0} in the record's own row order and writes the slot's three rows (image_lookup.hpp encode)
 void image_pack(const pbrt_hip_image_texture &t, std::vector<float4> *pool, float4 rows[3]);
 
+// a mapped light's record (every message holds "light map"): its kind, its rotation and its window -- everything but what
+// its `image` names, which is the table's to say
+int light_map_check(const pbrt_hip_light_map &m, const std::string &what);
+
 }  // namespace pbrt_hip

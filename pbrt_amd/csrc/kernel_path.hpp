@@ -4,6 +4,7 @@
 #include "envmap_core.hpp"
 #include "image_lookup.hpp"
 #include "kernel_walk.hpp"
+#include "light_map.hpp"
 #include "plastic_bsdf.hpp"
 #include "spot_light.hpp"
 
@@ -13,6 +14,12 @@ namespace {
 // the light table's type word of a spot light: position in row 0, {axis, cos_total} in row 1, cos_start in row 2, I in
 // row 3 (capi_scene.cpp gather_inputs).  sample_light below knows nothing of it: a spot light is taken BEFORE that chain, under PLS
 constexpr uint32_t kDevLightSpot = 5u;
+// ... and of the mapped lights, by their record's kind: position in row 0, {a row of world_to_light, inv_tan / sx / sy} in
+// rows 1, 2 and 4, {I, the bits of the image slot's 0-based number} in row 3.  Taken before sample_light's chain too, under PLS
+constexpr uint32_t kDevLightProjection = 6u, kDevLightGonio = 7u;
+// the types that are taken before sample_light's chain are the table's LARGEST (3 is an emissive triangle, 4 the environment map, which no
+// PLS kernel meets): ONE compare finds them, so a scene without them pays what it paid for the spot light's test alone
+__device__ __forceinline__ bool dev_light_beyond_chain(uint32_t type) { return type >= kDevLightSpot; }
 
 // One light of UniformSampleOneLight.  false: geometry rules the light out.
 // mis: the estimate weighted with the power heuristic pl^2 / (pl^2 + pb^2), pl = this strategy's density for the
@@ -98,12 +105,39 @@ __device__ __forceinline__ bool sample_light_spot(const DevScene &S, uint32_t li
   return true;
 }
 
+// A mapped light (light_map.hpp) of type kDevLightProjection or kDevLightGonio: the point light's (lc scale) and the image's
+// rgb apart, for the two callers to multiply in their own order.  `textures` and `texels` are RenderParams' rows and texel pool.
+__device__ __forceinline__ bool sample_light_map(const DevScene &S, const float4 *textures, const float4 *texels, uint32_t li, V3 po, V3 nf, float nLf, V3 &lc,
+                                                 float &scale, V3 &rgb, V3 &wi, float &tmax) {
+  const float4 l0 = S.lights[5 * li];
+  const float4 l1 = S.lights[5 * li + 1];
+  const float4 l2 = S.lights[5 * li + 2];
+  const float4 l3 = S.lights[5 * li + 3];
+  const float4 l4 = S.lights[5 * li + 4];
+  const uint32_t slot = __float_as_uint(l3.w);
+  const float4 t0 = textures[3u * slot], t2 = textures[3u * slot + 2u];
+  float s, t;
+  lc = xyz(l3);
+  return lightmap::sample(po, nf, mk(l0.y, l0.z, l0.w), __float_as_uint(l0.x) - kDevLightProjection, l1, l2, l4, nLf, texels, t0, t2.w, wi, tmax, scale, s, t, rgb);
+}
+// ... at a matte vertex: sample_light's outputs.  Called under PLS alone, as sample_light_spot is.  A delta light: no MIS weight.
+__device__ __forceinline__ bool sample_light_mapped(const DevScene &S, const float4 *textures, const float4 *texels, uint32_t li, V3 po, V3 nf, V3 kd, float nLf,
+                                                    V3 &Ld, V3 &wi, float &tmax) {
+  const V3 f = kd * kInvPi;
+  V3 lc, rgb;
+  float scale;
+  if (!sample_light_map(S, textures, texels, li, po, nf, nLf, lc, scale, rgb, wi, tmax)) return false;
+  Ld = ((f * lc) * scale) * rgb;
+  return true;
+}
+
 // sample_light's sibling for a BSDF that is not Lambertian (the plastic material; called under PLS alone, so that
 // sample_light and the instantiations built from it keep their machine code): the same light from the same (u1, u2), WITHOUT a BSDF
 // factor and without a MIS weight -- Lg = Li cos_i nL / pdf_l, the caller multiplies by f(wo, wi) -- and pl = the density that MIS
 // compares with the BSDF's for wi (light picked with 1 / nL), 0 for the point and the distant light.  The operations are sample_light's.
-__device__ __forceinline__ bool sample_light_general(const DevScene &S, uint32_t li, V3 po, V3 nf, float u1, float u2, float nLf, V3 &Lg, V3 &wi,
-                                                     float &tmax, float &pl) {
+// (textures, texels: RenderParams' rows and texel pool, which a mapped light's image is read from)
+__device__ __forceinline__ bool sample_light_general(const DevScene &S, const float4 *textures, const float4 *texels, uint32_t li, V3 po, V3 nf, float u1, float u2,
+                                                     float nLf, V3 &Lg, V3 &wi, float &tmax, float &pl) {
   const float4 l0 = S.lights[5 * li];
   const float4 l3 = S.lights[5 * li + 3];
   const uint32_t type = __float_as_uint(l0.x);
@@ -136,13 +170,21 @@ __device__ __forceinline__ bool sample_light_general(const DevScene &S, uint32_t
     pl = (z * kInvPi) / nLf;
     tmax = kInf;
     return true;
-  } else if (type == kDevLightSpot) {
-    // a spot light: the point light with the cone's falloff, a delta light like it (pl stays 0)
-    const float4 l1 = S.lights[5 * li + 1];
-    const float4 l2 = S.lights[5 * li + 2];
-    float fall, scale;
-    if (!spot::sample(po, nf, p0, xyz(l1), l1.w, l2.x, nLf, wi, tmax, fall, scale)) return false;
-    Lg = lc * scale;
+  } else if (dev_light_beyond_chain(type)) {
+    if (type == kDevLightSpot) {
+      // a spot light: the point light with the cone's falloff, a delta light like it (pl stays 0)
+      const float4 l1 = S.lights[5 * li + 1];
+      const float4 l2 = S.lights[5 * li + 2];
+      float fall, scale;
+      if (!spot::sample(po, nf, p0, xyz(l1), l1.w, l2.x, nLf, wi, tmax, fall, scale)) return false;
+      Lg = lc * scale;
+      return true;
+    }
+    // a mapped light: the point light times its image, a delta light like it (pl stays 0)
+    V3 lm, rgb;
+    float scale;
+    if (!sample_light_map(S, textures, texels, li, po, nf, nLf, lm, scale, rgb, wi, tmax)) return false;
+    Lg = (lm * scale) * rgb;
     return true;
   } else {
     // an emissive triangle (device type 3; the environment map's type 4 never arrives: a scene with plastic and a map is refused)

@@ -4,12 +4,14 @@
 // translation unit of its own so that the render and intersect kernels of kernels*.hip keep their names and their machine code.
 // Beside it pbrt_hip_filter_footprint_eval_device: filter_weight.inc's footprint and table index over arrays, and the kernel of
 // pbrt_hip_image_lookup_eval_device: image_lookup.hpp over arrays, and pbrt_hip_plastic_eval_device with its kernel:
-// plastic_bsdf.hpp over arrays, and pbrt_hip_spot_eval_device with its kernel: spot_light.hpp over arrays (3.22).
+// plastic_bsdf.hpp over arrays, and pbrt_hip_spot_eval_device with its kernel: spot_light.hpp over arrays (3.22), and
+// pbrt_hip_light_map_eval_device with its kernel: light_map.hpp over arrays (3.23).
 //
 //   blocks_eval_kernel  one element per thread, 256 threads per workgroup: switches on the op code and calls the PRODUCTION function
 //                       (nothing is restated here); kBlockWidth is how many floats an element reads and writes.
 #include "capi_internal.hpp"
 #include "envmap_core.hpp"
+#include "image_texture.hpp"
 #include "kernel_math.hpp"
 #include "kernel_path.hpp"
 #include "kernel_walk.hpp"
@@ -160,6 +162,19 @@ __global__ void __launch_bounds__(256) spot_eval_kernel(int64_t n, const float *
 #include "spot_eval.inc"
 }
 
+// light_map.hpp over arrays (pbrt_hip_light_map_eval_device): a mapped light's sample at a shading point.  rows = the image
+// slot's three rows, map = {a row of world_to_light, inv_tan / sx / sy} x 3
+__global__ void __launch_bounds__(256) light_map_eval_kernel(uint32_t e_kind, float4 e_r0, float4 e_r1, float4 e_r2, const float4 *rows, const float4 *e_pool, int64_t n,
+                                                             const float *in, float *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 e_t0 = rows[0];
+  const float e_offset = rows[2].w;
+  const float *x = in + i * (int64_t)PBRT_HIP_LIGHT_MAP_EVAL_IN;
+  float *y = out + i * (int64_t)PBRT_HIP_LIGHT_MAP_EVAL_OUT;
+#include "light_map_eval.inc"
+}
+
 }  // namespace
 
 hipError_t launch_image_lookup_eval(const float4 *rows, const float4 *pool, int64_t n, const float *uv, float *rgb, hipStream_t stream) {
@@ -251,6 +266,41 @@ extern "C" int pbrt_hip_spot_eval_device(int device, int64_t n, const float *in,
     hipLaunchKernelGGL(spot_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, d_in.p, d_out.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, d_out.p, 4 * PBRT_HIP_SPOT_EVAL_OUT * (size_t)n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PBRT_HIP_OK;
+  });
+}
+
+extern "C" int pbrt_hip_light_map_eval_device(int device, const pbrt_hip_image_texture *image, const pbrt_hip_light_map *map, int64_t n, const float *in, float *out) {
+  if (n < 0 || !image || !map || !in || !out) return fail(PBRT_HIP_ERR_INVALID, "light_map_eval_device: null argument or negative count");
+  return guarded([&]() -> int {
+    const std::string what = "light_map_eval_device: ";  // (the records checked as scene creation checks them, packed as it packs them)
+    if (image->type != PBRT_HIP_TEXTURE_IMAGE) return fail(PBRT_HIP_ERR_INVALID, what + "not an image texture's record (its first word must be 4)");
+    if (map->type != PBRT_HIP_TEXTURE_LIGHT_MAP) return fail(PBRT_HIP_ERR_INVALID, what + "not a light map's record (its first word must be 8)");
+    int rc;
+    if ((rc = image_check(*image, what)) || (rc = image_check_totals(1u, (uint64_t)image->width * image->height, what)) || (rc = image_check_texels(*image, what)) ||
+        (rc = light_map_check(*map, what)))
+      return rc;
+    if (n == 0) return PBRT_HIP_OK;
+    std::vector<float4> pool;
+    float4 rows[3];
+    image_pack(*image, &pool, rows);
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<float4> d_pool, d_rows;
+    DevBuf<float> d_in, d_out;
+    HIP_TRY(d_pool.alloc(pool.size()));
+    HIP_TRY(d_rows.alloc(3));
+    HIP_TRY(d_in.alloc(PBRT_HIP_LIGHT_MAP_EVAL_IN * (size_t)n));
+    HIP_TRY(d_out.alloc(PBRT_HIP_LIGHT_MAP_EVAL_OUT * (size_t)n));
+    const hipStream_t stream = nullptr;  // the device's default stream
+    HIP_TRY(hipMemcpyAsync(d_pool.p, pool.data(), 16 * pool.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_rows.p, rows, 16 * 3, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, 4 * PBRT_HIP_LIGHT_MAP_EVAL_IN * (size_t)n, hipMemcpyHostToDevice, stream));
+    const float *m = map->world_to_light;
+    hipLaunchKernelGGL(light_map_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, map->kind, make_float4(m[0], m[1], m[2], map->inv_tan),
+                       make_float4(m[3], m[4], m[5], map->sx), make_float4(m[6], m[7], m[8], map->sy), d_rows.p, d_pool.p, n, d_in.p, d_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, 4 * PBRT_HIP_LIGHT_MAP_EVAL_OUT * (size_t)n, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return PBRT_HIP_OK;
   });

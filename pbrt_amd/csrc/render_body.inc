@@ -243,8 +243,10 @@
                     if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
                   }
                 } else
-                if (PLS && __float_as_uint(S.lights[5 * li].x) == kDevLightSpot) {  // a spot light (3.22): taken before sample_light's chain, which does not know it
-                  if (sample_light_spot(S, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)) {
+                if (PLS && dev_light_beyond_chain(__float_as_uint(S.lights[5 * li].x))) {
+                  // a spot light (3.22) or a mapped light (3.23): taken before sample_light's chain, which does not know them, by ONE compare
+                  if (__float_as_uint(S.lights[5 * li].x) == kDevLightSpot ? sample_light_spot(S, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)
+                                                                           : sample_light_mapped(S, R.textures, R.image_texels, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)) {
                     need_shadow = true;
                     lpend = P.beta * Ld;
                     if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
@@ -282,7 +284,7 @@
                 li = min(li, nL - 1u);
                 V3 Lg;
                 float pl;
-                if (sample_light_general(S, li, po, nf, u1, u2, nLf, Lg, sh_d, sh_tmax, pl)) {
+                if (sample_light_general(S, R.textures, R.image_texels, li, po, nf, u1, u2, nLf, Lg, sh_d, sh_tmax, pl)) {
                   V3 f;
                   float pbl;
                   plastic::eval(nf, wo, sh_d, k, ks, gl.w, f, pbl);

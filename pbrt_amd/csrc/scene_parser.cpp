@@ -286,6 +286,14 @@ struct Api {
   // LightSource "spot" (DESIGN.md 3.22): the cones, in the order of their lights.  A spot light's `pad` holds its cone's 1-based place HERE
   // until the file has been read; parse_scene then appends the cones to the texture table and writes the slots' numbers
   std::vector<pbrt_hip_spot_cone> spot_cones;
+  // LightSource "projection" / "goniometric" (DESIGN.md 3.23): the records and their images, in the order of their lights.  A mapped
+  // light's `pad` holds its record's 1-based place HERE until the file has been read; parse_scene then appends each image's slot and each
+  // record behind the spot cones and writes the numbers
+  struct PendingLightMap {
+    pbrt_hip_light_map rec;
+    pbrt_hip_image_texture image;
+  };
+  std::vector<PendingLightMap> light_maps;
   // instancing multiplies geometry (instances x the object's triangles): a bound on what a small file can ask for (the tests lower it)
   const size_t kMaxSceneTriangles = [] {
     const char *on = std::getenv("PBRT_HIP_DEBUG_KNOBS"), *v = std::getenv("PBRT_HIP_MAX_SCENE_TRIANGLES");
@@ -425,6 +433,29 @@ struct Api {
     return id;
   }
 
+  // An image's texels for a pbrt_hip_image_texture record, read through pbrt_hip_read_image (a relative name against the scene file's
+  // directory) within the record's size caps, with pbrt-v3's InverseGammaCorrect where `gamma` and then `scale`.  false: the file cannot be
+  // used.  Texture "imagemap" and the mapped lights' "mapname"  read their images here.
+  bool read_image_texels(const std::string &file, bool gamma, float scale, int32_t *w, int32_t *h, std::vector<float> *rgb) {
+    const std::string path = (file.empty() || file[0] == '/' || cur_dir.empty()) ? file : cur_dir + "/" + file;
+    bool ok = !file.empty() && pbrt_hip_read_image(path.c_str(), nullptr, w, h) == PBRT_HIP_OK && *w > 0 && *h > 0 && (uint32_t)*w <= PBRT_HIP_IMAGE_MAX_SIZE &&
+              (uint32_t)*h <= PBRT_HIP_IMAGE_MAX_SIZE && out->image_texels + (uint64_t)*w * (uint64_t)*h <= PBRT_HIP_IMAGE_MAX_TEXELS;
+    if (ok) {
+      rgb->resize(3 * (size_t)*w * (size_t)*h);
+      ok = pbrt_hip_read_image(path.c_str(), rgb->data(), w, h) == PBRT_HIP_OK;
+    }
+    for (size_t i = 0; ok && i < rgb->size(); i++) {
+      float v = (*rgb)[i];
+      if (gamma) v = v <= 0.04045f ? v * (1.0f / 12.92f) : (float)std::pow(((double)v + 0.055) / 1.055, 2.4);  // pbrt-v3 InverseGammaCorrect, rounded once
+      (*rgb)[i] = v * scale;
+      ok = std::isfinite((*rgb)[i]) && (*rgb)[i] >= 0.f;
+    }
+    return ok;
+  }
+  static bool is_png(const std::string &file) {
+    return file.size() >= 4 && (file.compare(file.size() - 4, 4, ".png") == 0 || file.compare(file.size() - 4, 4, ".PNG") == 0);
+  }
+
   // Texture "name" "spectrum" "imagemap" (pbrt-v3 ImageTexture): the image read through pbrt_hip_read_image (PNG / PFM; a
   // relative name against the scene file's directory), "bool gamma" (default: true for .png) = pbrt-v3's InverseGammaCorrect, then "float
   // scale"; with the "uv" mapping it becomes a pbrt_hip_image_texture record that a matte Kd can name, and *mean = the mean texel, which is
@@ -433,7 +464,7 @@ struct Api {
     const std::string file = ps.one_string("filename", "");
     const std::string wrap = ps.one_string("wrap", "repeat"), filter = ps.one_string("filter", "bilinear"), mapping = ps.one_string("mapping", "uv");
     const float scale = ps.one_float("scale", 1.f);
-    const bool png = file.size() >= 4 && (file.compare(file.size() - 4, 4, ".png") == 0 || file.compare(file.size() - 4, 4, ".PNG") == 0);
+    const bool png = is_png(file);
     const bool gamma = ps.one_bool("gamma", png);
     const bool asked_trilinear = ps.find("trilinear", "bool") != nullptr, asked_aniso = ps.find("maxanisotropy", "float") != nullptr;
     if (asked_trilinear || asked_aniso)
@@ -441,21 +472,9 @@ struct Api {
     pbrt_hip_image_texture t{};
     t.su = ps.one_float("uscale", 1.f); t.sv = ps.one_float("vscale", 1.f);
     t.du = ps.one_float("udelta", 0.f); t.dv = ps.one_float("vdelta", 0.f);
-    const std::string path = (file.empty() || file[0] == '/' || cur_dir.empty()) ? file : cur_dir + "/" + file;
     int32_t w = 0, h = 0;
     std::vector<float> rgb;
-    bool ok = !file.empty() && pbrt_hip_read_image(path.c_str(), nullptr, &w, &h) == PBRT_HIP_OK && w > 0 && h > 0 && (uint32_t)w <= PBRT_HIP_IMAGE_MAX_SIZE &&
-              (uint32_t)h <= PBRT_HIP_IMAGE_MAX_SIZE && out->image_texels + (uint64_t)w * (uint64_t)h <= PBRT_HIP_IMAGE_MAX_TEXELS;
-    if (ok) {
-      rgb.resize(3 * (size_t)w * (size_t)h);
-      ok = pbrt_hip_read_image(path.c_str(), rgb.data(), &w, &h) == PBRT_HIP_OK;
-    }
-    for (size_t i = 0; ok && i < rgb.size(); i++) {
-      float v = rgb[i];
-      if (gamma) v = v <= 0.04045f ? v * (1.0f / 12.92f) : (float)std::pow(((double)v + 0.055) / 1.055, 2.4);  // pbrt-v3 InverseGammaCorrect, rounded once
-      rgb[i] = v * scale;
-      ok = std::isfinite(rgb[i]) && rgb[i] >= 0.f;
-    }
+    const bool ok = read_image_texels(file, gamma, scale, &w, &h, &rgb);
     if (!ok) {
       warn("Texture \"" + name + "\" (imagemap): \"" + file + "\" cannot be used (missing, unreadable, larger than 16384 x 16384 or 2^26 texels in all, or texels that are negative / not finite): replaced by grey 0.5");
       return;
@@ -741,6 +760,30 @@ struct Api {
     return true;
   }
 
+  // world_to_light = the rotation of the CTM, inverted (an environment map's; a mapped light's, 3.23).  A CTM that is a
+  // rotation gives its inverse's 3 x 3 as it stands; one that scales or shears: the rotation that Gram-Schmidt leaves of the light's axes
+  // (x kept, y made orthogonal to it, z completing them), for the caller to warn about; a singular one leaves nothing
+  enum class CtmRotation { kExact, kGramSchmidt, kSingular };
+  CtmRotation ctm_world_to_light(float world_to_light[9]) {
+    const float *m = ctm[0].m, *mi = ctm[0].inv;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) world_to_light[3 * i + j] = mi[4 * i + j];
+    // (the library's own test and bound, envmap_check: what passes here is not refused there, and a chain of Rotate directives has
+    // fp32 rounding's room)
+    if (envmap_orthonormal_error(world_to_light) <= kEnvOrthonormalTolerance) return CtmRotation::kExact;
+    double x[3] = {m[0], m[4], m[8]}, y[3] = {m[1], m[5], m[9]}, c2[3] = {m[2], m[6], m[10]};
+    auto norm = [](double *v) { const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); for (int k = 0; k < 3; k++) v[k] = n > 0.0 ? v[k] / n : 0.0; return n; };
+    bool good = norm(x) > 0.0;
+    const double xy = x[0] * y[0] + x[1] * y[1] + x[2] * y[2];
+    for (int k = 0; k < 3; k++) y[k] -= xy * x[k];
+    good = norm(y) > 0.0 && good;
+    double z[3] = {x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]};
+    if (z[0] * c2[0] + z[1] * c2[1] + z[2] * c2[2] < 0.0) for (int k = 0; k < 3; k++) z[k] = -z[k];  // (a mirroring CTM keeps its handedness)
+    if (!good) return CtmRotation::kSingular;
+    for (int k = 0; k < 3; k++) { world_to_light[k] = (float)x[k]; world_to_light[3 + k] = (float)y[k]; world_to_light[6 + k] = (float)z[k]; }
+    return CtmRotation::kGramSchmidt;
+  }
+
   // turns the constant infinite light *l into the environment-map light of image `map` (type 3, its record in a slot of out->textures)
   void environment_map(const std::string &map, pbrt_hip_light *l) {
     if (!out->env_rgb.empty()) { warn("infinite light \"" + map + "\": one environment map per scene, constant L used for this one"); return; }
@@ -754,29 +797,11 @@ struct Api {
     }
     for (size_t i = 0; ok && i < rgb.size(); i++) ok = std::isfinite(rgb[i]) && rgb[i] >= 0.f;
     if (!ok) { warn("infinite light: environment map \"" + map + "\" cannot be read (missing, too large, or texels that are negative / not finite): constant L used"); return; }
-    // world_to_light = the rotation of the CTM, inverted.  A CTM that is a rotation gives its inverse's 3 x 3 as it stands; one that scales
-    // or shears: a warning, and the rotation that Gram-Schmidt leaves of the light's axes (x kept, y made orthogonal to it, z completing them)
     pbrt_hip_envmap e{};
     e.width = (uint32_t)w; e.height = (uint32_t)h;
-    const float *m = ctm[0].m, *mi = ctm[0].inv;
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) e.world_to_light[3 * i + j] = mi[4 * i + j];
-    // (the library's own test and bound, envmap_check: what passes here is not refused there, and a chain of Rotate directives has
-    // fp32 rounding's room)
-    if (envmap_orthonormal_error(e.world_to_light) <= kEnvOrthonormalTolerance) {
-    } else {
-      warn("infinite light: the transformation of an environment map scales or shears; its rotation part is used");
-      double x[3] = {m[0], m[4], m[8]}, y[3] = {m[1], m[5], m[9]}, c2[3] = {m[2], m[6], m[10]};
-      auto norm = [](double *v) { const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); for (int k = 0; k < 3; k++) v[k] = n > 0.0 ? v[k] / n : 0.0; return n; };
-      bool good = norm(x) > 0.0;
-      const double xy = x[0] * y[0] + x[1] * y[1] + x[2] * y[2];
-      for (int k = 0; k < 3; k++) y[k] -= xy * x[k];
-      good = norm(y) > 0.0 && good;
-      double z[3] = {x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]};
-      if (z[0] * c2[0] + z[1] * c2[1] + z[2] * c2[2] < 0.0) for (int k = 0; k < 3; k++) z[k] = -z[k];  // (a mirroring CTM keeps its handedness)
-      if (!good) { warn("infinite light: the transformation of an environment map is singular: constant L used"); return; }
-      for (int k = 0; k < 3; k++) { e.world_to_light[k] = (float)x[k]; e.world_to_light[3 + k] = (float)y[k]; e.world_to_light[6 + k] = (float)z[k]; }
-    }
+    const CtmRotation rot = ctm_world_to_light(e.world_to_light);
+    if (rot != CtmRotation::kExact) warn("infinite light: the transformation of an environment map scales or shears; its rotation part is used");
+    if (rot == CtmRotation::kSingular) { warn("infinite light: the transformation of an environment map is singular: constant L used"); return; }
     out->env_rgb.swap(rgb);
     e.rgb = out->env_rgb.data();  // (filled once: the vector is not touched again)
     out->textures.push_back(write_slot(e));
@@ -883,8 +908,67 @@ struct Api {
       l.type = PBRT_HIP_LIGHT_SPOT;
       std::memcpy(&l.pad, &pending, 4);
       for (int i = 0; i < 3; i++) { l.p[i] = p[i]; l.c[i] = I[i] * scale[i]; }
+    } else if (name == "projection" || name == "goniometric") {
+      // DESIGN.md 3.23 (pbrt-v3 CreateProjectionLight / CreateGoniometricLight): a point light at the CTM's origin times an image looked up
+      // in the direction from the light, in the light's own frame: world_to_light is the rotation of the CTM, inverted
+      const bool proj = name == "projection";
+      const std::string say = "LightSource \"" + name + "\": ";
+      float I[3] = {1, 1, 1}, p[3];
+      const float origin[3] = {0, 0, 0};
+      spectrum(ps, "I", I);
+      float fov = proj ? ps.one_float("fov", 45.f) : 0.f;
+      const std::string map = ps.one_string("mapname", "");
+      xf_point(ctm[0].m, origin, p);
+      l.type = 0;
+      for (int i = 0; i < 3; i++) { l.p[i] = p[i]; l.c[i] = I[i] * scale[i]; }
+      PendingLightMap lm{};
+      int32_t w = 0, h = 0;
+      std::vector<float> rgb;
+      bool have = !map.empty() && out->image_rgb.size() < PBRT_HIP_IMAGE_MAX_SLOTS && read_image_texels(map, is_png(map), 1.f, &w, &h, &rgb);
+      if (!have && proj) {  // (pbrt-v3 projects plain I into the frustum: an image of ones)
+        warn(say + (map.empty() ? std::string("no \"mapname\"") : "\"" + map + "\" cannot be used (missing, unreadable, too large, or texels that are negative / not finite)") +
+             ": the light projects plain I into its frustum (a 1 x 1 image of ones)");
+        w = h = 1;
+        rgb.assign(3, 1.0f);
+        have = true;
+      }
+      if (!have) {  // (pbrt-v3 renders a goniometric light without its map as a point light)
+        warn(say + (map.empty() ? std::string("no \"mapname\"") : "\"" + map + "\" cannot be used (missing, unreadable, too large, or texels that are negative / not finite)") +
+             ": rendered as a point light");
+      } else {
+        const CtmRotation rot = ctm_world_to_light(lm.rec.world_to_light);
+        if (rot == CtmRotation::kSingular) {
+          warn(say + "the transformation is singular: the light has no frame and is skipped");
+          report_unused("LightSource", ps);
+          return;
+        }
+        if (rot != CtmRotation::kExact) warn(say + "the transformation scales or shears; its rotation part is used");
+        lm.rec.kind = proj ? PBRT_HIP_LIGHT_MAP_PROJECTION : PBRT_HIP_LIGHT_MAP_GONIOMETRIC;
+        if (proj) {
+          if (!(fov > 0.f && fov < 180.f)) {
+            warn(say + "fov " + std::to_string(fov) + " lies outside (0, 180), the default 45 is used");
+            fov = 45.f;
+          }
+          // (in double from the float angle and rounded once; the screen window is pbrt-v3's, from the image's aspect)
+          lm.rec.inv_tan = (float)(1.0 / std::tan((double)fov * (3.14159265358979323846 / 360.0)));
+          const float aspect = (float)w / (float)h;
+          lm.rec.sx = aspect > 1.f ? aspect : 1.f;
+          lm.rec.sy = aspect > 1.f ? 1.f : 1.f / aspect;
+        }
+        lm.image.width = (uint32_t)w; lm.image.height = (uint32_t)h;
+        lm.image.wrap = proj ? PBRT_HIP_WRAP_CLAMP : PBRT_HIP_WRAP_REPEAT;
+        lm.image.filter = PBRT_HIP_TEXFILTER_BILINEAR;
+        lm.image.su = lm.image.sv = 1.f;
+        out->image_texels += (uint64_t)w * (uint64_t)h;
+        out->image_rgb.emplace_back(std::move(rgb));
+        lm.image.rgb = out->image_rgb.back().data();  // (an inner vector is filled once and keeps its storage when the outer one grows)
+        light_maps.push_back(lm);
+        const uint32_t pending = (uint32_t)light_maps.size();  // (1-based, into light_maps: parse_scene turns it into the slot's number)
+        l.type = PBRT_HIP_LIGHT_MAPPED;
+        std::memcpy(&l.pad, &pending, 4);
+      }
     } else {
-      warn("light_source: light type '" + name + "' unknown.");  // api.rs:692 (goniometric, projection: not on this path either)
+      warn("light_source: light type '" + name + "' unknown.");  // api.rs:692
       return;
     }
     out->lights.push_back(l);
@@ -1367,6 +1451,34 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
     }
     if (api.any_normals) {  // (the same family rule as plastic's, below)
       api.warn("a scene with a \"spot\" light: the meshes' normals \"N\" are ignored (every mesh renders flat)");
+      api.any_normals = false;
+    }
+  }
+  // the mapped lights' images and records follow the cones, under the same two family rules
+  if (!api.light_maps.empty() && !out->env_rgb.empty()) {
+    api.warn("a scene with an environment map (\"mapname\"): its " + std::to_string(api.light_maps.size()) + " \"projection\" / \"goniometric\" light(s) are ignored");
+    std::vector<pbrt_hip_light> kept;
+    for (const pbrt_hip_light &l : out->lights)
+      if (l.type != PBRT_HIP_LIGHT_MAPPED) kept.push_back(l);
+    out->lights.swap(kept);
+    api.light_maps.clear();  // (their texels stay in out->image_rgb, which nothing names)
+  }
+  if (!api.light_maps.empty()) {
+    std::vector<uint32_t> number(api.light_maps.size());  // the 1-based slot of record k
+    for (size_t k = 0; k < api.light_maps.size(); k++) {
+      out->textures.push_back(write_slot(api.light_maps[k].image));
+      api.light_maps[k].rec.image = (uint32_t)out->textures.size();
+      out->textures.push_back(write_slot(api.light_maps[k].rec));
+      number[k] = (uint32_t)out->textures.size();
+    }
+    for (pbrt_hip_light &l : out->lights) {
+      if (l.type != PBRT_HIP_LIGHT_MAPPED) continue;
+      uint32_t pending;
+      std::memcpy(&pending, &l.pad, 4);
+      std::memcpy(&l.pad, &number[pending - 1u], 4);
+    }
+    if (api.any_normals) {
+      api.warn("a scene with a \"projection\" / \"goniometric\" light: the meshes' normals \"N\" are ignored (every mesh renders flat)");
       api.any_normals = false;
     }
   }

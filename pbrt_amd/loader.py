@@ -6,9 +6,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (SLOT_ENVMAP, SLOT_FILTER, SLOT_IMAGE, SLOT_NORMALS, SLOT_SPOT, EnvMap, ImageTexture, Normals, PixelFilter, RenderDesc, SceneDesc,
+from ._lib import (SLOT_ENVMAP, SLOT_FILTER, SLOT_IMAGE, SLOT_LIGHT_MAP, SLOT_NORMALS, SLOT_SPOT, EnvMap, ImageTexture, LightMap, Normals, PixelFilter, RenderDesc, SceneDesc,
                    SpotCone, check, lib, read_slot)
-from .api import GLASS, LIGHT_SPOT, PLASTIC, SceneData
+from .api import GLASS, LIGHT_MAPPED, LIGHT_SPOT, PLASTIC, SceneData
 
 
 @dataclass
@@ -52,7 +52,7 @@ def _collect(h):
         def first(kind, cls):
             return read_slot(d.textures, slots[kind][0], cls) if kind in slots else None
 
-        tex_slots = sorted(i for kind, at in slots.items() if kind not in (SLOT_ENVMAP, SLOT_NORMALS, SLOT_FILTER, SLOT_SPOT) for i in at)
+        tex_slots = sorted(i for kind, at in slots.items() if kind not in (SLOT_ENVMAP, SLOT_NORMALS, SLOT_FILTER, SLOT_SPOT, SLOT_LIGHT_MAP) for i in at)
         renum = {0: 0, **{i + 1: k + 1 for k, i in enumerate(tex_slots)}}
         e, nr, pf = first(SLOT_ENVMAP, EnvMap), first(SLOT_NORMALS, Normals), first(SLOT_FILTER, PixelFilter)
         envmap = arr(e.rgb, 3 * e.width * e.height, np.float32).reshape(e.height, e.width, 3) if e else np.zeros((0, 0, 3), np.float32)
@@ -76,7 +76,14 @@ def _collect(h):
             if d.lights[i].type == LIGHT_SPOT:
                 c = read_slot(d.textures, int(np.array([d.lights[i].pad], np.float32).view(np.uint32)[0]) - 1, SpotCone)
                 cones.append([*c.axis, c.cos_total, c.cos_start])
+        # a mapped light's likewise, of its record's slot (3.23): the records in the order of their lights, their images renumbered as rows
+        maps = []
+        for i in range(d.n_lights):
+            if d.lights[i].type == LIGHT_MAPPED:
+                m = read_slot(d.textures, int(np.array([d.lights[i].pad], np.float32).view(np.uint32)[0]) - 1, LightMap)
+                maps.append([m.kind, renum[m.image], *m.world_to_light, m.inv_tan, m.sx, m.sy])
         sd = SceneData(
+            light_maps=np.array(maps, np.float32).reshape(-1, 14),
             spot_cones=np.array(cones, np.float32).reshape(-1, 5),
             images=images, pixel_filter=pixel_filter, tri_n=tri_n, envmap=envmap, envmap_world_to_light=env_m,
             P=arr(d.P, 3 * d.n_verts, np.float32).reshape(-1, 3), idx=arr(d.idx, 3 * d.n_tris, np.uint32).reshape(-1, 3),

@@ -8,6 +8,8 @@
   glass_sphere_scene  a glass sphere and a glass cube in a Cornell-style box (= scenes/glass_sphere.pbrt)
   plastic_scene       a plastic floor and two plastic spheres in a Cornell-style box (= scenes/plastic_spheres.pbrt)
   spot_scene          a plastic and a matte sphere in a Cornell-style box lit by two spot lights (= scenes/spot_cornell.pbrt)
+  projector_scene     the same box lit by a projection light that throws a slide onto the back wall and a goniometric light (DESIGN.md 3.23;
+                      = scenes/projector_cornell.pbrt)
   envmap_scene        a matte ground, a glass and a mirror sphere under an environment map (= scenes/envmap_spheres.pbrt)
   icosphere_scene     C1 with its sphere tessellated, with or without shading normals
   smooth_mesh_scene   two octahedra with per-vertex normals over a flat ground (= scenes/smooth_mesh.pbrt)
@@ -357,6 +359,50 @@ def spot_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0)):
     ).normalized()
 
 
+def procedural_slide(width=64, height=48):
+    """The slide of the projection light's demo, (height, width, 3) float32, row 0 = the top: a white frame, eight colour
+    bars over the upper two thirds and a black-and-white checker below.  Every channel is exactly 0 or 1, which an 8-bit PNG and its inverse
+    gamma carry without rounding: what the scene file reads back is this array bit for bit."""
+    y, x = np.mgrid[0:height, 0:width]
+    bar = (x * 8) // width
+    bars = np.stack([(bar & 4) == 0, (bar & 2) == 0, (bar & 1) == 0], -1)
+    bars[bar == 7] = True  # (no black bar: white again)
+    check = ((x * 16) // width + (y * 12) // height) % 2 == 0
+    rgb = np.where((y * 3 < height * 2)[..., None], bars, check[..., None])
+    frame = (x < 2) | (x >= width - 2) | (y < 2) | (y >= height - 2)
+    return np.where(frame[..., None], True, rgb).astype(np.float32)
+
+
+def procedural_gonio(width=32, height=16):
+    """A small latitude-longitude intensity map for the goniometric light's demo, (height, width, 3) float32 with row 0 at the
+    light's +y pole: three lobes around the equator that fade towards the poles, tinted warm on one side and cool on the other, nowhere
+    below 0.05."""
+    r, c = np.mgrid[0:height, 0:width].astype(np.float64)
+    theta, phi = np.pi * (r + 0.5) / height, 2.0 * np.pi * (c + 0.5) / width
+    lobes = (0.5 + 0.5 * np.cos(3.0 * phi)) * np.sin(theta) ** 2
+    warm = 0.5 + 0.5 * np.cos(phi)
+    rgb = np.stack([0.05 + 0.95 * lobes * (0.6 + 0.4 * warm), 0.05 + 0.85 * lobes, 0.05 + 0.95 * lobes * (1.0 - 0.4 * warm)], -1)
+    return rgb.astype(np.float32)
+
+
+def projector_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0)):
+    """The mapped lights' scene, array for array what scenes/projector_cornell.pbrt loads to: spot_scene's box and spheres
+    WITHOUT its spot lights, a projection light in front of the box's opening that throws procedural_slide onto the back wall (it looks along
+    the world's +y with +z up: the light's +x is the world's -x), and a goniometric light under the ceiling whose pole is the world's +z and
+    whose map is procedural_gonio -- so a matte vertex and a plastic vertex both sample a mapped light of each kind."""
+    from .api import WRAP_CLAMP, WRAP_REPEAT, goniometric_light, image_texture_row, plastic_material, projection_light
+    sd = spot_scene(xres, yres, crop)
+    slide, gonio = procedural_slide(), procedural_gonio()
+    frame = [[-1, 0, 0], [0, 0, 1], [0, 1, 0]]  # world_to_light: the rows are the light's x, y, z axes in world space
+    lights, maps = zip(projection_light((0.0, -0.95, 0.1), 1, (12.0, 12.0, 12.0), 40.0, slide.shape[1] / slide.shape[0], frame),
+                       goniometric_light((0.3, 0.1, 0.8), 2, (2.5, 2.5, 2.5), frame))
+    sd.lights, sd.light_maps = np.array(lights, np.float32), np.array(maps, np.float32)
+    sd.spot_cones = np.zeros((0, 5), np.float32)
+    sd.textures = np.array([image_texture_row(0, WRAP_CLAMP), image_texture_row(1, WRAP_REPEAT)], np.float32)
+    sd.images = [slide, gonio]
+    return sd.normalized()
+
+
 def procedural_sky(width=64, height=32):
     """A latitude-longitude sky, (height, width, 3) float32 with row 0 at the zenith (+z of the light): a gradient from a blue zenith to a
     pale horizon, a dark ground below it, and a small sun -- radiance (600, 540, 420) in the texels whose centre lies within
@@ -418,12 +464,15 @@ def procedural_planks(width=64, height=64):
 
 def write_demo_textures(directory):
     """scenes/textures/planks.png, the image scenes/textured_cornell.pbrt names: procedural_planks through the library's own PNG writer (the build calls this,
-    build.py ensure_demo_textures: the file is a build product)"""
+    build.py ensure_demo_textures: the file is a build product); and slide.png and gonio.pfm, which scenes/projector_cornell.pbrt names
+    (DESIGN.md 3.23): procedural_slide and procedural_gonio"""
     import os
 
     from .api import write_image
     os.makedirs(directory, exist_ok=True)
     write_image(os.path.join(directory, "planks.png"), procedural_planks())
+    write_image(os.path.join(directory, "slide.png"), procedural_slide())
+    write_image(os.path.join(directory, "gonio.pfm"), procedural_gonio())
 
 
 def image_plane_scene(res=256, image=None, wrap="repeat", filter="bilinear", mapping=(3.0, 3.0, 0.0, 0.0)):

@@ -28,6 +28,12 @@ pub const LIGHT_ENVMAP: u32 = 3;
 // holds the light's cone, a pbrt_hip_spot_cone (first word 6): a unit axis from the light into the cone, cos_total <= cos_start
 pub const LIGHT_SPOT: u32 = 5;
 #[repr(C)] pub struct HipSpotCone { pub kind: u32 /* = 6 */, pub axis: [f32; 3], pub cos_total: f32, pub cos_start: f32, pub pad: [u32; 10] }
+// kind == LIGHT_MAPPED (6; DESIGN.md 3.23: LightSource "projection" / "goniometric"): p = the position, c = I * scale; pad = f32::from_bits(n), n = the
+// 1-based number of the slot of `textures` that holds the light's pbrt_hip_light_map (first word 8): map_kind 0 projection / 1 goniometric, image = the
+// 1-based number of a type-4 slot (a pbrt_hip_image_texture), world_to_light a row-major rotation, inv_tan = 1 / tan(fov / 2) and the screen
+// window's half extents sx, sy (all three 0 for a goniometric map)
+pub const LIGHT_MAPPED: u32 = 6;
+#[repr(C)] pub struct HipLightMap { pub kind: u32 /* = 8 */, pub map_kind: u32, pub image: u32, pub world_to_light: [f32; 9], pub inv_tan: f32, pub sx: f32, pub sy: f32, pub pad: [u32; 1] }
 #[repr(C)] pub struct HipSphere   { pub c: [f32; 3], pub r: f32, pub mat: u32, pub pad: [u32; 3] }
 #[repr(C)] pub struct HipSceneDesc {
     pub p: *const f32, pub idx: *const u32, pub mat_id: *const u16,

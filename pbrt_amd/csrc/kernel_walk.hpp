@@ -217,6 +217,24 @@ __device__ __forceinline__ void quad_step(const uint4 W0, const uint4 W1, const 
   }
 }
 
+// The control code of trav_run below: how its scheduling decisions are formed, not what they decide (DESIGN.md section 6, row r08a:
+// C3 -4.3 % frame time, films and counters unchanged).  One switch per part puts the earlier form back for an A-B; with all of them
+// set the kernels are the earlier machine code byte for byte (pbrt_amd/isa_id.py):
+//   PBRT_WALK_MASKS_OLD      every decision ballots a bool of its own, `alive` included, in every iteration      (worth 1.0 % on C3)
+//   PBRT_WALK_ROTATE_OLD     the exit test at the loop's head, two breaks                                          (0.9 %)
+//   PBRT_WALK_LEAF_LOOP_OLD  the leaf pass is the counted loop for every tree                                      (2.6 %)
+// (A fourth part, the push stride kept in a register instead of a literal moved into one in every step, measured 0.0 % and is not here.)
+// wave_vote: the lanes for which a PER-LANE predicate holds, as the compare's own mask.  (__ballot goes through an int: the compiler
+// materialises 0 / 1 in a register and compares it again, two vector instructions per vote on a mask that already sits in scalar
+// registers.)  A predicate that is a function of votes already taken is formed from their masks on the scalar unit and not voted again.
+__device__ __forceinline__ unsigned long long wave_vote(bool p) {
+#ifdef PBRT_WALK_MASKS_OLD
+  return __ballot(p);
+#else
+  return __builtin_amdgcn_ballot_w64(p);
+#endif
+}
+
 // The traversal loop of a whole wave ("while-while" with parked leaves) over the child-pair nodes.
 // Every lane walks its own ray through the binary tree of DESIGN.md 3.3 in the order of 3.4 (near
 // child by the sign of the split axis first, far child pushed); one step fetches ONE 64-byte record
@@ -255,15 +273,40 @@ __device__ __forceinline__ void trav_run(const DevScene &S, Trav &T, uint32_t *s
   const char *nodes = reinterpret_cast<const char *>(S.nodes);
   const char *quads = reinterpret_cast<const char *>(S.quads);
   const char *tris = reinterpret_cast<const char *>(S.tris);
+#ifndef PBRT_WALK_MASKS_OLD
+  // `alive` does not change in here: its vote, and the walkers the exit test asks for, are taken once
+  const unsigned long long malive = wave_vote(alive);
+  const uint32_t walkers_x64 = tune.min_walkers * (uint32_t)__popcll(malive);
+#endif
+#ifndef PBRT_WALK_ROTATE_OLD
+  // The loop is rotated: the exit test stands once before it and once at its bottom, so that the loop has one exit, behind its last
+  // statement, and the walk state stays in one set of registers (with the test at the head and two breaks below it the compiler kept
+  // T.cur, T.sp and the hit record in two sets and copied them across at the head and at every way round: eight v_mov per batch).
+  const auto go_on = [&]() -> bool {
+    const bool walking = T.cur != kDone;
+    const unsigned long long mwalk = wave_vote(walking);
+#ifdef PBRT_WALK_MASKS_OLD
+    return mwalk != 0ull && !((uint32_t)__popcll(mwalk) * 64u < tune.min_walkers * (uint32_t)__popcll(__ballot(alive)) && __ballot(!walking && alive) != 0ull);
+#else
+    return mwalk != 0ull && !((uint32_t)__popcll(mwalk) * 64u < walkers_x64 && (malive & ~mwalk) != 0ull);  // (alive and not walking: waiting to be served)
+#endif
+  };
+  if (go_on()) do {
+#else
   for (;;) {
     const bool walking = T.cur != kDone;
-    const unsigned long long mwalk = __ballot(walking);
+    const unsigned long long mwalk = wave_vote(walking);
     if (mwalk == 0ull) break;
     // (min_walkers is meant for a full wave: it scales with the lanes that still have work at all, so that a wave whose
     // pixel list has run dry does not visit the service stage for every single ray)
+#ifdef PBRT_WALK_MASKS_OLD
     if ((uint32_t)__popcll(mwalk) * 64u < tune.min_walkers * (uint32_t)__popcll(__ballot(alive)) && __ballot(!walking && alive) != 0ull) break;
+#else
+    if ((uint32_t)__popcll(mwalk) * 64u < walkers_x64 && (malive & ~mwalk) != 0ull) break;  // (alive and not walking: waiting to be served)
+#endif
+#endif
 
-    if (EXACT && walking && !trav_parked(T)) {
+    if (EXACT && T.cur != kDone && !trav_parked(T)) {
       // ---- one step: both children of interior node T.cur ----
       const uint32_t off = T.cur * 64u;
       const uint4 q0 = *reinterpret_cast<const uint4 *>(nodes + off);
@@ -352,7 +395,7 @@ __device__ __forceinline__ void trav_run(const DevScene &S, Trav &T, uint32_t *s
       // compare against a constant: the stack array's base is a link-time constant, the lane's column offset is
       // smaller than a row.  A test per batch of steps instead, with a threshold three times as far from the end,
       // measured 1.5 % slower.  __builtin_expect moves the slow form out of line: the fast form falls through, +1.2 %.)
-      if (OVFR != 0u && __builtin_expect(__ballot(T.sp >= lds_addr(stk - (threadIdx.x & 63u)) + (OVFR - 4u) * kRowBytes) != 0ull, 0)) {
+      if (OVFR != 0u && __builtin_expect(wave_vote(T.sp >= lds_addr(stk - (threadIdx.x & 63u)) + (OVFR - 4u) * kRowBytes) != 0ull, 0)) {
         if (hit[3] && !n3) trav_push<OVFR>(T, stk, ovf, W3.w);
         if (hit[2] && !n2) trav_push<OVFR>(T, stk, ovf, W3.z);
         if (hit[1] && !n1) trav_push<OVFR>(T, stk, ovf, W3.y);
@@ -379,61 +422,51 @@ __device__ __forceinline__ void trav_run(const DevScene &S, Trav &T, uint32_t *s
 
     // ---- leaf flush (wave-uniform decision) ----
     const bool parked = trav_parked(T);
-    const unsigned long long mleaf = __ballot(parked);
+    const unsigned long long mleaf = wave_vote(parked);
     if (mleaf != 0ull &&
         ((uint32_t)__popcll(mleaf) >= tune.min_parked ||
          // ... or when the parked lanes are at least half as many as the lanes that can still step (with few
          // steppers left, waiting for min_parked only idles the parked ones; this also covers "nobody can step")
-         (uint32_t)__popcll(mleaf) * 2u >= (uint32_t)__popcll(__ballot(T.cur != kDone && !parked)))) {
+         (uint32_t)__popcll(mleaf) * 2u >= (uint32_t)__popcll(wave_vote(T.cur != kDone && !parked)))) {
       const uint32_t cnt = parked ? (T.cur >> 24) & 0x7fu : 0u, first = T.cur & 0xffffffu;
       bool stop = false;  // any-hit ray found its hit
       EXP_LEAF_PREFETCH_BEGIN(parked, quads, T);
       EXP_PROBE_FLUSH(cnt);
-      for (uint32_t i = 0;; i++) {
-        if (__ballot(cnt > i && !stop) == 0ull) break;
+#ifndef PBRT_WALK_LEAF_LOOP_OLD
+      // The production walk's trees have single-triangle leaves (a leaf of 2 .. 4 triangles is a quad node of them,
+      // quad_nodes.cpp splittable; the device builder makes no other leaf) and empty ones.  So the pass is the body once, straight-line,
+      // and the hit record is updated by selects where it lives; the counted loop, out of line behind one vote, goes on from the
+      // second triangle for a tree that was built with larger leaves.  The exact walk's leaves are the canonical tree's: the loop alone.
+      constexpr uint32_t kStraight = EXACT ? 0u : 1u;
+      if (!EXACT) {
+        constexpr uint32_t i = 0u;
+        EXP_PROBE_LANES(2, cnt != 0u);
+        if (cnt != 0u) {  // (an empty leaf, kEmptyLeafRef, tests nothing and pops)
+#include "leaf_test.inc"
+        }
+      }
+      if (EXACT || __builtin_expect(wave_vote(cnt > 1u) != 0ull, 0))
+#else
+      constexpr uint32_t kStraight = 0u;
+#endif
+      for (uint32_t i = kStraight;; i++) {
+        if (wave_vote(cnt > i && !stop) == 0ull) break;
         EXP_PROBE_LANES(2, cnt > i && !stop);
         if (cnt > i && !stop) {
-          const uint32_t slot = first + i;
-          wave_prio(PBRT_PRIO_FETCH);  // (as for the node fetch)
-          const float4 a = EXP_TRI_LOAD(reinterpret_cast<const float4 *>(tris + slot * (16u * kTriStride)));
-          const float4 b = EXP_TRI_LOAD(reinterpret_cast<const float4 *>(tris + slot * (16u * kTriStride) + 16u));
-          const float4 c = EXP_TRI_LOAD(reinterpret_cast<const float4 *>(tris + slot * (16u * kTriStride) + 32u));
-          wave_prio(PBRT_PRIO_ARITH);
-          if (COUNT) ct++;
-#include "tri_test.inc"
-          float ht = tsnap, hu = u, hv = v;
-          if (SPH && __float_as_uint(c.w) != 0u) {
-            // a SPHERE's record (round 6: spheres are primitives of the tree): {centre, primitive id}{radius, -, -, material}
-            // {-, -, -, 1}.  Sphere::Intersect with the f64 quadratic of lib.rs:181-203, then the own-box rule on [c - r, c + r] (the
-            // "vertices" lo, hi, lo) exactly as for a triangle.
-            const float r = b.x;
-            float ts = 0.f;
-            valid = sphere_hit(make_float4(a.x, a.y, a.z, r), o, d, T.tmax, ts);
-            const V3 lo = {a.x - r, a.y - r, a.z - r}, hi = {a.x + r, a.y + r, a.z + r};
-            const float sx0 = (lo.x - o.x) * inv1.x, sx1 = (hi.x - o.x) * inv1.x, sy0 = (lo.y - o.y) * inv1.y, sy1 = (hi.y - o.y) * inv1.y;
-            const float sz0 = (lo.z - o.z) * inv1.z, sz1 = (hi.z - o.z) * inv1.z;
-            const float stn = fmaxf(fmaxf(fminf(fminf(sx0, sx1), sx0), fminf(fminf(sy0, sy1), sy0)), fmaxf(fminf(fminf(sz0, sz1), sz0), kRayTMin));
-            const float stf = fminf(fminf(fmaxf(fmaxf(sx0, sx1), sx0), fmaxf(fmaxf(sy0, sy1), sy0)), fmaxf(fmaxf(sz0, sz1), sz0));
-            ht = fmaxf(ts, stn);
-            valid = valid && stn <= stf * kOwnPad && ht < T.tmax;
-            hu = 0.f; hv = 0.f;
-          }
-          const uint32_t id = __float_as_uint(a.w);
-          const bool occl = valid && T.any != 0u;  // any-hit ray: the walk ends at the first valid hit
-          const bool closer = valid && T.any == 0u && (ht < T.h.t || (ht == T.h.t && id < T.h.prim));
-          T.any = occl ? 3u : T.any;
-          stop = stop || occl;
-          T.h.t = closer ? ht : T.h.t;
-          T.h.prim = closer ? id : T.h.prim;
-          T.h.slot = closer ? slot : T.h.slot;
-          T.h.b1 = closer ? hu : T.h.b1;
-          T.h.b2 = closer ? hv : T.h.b2;
+#include "leaf_test.inc"
         }
       }
       EXP_LEAF_PREFETCH_END();
       // (OVF: is any entry about to be popped one of the rare ones beyond the LDS part?  wave-uniform, as for the pushes)
+#ifdef PBRT_WALK_MASKS_OLD
       const bool far_pop = OVFR != 0u && !EXACT &&
                            __ballot(parked && !stop && T.sp >= lds_addr(stk - (threadIdx.x & 63u)) + OVFR * kRowBytes) != 0ull;
+#else
+      // (the vote is the compare's own mask, met with the parked lanes' on the scalar unit.  A lane that stops no longer counts out: the
+      // test only picks the FORM of the pop for the wave, each lane takes its own way through either, and an any-hit ray that ends
+      // with a stack that deep is as rare as the deep stack itself.)
+      const bool far_pop = OVFR != 0u && !EXACT && (wave_vote(T.sp >= lds_addr(stk - (threadIdx.x & 63u)) + OVFR * kRowBytes) & mleaf) != 0ull;
+#endif
       if (parked) {  // leave the leaf: the walk is over (any-hit found) or the next node comes off the stack
         if (stop) {
           T.cur = kDone;
@@ -445,7 +478,11 @@ __device__ __forceinline__ void trav_run(const DevScene &S, Trav &T, uint32_t *s
         }
       }
     }
+#ifndef PBRT_WALK_ROTATE_OLD
+  } while (go_on());
+#else
   }
+#endif
 }
 
 }  // namespace

@@ -43,6 +43,7 @@ typedef enum {
 #define PBRT_HIP_MATERIAL_MIRROR 1u
 #define PBRT_HIP_MATERIAL_GLASS 2u
 #define PBRT_HIP_MATERIAL_PLASTIC 3u
+#define PBRT_HIP_MATERIAL_SUBSTRATE 4u
 /* Material "matte" / "mirror" / "glass" (scene files name them: scenes/check-sphere.pbrt:21,29; the
  * reference only has the TODO at api.rs:255-269).  32 bytes.
  * GLASS (type 2) is pbrt-v3's GlassMaterial with zero roughness: one FresnelSpecular lobe, an interface between index 1
@@ -62,13 +63,21 @@ typedef enum {
  * draws what a matte one draws, in the same order; its lobe is about the GEOMETRIC normal.  Rendered for every integrator, sampler and
  * filter, with spheres, textures on other materials, glass; NOT in a scene whose texture table holds an environment map (slot type 1) or
  * shading normals (slot type 2): pbrt_hip_scene_create refuses the pair with PBRT_HIP_ERR_LIMIT (the message holds "plastic").  Not with
- * the counter flags (PBRT_HIP_ERR_LIMIT at render, as for glass). */
+ * the counter flags (PBRT_HIP_ERR_LIMIT at render, as for glass).
+ * SUBSTRATE (type 4) is pbrt-v3's SubstrateMaterial, a FresnelBlend BSDF: a diffuse base Kd (1 - Ks) that darkens at grazing
+ * angles under a glossy coat, one Trowbridge-Reitz lobe of isotropic width alpha with Schlick's Fresnel term on Ks and no masking term.  The
+ * record is reused as plastic reuses it:
+ *   k = Kd, le = Ks (a substrate surface does not emit), kd_tex = the IEEE-754 bits of the float alpha.
+ * Kd finite and >= 0, Ks finite and in [0, 1] (beyond 1 the factor 1 - Ks makes the BSDF negative), alpha finite and in [1e-3, 1]
+ * (PBRT_HIP_ERR_INVALID otherwise, the message holds "substrate").  A substrate vertex draws what a plastic one draws, in the same order,
+ * from the same direction sampler; it is rendered where plastic is and refused where plastic is (PBRT_HIP_ERR_LIMIT beside an environment
+ * map or shading normals, the message holds "substrate"; the counter flags as for glass).  Type 5 and above are unknown material types. */
 typedef struct {
-  uint32_t type; /* PBRT_HIP_MATERIAL_*: 0 = matte (Lambertian, k = Kd), 1 = mirror (perfect specular, k = Kr), 2 = glass, 3 = plastic (above) */
+  uint32_t type; /* PBRT_HIP_MATERIAL_*: 0 = matte (Lambertian, k = Kd), 1 = mirror (perfect specular, k = Kr), 2 = glass, 3 = plastic, 4 = substrate (above) */
   float k[3];
   float le[3]; /* emitted radiance; non-zero turns every triangle using it into an area light
-                  (replaces api.rs:476-478 area_light_source -> todo!()).  GLASS: Kt.  PLASTIC: Ks */
-  uint32_t kd_tex; /* GLASS: the bits of the float eta.  PLASTIC: the bits of the float alpha.  Matte only: 0 = Kd is k; t > 0 = Kd is textures[t - 1] evaluated at the hit's (u, v): a triangle's corner (u, v)
+                  (replaces api.rs:476-478 area_light_source -> todo!()).  GLASS: Kt.  PLASTIC, SUBSTRATE: Ks */
+  uint32_t kd_tex; /* GLASS: the bits of the float eta.  PLASTIC, SUBSTRATE: the bits of the float alpha.  Matte only: 0 = Kd is k; t > 0 = Kd is textures[t - 1] evaluated at the hit's (u, v): a triangle's corner (u, v)
                       (tri_uv) interpolated like the hit point; a SPHERE's own (u, v) = (phi / 2 pi, 1 - theta / pi) with phi = atan2(n.y, n.x)
                       in [0, 2 pi), theta = acos(n.z) of the unit normal n about the WORLD's z axis (pbrt-v3 Sphere::Intersect for an
                       unrotated sphere: a sphere here is a centre and a radius, its CTM's rotation is not carried -- the parser warns) */
@@ -351,7 +360,8 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.12 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10 and 0.11)": 0.12 = light type 6, a mapped light, and
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.13 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10, 0.11 and 0.12)": 0.13 = material type 4, substrate, inside
+                                       the same struct sizes; 0.12 = light type 6, a mapped light, and
                                        texture-table slot type 8, its record, inside the same struct sizes; 0.11 = material type 3, plastic, inside
                                        the same struct sizes; 0.10 = texture-table slot type 4, the
                                        image texture, inside the same struct sizes; 0.9 = texture-table slot type 3, the pixel

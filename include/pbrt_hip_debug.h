@@ -212,6 +212,14 @@ int pbrt_hip_image_lookup_eval_device(int device, const pbrt_hip_image_texture *
 #define PBRT_HIP_PLASTIC_EVAL_OUT 10
 int pbrt_hip_plastic_eval_device(int device, int64_t n, const float *in, float *out);
 
+/* ---- the substrate material's BSDF (pbrt_amd/csrc/substrate_bsdf.hpp is the one statement of the arithmetic) ---- */
+/* substrate_bsdf.hpp over arrays on `device` (a small kernel of kernels_blocks.hip), in pbrt_hip_plastic_eval_device's layout: 18 floats
+ * in -- nf, wo, wi, u1, u2, Kd.rgb, Ks.rgb, alpha --, 10 floats out -- f(wo, wi).rgb, pdf_b(wi), the sampled wi', f(wo, wi') cos /
+ * pdf_b(wi').rgb (the last six zero where the sample dies).  in / out are HOST arrays.  The same refusals. */
+#define PBRT_HIP_SUBSTRATE_EVAL_IN 18
+#define PBRT_HIP_SUBSTRATE_EVAL_OUT 10
+int pbrt_hip_substrate_eval_device(int device, int64_t n, const float *in, float *out);
+
 /* ---- the spot light's sample (pbrt_amd/csrc/spot_light.hpp is the one statement of the arithmetic) ---- */
 /* spot_light.hpp over arrays on `device` (a small kernel of kernels_blocks.hip): element i reads 15 floats of `in` -- the shading point po,
  * its normal nf, the light's position p, the cone's axis, cos_total, cos_start, nL (the scene's light count as a float) -- and writes 7

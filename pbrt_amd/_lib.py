@@ -188,6 +188,7 @@ SYMBOLS = {
     "pbrt_hip_image_lookup_eval_device": (C.c_int, [C.c_int, C.POINTER(ImageTexture), _u32, _u32, _i64, _pf, _pf]),
     "pbrt_hip_blocks_eval_device": (C.c_int, [C.c_int, _u32, _i64, _pf, _pf]),
     "pbrt_hip_plastic_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
+    "pbrt_hip_substrate_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
     "pbrt_hip_spot_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
     "pbrt_hip_light_map_eval_device": (C.c_int, [C.c_int, C.POINTER(ImageTexture), C.POINTER(LightMap), _i64, _pf, _pf]),
     "pbrt_hip_shading_normal_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),

@@ -13,6 +13,7 @@ from ._lib import EnvMap, ImageTexture, Light, LightMap, Material, Normals, Pixe
 
 MATTE, MIRROR, GLASS = 0, 1, 2  # PBRT_HIP_MATERIAL_*; GLASS: DESIGN.md 3.16
 PLASTIC = 3  # PBRT_HIP_MATERIAL_PLASTIC: DESIGN.md 3.21
+SUBSTRATE = 4  # PBRT_HIP_MATERIAL_SUBSTRATE: DESIGN.md 3.24
 LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2
 LIGHT_ENVMAP = 3  # PBRT_HIP_LIGHT_ENVMAP: the infinite light with an environment map
 LIGHT_SPOT = 5  # PBRT_HIP_LIGHT_SPOT: a point light inside a cone with a smooth edge; 4 is no light type
@@ -53,7 +54,7 @@ class SceneData:
     dv), `tri_uv` rows: (u0, v0, u1, v1, u2, v2) per triangle (needed when a triangle's material is textured).  Glass:
     a `materials` row (GLASS, Kr rgb, Kt rgb) -- a glass surface does not emit -- and `mat_eta[i]` = its index of refraction (an empty
     `mat_eta` = 1.5 for every glass row; the entries of other rows are not read).  Plastic: a `materials` row (PLASTIC, Kd rgb,
-    Ks rgb) and `mat_eta[i]` = its alpha, the float that rides where glass keeps eta (plastic_material makes the pair).  An environment map: a `lights` row
+    Ks rgb) and `mat_eta[i]` = its alpha, the float that rides where glass keeps eta (plastic_material makes the pair).  Substrate: a row (SUBSTRATE, Kd rgb, Ks rgb) and its alpha likewise (substrate_material).  An environment map: a `lights` row
     (LIGHT_ENVMAP, 0, 0, 0, c rgb) -- c the factor on the texels -- and `envmap` = its (H, W, 3) texels, row 0 = the light's +z, with
     `envmap_world_to_light` = the 3 x 3 rotation; the record travels in a slot appended to the texture table (fill_desc).  Shading normals
     (DESIGN.md 3.18): `tri_n` rows: the normals of a triangle's three corners (n0 xyz, n1 xyz, n2 xyz), world space, any length, zeros = the
@@ -141,7 +142,7 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         if int(m[0]) == GLASS:  # include/pbrt_hip.h: k = Kr, le = Kt, kd_tex = the IEEE-754 bits of eta
             eta = sd.mat_eta[i:i + 1] if len(sd.mat_eta) else np.array([1.5], np.float32)
             mats[i].kd_tex = int(eta.view(np.uint32)[0])
-        if int(m[0]) == PLASTIC:  # k = Kd, le = Ks, kd_tex = the IEEE-754 bits of alpha
+        if int(m[0]) in (PLASTIC, SUBSTRATE):  # k = Kd, le = Ks, kd_tex = the IEEE-754 bits of alpha
             mats[i].kd_tex = int(sd.mat_eta[i:i + 1].view(np.uint32)[0]) if len(sd.mat_eta) else 0  # (no alpha given: 0, which scene creation refuses)
     # the table: every `textures` row in its own slot (mat_tex numbering does not move), then the records that travel with the scene, each in a
     # slot of its own -- the map's, the pixel filter's, the spot lights' cones, the mapped lights' records, the normals' (include/pbrt_hip.h
@@ -289,6 +290,22 @@ def spot_eval_device(x, device=0):
     x = np.ascontiguousarray(x, np.float32).reshape(-1, 15)
     out = np.zeros((x.shape[0], 7), np.float32)
     check(lib().pbrt_hip_spot_eval_device(int(device), x.shape[0], _fp(x), _fp(out)), "pbrt_hip_spot_eval_device")
+    return out
+
+
+def substrate_material(kd=(0.5, 0.5, 0.5), ks=(0.5, 0.5, 0.5), uroughness=0.1, vroughness=0.1, remap=True):
+    """-> (the `materials` row (SUBSTRATE, Kd, Ks), alpha for `mat_eta`) of Material "substrate" with these parameters (pbrt-v3's defaults), as
+    the scene parser forms them: Ks clamped to 1, alpha = sqrt(alpha_u alpha_v) in double, rounded to float32"""
+    import math
+    au, av = (float(roughness_to_alpha(r, remap)) for r in (uroughness, vroughness))
+    return [SUBSTRATE, *kd, *(min(float(np.float32(v)), 1.0) for v in ks)], np.float32(math.sqrt(au * av))
+
+
+def substrate_eval_device(x, device=0):
+    """pbrt_hip_substrate_eval_device: csrc/substrate_bsdf.hpp over arrays on the device, in plastic_eval_device's layout"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 18)
+    out = np.zeros((x.shape[0], 10), np.float32)
+    check(lib().pbrt_hip_substrate_eval_device(int(device), x.shape[0], _fp(x), _fp(out)), "pbrt_hip_substrate_eval_device")
     return out
 
 

@@ -108,7 +108,9 @@ constexpr float kPlasticAlphaMin = 1e-3f, kPlasticAlphaMax = 1.0f;
 // how far a spot cone's axis may be from unit length, as a squared length
 constexpr float kSpotAxisTolerance = 1e-4f;
 // the materials that reuse `le` and `kd_tex` for parameters of their own: they do not emit and name no texture
-bool reuses_le(const pbrt_hip_material &m) { return m.type == PBRT_HIP_MATERIAL_GLASS || m.type == PBRT_HIP_MATERIAL_PLASTIC; }
+bool reuses_le(const pbrt_hip_material &m) {
+  return m.type == PBRT_HIP_MATERIAL_GLASS || m.type == PBRT_HIP_MATERIAL_PLASTIC || m.type == PBRT_HIP_MATERIAL_SUBSTRATE;
+}
 
 // ---- check_scene_desc in stages: every refusal that depends on the description alone, before any HIP call.  Which of two faults is
 // reported is part of the behaviour, so a concern whose refusals lie apart in that order has a stage for each part: the lights' and the
@@ -275,7 +277,7 @@ int check_kd_tex(const pbrt_hip_scene_desc *d, const TextureTable &table) {
 }
 int check_material_kinds(const pbrt_hip_scene_desc *d) {
   for (uint32_t i = 0; i < d->n_mats; i++)
-    if (d->mats[i].type > PBRT_HIP_MATERIAL_PLASTIC) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
+    if (d->mats[i].type > PBRT_HIP_MATERIAL_SUBSTRATE) return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown material type");
   // (a plastic record is checked HERE, where its kind is recognised -- the place a type-3 record was refused as unknown before there was
   // plastic --, so that every fault that used to win against it still does)
   for (uint32_t i = 0; i < d->n_mats; i++) {  // plastic: k = Kd, le = Ks, kd_tex = the bits of alpha
@@ -292,17 +294,34 @@ int check_material_kinds(const pbrt_hip_scene_desc *d) {
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": plastic alpha (the float in kd_tex) must be finite and lie in [1e-3, 1]; "
                   "type 3 is plastic since 0.11, to a caller that meant anything else it is an unknown material type");
   }
+  for (uint32_t i = 0; i < d->n_mats; i++) {  // substrate: the record as plastic reuses it; 1 - Ks must not go negative
+    const pbrt_hip_material &m = d->mats[i];
+    if (m.type != PBRT_HIP_MATERIAL_SUBSTRATE) continue;
+    for (int k = 0; k < 3; k++) {
+      if (!std::isfinite(m.k[k]) || !(m.k[k] >= 0.f))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": substrate Kd must be finite and >= 0");
+      if (!std::isfinite(m.le[k]) || !(m.le[k] >= 0.f && m.le[k] <= 1.0f))
+        return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": substrate Ks must be finite and lie in [0, 1]");
+    }
+    const float alpha = plastic_alpha(m);
+    if (!std::isfinite(alpha) || !(alpha >= kPlasticAlphaMin && alpha <= kPlasticAlphaMax))
+      return fail(PBRT_HIP_ERR_INVALID, "scene_create: material " + std::to_string(i) + ": substrate alpha (the float in kd_tex) must be finite and lie in [1e-3, 1]");
+  }
   return PBRT_HIP_OK;
 }
 // plastic is rendered by the GLS instantiations of render_kernel_x alone: the families that render an environment map or
-// shading normals do not carry its branch, and the scene is refused here, not at render time
+// shading normals do not carry its branch, and the scene is refused here, not at render time.  Substrate (3.24) shares the branch and the
+// refusal, each under its own name (plastic's first: a scene with both keeps the message it had)
 int check_plastic_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
-  bool plastic = false;
-  for (uint32_t i = 0; i < d->n_mats && !plastic; i++) plastic = d->mats[i].type == PBRT_HIP_MATERIAL_PLASTIC;
-  if (!plastic) return PBRT_HIP_OK;
-  for (const SlotKind kind : table.kinds) {
-    if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a plastic material is not available in a scene with an environment map");
-    if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a plastic material is not available in a scene with shading normals");
+  for (const uint32_t type : {PBRT_HIP_MATERIAL_PLASTIC, PBRT_HIP_MATERIAL_SUBSTRATE}) {
+    bool present = false;
+    for (uint32_t i = 0; i < d->n_mats && !present; i++) present = d->mats[i].type == type;
+    if (!present) continue;
+    const std::string name = type == PBRT_HIP_MATERIAL_PLASTIC ? "plastic" : "substrate";
+    for (const SlotKind kind : table.kinds) {
+      if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a " + name + " material is not available in a scene with an environment map");
+      if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a " + name + " material is not available in a scene with shading normals");
+    }
   }
   return PBRT_HIP_OK;
 }
@@ -509,7 +528,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, Scen
   }
   for (uint32_t t = 0; t < d.n_tris; t++) {
     const pbrt_hip_material &m = d.mats[d.mat_id[t]];
-    if (reuses_le(m)) continue;  // (its le is Kt / Ks: glass and plastic do not emit)
+    if (reuses_le(m)) continue;  // (its le is Kt / Ks: glass, plastic and substrate do not emit)
     if (!(m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) continue;
     F3 p[3];
     for (int v = 0; v < 3; v++) {
@@ -534,7 +553,7 @@ void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, Scen
       if (in->glass.empty()) in->glass.assign(d.n_mats, make_float4(0.f, 0.f, 0.f, 1.f));
       in->glass[i] = make_float4(m.le[0], m.le[1], m.le[2], glass_eta(m));
     }
-    if (m.type == PBRT_HIP_MATERIAL_PLASTIC) {  // the same table carries {Ks, alpha}: no emission, no texture word
+    if (m.type == PBRT_HIP_MATERIAL_PLASTIC || m.type == PBRT_HIP_MATERIAL_SUBSTRATE) {  // the same table carries {Ks, alpha}: no emission, no texture word
       in->mats[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (in->glass.empty()) in->glass.assign(d.n_mats, make_float4(0.f, 0.f, 0.f, 1.f));
       in->glass[i] = make_float4(m.le[0], m.le[1], m.le[2], plastic_alpha(m));
@@ -739,7 +758,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.12 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10 and 0.11)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.13 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10, 0.11 and 0.12)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif

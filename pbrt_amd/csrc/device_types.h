@@ -208,7 +208,8 @@ struct RenderParams {
   const float4 *textures;
   // glass materials (render_kernel_x<..., GLS>): 16 B per MATERIAL {Kt.rgb, eta}, read for the materials of type 2 alone
   // (mats[2 i] = {2, Kr}, mats[2 i + 1] = 0: glass does not emit).  At the end, for the reason given above.
-  // A plastic material's row (type 3) is {Ks.rgb, alpha}, read by the same instantiations (mats[2 i] = {3, Kd}).
+  // A plastic material's row (type 3) is {Ks.rgb, alpha}, read by the same instantiations (mats[2 i] = {3, Kd}); a
+  // substrate material's (type 4, 3.24) likewise.
   const float4 *glass;
   // an environment-map infinite light (render_kernel_env): the texels {r, g, b, p_uv} row-major (row 0 = theta 0), the
   // marginal CDF over rows (env_h + 1 floats) and the rows' conditional CDFs (env_h x (env_w + 1)), world_to_light (row-major 3 x 3) and

@@ -6,6 +6,7 @@
 #include "kernel_walk.hpp"
 #include "light_map.hpp"
 #include "plastic_bsdf.hpp"
+#include "substrate_bsdf.hpp"
 #include "spot_light.hpp"
 
 namespace pbrt_hip {

@@ -117,7 +117,7 @@
             }
             m0 = S.mats[2 * mid];
             m1 = S.mats[2 * mid + 1];
-            if (GLS && (__float_as_uint(m0.x) == 2u || (PLS && __float_as_uint(m0.x) == 3u))) gl = R.glass[mid];  // (PLS: {Ks, alpha} of a plastic material, 3.21)
+            if (GLS && (__float_as_uint(m0.x) == 2u || (PLS && __float_as_uint(m0.x) - 3u <= 1u))) gl = R.glass[mid];  // (PLS: {Ks, alpha} of a plastic or a substrate material, 3.21, 3.24)
           }
           if (P.bounces == 0 || P.specular) {
             if (hit) {
@@ -271,11 +271,13 @@
                 // MIS: the pending light sample and, beside it, the density the bounce ray was drawn with (read where it lands)
                 if (MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, z * kInvPi));
               }
-            } else if (PLS && __float_as_uint(m0.x) == 3u) {
-              // plastic (DESIGN.md 3.21; plastic_bsdf.hpp): k = Kd, gl = {Ks, alpha}.  The requests of a matte vertex in their order -- the
+            } else if (PLS && __float_as_uint(m0.x) - 3u <= 1u) {  // (types 3 and 4 by ONE compare)
+              // plastic (DESIGN.md 3.21; plastic_bsdf.hpp) and substrate (3.24; substrate_bsdf.hpp: the same direction sampler, another f; only
+              // the BSDF inside the eval / sample_f calls is chosen by the type word): k = Kd, gl = {Ks, alpha}.  The requests of a matte vertex in their order -- the
               // pick, the light's pair, the bounce's pair --; the light sample carries f(wo, wi) in the Lambertian factor's place and, with
               // MIS, the weight against THIS BSDF's density; the bounce keeps its density beside the pending light sample as matte does
               const V3 ks = mk(gl.x, gl.y, gl.z);
+              const bool coat = __float_as_uint(m0.x) == 4u;  // substrate
               if (nL > 0u) {
                 const float xi = sample_1d<SND>(P, sobol, spp_mask, R.sobol_mat, halton);
                 float u1, u2;
@@ -287,7 +289,7 @@
                 if (sample_light_general(S, R.textures, R.image_texels, li, po, nf, u1, u2, nLf, Lg, sh_d, sh_tmax, pl)) {
                   V3 f;
                   float pbl;
-                  plastic::eval(nf, wo, sh_d, k, ks, gl.w, f, pbl);
+                  coated::eval(coat, nf, wo, sh_d, k, ks, gl.w, f, pbl);
                   V3 Ld = f * Lg;
                   if (MIS && pl > 0.f) {
                     // (the constant infinite light keeps 3.14's constant pair of weights, 1 / (1 + nL^2) here and nL^2 / (nL^2 + 1) where a
@@ -306,7 +308,7 @@
                 sample_2d<SND>(P, sobol, spp_mask, u1, u2, R.sobol_mat, halton);
                 V3 wgt;
                 float pb;
-                if (!plastic::sample_f(nf, wo, u1, u2, k, ks, gl.w, P.wi_next, wgt, pb)) alive = false;
+                if (!coated::sample_f(coat, nf, wo, u1, u2, k, ks, gl.w, P.wi_next, wgt, pb)) alive = false;
                 else { P.beta = P.beta * wgt; P.specular = false; }
                 if (MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, pb));
               }

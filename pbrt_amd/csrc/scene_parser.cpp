@@ -355,6 +355,23 @@ struct Api {
     return false;
   }
 
+  // alpha of a microfacet lobe from a roughness: pbrt-v3 TrowbridgeReitzDistribution::RoughnessToAlpha where `remap`, in
+  // double, rounded to float and clamped to what pbrt_hip_scene_create takes (a NaN goes to the lower end)
+  float roughness_to_alpha(const char *material, double rough, bool remap) {
+    double a = rough;
+    if (remap) {
+      const double x = std::log(std::max(rough, 1e-3));
+      a = 1.62142 + 0.819955 * x + 0.1734 * x * x + 0.0171201 * x * x * x + 0.000640711 * x * x * x * x;
+    }
+    float alpha = (float)a;
+    if (!(alpha >= 1e-3f && alpha <= 1.0f)) {
+      alpha = alpha > 1.0f ? 1.0f : 1e-3f;
+      warn(std::string("Material \"") + material + "\": the roughness gives alpha " + std::to_string(a) + ", clamped to " + (alpha == 1.0f ? "1" : "1e-3") +
+           " (alpha lies in [1e-3, 1])");
+    }
+    return alpha;
+  }
+
   MaterialDef make_material(const std::string &type, const ParamSet &ps) {
     MaterialDef m;
     if (type == "matte") {
@@ -395,18 +412,33 @@ struct Api {
       spectrum(ps, "Ks", m.kt);
       if (ps.find("roughness", "texture")) warn("Material \"plastic\": a \"roughness\" texture is not supported, the default roughness 0.1 is used");
       const double rough = ps.one_float("roughness", 0.1f);
-      double a = rough;
-      if (ps.one_bool("remaproughness", true)) {  // pbrt-v3 TrowbridgeReitzDistribution::RoughnessToAlpha
-        const double x = std::log(std::max(rough, 1e-3));
-        a = 1.62142 + 0.819955 * x + 0.1734 * x * x + 0.0171201 * x * x * x + 0.000640711 * x * x * x * x;
-      }
-      float alpha = (float)a;
-      if (!(alpha >= 1e-3f && alpha <= 1.0f)) {  // (a NaN goes to the lower end)
-        alpha = alpha > 1.0f ? 1.0f : 1e-3f;
-        warn("Material \"plastic\": the roughness gives alpha " + std::to_string(a) + ", clamped to " + (alpha == 1.0f ? "1" : "1e-3") + " (alpha lies in [1e-3, 1])");
-      }
-      m.eta = alpha;
+      m.eta = roughness_to_alpha("plastic", rough, ps.one_bool("remaproughness", true));
       if (ps.find("bumpmap", "texture", "float")) warn("Material \"plastic\": \"bumpmap\" is ignored (no bump mapping on this path)");
+    } else if (type == "substrate") {
+      // pbrt-v3 SubstrateMaterial: Kd, Ks (default 0.5), "float uroughness" / "vroughness" (default 0.1), "bool
+      // remaproughness" (default true).  Each roughness goes to its alpha as plastic's does; the lobe here is isotropic, alpha = the
+      // geometric mean of the two (in double, rounded to float), which keeps the lobe's peak 1 / (pi alpha_u alpha_v).  Ks above 1 is clamped:
+      // the base is scaled by 1 - Ks.  A texture given as Kd / Ks is reduced to its constant colour; a roughness texture to the default.
+      m.type = PBRT_HIP_MATERIAL_SUBSTRATE;
+      m.kt[0] = m.kt[1] = m.kt[2] = 0.5f;
+      spectrum(ps, "Kd", m.k);
+      spectrum(ps, "Ks", m.kt);
+      bool clamped = false;
+      for (int i = 0; i < 3; i++)
+        if (m.kt[i] > 1.0f) { m.kt[i] = 1.0f; clamped = true; }
+      if (clamped) warn("Material \"substrate\": Ks above 1 is clamped to 1 (the diffuse base is scaled by 1 - Ks)");
+      float a_uv[2];
+      const char *names[2] = {"uroughness", "vroughness"};
+      const bool remap = ps.one_bool("remaproughness", true);
+      for (int i = 0; i < 2; i++) {
+        if (ps.find(names[i], "texture"))
+          warn(std::string("Material \"substrate\": a \"") + names[i] + "\" texture is not supported, the default roughness 0.1 is used");
+        a_uv[i] = roughness_to_alpha("substrate", ps.one_float(names[i], 0.1f), remap);
+      }
+      if (a_uv[0] != a_uv[1])
+        warn("Material \"substrate\": \"uroughness\" and \"vroughness\" differ; the lobe is isotropic, alpha = sqrt(alpha_u alpha_v)");
+      m.eta = (float)std::sqrt((double)a_uv[0] * (double)a_uv[1]);
+      if (ps.find("bumpmap", "texture", "float")) warn("Material \"substrate\": \"bumpmap\" is ignored (no bump mapping on this path)");
     } else {
       warn("Material \"" + type + "\" is not supported by this path: using matte Kd 0.5");
     }
@@ -414,7 +446,8 @@ struct Api {
   }
 
   uint16_t material_id(const MaterialDef &m, const float le[3]) {
-    const bool glass = m.type == PBRT_HIP_MATERIAL_GLASS || m.type == PBRT_HIP_MATERIAL_PLASTIC;  // (the others keep the key they had: Kt = eta = 0; plastic: Ks, alpha)
+    const bool glass = m.type == PBRT_HIP_MATERIAL_GLASS || m.type == PBRT_HIP_MATERIAL_PLASTIC ||
+                       m.type == PBRT_HIP_MATERIAL_SUBSTRATE;  // (the others keep the key they had: Kt = eta = 0; plastic, substrate: Ks, alpha)
     auto key = std::make_tuple(m.type, m.k[0], m.k[1], m.k[2], le[0], le[1], le[2], m.kd_tex, glass ? m.kt[0] : 0.f, glass ? m.kt[1] : 0.f,
                                glass ? m.kt[2] : 0.f, glass ? m.eta : 0.f);
     auto it = material_ids.find(key);
@@ -619,8 +652,10 @@ struct Api {
       shape_mat = MaterialDef();
       shape_mat.k[0] = shape_mat.k[1] = shape_mat.k[2] = 0.f;
     }
-    if (shape_mat.type == PBRT_HIP_MATERIAL_PLASTIC && (le[0] > 0.f || le[1] > 0.f || le[2] > 0.f)) {  // (its `le` is Ks: as glass)
-      warn("Material \"plastic\" under an AreaLightSource: the shape emits and is rendered as black matte");
+    if ((shape_mat.type == PBRT_HIP_MATERIAL_PLASTIC || shape_mat.type == PBRT_HIP_MATERIAL_SUBSTRATE) &&
+        (le[0] > 0.f || le[1] > 0.f || le[2] > 0.f)) {  // (its `le` is Ks: as glass)
+      warn(std::string("Material \"") + (shape_mat.type == PBRT_HIP_MATERIAL_PLASTIC ? "plastic" : "substrate") +
+           "\" under an AreaLightSource: the shape emits and is rendered as black matte");
       shape_mat = MaterialDef();
       shape_mat.k[0] = shape_mat.k[1] = shape_mat.k[2] = 0.f;
     }
@@ -1485,10 +1520,13 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
   // shading normals travel only when some mesh has them: then their record is the LAST slot of the texture table; a file
   // without them keeps the description it always had
   if (api.any_normals) {  // (plastic reflects about the geometric normal, and a scene with plastic takes no normals record: DESIGN.md 3.21)
-    bool plastic = false;
-    for (const pbrt_hip_material &m : out->mats) plastic = plastic || m.type == PBRT_HIP_MATERIAL_PLASTIC;
-    if (plastic) {
-      api.warn("a scene with a \"plastic\" material: the meshes' normals \"N\" are ignored (every mesh renders flat)");
+    bool plastic = false, substrate = false;  // (substrate: the same rule)
+    for (const pbrt_hip_material &m : out->mats) {
+      plastic = plastic || m.type == PBRT_HIP_MATERIAL_PLASTIC;
+      substrate = substrate || m.type == PBRT_HIP_MATERIAL_SUBSTRATE;
+    }
+    if (plastic || substrate) {
+      api.warn(std::string("a scene with a \"") + (plastic ? "plastic" : "substrate") + "\" material: the meshes' normals \"N\" are ignored (every mesh renders flat)");
       api.any_normals = false;
     }
   }

@@ -8,7 +8,7 @@ import numpy as np
 
 from ._lib import (SLOT_ENVMAP, SLOT_FILTER, SLOT_IMAGE, SLOT_LIGHT_MAP, SLOT_NORMALS, SLOT_SPOT, EnvMap, ImageTexture, LightMap, Normals, PixelFilter, RenderDesc, SceneDesc,
                    SpotCone, check, lib, read_slot)
-from .api import GLASS, LIGHT_MAPPED, LIGHT_SPOT, PLASTIC, SceneData
+from .api import GLASS, LIGHT_MAPPED, LIGHT_SPOT, PLASTIC, SUBSTRATE, SceneData
 
 
 @dataclass
@@ -93,10 +93,10 @@ def _collect(h):
             spheres=np.array([[*d.spheres[i].c, d.spheres[i].r, d.spheres[i].mat] for i in range(d.n_spheres)], np.float32).reshape(-1, 5),
             cam_to_world=np.array(list(d.cam_to_world), np.float32).reshape(4, 4), fov=d.fov, xres=d.xres, yres=d.yres,
             crop=tuple(d.crop),
-            # (a glass row's kd_tex holds eta, a plastic row's alpha: DESIGN.md 3.16, 3.21)
-            mat_tex=np.array([0 if d.mats[i].type in (GLASS, PLASTIC) else renum[d.mats[i].kd_tex] for i in range(d.n_mats)], np.uint32),
-            mat_eta=(np.array([d.mats[i].kd_tex if d.mats[i].type in (GLASS, PLASTIC) else 0x3FC00000 for i in range(d.n_mats)], np.uint32).view(np.float32)
-                     if any(d.mats[i].type in (GLASS, PLASTIC) for i in range(d.n_mats)) else np.zeros(0, np.float32)),
+            # (a glass row's kd_tex holds eta, a plastic or a substrate row's alpha: DESIGN.md 3.16, 3.21, 3.24)
+            mat_tex=np.array([0 if d.mats[i].type in (GLASS, PLASTIC, SUBSTRATE) else renum[d.mats[i].kd_tex] for i in range(d.n_mats)], np.uint32),
+            mat_eta=(np.array([d.mats[i].kd_tex if d.mats[i].type in (GLASS, PLASTIC, SUBSTRATE) else 0x3FC00000 for i in range(d.n_mats)], np.uint32).view(np.float32)
+                     if any(d.mats[i].type in (GLASS, PLASTIC, SUBSTRATE) for i in range(d.n_mats)) else np.zeros(0, np.float32)),
             textures=np.array(tex_rows, np.float32).reshape(-1, 11),
             tri_uv=(arr(d.tri_uv, 6 * d.n_tris, np.float32).reshape(-1, 6) if d.tri_uv else np.zeros((0, 6), np.float32))).normalized()
         wbuf = C.create_string_buffer(1 << 16)

@@ -7,6 +7,7 @@
   cornell_scene       C4: Cornell-style box
   glass_sphere_scene  a glass sphere and a glass cube in a Cornell-style box (= scenes/glass_sphere.pbrt)
   plastic_scene       a plastic floor and two plastic spheres in a Cornell-style box (= scenes/plastic_spheres.pbrt)
+  substrate_scene     a substrate floor and two substrate spheres in a Cornell-style box (= scenes/substrate_spheres.pbrt)
   spot_scene          a plastic and a matte sphere in a Cornell-style box lit by two spot lights (= scenes/spot_cornell.pbrt)
   projector_scene     the same box lit by a projection light that throws a slide onto the back wall and a goniometric light (DESIGN.md 3.23;
                       = scenes/projector_cornell.pbrt)
@@ -16,7 +17,7 @@
 """
 import numpy as np
 
-from .api import GLASS, PLASTIC, roughness_to_alpha, LIGHT_DISTANT, LIGHT_ENVMAP, LIGHT_INFINITE, LIGHT_POINT, MATTE, MIRROR, SceneData, look_at
+from .api import GLASS, PLASTIC, SUBSTRATE, roughness_to_alpha, LIGHT_DISTANT, LIGHT_ENVMAP, LIGHT_INFINITE, LIGHT_POINT, MATTE, MIRROR, SceneData, look_at
 
 MESH_SEED = 0x5EED0001
 
@@ -319,6 +320,44 @@ def plastic_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), plastic=True, l
     return SceneData(
         P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
         materials=np.array(mats, np.float32), mat_eta=np.array(alpha if plastic else [], np.float32),
+        spheres=np.array([[-0.45, 0.15, -0.65, 0.35, BLUE], [0.45, -0.2, -0.65, 0.35, ORANGE]], np.float32),
+        cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
+    ).normalized()
+
+
+def substrate_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0), substrate=True):
+    """The substrate material's scene, array for array what scenes/substrate_spheres.pbrt loads to: plastic_scene's box --
+    [-1, 1]^3 open towards the camera, white ceiling and back wall, red left and green right walls, the 1 x 1 ceiling emitter with Le (10, 9,
+    7) -- with a grey SUBSTRATE floor (Ks 0.2, roughness 0.2) and two substrate spheres of radius 0.35 standing on it: a sharp blue one (Ks
+    0.5, roughness 0.05) and a broad orange one (Ks 0.5, the default; roughness 0.4).  `substrate=False`: the same scene with every substrate
+    material replaced by matte of the same Kd."""
+    from .api import substrate_material
+    FLOOR, WHITE, RED, GREEN, LIGHT, BLUE, ORANGE = range(7)  # (numbered in the order the scene file's shapes first use them)
+    coats = {FLOOR: substrate_material((0.4, 0.4, 0.4), (0.2, 0.2, 0.2), 0.2, 0.2), BLUE: substrate_material((0.1, 0.2, 0.6), (0.5, 0.5, 0.5), 0.05, 0.05),
+             ORANGE: substrate_material((0.6, 0.3, 0.05), uroughness=0.4, vroughness=0.4)}
+    mats = [None, _mat(MATTE, (0.73, 0.73, 0.73)), _mat(MATTE, (0.65, 0.05, 0.05)), _mat(MATTE, (0.12, 0.45, 0.15)), _mat(MATTE, (0, 0, 0), (10, 9, 7)), None, None]
+    alpha = [1.5] * 7  # (mat_eta: the float beside a row; what a row that is neither glass, plastic nor substrate carries is not read)
+    for m, (row, a) in coats.items():
+        mats[m] = row if substrate else _mat(MATTE, row[1:4])
+        alpha[m] = a
+    V, I, M = [], [], []
+
+    def add(q, m):
+        base = len(V)
+        v, t = _quad(*q)
+        V.extend(v)
+        I.extend([[base + a for a in tri] for tri in t])
+        M.extend([m, m])
+
+    add(((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1)), FLOOR)  # floor
+    add(((-1, -1, 1), (-1, 1, 1), (1, 1, 1), (1, -1, 1)), WHITE)      # ceiling
+    add(((-1, 1, -1), (1, 1, -1), (1, 1, 1), (-1, 1, 1)), WHITE)      # back wall (y = +1)
+    add(((-1, -1, -1), (-1, 1, -1), (-1, 1, 1), (-1, -1, 1)), RED)    # left
+    add(((1, -1, -1), (1, -1, 1), (1, 1, 1), (1, 1, -1)), GREEN)      # right
+    add(((-0.5, -0.5, 0.999), (-0.5, 0.5, 0.999), (0.5, 0.5, 0.999), (0.5, -0.5, 0.999)), LIGHT)  # normal -z
+    return SceneData(
+        P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
+        materials=np.array(mats, np.float32), mat_eta=np.array(alpha if substrate else [], np.float32),
         spheres=np.array([[-0.45, 0.15, -0.65, 0.35, BLUE], [0.45, -0.2, -0.65, 0.35, ORANGE]], np.float32),
         cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
     ).normalized()

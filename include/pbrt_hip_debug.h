@@ -239,6 +239,22 @@ int pbrt_hip_spot_eval_device(int device, int64_t n, const float *in, float *out
 #define PBRT_HIP_LIGHT_MAP_EVAL_OUT 11
 int pbrt_hip_light_map_eval_device(int device, const pbrt_hip_image_texture *image, const pbrt_hip_light_map *map, int64_t n, const float *in, float *out);
 
+/* ---- the small device tables of a scene, as scene creation assembles them on the host (pbrt_amd/csrc/scene_tables.hpp states their rows) ---- */
+/* HOST arrays of 32-bit words that pbrt_hip_scene_tables_host fills, each of which may be NULL, and beside each the count of words it holds
+ * (set whether or not the array is given: a first call with every array NULL sizes a second one).  P / idx / mat: the primitives the tree
+ * builders get -- the triangles, then the spheres' proxy triangles; a material id is widened to a word.  lights, mats, mat_extra, spheres,
+ * textures, image_texels: the kernels' tables, 4 words per row.  The scalars are the gather stage's. */
+typedef struct pbrt_hip_scene_tables {
+  uint32_t *P, *idx, *mat, *lights, *mats, *mat_extra, *spheres, *textures, *image_texels;
+  uint32_t n_P, n_idx, n_mat, n_lights, n_mats, n_mat_extra, n_spheres, n_textures, n_image_texels;
+  float le_inf[3];
+  uint32_t has_inf, env, has_spot, has_mapped, env_w, env_h;
+  float env_m[9], env_c[3];
+} pbrt_hip_scene_tables;
+/* host only, no HIP call (it works on a machine without a device): checks `desc` as pbrt_hip_scene_create does (the same refusals, flags 0)
+ * and runs the gather stage on it.  PBRT_HIP_ERR_INVALID for a null argument. */
+int pbrt_hip_scene_tables_host(const pbrt_hip_scene_desc *desc, pbrt_hip_scene_tables *out);
+
 /* ---- the parser's state and its tokenizer alone (conformance tests replay parser.rs:778-880, api.rs:979-1045) ---- */
 /* CTM (current_transform[0].m) when parsing stopped, and the directive names stored by the option setters
  * (api.rs:778-820) as "camera sampler integrator filter accelerator film" */

@@ -79,6 +79,13 @@ class BuildStages(C.Structure):
                 ("stack_need", C.c_uint32)]
 
 
+class SceneTables(C.Structure):
+    """pbrt_hip_scene_tables (include/pbrt_hip_debug.h): the host arrays pbrt_hip_scene_tables_host fills, their word counts, the gather stage's scalars"""
+    ARRAYS = ("P", "idx", "mat", "lights", "mats", "mat_extra", "spheres", "textures", "image_texels")
+    _fields_ = ([(a, C.POINTER(C.c_uint32)) for a in ARRAYS] + [("n_" + a, C.c_uint32) for a in ARRAYS] + [("le_inf", C.c_float * 3)] +
+                [(f, C.c_uint32) for f in ("has_inf", "env", "has_spot", "has_mapped", "env_w", "env_h")] + [("env_m", C.c_float * 9), ("env_c", C.c_float * 3)])
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_uint32), ("p", C.c_float * 3), ("c", C.c_float * 3), ("pad", C.c_float)]
 
@@ -143,6 +150,7 @@ SYMBOLS = {
     "pbrt_hip_gpu_build_stages_device": (C.c_int, [C.c_int, _pf, _u32, _pu32, _u32, _u32, C.POINTER(BuildStages)]),
     "pbrt_hip_reinsert_links_host": (C.c_int, [_u32, _pu32, _pf, _pu32, _pu32, _pu32, _pf, _pu64, _pi32, _pu32]),
     "pbrt_hip_collapse_host": (C.c_int, [_u32, _pu32, _pf, _pu32, _u32, _pu32, _u32, _pu32, _pu32]),
+    "pbrt_hip_scene_tables_host": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneTables)]),
     "pbrt_hip_render": (C.c_int, [_vp, C.POINTER(RenderDesc), _pf, C.POINTER(Stats)]),
     "pbrt_hip_render_device": (C.c_int, [_vp, C.POINTER(RenderDesc), _vp, _vp]),
     "pbrt_hip_render_prepare": (C.c_int, [_vp, C.POINTER(RenderDesc)]),

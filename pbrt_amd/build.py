@@ -18,7 +18,7 @@ CLI_PATH = os.path.join(LIB_DIR, "pbrt")  # the C++ command line (csrc/pbrt_main
 # render kernels (csrc/render_variant.hpp says which), built from the same headers, kernel_math.hpp / kernel_walk.hpp / kernel_path.hpp,
 # and render_body.inc; they compile side by side.  kernels_blocks.hip holds the debug hook that runs the headers' building blocks over
 # arrays and no render kernel)
-SOURCES = ["kernels.hip", "kernels_x.hip", "kernels_n.hip", "kernels_env.hip", "bvh_gpu.hip", "kernels_blocks.hip", "capi_scene.cpp", "capi_render.cpp", "capi_load.cpp", "multi_gpu.cpp", "bvh_build.cpp", "quad_nodes.cpp", "reinsert_batch.cpp", "imageio.cpp",
+SOURCES = ["kernels.hip", "kernels_x.hip", "kernels_n.hip", "kernels_env.hip", "bvh_gpu.hip", "kernels_blocks.hip", "capi_scene.cpp", "scene_inputs.cpp", "capi_render.cpp", "capi_load.cpp", "multi_gpu.cpp", "bvh_build.cpp", "quad_nodes.cpp", "reinsert_batch.cpp", "imageio.cpp",
            "scene_parser.cpp", "ply_reader.cpp", "envmap.cpp", "pixel_filter.cpp", "image_texture.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -44,7 +44,7 @@ struct SceneStream {
 // The device arrays that ARE a scene: what scene creation uploads and builds, what device_bytes counts and what a clone on another device
 // carries.  Per-render scratch (slab, film, lane state, partial sums, counters, stack overflow, sampler tables) is not part of it.
 struct SceneArrays {
-  DevBuf<float> d_P;  // vertices and indices of the tree's primitives: the triangles, then the spheres' proxy triangles (capi_scene.cpp SceneInputs)
+  DevBuf<float> d_P;  // vertices and indices of the tree's primitives: the triangles, then the spheres' proxy triangles (scene_inputs.hpp SceneInputs)
   DevBuf<uint32_t> d_idx, d_order;
   DevBuf<uint16_t> d_mat_id;
   DevBuf<uint4> d_nodes, d_quads;
@@ -52,7 +52,7 @@ struct SceneArrays {
   DevBuf<float> d_tri_uv_in;  // textured scenes: corner (u, v) as uploaded (triangle order) ...
   DevBuf<float2> d_tri_uv;    // ... and in leaf-slot order (3 per slot)
   DevBuf<float4> d_textures;
-  DevBuf<float4> d_glass;  // {Kt, eta} per material of a scene with glass; empty otherwise
+  DevBuf<float4> d_mat_extra;  // a row per material of a scene with glass, plastic or substrate (scene_tables.hpp mat_extra); empty otherwise
   // an environment-map infinite light: texels {r, g, b, p_uv}, the marginal and conditional CDFs (envmap.hpp EnvTables)
   DevBuf<float4> d_env_texels;
   DevBuf<float> d_env_marginal, d_env_conditional;
@@ -73,7 +73,7 @@ struct SceneArrays {
     f(&SceneArrays::d_nodes, true); f(&SceneArrays::d_quads, true);
     f(&SceneArrays::d_tris, true); f(&SceneArrays::d_mats, true); f(&SceneArrays::d_lights, true); f(&SceneArrays::d_spheres, true);
     f(&SceneArrays::d_tri_uv_in, false);  // (read by pack_uv during scene creation and by nothing after it)
-    f(&SceneArrays::d_tri_uv, true); f(&SceneArrays::d_textures, true); f(&SceneArrays::d_glass, true);
+    f(&SceneArrays::d_tri_uv, true); f(&SceneArrays::d_textures, true); f(&SceneArrays::d_mat_extra, true);
     f(&SceneArrays::d_env_texels, true); f(&SceneArrays::d_env_marginal, true); f(&SceneArrays::d_env_conditional, true);
     f(&SceneArrays::d_tri_n_in, false);  // (read by pack_nrm during scene creation and by nothing after it: released there)
     f(&SceneArrays::d_tri_n, true); f(&SceneArrays::d_image_texels, true);

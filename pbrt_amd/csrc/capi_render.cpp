@@ -269,7 +269,7 @@ int ensure_render_scratch(pbrt_hip_scene *s, const pbrt_hip_render_desc *r, cons
 void scene_render_params(const pbrt_hip_scene *s, RenderParams *R) {
   R->tri_uv = s->d_tri_uv.p;
   R->textures = s->d_textures.p;
-  R->glass = s->d_glass.p;
+  R->mat_extra = s->d_mat_extra.p;
   R->env_texels = s->d_env_texels.p;
   R->env_marginal = s->d_env_marginal.p;
   R->env_conditional = s->d_env_conditional.p;

@@ -1,5 +1,5 @@
-// capi_scene.cpp -- everything up to a finished scene behind the C ABI of include/pbrt_hip.h: checking a description, flattening it,
-// the upload, the tree (and the canonical tree a device-built scene gets on first use), the scene's getters, the host tree builders'
+// capi_scene.cpp -- everything up to a finished scene behind the C ABI of include/pbrt_hip.h: checking a description, flattening it
+// (scene_inputs.hpp), the upload, the tree (and the canonical tree a device-built scene gets on first use), the scene's getters, the host tree builders'
 // entry points and the library's error text.  capi_render.cpp uses what is made here.  (Together they replace the empty body of
 // PbrtAPI::world_end, /root/reference/src/core/api.rs:432-473.)
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@
 #include "image_texture.hpp"
 #include "pixel_filter.hpp"
 #include "quad_nodes.hpp"
+#include "scene_inputs.hpp"
 #include "texture_table.hpp"
 
 using namespace pbrt_hip;
@@ -93,9 +94,6 @@ int build_canonical(pbrt_hip_scene *s, const float *P, const uint32_t *idx, uint
 // request (PBRT_HIP_SCENE_HOST_BUILD / _OPTIMIZED_TREE, or PBRT_HIP_BUILDER=host in the environment when the caller left the choice open).
 enum class Builder { kHost, kHostOptimized, kGpu, kGpuPlain };
 
-// the 1-based texture-table number an environment-map light carries as the bits of its `pad`; a spot light names its cone's
-// slot the same way (3.22)
-uint32_t light_env_slot(const pbrt_hip_light &l) { uint32_t u; std::memcpy(&u, &l.pad, 4); return u; }
 // a glass material's index of refraction: the float whose bits ride in kd_tex
 float glass_eta(const pbrt_hip_material &m) { float e; std::memcpy(&e, &m.kd_tex, 4); return e; }
 // glass is an interface between index 1 and eta: eta = 1 (index-matched: nothing reflects, nothing bends) is legal; 16 is four times
@@ -107,11 +105,6 @@ float plastic_alpha(const pbrt_hip_material &m) { return glass_eta(m); }
 constexpr float kPlasticAlphaMin = 1e-3f, kPlasticAlphaMax = 1.0f;
 // how far a spot cone's axis may be from unit length, as a squared length
 constexpr float kSpotAxisTolerance = 1e-4f;
-// the materials that reuse `le` and `kd_tex` for parameters of their own: they do not emit and name no texture
-bool reuses_le(const pbrt_hip_material &m) {
-  return m.type == PBRT_HIP_MATERIAL_GLASS || m.type == PBRT_HIP_MATERIAL_PLASTIC || m.type == PBRT_HIP_MATERIAL_SUBSTRATE;
-}
-
 // ---- check_scene_desc in stages: every refusal that depends on the description alone, before any HIP call.  Which of two faults is
 // reported is part of the behaviour, so a concern whose refusals lie apart in that order has a stage for each part: the lights' and the
 // materials' values early and their kinds last, the spheres' material ids and boxes apart from the mesh (check_scene_desc, below, is the order;
@@ -205,7 +198,7 @@ int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   for (uint32_t i = 0; i < d->n_lights; i++) {
     if (d->lights[i].type != PBRT_HIP_LIGHT_SPOT) continue;
     const std::string what = "scene_create: light " + std::to_string(i) + ": ";
-    const pbrt_hip_spot_cone *cone = table.cone(light_env_slot(d->lights[i]));
+    const pbrt_hip_spot_cone *cone = table.cone(light_slot(d->lights[i]));
     if (!cone) return fail(PBRT_HIP_ERR_INVALID, what + "a spot light (type 5) must name a type-6 slot of the texture table, its cone, in `pad`");
     const int rc = check_spot_cone(*cone, what);
     if (rc) return rc;
@@ -218,7 +211,7 @@ int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   for (uint32_t i = 0; i < d->n_lights; i++) {
     if (d->lights[i].type != PBRT_HIP_LIGHT_MAPPED) continue;
     const std::string what = "scene_create: light " + std::to_string(i) + ": ";
-    const pbrt_hip_light_map *map = table.light_map(light_env_slot(d->lights[i]));
+    const pbrt_hip_light_map *map = table.light_map(light_slot(d->lights[i]));
     if (!map) return fail(PBRT_HIP_ERR_INVALID, what + "a mapped light (type 6) must name a type-8 slot of the texture table, its light map, in `pad`");
     const int rc = check_light_map(*map, table, what);
     if (rc) return rc;
@@ -230,7 +223,7 @@ int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   uint32_t n_env = 0;
   for (uint32_t i = 0; i < d->n_lights; i++) {  // an environment-map light names a type-1 slot of the texture table; one per scene
     if (d->lights[i].type != PBRT_HIP_LIGHT_ENVMAP) continue;
-    if (table.named(light_env_slot(d->lights[i])) != SlotKind::kEnvmap)
+    if (table.named(light_slot(d->lights[i])) != SlotKind::kEnvmap)
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: light " + std::to_string(i) + ": an environment-map light (type 3) must name a type-1 slot of the texture table in `pad`");
     if (++n_env > 1u) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: more than one environment-map light (type 3)");
   }
@@ -309,41 +302,24 @@ int check_material_kinds(const pbrt_hip_scene_desc *d) {
   }
   return PBRT_HIP_OK;
 }
-// plastic is rendered by the GLS instantiations of render_kernel_x alone: the families that render an environment map or
+// Plastic is rendered by the GLS instantiations of render_kernel_x alone: the families that render an environment map or
 // shading normals do not carry its branch, and the scene is refused here, not at render time.  Substrate (3.24) shares the branch and the
-// refusal, each under its own name (plastic's first: a scene with both keeps the message it had)
-int check_plastic_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
-  for (const uint32_t type : {PBRT_HIP_MATERIAL_PLASTIC, PBRT_HIP_MATERIAL_SUBSTRATE}) {
-    bool present = false;
-    for (uint32_t i = 0; i < d->n_mats && !present; i++) present = d->mats[i].type == type;
-    if (!present) continue;
-    const std::string name = type == PBRT_HIP_MATERIAL_PLASTIC ? "plastic" : "substrate";
+// refusal; a spot light (3.22) and a mapped light (3.23) are sampled under PLS alone, in the same instantiations.  Each is refused under its
+// own name, and of several the first in this order is the one named
+int check_pls_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
+  auto has_material = [&](uint32_t type) { return std::any_of(d->mats, d->mats + d->n_mats, [&](const pbrt_hip_material &m) { return m.type == type; }); };
+  auto has_light = [&](uint32_t type) { return std::any_of(d->lights, d->lights + d->n_lights, [&](const pbrt_hip_light &l) { return l.type == type; }); };
+  const struct { bool present; const char *noun; } needs_pls[] = {
+      {has_material(PBRT_HIP_MATERIAL_PLASTIC), "a plastic material"},
+      {has_material(PBRT_HIP_MATERIAL_SUBSTRATE), "a substrate material"},
+      {has_light(PBRT_HIP_LIGHT_SPOT), "a spot light"},
+      {has_light(PBRT_HIP_LIGHT_MAPPED), "a light map (a projection or goniometric light)"}};
+  for (const auto &n : needs_pls) {
+    if (!n.present) continue;
     for (const SlotKind kind : table.kinds) {
-      if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a " + name + " material is not available in a scene with an environment map");
-      if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a " + name + " material is not available in a scene with shading normals");
+      if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, std::string("scene_create: ") + n.noun + " is not available in a scene with an environment map");
+      if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, std::string("scene_create: ") + n.noun + " is not available in a scene with shading normals");
     }
-  }
-  return PBRT_HIP_OK;
-}
-// a spot light is sampled under PLS alone: the same families, the same refusal
-int check_spot_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
-  bool spot = false;
-  for (uint32_t i = 0; i < d->n_lights && !spot; i++) spot = d->lights[i].type == PBRT_HIP_LIGHT_SPOT;
-  if (!spot) return PBRT_HIP_OK;
-  for (const SlotKind kind : table.kinds) {
-    if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a spot light is not available in a scene with an environment map");
-    if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a spot light is not available in a scene with shading normals");
-  }
-  return PBRT_HIP_OK;
-}
-// a mapped light is sampled under PLS alone too
-int check_light_map_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
-  bool mapped = false;
-  for (uint32_t i = 0; i < d->n_lights && !mapped; i++) mapped = d->lights[i].type == PBRT_HIP_LIGHT_MAPPED;
-  if (!mapped) return PBRT_HIP_OK;
-  for (const SlotKind kind : table.kinds) {
-    if (kind == SlotKind::kEnvmap) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a light map (a projection or goniometric light) is not available in a scene with an environment map");
-    if (kind == SlotKind::kNormals) return fail(PBRT_HIP_ERR_LIMIT, "scene_create: a light map (a projection or goniometric light) is not available in a scene with shading normals");
   }
   return PBRT_HIP_OK;
 }
@@ -421,7 +397,7 @@ int check_flags(uint32_t flags, Builder *builder) {
 }
 
 // The stages in their order; the description's table is decoded once the indices it goes by are known to be sound (*table: what
-// gather_inputs and upload_inputs go by)
+// gather_inputs -- scene_inputs.hpp -- and upload_inputs go by)
 int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *builder, TextureTable *table) {
   int rc;
   if ((rc = check_mesh(d)) || (rc = check_light_values(d)) || (rc = check_material_values(d)) || (rc = check_view(d)) || (rc = check_sphere_materials(d))) return rc;
@@ -430,153 +406,7 @@ int check_scene_desc(const pbrt_hip_scene_desc *d, uint32_t flags, Builder *buil
   if ((rc = check_kd_tex(d, *table)) || (rc = check_table(d, *table)) || (rc = check_flags(flags, builder)) || (rc = check_sphere_boxes(d))) return rc;
   if ((rc = check_light_kinds(d, *table))) return rc;
   if ((rc = check_material_kinds(d))) return rc;
-  if ((rc = check_plastic_family(d, *table))) return rc;
-  if ((rc = check_spot_family(d, *table))) return rc;
-  return check_light_map_family(d, *table);
-}
-
-// What a checked description puts on the device, assembled on the host.
-// Spheres are PRIMITIVES OF THE TREE (round 6; until round 5 every ray tested every sphere after the walk).  Every builder here --
-// the host's binned SAH, the device builder, the collapse, the lazily built canonical tree -- bounds a primitive by the box of its
-// three vertices, so sphere s enters the vertex / index buffers as a degenerate PROXY TRIANGLE (c - r, c + r, c - r): primitive
-// n_tris + s, bounded by exactly the sphere's box [c - r, c + r] (fp32 per component: the oracle's sphere_box), centroid its centre.
-// Its leaf record is a sphere's (pack_tris_kernel) and the leaf pass runs the sphere test on it (trav_run<..., SPH>).
-struct SceneInputs {
-  const float *P = nullptr;  // the primitives' vertices, indices and material ids: the caller's arrays, or *_aug with spheres
-  const uint32_t *idx = nullptr;
-  const uint16_t *mat = nullptr;
-  uint32_t n_verts = 0, n_prims = 0;  // primitives: the triangles + the spheres' proxies
-  std::vector<float> P_aug;
-  std::vector<uint32_t> idx_aug;
-  std::vector<uint16_t> mat_aug;
-  std::vector<float4> lights, mats, spheres, textures;  // the kernels' records: 5, 2, 2 and 3 per light / material / sphere / texture
-  std::vector<float4> glass;  // {Kt, eta} per material, when the scene has a glass one; else empty
-  std::vector<float4> image_texels;  // the texel pool of the image textures, when something is textured or a mapped light reads an image (3.23); else empty
-  // an environment-map light: its tables, world_to_light and factor
-  bool env = false;
-  EnvTables env_tables;
-  uint32_t env_w = 0, env_h = 0;
-  float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};
-  float le_inf[3] = {0.f, 0.f, 0.f};
-  bool has_inf = false;
-  bool has_spot = false;  // a spot light: the scene needs the GLS instantiations
-  bool has_mapped = false;  // a mapped light: likewise, and the texture rows and the texel pool go up for its image
-};
-void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, SceneInputs *in) {
-  auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
-  in->P = d.P; in->idx = d.idx; in->mat = d.mat_id;
-  in->n_verts = d.n_verts;
-  in->n_prims = d.n_tris + d.n_spheres;
-  if (d.n_spheres) {
-    in->P_aug.assign(d.P, d.P + (d.n_tris ? 3 * (size_t)d.n_verts : 0));
-    if (!d.n_tris) in->n_verts = 0;  // (a scene without triangles drops the caller's vertices)
-    in->idx_aug.assign(d.idx, d.idx + 3 * (size_t)d.n_tris);
-    in->mat_aug.assign(d.mat_id, d.mat_id + d.n_tris);
-    for (uint32_t i = 0; i < d.n_spheres; i++) {
-      const pbrt_hip_sphere &sp = d.spheres[i];
-      const uint32_t v0 = in->n_verts + 2 * i;
-      for (int k = 0; k < 3; k++) in->P_aug.push_back(sp.c[k] - sp.r);
-      for (int k = 0; k < 3; k++) in->P_aug.push_back(sp.c[k] + sp.r);
-      in->idx_aug.push_back(v0); in->idx_aug.push_back(v0 + 1); in->idx_aug.push_back(v0);
-      in->mat_aug.push_back((uint16_t)sp.mat);
-    }
-    in->n_verts += 2 * d.n_spheres;
-    in->P = in->P_aug.data(); in->idx = in->idx_aug.data(); in->mat = in->mat_aug.data();
-  }
-  // light table: explicit lights, then every emissive triangle in index order
-  for (uint32_t i = 0; i < d.n_lights; i++) {
-    const pbrt_hip_light &l = d.lights[i];
-    // (type 3 of the boundary, the environment map, is 4 in this table: 3 is an emissive triangle here -- kernel_path.hpp kDevLightEnv;
-    // a spot light keeps its 5, kDevLightSpot, with the cone in the rows a point light leaves free: DESIGN.md 3.22; a mapped light is 6,
-    // kDevLightProjection, or 7, kDevLightGonio, by its record's kind, with {a row of world_to_light, inv_tan / sx / sy} in rows 1, 2 and 4 and
-    // the bits of its image slot's 0-based number in row 3's w: 3.23)
-    const pbrt_hip_light_map *map = l.type == PBRT_HIP_LIGHT_MAPPED ? table.light_map(light_env_slot(l)) : nullptr;
-    const uint32_t dev_type = l.type == PBRT_HIP_LIGHT_ENVMAP ? 4u : (map ? 6u + map->kind : l.type);
-    in->lights.push_back(make_float4(as_f(dev_type), l.p[0], l.p[1], l.p[2]));
-    if (map) {
-      const float *m = map->world_to_light;
-      in->lights.push_back(make_float4(m[0], m[1], m[2], map->inv_tan));
-      in->lights.push_back(make_float4(m[3], m[4], m[5], map->sx));
-      in->lights.push_back(make_float4(l.c[0], l.c[1], l.c[2], as_f(map->image - 1u)));
-      in->lights.push_back(make_float4(m[6], m[7], m[8], map->sy));
-      in->has_mapped = true;
-      continue;
-    }
-    if (l.type == PBRT_HIP_LIGHT_SPOT) {
-      const pbrt_hip_spot_cone &c = *table.cone(light_env_slot(l));
-      in->lights.push_back(make_float4(c.axis[0], c.axis[1], c.axis[2], c.cos_total));
-      in->lights.push_back(make_float4(c.cos_start, 0, 0, 0));
-      in->has_spot = true;
-    } else {
-      in->lights.push_back(make_float4(0, 0, 0, 0));
-      in->lights.push_back(make_float4(0, 0, 0, 0));
-    }
-    in->lights.push_back(make_float4(l.c[0], l.c[1], l.c[2], 0));
-    in->lights.push_back(make_float4(0, 0, 0, 0));
-    if (l.type == 2) {
-      for (int k = 0; k < 3; k++) in->le_inf[k] = in->le_inf[k] + l.c[k];
-      in->has_inf = true;
-    }
-    if (l.type == PBRT_HIP_LIGHT_ENVMAP) {
-      const pbrt_hip_envmap e = *table.envmap(light_env_slot(l));
-      in->env = true;
-      in->env_w = e.width; in->env_h = e.height;
-      for (int k = 0; k < 9; k++) in->env_m[k] = e.world_to_light[k];
-      for (int k = 0; k < 3; k++) in->env_c[k] = l.c[k];
-      envmap_build_tables(e.rgb, e.width, e.height, &in->env_tables);
-    }
-  }
-  for (uint32_t t = 0; t < d.n_tris; t++) {
-    const pbrt_hip_material &m = d.mats[d.mat_id[t]];
-    if (reuses_le(m)) continue;  // (its le is Kt / Ks: glass, plastic and substrate do not emit)
-    if (!(m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) continue;
-    F3 p[3];
-    for (int v = 0; v < 3; v++) {
-      const float *q = d.P + 3 * (size_t)d.idx[3 * (size_t)t + v];
-      p[v] = {q[0], q[1], q[2]};
-    }
-    F3 cr = cross3(sub(p[1], p[0]), sub(p[2], p[0]));
-    float len = std::sqrt(dot3(cr, cr));
-    in->lights.push_back(make_float4(as_f(3u), p[0].x, p[0].y, p[0].z));
-    in->lights.push_back(make_float4(p[1].x, p[1].y, p[1].z, 0.5f * len));
-    in->lights.push_back(make_float4(p[2].x, p[2].y, p[2].z, 0));
-    in->lights.push_back(make_float4(m.le[0], m.le[1], m.le[2], 0));
-    in->lights.push_back(make_float4(cr.x / len, cr.y / len, cr.z / len, 0));
-  }
-  in->mats.resize(2 * (size_t)d.n_mats);
-  for (uint32_t i = 0; i < d.n_mats; i++) {
-    const pbrt_hip_material &m = d.mats[i];
-    in->mats[2 * i] = make_float4(as_f(m.type), m.k[0], m.k[1], m.k[2]);
-    in->mats[2 * i + 1] = make_float4(m.le[0], m.le[1], m.le[2], as_f(m.type == 0u ? m.kd_tex : 0u));
-    if (m.type == PBRT_HIP_MATERIAL_GLASS) {  // no emission on the device; {Kt, eta} in the table of the GLS instantiations
-      in->mats[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (in->glass.empty()) in->glass.assign(d.n_mats, make_float4(0.f, 0.f, 0.f, 1.f));
-      in->glass[i] = make_float4(m.le[0], m.le[1], m.le[2], glass_eta(m));
-    }
-    if (m.type == PBRT_HIP_MATERIAL_PLASTIC || m.type == PBRT_HIP_MATERIAL_SUBSTRATE) {  // the same table carries {Ks, alpha}: no emission, no texture word
-      in->mats[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (in->glass.empty()) in->glass.assign(d.n_mats, make_float4(0.f, 0.f, 0.f, 1.f));
-      in->glass[i] = make_float4(m.le[0], m.le[1], m.le[2], plastic_alpha(m));
-    }
-  }
-  in->spheres.resize(2 * (size_t)d.n_spheres);
-  for (uint32_t i = 0; i < d.n_spheres; i++) {
-    const pbrt_hip_sphere &sp = d.spheres[i];
-    in->spheres[2 * i] = make_float4(sp.c[0], sp.c[1], sp.c[2], sp.r);
-    in->spheres[2 * i + 1] = make_float4(as_f(sp.mat), 0, 0, 0);
-  }
-  if (table.textured_tris || table.textured_sph || in->has_mapped) {  // (the texture table goes up only when something is textured, or a mapped light reads an image)
-    in->textures.resize(3 * table.kinds.size());  // (an environment map's / the normals' / the filter's / a cone's / a light map's slot: nothing on the device reads it, its rows stay zero)
-    for (uint32_t i = 0; i < table.kinds.size(); i++) {
-      if (table.kinds[i] != SlotKind::kChecker) continue;
-      const pbrt_hip_texture tx = read_slot<pbrt_hip_texture>(table.slots, i);
-      in->textures[3 * i] = make_float4(as_f(tx.type), tx.tex1[0], tx.tex1[1], tx.tex1[2]);
-      in->textures[3 * i + 1] = make_float4(tx.tex2[0], tx.tex2[1], tx.tex2[2], tx.su);
-      in->textures[3 * i + 2] = make_float4(tx.sv, tx.du, tx.dv, 0.f);
-    }
-    for (const TextureTable::Image &im : table.images)  // (its texels join the pool, its rows say where)
-      image_pack(im.rec, &in->image_texels, &in->textures[3 * (size_t)im.slot]);
-  }
+  return check_pls_family(d, *table);
 }
 
 // The inputs into the scene's arrays (asynchronously: `in` outlives the stream's synchronisation) and the counts of s->dev they make
@@ -588,7 +418,7 @@ int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const Texture
   HIP_TRY(upload(&s->d_lights, in.lights.data(), in.lights.size(), s->stream));
   HIP_TRY(upload(&s->d_spheres, in.spheres.data(), in.spheres.size(), s->stream));
   HIP_TRY(upload(&s->d_textures, in.textures.data(), in.textures.size(), s->stream));
-  HIP_TRY(upload(&s->d_glass, in.glass.data(), in.glass.size(), s->stream));
+  HIP_TRY(upload(&s->d_mat_extra, in.mat_extra.data(), in.mat_extra.size(), s->stream));
   HIP_TRY(upload(&s->d_image_texels, in.image_texels.data(), in.image_texels.size(), s->stream));
   if (in.env) {
     HIP_TRY(upload(&s->d_env_texels, in.env_tables.texels.data(), in.env_tables.texels.size(), s->stream));
@@ -607,7 +437,7 @@ int upload_inputs(pbrt_hip_scene *s, const pbrt_hip_scene_desc &d, const Texture
   DevScene &D = s->dev;
   D.n_tris = d.n_tris;  // (the triangles: a hit's primitive id >= this is sphere id - n_tris)
   D.n_spheres = d.n_spheres;
-  D.n_lights = (uint32_t)(in.lights.size() / 5);
+  D.n_lights = (uint32_t)(in.lights.size() / kLightRows);
   D.n_lights_f = (float)D.n_lights;
   for (int k = 0; k < 3; k++) D.le_inf[k] = in.le_inf[k];
   D.has_inf = in.has_inf ? 1u : 0u;
@@ -928,7 +758,7 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
     gather_inputs(*d, table, &in);
     s->n_prims = in.n_prims;
     s->textured = table.textured_tris || table.textured_sph;
-    s->glass = !in.glass.empty() || in.has_spot || in.has_mapped;  // (a spot and a mapped light are sampled under PLS, in the GLS instantiations: DESIGN.md 3.22, 3.23)
+    s->glass = !in.mat_extra.empty() || in.has_spot || in.has_mapped;  // (a spot and a mapped light are sampled under PLS, in the GLS instantiations: DESIGN.md 3.22, 3.23)
     if ((rc = upload_inputs(s.get(), *d, table, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
     if (table.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
       HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));
@@ -1020,6 +850,41 @@ int pbrt_hip_scene_export_bvh(const pbrt_hip_scene *s, uint32_t *nodes, uint32_t
   if (nodes && !s->bvh.nodes.empty()) std::memcpy(nodes, s->bvh.nodes.data(), s->bvh.nodes.size() * sizeof(BvhNode));
   if (order && !s->bvh.order.empty()) std::memcpy(order, s->bvh.order.data(), s->bvh.order.size() * 4);
   return PBRT_HIP_OK;
+}
+
+
+int pbrt_hip_scene_tables_host(const pbrt_hip_scene_desc *d, pbrt_hip_scene_tables *out) {
+  if (!d || !out) return fail(PBRT_HIP_ERR_INVALID, "scene_tables_host: null argument");
+  return guarded([&]() -> int {
+    Builder builder;
+    TextureTable table;
+    const int rc = check_scene_desc(d, 0u, &builder, &table);
+    if (rc) return rc;
+    SceneInputs in;
+    gather_inputs(*d, table, &in);
+    // the words of `n` elements of T at src into dst (unless NULL; a 16-bit element widens to a word of its own); *count = the words
+    auto words = [](uint32_t *dst, uint32_t *count, const auto *src, size_t n) {
+      constexpr size_t per = sizeof(*src) < 4 ? 1 : sizeof(*src) / 4;
+      *count = (uint32_t)(n * per);
+      if (!dst || !n) return;
+      if (sizeof(*src) < 4) for (size_t i = 0; i < n; i++) dst[i] = (uint32_t)((const uint16_t *)src)[i];
+      else std::memcpy(dst, src, n * sizeof(*src));
+    };
+    words(out->P, &out->n_P, in.P, 3 * (size_t)in.n_verts);
+    words(out->idx, &out->n_idx, in.idx, 3 * (size_t)in.n_prims);
+    words(out->mat, &out->n_mat, in.mat, in.n_prims);
+    words(out->lights, &out->n_lights, in.lights.data(), in.lights.size());
+    words(out->mats, &out->n_mats, in.mats.data(), in.mats.size());
+    words(out->mat_extra, &out->n_mat_extra, in.mat_extra.data(), in.mat_extra.size());
+    words(out->spheres, &out->n_spheres, in.spheres.data(), in.spheres.size());
+    words(out->textures, &out->n_textures, in.textures.data(), in.textures.size());
+    words(out->image_texels, &out->n_image_texels, in.image_texels.data(), in.image_texels.size());
+    for (int k = 0; k < 3; k++) { out->le_inf[k] = in.le_inf[k]; out->env_c[k] = in.env_c[k]; }
+    for (int k = 0; k < 9; k++) out->env_m[k] = in.env_m[k];
+    out->has_inf = in.has_inf; out->env = in.env; out->has_spot = in.has_spot; out->has_mapped = in.has_mapped;
+    out->env_w = in.env_w; out->env_h = in.env_h;
+    return PBRT_HIP_OK;
+  });
 }
 
 }  // extern "C"

@@ -6,9 +6,8 @@
 //             ref = interior index, or 0x80000000 | n_prims << 24 | first leaf slot
 //   tris    : 3 x 16 B per LEAF SLOT  {p0.xyz, triangle id} {p1.xyz, material id} {p2.xyz, 0}
 //             (leaf order, so the <=4 triangles of a leaf are one contiguous 48..192 B run)
-//   mats    : 2 x 16 B per material   {type, k.xyz} {le.xyz, 0}
-//   lights  : 5 x 16 B per light      {type, p0.xyz} {p1.xyz, area} {p2.xyz, 0} {c.xyz, 0} {n.xyz, 0}
-//   spheres : 2 x 16 B per sphere     {c.xyz, r} {material id, 0, 0, 0}   (shading; in the tree a sphere is a leaf record of `tris`:
+//   mats, lights, spheres : the small tables of 2, 5 and 2 x 16 B per material / light / sphere -- scene_tables.hpp states their rows, for
+//             every kind of light and material, and holds their readers and writers.  (In the tree a sphere is a leaf record of `tris`:
 //             {c.xyz, primitive id} {r, 0, 0, material id} {0, 0, 0, 1} -- word 3 of the third float4 flags it)
 #pragma once
 #include <stdint.h>
@@ -201,16 +200,15 @@ struct RenderParams {
   // sampler 2 (render_kernel<..., SND>): generator matrices of the first ten Sobol' dimensions, 32 columns each
   const uint32_t *sobol_mat;
   // textured materials (render_kernel_x<..., TEX>): corner (u, v) per leaf slot -- 3 x float2 --, and 3 x 16 B per
-  // texture {type, tex1.rgb}{tex2.rgb, su}{sv, du, dv, 0}; a material's texture number rides in mats[2 i + 1].w (0 = none).  (Scene
+  // texture {type, tex1.rgb}{tex2.rgb, su}{sv, du, dv, 0}; a material's texture number rides in its second row's w (0 = none: scene_tables.hpp).  (Scene
   // data -- but appended HERE, to the kernel's last argument: a field added to DevScene would move every offset of this block and
   // with them the machine code of the instantiations the counter profiles are keyed by.)
   const float2 *tri_uv;
   const float4 *textures;
-  // glass materials (render_kernel_x<..., GLS>): 16 B per MATERIAL {Kt.rgb, eta}, read for the materials of type 2 alone
-  // (mats[2 i] = {2, Kr}, mats[2 i + 1] = 0: glass does not emit).  At the end, for the reason given above.
-  // A plastic material's row (type 3) is {Ks.rgb, alpha}, read by the same instantiations (mats[2 i] = {3, Kd}); a
-  // substrate material's (type 4, 3.24) likewise.
-  const float4 *glass;
+  // the materials' extra rows (render_kernel_x<..., GLS>; scene_tables.hpp mat_extra): 16 B per MATERIAL, read for
+  // glass ({Kt.rgb, eta}) and, under PLS, for plastic and substrate ({Ks.rgb, alpha}) alone; null for a scene without such a material.  At the
+  // end, for the reason given above.
+  const float4 *mat_extra;
   // an environment-map infinite light (render_kernel_env): the texels {r, g, b, p_uv} row-major (row 0 = theta 0), the
   // marginal CDF over rows (env_h + 1 floats) and the rows' conditional CDFs (env_h x (env_w + 1)), world_to_light (row-major 3 x 3) and
   // the light's factor on the texels (envmap_core.hpp).  At the end, for the reason given above.

@@ -6,34 +6,25 @@
 #include "kernel_walk.hpp"
 #include "light_map.hpp"
 #include "plastic_bsdf.hpp"
+#include "scene_tables.hpp"
 #include "substrate_bsdf.hpp"
 #include "spot_light.hpp"
 
 namespace pbrt_hip {
 namespace {
 
-// the light table's type word of a spot light: position in row 0, {axis, cos_total} in row 1, cos_start in row 2, I in
-// row 3 (capi_scene.cpp gather_inputs).  sample_light below knows nothing of it: a spot light is taken BEFORE that chain, under PLS
-constexpr uint32_t kDevLightSpot = 5u;
-// ... and of the mapped lights, by their record's kind: position in row 0, {a row of world_to_light, inv_tan / sx / sy} in
-// rows 1, 2 and 4, {I, the bits of the image slot's 0-based number} in row 3.  Taken before sample_light's chain too, under PLS
-constexpr uint32_t kDevLightProjection = 6u, kDevLightGonio = 7u;
-// the types that are taken before sample_light's chain are the table's LARGEST (3 is an emissive triangle, 4 the environment map, which no
-// PLS kernel meets): ONE compare finds them, so a scene without them pays what it paid for the spot light's test alone
-__device__ __forceinline__ bool dev_light_beyond_chain(uint32_t type) { return type >= kDevLightSpot; }
-
 // One light of UniformSampleOneLight.  false: geometry rules the light out.
 // mis: the estimate weighted with the power heuristic pl^2 / (pl^2 + pb^2), pl = this strategy's density for the
 // direction (light picked with 1 / nL), pb = cos / pi the BSDF's; delta lights keep weight 1
 __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 po, V3 nf, V3 kd, float u1, float u2,
                                              float nLf, V3 &Ld, V3 &wi, float &tmax, const bool mis = false) {
-  const float4 l0 = S.lights[5 * li];
-  const float4 l3 = S.lights[5 * li + 3];
+  const float4 l0 = light_row(S, li, 0u);
+  const float4 l3 = light_row(S, li, 3u);
   const uint32_t type = __float_as_uint(l0.x);
   const V3 p0 = {l0.y, l0.z, l0.w};
   const V3 lc = xyz(l3);
   const V3 f = kd * kInvPi;
-  if (type == 0u) {
+  if (type == kDevLightPoint) {
     V3 dv = p0 - po;
     float dist2 = dot(dv, dv);
     if (!(dist2 > 0.f)) return false;
@@ -45,7 +36,7 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
     Ld = (f * lc) * scale;
     tmax = dist * kShadowShrink;
     return true;
-  } else if (type == 1u) {
+  } else if (type == kDevLightDistant) {
     wi = p0;
     float cs = dot(wi, nf);
     if (!(cs > 0.f)) return false;
@@ -53,7 +44,7 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
     Ld = (f * lc) * scale;
     tmax = kInf;
     return true;
-  } else if (type == 2u) {
+  } else if (type == kDevLightInfinite) {
     float z = cosine_about(nf, u1, u2, wi);
     if (z == 0.f) return false;
     Ld = (kd * lc) * nLf;
@@ -61,11 +52,11 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
     tmax = kInf;
     return true;
   } else {
-    // (an emissive triangle: device type 3.  Device type 4, an environment map, never arrives here: a kernel with ENV takes it before
+    // (kDevLightTriangle.  kDevLightEnv, an environment map, never arrives here: a kernel with ENV takes it before
     // this chain, and a scene with a map is rendered by a family with ENV alone: render_variant.hpp render_family)
-    const float4 l1 = S.lights[5 * li + 1];
-    const float4 l2 = S.lights[5 * li + 2];
-    const float4 l4 = S.lights[5 * li + 4];
+    const float4 l1 = light_row(S, li, 1u);
+    const float4 l2 = light_row(S, li, 2u);
+    const float4 l4 = light_row(S, li, 4u);
     float su0 = sqrtf(u1);
     float b0 = 1.0f - su0;
     float b1 = u2 * su0;
@@ -95,10 +86,10 @@ __device__ __forceinline__ bool sample_light(const DevScene &S, uint32_t li, V3 
 // type kDevLightSpot.  Called under PLS alone -- the GLS instantiations of render_kernel_x --, so that sample_light and the instantiations
 // built from it keep their machine code.  A delta light: no MIS weight.
 __device__ __forceinline__ bool sample_light_spot(const DevScene &S, uint32_t li, V3 po, V3 nf, V3 kd, float nLf, V3 &Ld, V3 &wi, float &tmax) {
-  const float4 l0 = S.lights[5 * li];
-  const float4 l1 = S.lights[5 * li + 1];
-  const float4 l2 = S.lights[5 * li + 2];
-  const float4 l3 = S.lights[5 * li + 3];
+  const float4 l0 = light_row(S, li, 0u);
+  const float4 l1 = light_row(S, li, 1u);
+  const float4 l2 = light_row(S, li, 2u);
+  const float4 l3 = light_row(S, li, 3u);
   const V3 f = kd * kInvPi;
   float fall, scale;
   if (!spot::sample(po, nf, mk(l0.y, l0.z, l0.w), xyz(l1), l1.w, l2.x, nLf, wi, tmax, fall, scale)) return false;
@@ -110,11 +101,11 @@ __device__ __forceinline__ bool sample_light_spot(const DevScene &S, uint32_t li
 // rgb apart, for the two callers to multiply in their own order.  `textures` and `texels` are RenderParams' rows and texel pool.
 __device__ __forceinline__ bool sample_light_map(const DevScene &S, const float4 *textures, const float4 *texels, uint32_t li, V3 po, V3 nf, float nLf, V3 &lc,
                                                  float &scale, V3 &rgb, V3 &wi, float &tmax) {
-  const float4 l0 = S.lights[5 * li];
-  const float4 l1 = S.lights[5 * li + 1];
-  const float4 l2 = S.lights[5 * li + 2];
-  const float4 l3 = S.lights[5 * li + 3];
-  const float4 l4 = S.lights[5 * li + 4];
+  const float4 l0 = light_row(S, li, 0u);
+  const float4 l1 = light_row(S, li, 1u);
+  const float4 l2 = light_row(S, li, 2u);
+  const float4 l3 = light_row(S, li, 3u);
+  const float4 l4 = light_row(S, li, 4u);
   const uint32_t slot = __float_as_uint(l3.w);
   const float4 t0 = textures[3u * slot], t2 = textures[3u * slot + 2u];
   float s, t;
@@ -139,13 +130,13 @@ __device__ __forceinline__ bool sample_light_mapped(const DevScene &S, const flo
 // (textures, texels: RenderParams' rows and texel pool, which a mapped light's image is read from)
 __device__ __forceinline__ bool sample_light_general(const DevScene &S, const float4 *textures, const float4 *texels, uint32_t li, V3 po, V3 nf, float u1, float u2,
                                                      float nLf, V3 &Lg, V3 &wi, float &tmax, float &pl) {
-  const float4 l0 = S.lights[5 * li];
-  const float4 l3 = S.lights[5 * li + 3];
+  const float4 l0 = light_row(S, li, 0u);
+  const float4 l3 = light_row(S, li, 3u);
   const uint32_t type = __float_as_uint(l0.x);
   const V3 p0 = {l0.y, l0.z, l0.w};
   const V3 lc = xyz(l3);
   pl = 0.f;
-  if (type == 0u) {
+  if (type == kDevLightPoint) {
     V3 dv = p0 - po;
     float dist2 = dot(dv, dv);
     if (!(dist2 > 0.f)) return false;
@@ -156,14 +147,14 @@ __device__ __forceinline__ bool sample_light_general(const DevScene &S, const fl
     Lg = lc * ((cs / dist2) * nLf);
     tmax = dist * kShadowShrink;
     return true;
-  } else if (type == 1u) {
+  } else if (type == kDevLightDistant) {
     wi = p0;
     float cs = dot(wi, nf);
     if (!(cs > 0.f)) return false;
     Lg = lc * (cs * nLf);
     tmax = kInf;
     return true;
-  } else if (type == 2u) {
+  } else if (type == kDevLightInfinite) {
     // the constant infinite light: a cosine-sampled direction, pdf_l = cos_i / pi, so Lg = Le pi nL
     float z = cosine_about(nf, u1, u2, wi);
     if (z == 0.f) return false;
@@ -174,8 +165,8 @@ __device__ __forceinline__ bool sample_light_general(const DevScene &S, const fl
   } else if (dev_light_beyond_chain(type)) {
     if (type == kDevLightSpot) {
       // a spot light: the point light with the cone's falloff, a delta light like it (pl stays 0)
-      const float4 l1 = S.lights[5 * li + 1];
-      const float4 l2 = S.lights[5 * li + 2];
+      const float4 l1 = light_row(S, li, 1u);
+      const float4 l2 = light_row(S, li, 2u);
       float fall, scale;
       if (!spot::sample(po, nf, p0, xyz(l1), l1.w, l2.x, nLf, wi, tmax, fall, scale)) return false;
       Lg = lc * scale;
@@ -188,10 +179,10 @@ __device__ __forceinline__ bool sample_light_general(const DevScene &S, const fl
     Lg = (lm * scale) * rgb;
     return true;
   } else {
-    // an emissive triangle (device type 3; the environment map's type 4 never arrives: a scene with plastic and a map is refused)
-    const float4 l1 = S.lights[5 * li + 1];
-    const float4 l2 = S.lights[5 * li + 2];
-    const float4 l4 = S.lights[5 * li + 4];
+    // an emissive triangle (kDevLightTriangle; the environment map's kDevLightEnv never arrives: a scene with plastic and a map is refused)
+    const float4 l1 = light_row(S, li, 1u);
+    const float4 l2 = light_row(S, li, 2u);
+    const float4 l4 = light_row(S, li, 4u);
     float su0 = sqrtf(u1);
     float b0 = 1.0f - su0;
     float b1 = u2 * su0;
@@ -215,7 +206,6 @@ __device__ __forceinline__ bool sample_light_general(const DevScene &S, const fl
 
 // ---- the environment-map infinite light (the arithmetic is envmap_core.hpp's, shared with the host).  Used by the ENV
 // instantiation alone (kernels_env.hip render_kernel_env): nothing below is reachable from render_kernel / render_kernel_x. ----
-constexpr uint32_t kDevLightEnv = 4u;  // the light table's type word of the map's light (3 is an emissive triangle there: capi_scene.cpp gather_inputs)
 __device__ __forceinline__ envmap::Map env_map(const RenderParams &R) {
   envmap::Map m;
   m.texels = R.env_texels;

@@ -128,14 +128,14 @@ __global__ void __launch_bounds__(256, (COUNT ? 1 : (SPH ? 4 : PBRT_INTERSECT_WA
 }
 
 // n_prims = n_tris + the spheres: primitive t >= n_tris is sphere t - n_tris (its place in the vertex / index buffers is taken by a
-// degenerate proxy triangle spanning its box, so that every builder bounds it: capi_scene.cpp) and gets a sphere's record
+// degenerate proxy triangle spanning its box, so that every builder bounds it: scene_inputs.hpp) and gets a sphere's record
 __global__ void pack_tris_kernel(const float *P, const uint32_t *idx, const uint16_t *mat_id, const uint32_t *order,
                                  uint32_t n_prims, uint32_t n_tris, const float4 *spheres, float4 *tris) {
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= n_prims) return;
   const uint32_t t = order[slot];
   if (t >= n_tris) {
-    const float4 cr = spheres[2 * (t - n_tris)], m = spheres[2 * (t - n_tris) + 1];
+    const float4 cr = spheres[kSphereRows * (t - n_tris)], m = spheres[kSphereRows * (t - n_tris) + 1u];
     tris[kTriStride * slot] = make_float4(cr.x, cr.y, cr.z, __uint_as_float(t));
     tris[kTriStride * slot + 1] = make_float4(cr.w, 0.f, 0.f, m.x);
     tris[kTriStride * slot + 2] = make_float4(0.f, 0.f, 0.f, __uint_as_float(1u));

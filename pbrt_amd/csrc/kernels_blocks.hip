@@ -94,8 +94,8 @@ __global__ void __launch_bounds__(256) blocks_eval_kernel(uint32_t op, int64_t n
     case PBRT_HIP_BLOCK_MIS_W_BSDF: y[0] = mis_weight_bsdf(x[1], x[0]); break;
     case PBRT_HIP_BLOCK_LIGHT: {
       // the light's records in a local table (no alignment asked of the input row), light 0 of a scene that holds nothing else
-      float4 rec[5];
-      for (int k = 0; k < 5; k++) rec[k] = make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
+      float4 rec[kLightRows];
+      for (int k = 0; k < (int)kLightRows; k++) rec[k] = make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
       DevScene S{};
       S.lights = rec;
       const V3 po = mk(x[20], x[21], x[22]), nf = mk(x[23], x[24], x[25]), kd = mk(x[26], x[27], x[28]);

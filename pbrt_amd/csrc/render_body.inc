@@ -94,7 +94,7 @@
           V3 p = {0.f, 0.f, 0.f}, ng = {0.f, 0.f, 1.f};
           float4 m0 = {0.f, 0.f, 0.f, 0.f}, m1 = {0.f, 0.f, 0.f, 0.f};
           float tri_area = 0.f;  // MIS: the hit triangle's area
-          float4 gl = {0.f, 0.f, 0.f, 1.f};  // GLS: {Kt, eta} of a glass material (DESIGN.md 3.16)
+          float4 gl = {0.f, 0.f, 0.f, 1.f};  // GLS: the material's row of mat_extra (scene_tables.hpp): {Kt, eta} of glass, {Ks, alpha} of plastic and substrate
           const V3 wo = -T.d;
           if (hit) {
             uint32_t mid;
@@ -108,16 +108,16 @@
               mid = __float_as_uint(b.w);
             } else {
               const uint32_t si = h.prim - S.n_tris;
-              const float4 cr = S.spheres[2 * si];
+              const float4 cr = S.spheres[kSphereRows * si];
               const V3 c = xyz(cr);
               const V3 ph = (T.o - c) + T.d * h.t;
               ng = ph / cr.w;
               p = c + ph;
-              mid = __float_as_uint(S.spheres[2 * si + 1].x);
+              mid = __float_as_uint(S.spheres[kSphereRows * si + 1u].x);
             }
-            m0 = S.mats[2 * mid];
-            m1 = S.mats[2 * mid + 1];
-            if (GLS && (__float_as_uint(m0.x) == 2u || (PLS && __float_as_uint(m0.x) - 3u <= 1u))) gl = R.glass[mid];  // (PLS: {Ks, alpha} of a plastic or a substrate material, 3.21, 3.24)
+            m0 = S.mats[kMatRows * mid];
+            m1 = S.mats[kMatRows * mid + 1u];
+            if (GLS && (mat_is_glass(__float_as_uint(m0.x)) || (PLS && mat_is_coated(__float_as_uint(m0.x))))) gl = R.mat_extra[mid];  // (PLS: {Ks, alpha} of a plastic or a substrate material, 3.21, 3.24)
           }
           if (P.bounces == 0 || P.specular) {
             if (hit) {
@@ -209,7 +209,7 @@
             bool alive = true;
             V3 lpend = {0.f, 0.f, 0.f};
             bool transmitted = false;  // GLS: the bounce ray leaves on the far side of the surface
-            if (GLS && __float_as_uint(m0.x) == 2u) {
+            if (GLS && mat_is_glass(__float_as_uint(m0.x))) {
               // glass (DESIGN.md 3.16; pbrt-v3 FresnelSpecular): ONE 1-D request chooses reflection (probability F, weight Kr) or
               // refraction (1 - F, weight Kt eta_i^2 / eta_t^2); no light sample, no shadow ray; specular like the mirror
               const float cos_o = dot(ng, wo);
@@ -227,7 +227,7 @@
                 transmitted = true;
               }
               P.specular = true;
-            } else if (__float_as_uint(m0.x) == 0u) {  // matte
+            } else if (mat_is_matte(__float_as_uint(m0.x))) {
               if (nL > 0u) {
                 const float xi = sample_1d<SND>(P, sobol, spp_mask, R.sobol_mat, halton);
                 float u1, u2;
@@ -235,7 +235,7 @@
                 uint32_t li = (uint32_t)(xi * nLf);
                 li = min(li, nL - 1u);
                 V3 Ld;
-                if (ENV && __float_as_uint(S.lights[5 * li].x) == kDevLightEnv) {  // the environment map's light (3.17): the same (u1, u2)
+                if (ENV && light_type(S, li) == kDevLightEnv) {  // the environment map's light (3.17): the same (u1, u2)
                   // (NRM: a light sample counts only from the geometric front side as well)
                   if (sample_env_light(R, nsh, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS) && (!(NRM && smooth) || dot(sh_d, nf) > 0.f)) {
                     need_shadow = true;
@@ -243,9 +243,9 @@
                     if (!MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, 0.f));
                   }
                 } else
-                if (PLS && dev_light_beyond_chain(__float_as_uint(S.lights[5 * li].x))) {
+                if (PLS && dev_light_beyond_chain(light_type(S, li))) {
                   // a spot light (3.22) or a mapped light (3.23): taken before sample_light's chain, which does not know them, by ONE compare
-                  if (__float_as_uint(S.lights[5 * li].x) == kDevLightSpot ? sample_light_spot(S, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)
+                  if (light_type(S, li) == kDevLightSpot ? sample_light_spot(S, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)
                                                                            : sample_light_mapped(S, R.textures, R.image_texels, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)) {
                     need_shadow = true;
                     lpend = P.beta * Ld;
@@ -271,13 +271,13 @@
                 // MIS: the pending light sample and, beside it, the density the bounce ray was drawn with (read where it lands)
                 if (MIS) rec_store(rec, kRecLpend, make_float4(lpend.x, lpend.y, lpend.z, z * kInvPi));
               }
-            } else if (PLS && __float_as_uint(m0.x) - 3u <= 1u) {  // (types 3 and 4 by ONE compare)
+            } else if (PLS && mat_is_coated(__float_as_uint(m0.x))) {  // (plastic and substrate by ONE compare)
               // plastic (DESIGN.md 3.21; plastic_bsdf.hpp) and substrate (3.24; substrate_bsdf.hpp: the same direction sampler, another f; only
               // the BSDF inside the eval / sample_f calls is chosen by the type word): k = Kd, gl = {Ks, alpha}.  The requests of a matte vertex in their order -- the
               // pick, the light's pair, the bounce's pair --; the light sample carries f(wo, wi) in the Lambertian factor's place and, with
               // MIS, the weight against THIS BSDF's density; the bounce keeps its density beside the pending light sample as matte does
               const V3 ks = mk(gl.x, gl.y, gl.z);
-              const bool coat = __float_as_uint(m0.x) == 4u;  // substrate
+              const bool coat = mat_is_substrate(__float_as_uint(m0.x));
               if (nL > 0u) {
                 const float xi = sample_1d<SND>(P, sobol, spp_mask, R.sobol_mat, halton);
                 float u1, u2;
@@ -294,7 +294,7 @@
                   if (MIS && pl > 0.f) {
                     // (the constant infinite light keeps 3.14's constant pair of weights, 1 / (1 + nL^2) here and nL^2 / (nL^2 + 1) where a
                     // bounce ray escapes: the escape does not know the vertex it left, and the pair sums to one whatever the BSDF)
-                    Ld = Ld * (__float_as_uint(S.lights[5 * li].x) == 2u ? 1.0f / (1.0f + nLf * nLf) : mis_weight_light(pl, pbl));
+                    Ld = Ld * (light_type(S, li) == kDevLightInfinite ? 1.0f / (1.0f + nLf * nLf) : mis_weight_light(pl, pbl));
                   }
                   need_shadow = true;
                   lpend = P.beta * Ld;

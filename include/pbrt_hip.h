@@ -267,12 +267,27 @@ typedef struct {
   float inv_tan, sx, sy;
   uint32_t pad[1];
 } pbrt_hip_light_map;
+/* AreaLightSource "diffuse" on a Shape "sphere" (pbrt-v3's DiffuseAreaLight over Sphere::Sample): type 8 -- 4 and 7 stay
+ * unknown light types --, a light that NAMES a sphere of the scene: `pad` = the BITS of the sphere's 1-based number in `spheres`, c = the
+ * radiance L, which must equal the `le` of that sphere's material bit for bit (the surface a ray hits and the light a vertex samples then
+ * cannot disagree), p is not used (it must be finite, as every light's p must).  The named sphere is held to every sphere's
+ * rules first: its radius is finite and positive before the light is looked at.  The sphere stays the primitive it is: camera rays and specular paths see its emission through the
+ * material.  What the light adds is the direct-light estimate: a matte, plastic or substrate vertex samples the sphere uniformly in the
+ * solid angle it subtends (one-sided, outward: a vertex inside the sphere gets nothing), and under MIS a BSDF-sampled ray that lands on the
+ * sphere from outside carries the power heuristic's other half.  An emissive sphere that NO light names renders as it always did: seen
+ * by camera rays and after specular bounces only.  Refused at scene creation before any device work (PBRT_HIP_ERR_INVALID, the message
+ * holds "sphere light"): a `pad` that names no sphere; two lights that name one sphere; a sphere whose material is glass, plastic or
+ * substrate (they reuse `le`); an `le` with no positive channel; a c that differs from `le`.  Rendered by the kernels that render glass,
+ * plastic, spot and mapped lights (the GLS instantiations of render_kernel_x), for every integrator, sampler and filter; NOT in a scene
+ * whose texture table holds an environment map (slot type 1) or shading normals (slot type 2): PBRT_HIP_ERR_LIMIT (the message holds
+ * "sphere light").  Not with the counter flags (PBRT_HIP_ERR_LIMIT at render, as for glass). */
+#define PBRT_HIP_LIGHT_SPHERE 8u
 typedef struct {
-  uint32_t type; /* 0 point, 1 distant, 2 infinite with constant radiance, 3 infinite with an environment map, 5 spot, 6 mapped */
+  uint32_t type; /* 0 point, 1 distant, 2 infinite with constant radiance, 3 infinite with an environment map, 5 spot, 6 mapped, 8 sphere */
   float p[3];    /* point, spot, mapped: position; distant: unit direction TOWARDS the light */
-  float c[3];    /* point, spot, mapped: intensity I; distant / infinite: radiance L; 3: the factor on the texels */
+  float c[3];    /* point, spot, mapped: intensity I; distant / infinite / sphere: radiance L; 3: the factor on the texels */
   float pad;     /* 3: the bits of the texture-table number (1-based) of the pbrt_hip_envmap; 5: of the pbrt_hip_spot_cone; 6: of the
-                    pbrt_hip_light_map */
+                    pbrt_hip_light_map; 8: of the sphere's number (1-based) in `spheres` */
 } pbrt_hip_light;
 
 /* Shape "sphere" (check-sphere.pbrt:22), world space.  A primitive of the BVH like a triangle (primitive number n_tris + index, which is
@@ -360,7 +375,8 @@ typedef struct pbrt_hip_scene pbrt_hip_scene;
 /* number of visible HIP devices (0 when there is none; never fails) */
 int pbrt_hip_device_count(void);
 const char *pbrt_hip_last_error(void);
-const char *pbrt_hip_version(void); /* "pbrt_hip 0.13 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10, 0.11 and 0.12)": 0.13 = material type 4, substrate, inside
+const char *pbrt_hip_version(void); /* "pbrt_hip 0.14 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10, 0.11, 0.12 and 0.13)": 0.14 = light type 8, a sphere
+                                       light, inside the same struct sizes; 0.13 = material type 4, substrate, inside
                                        the same struct sizes; 0.12 = light type 6, a mapped light, and
                                        texture-table slot type 8, its record, inside the same struct sizes; 0.11 = material type 3, plastic, inside
                                        the same struct sizes; 0.10 = texture-table slot type 4, the

@@ -239,6 +239,16 @@ int pbrt_hip_spot_eval_device(int device, int64_t n, const float *in, float *out
 #define PBRT_HIP_LIGHT_MAP_EVAL_OUT 11
 int pbrt_hip_light_map_eval_device(int device, const pbrt_hip_image_texture *image, const pbrt_hip_light_map *map, int64_t n, const float *in, float *out);
 
+/* ---- a sphere light's sample (pbrt_amd/csrc/sphere_light.hpp is the one statement of the arithmetic) ---- */
+/* sphere_light.hpp over arrays on `device` (a small kernel of kernels_blocks.hip): element i reads 13 floats of `in` -- the shading point
+ * po, its normal nf, the sphere's centre c and radius r, the pair u1 u2, nL (the scene's light count as a float) -- and writes 8 floats of
+ * `out`: ok (1 or 0), wi.xyz, tmax, scale = cos (1 / pdf_omega) nL, pdf_omega (these six are zero where ok is), and the hit side's
+ * pdf_omega from po (0 where po is not outside the sphere; it does not depend on ok).  in / out are HOST arrays.  PBRT_HIP_ERR_INVALID for
+ * a negative n or a null array, PBRT_HIP_ERR_NO_DEVICE without a device. */
+#define PBRT_HIP_SPHERE_LIGHT_EVAL_IN 13
+#define PBRT_HIP_SPHERE_LIGHT_EVAL_OUT 8
+int pbrt_hip_sphere_light_eval_device(int device, int64_t n, const float *in, float *out);
+
 /* ---- the small device tables of a scene, as scene creation assembles them on the host (pbrt_amd/csrc/scene_tables.hpp states their rows) ---- */
 /* HOST arrays of 32-bit words that pbrt_hip_scene_tables_host fills, each of which may be NULL, and beside each the count of words it holds
  * (set whether or not the array is given: a first call with every array NULL sizes a second one).  P / idx / mat: the primitives the tree

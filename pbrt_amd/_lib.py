@@ -198,6 +198,7 @@ SYMBOLS = {
     "pbrt_hip_plastic_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
     "pbrt_hip_substrate_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
     "pbrt_hip_spot_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
+    "pbrt_hip_sphere_light_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
     "pbrt_hip_light_map_eval_device": (C.c_int, [C.c_int, C.POINTER(ImageTexture), C.POINTER(LightMap), _i64, _pf, _pf]),
     "pbrt_hip_shading_normal_eval_device": (C.c_int, [C.c_int, _i64, _pf, _pf]),
 }

@@ -19,6 +19,7 @@ LIGHT_ENVMAP = 3  # PBRT_HIP_LIGHT_ENVMAP: the infinite light with an environmen
 LIGHT_SPOT = 5  # PBRT_HIP_LIGHT_SPOT: a point light inside a cone with a smooth edge; 4 is no light type
 LIGHT_MAPPED = 6  # PBRT_HIP_LIGHT_MAPPED: a point light times an image looked up in the direction from the light; 7 is no light type
 LIGHT_MAP_PROJECTION, LIGHT_MAP_GONIOMETRIC = 0, 1  # PBRT_HIP_LIGHT_MAP_*: a light map's kind
+LIGHT_SPHERE = 8  # PBRT_HIP_LIGHT_SPHERE: a sphere of the scene as an area light, sampled by solid angle
 INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_PATH_MIS = 0, 1, 2  # 2: the path integrator with MIS
 FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_SINC = 1, 2, 3, 4  # PBRT_HIP_FILTER_*: the weighted pixel filters
 FILTER_KINDS = {"triangle": FILTER_TRIANGLE, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL, "sinc": FILTER_SINC}
@@ -69,7 +70,8 @@ class SceneData:
     behind the filter's and before the normals'.  Mapped lights: a `lights` row (LIGHT_MAPPED, position, I rgb) and `light_maps`
     rows of 14 (kind, the 1-based number of a TEXTURE_IMAGE row of `textures`, world_to_light[9] row-major, inv_tan, sx, sy), the k-th row the
     record of the k-th LIGHT_MAPPED row (projection_light / goniometric_light make the pair); each record travels in a slot of its own behind
-    the cones."""
+    the cones.  Sphere lights: a `lights` row (LIGHT_SPHERE, k, 0, 0, L rgb), k the 0-based row of `spheres` it names and L the
+    le of that sphere's material (sphere_light makes the row)."""
     P: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
     idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.uint32))
     mat_id: np.ndarray = field(default_factory=lambda: np.zeros((0,), np.uint16))
@@ -187,6 +189,9 @@ def fill_desc(desc, sd, mat_t, light_t, sphere_t, tex_t=None):
         if int(l[0]) == LIGHT_MAPPED:  # likewise, of its record's slot
             lights[i].pad = float(np.array([first_map + n_mapped + 1 if n_mapped < len(sd.light_maps) else 0], np.uint32).view(np.float32)[0])
             n_mapped += 1
+        if int(l[0]) == LIGHT_SPHERE:  # `pad` = the bits of the sphere's 1-based number (the row's first word is its 0-based row); p is not used
+            lights[i].pad = float(np.array([int(l[1]) + 1 if 0 <= l[1] < 2 ** 24 else 0], np.uint32).view(np.float32)[0])
+            lights[i].p[:] = [0.0, 0.0, 0.0]
     spheres = (sphere_t * max(len(sd.spheres), 1))()
     for i, s in enumerate(sd.spheres):
         spheres[i].c[:] = [float(x) for x in s[0:3]]
@@ -290,6 +295,22 @@ def spot_eval_device(x, device=0):
     x = np.ascontiguousarray(x, np.float32).reshape(-1, 15)
     out = np.zeros((x.shape[0], 7), np.float32)
     check(lib().pbrt_hip_spot_eval_device(int(device), x.shape[0], _fp(x), _fp(out)), "pbrt_hip_spot_eval_device")
+    return out
+
+
+def sphere_light(sd, k):
+    """-> the `lights` row (LIGHT_SPHERE, k, 0, 0, L) that makes sphere k of `sd` a sphere light: L is the le of the sphere's
+    material, which scene creation holds the row to bit for bit"""
+    mat = int(np.asarray(sd.spheres, np.float32).reshape(-1, 5)[k, 4])
+    return [LIGHT_SPHERE, float(k), 0.0, 0.0, *np.asarray(sd.materials, np.float32).reshape(-1, 7)[mat, 4:7]]
+
+
+def sphere_light_eval(x, device=0):
+    """pbrt_hip_sphere_light_eval_device: csrc/sphere_light.hpp over arrays on the device.  x (n, 13): po, nf, c, r, u1, u2, nL -> (n, 8)
+    float32: ok, wi, tmax, scale = cos (1 / pdf_omega) nL, pdf_omega (zeros behind ok = 0), and the hit side's pdf_omega from po"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 13)
+    out = np.zeros((x.shape[0], 8), np.float32)
+    check(lib().pbrt_hip_sphere_light_eval_device(int(device), x.shape[0], _fp(x), _fp(out)), "pbrt_hip_sphere_light_eval_device")
     return out
 
 

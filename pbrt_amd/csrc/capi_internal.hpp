@@ -99,7 +99,7 @@ struct SceneTraits {
   bool gpu_built = false;  // accelerator built on the device: the canonical tree (counter flags) is made on first use
   uint32_t n_quads_gpu = 0;
   bool textured = false;  // some primitive's material has kd_tex != 0: the TEX instantiations render the scene
-  bool glass = false;     // some material is glass or plastic (beyond matte and mirror), or some light is a spot or a mapped light: the GLS instantiations render the scene
+  bool glass = false;     // some material is glass or plastic (beyond matte and mirror), or some light is a spot, a mapped or a sphere light: the GLS instantiations render the scene
   bool env = false;       // an environment-map light: render_kernel_env renders the scene; the map's size, world_to_light and the light's factor
   uint32_t env_w = 0, env_h = 0;
   float env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, env_c[3] = {0, 0, 0};

@@ -191,8 +191,25 @@ int check_light_map(const pbrt_hip_light_map &m, const TextureTable &table, cons
 }
 int check_light_kinds(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   for (uint32_t i = 0; i < d->n_lights; i++)
-    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP && d->lights[i].type != PBRT_HIP_LIGHT_SPOT && d->lights[i].type != PBRT_HIP_LIGHT_MAPPED)
+    if (d->lights[i].type > PBRT_HIP_LIGHT_ENVMAP && d->lights[i].type != PBRT_HIP_LIGHT_SPOT && d->lights[i].type != PBRT_HIP_LIGHT_MAPPED &&
+        d->lights[i].type != PBRT_HIP_LIGHT_SPHERE)
       return fail(PBRT_HIP_ERR_INVALID, "scene_create: unknown light type");
+  // (a sphere light -- DESIGN.md 3.25 -- likewise HERE, where a type-8 light was refused as unknown: the sphere it names, once, and a
+  // material that emits what the light says.  check_mesh has held every sphere's radius to be finite and positive by now, and
+  // check_light_values every light's p -- which this light does not use -- to be finite)
+  std::vector<bool> listed(d->n_spheres, false);
+  for (uint32_t i = 0; i < d->n_lights; i++) {
+    if (d->lights[i].type != PBRT_HIP_LIGHT_SPHERE) continue;
+    const std::string what = "scene_create: light " + std::to_string(i) + ": ";
+    const uint32_t number = light_slot(d->lights[i]);
+    if (number == 0u || number > d->n_spheres) return fail(PBRT_HIP_ERR_INVALID, what + "a sphere light (type 8) must name a sphere of the scene in `pad` (1-based)");
+    if (listed[number - 1u]) return fail(PBRT_HIP_ERR_INVALID, what + "a second sphere light names sphere " + std::to_string(number - 1u));
+    listed[number - 1u] = true;
+    const pbrt_hip_material &m = d->mats[d->spheres[number - 1u].mat];
+    if (reuses_le(m)) return fail(PBRT_HIP_ERR_INVALID, what + "sphere light: the sphere's material is glass, plastic or substrate, which do not emit");
+    if (!(m.le[0] > 0.f || m.le[1] > 0.f || m.le[2] > 0.f)) return fail(PBRT_HIP_ERR_INVALID, what + "sphere light: the sphere's material has no positive le");
+    if (std::memcmp(d->lights[i].c, m.le, sizeof m.le) != 0) return fail(PBRT_HIP_ERR_INVALID, what + "sphere light: c must equal the le of the sphere's material bit for bit");
+  }
   // (a spot light and its cone are checked HERE, where the light's kind is recognised -- the place a type-5 light was refused as unknown
   // before there were spot lights --, so that every fault that used to win against it still does)
   for (uint32_t i = 0; i < d->n_lights; i++) {
@@ -304,7 +321,7 @@ int check_material_kinds(const pbrt_hip_scene_desc *d) {
 }
 // Plastic is rendered by the GLS instantiations of render_kernel_x alone: the families that render an environment map or
 // shading normals do not carry its branch, and the scene is refused here, not at render time.  Substrate (3.24) shares the branch and the
-// refusal; a spot light (3.22) and a mapped light (3.23) are sampled under PLS alone, in the same instantiations.  Each is refused under its
+// refusal; a spot light (3.22), a mapped light (3.23) and a sphere light (3.25) are sampled under PLS alone, in the same instantiations.  Each is refused under its
 // own name, and of several the first in this order is the one named
 int check_pls_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
   auto has_material = [&](uint32_t type) { return std::any_of(d->mats, d->mats + d->n_mats, [&](const pbrt_hip_material &m) { return m.type == type; }); };
@@ -313,7 +330,8 @@ int check_pls_family(const pbrt_hip_scene_desc *d, const TextureTable &table) {
       {has_material(PBRT_HIP_MATERIAL_PLASTIC), "a plastic material"},
       {has_material(PBRT_HIP_MATERIAL_SUBSTRATE), "a substrate material"},
       {has_light(PBRT_HIP_LIGHT_SPOT), "a spot light"},
-      {has_light(PBRT_HIP_LIGHT_MAPPED), "a light map (a projection or goniometric light)"}};
+      {has_light(PBRT_HIP_LIGHT_MAPPED), "a light map (a projection or goniometric light)"},
+      {has_light(PBRT_HIP_LIGHT_SPHERE), "a sphere light"}};
   for (const auto &n : needs_pls) {
     if (!n.present) continue;
     for (const SlotKind kind : table.kinds) {
@@ -588,7 +606,7 @@ int pbrt_hip_device_count(void) {
 }
 
 const char *pbrt_hip_last_error(void) { return pbrt_hip::last_error_message(); }
-const char *pbrt_hip_version(void) { return "pbrt_hip 0.13 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10, 0.11 and 0.12)"; }
+const char *pbrt_hip_version(void) { return "pbrt_hip 0.14 (gfx950; struct sizes of 0.6, as 0.7, 0.8, 0.9, 0.10, 0.11, 0.12 and 0.13)"; }
 #ifndef PBRT_HIP_BUILD_ID
 #define PBRT_HIP_BUILD_ID "unknown"
 #endif
@@ -758,7 +776,7 @@ int pbrt_hip_scene_create_ex(const pbrt_hip_scene_desc *d, int device, uint32_t 
     gather_inputs(*d, table, &in);
     s->n_prims = in.n_prims;
     s->textured = table.textured_tris || table.textured_sph;
-    s->glass = !in.mat_extra.empty() || in.has_spot || in.has_mapped;  // (a spot and a mapped light are sampled under PLS, in the GLS instantiations: DESIGN.md 3.22, 3.23)
+    s->glass = !in.mat_extra.empty() || in.has_spot || in.has_mapped || in.has_sphere_light;  // (a spot, a mapped and a sphere light are sampled under PLS, in the GLS instantiations: DESIGN.md 3.22, 3.23, 3.25)
     if ((rc = upload_inputs(s.get(), *d, table, in)) || (rc = build_tree(s.get(), in, builder))) return rc;
     if (table.textured_tris) {  // corner (u, v) into leaf-slot order (whichever builder made d_order)
       HIP_TRY(s->d_tri_uv.alloc(3 * (size_t)in.n_prims));

@@ -8,6 +8,7 @@
 #include "plastic_bsdf.hpp"
 #include "scene_tables.hpp"
 #include "substrate_bsdf.hpp"
+#include "sphere_light.hpp"
 #include "spot_light.hpp"
 
 namespace pbrt_hip {
@@ -97,6 +98,25 @@ __device__ __forceinline__ bool sample_light_spot(const DevScene &S, uint32_t li
   return true;
 }
 
+// A sphere light at a matte vertex (sphere_light.hpp): sample_light's outputs for light li, which the caller has found to be of
+// type kDevLightSphere, from the pair (u1, u2) the vertex drew for its light.  Called under PLS alone, as sample_light_spot is.  An area
+// light: with mis the estimate carries pl^2 / (pl^2 + pb^2), pl = pdf_omega / nL, pb = cos / pi, as an emissive triangle's does.
+__device__ __forceinline__ bool sample_light_sphere(const DevScene &S, uint32_t li, V3 po, V3 nf, V3 kd, float u1, float u2, float nLf, V3 &Ld, V3 &wi, float &tmax,
+                                                    const bool mis) {
+  const float4 l0 = light_row(S, li, 0u);
+  const float4 l1 = light_row(S, li, 1u);
+  const float4 l3 = light_row(S, li, 3u);
+  const V3 f = kd * kInvPi;
+  float scale, pdf, cs;
+  if (!sphere_light::sample(po, nf, mk(l0.y, l0.z, l0.w), l1.x, u1, u2, nLf, wi, tmax, scale, pdf, cs)) return false;
+  if (mis) {
+    const float pl = pdf / nLf, pbl = cs * kInvPi;
+    scale = scale * mis_weight_light(pl, pbl);
+  }
+  Ld = (f * xyz(l3)) * scale;
+  return true;
+}
+
 // A mapped light (light_map.hpp) of type kDevLightProjection or kDevLightGonio: the point light's (lc scale) and the image's
 // rgb apart, for the two callers to multiply in their own order.  `textures` and `texels` are RenderParams' rows and texel pool.
 __device__ __forceinline__ bool sample_light_map(const DevScene &S, const float4 *textures, const float4 *texels, uint32_t li, V3 po, V3 nf, float nLf, V3 &lc,
@@ -170,6 +190,15 @@ __device__ __forceinline__ bool sample_light_general(const DevScene &S, const fl
       float fall, scale;
       if (!spot::sample(po, nf, p0, xyz(l1), l1.w, l2.x, nLf, wi, tmax, fall, scale)) return false;
       Lg = lc * scale;
+      return true;
+    }
+    if (type == kDevLightSphere) {
+      // a sphere light: an area light, pl = pdf_omega / nL for the caller's MIS rule
+      const float4 l1 = light_row(S, li, 1u);
+      float scale, pdf, cs;
+      if (!sphere_light::sample(po, nf, p0, l1.x, u1, u2, nLf, wi, tmax, scale, pdf, cs)) return false;
+      Lg = lc * scale;
+      pl = pdf / nLf;
       return true;
     }
     // a mapped light: the point light times its image, a delta light like it (pl stays 0)

@@ -6,7 +6,7 @@
 // pbrt_hip_image_lookup_eval_device: image_lookup.hpp over arrays, and pbrt_hip_plastic_eval_device with its kernel:
 // plastic_bsdf.hpp over arrays, and pbrt_hip_spot_eval_device with its kernel: spot_light.hpp over arrays (3.22), and
 // pbrt_hip_light_map_eval_device with its kernel: light_map.hpp over arrays (3.23), and pbrt_hip_substrate_eval_device with its kernel:
-// substrate_bsdf.hpp over arrays (3.24).
+// substrate_bsdf.hpp over arrays (3.24), and pbrt_hip_sphere_light_eval_device with its kernel: sphere_light.hpp over arrays (3.25).
 //
 //   blocks_eval_kernel  one element per thread, 256 threads per workgroup: switches on the op code and calls the PRODUCTION function
 //                       (nothing is restated here); kBlockWidth is how many floats an element reads and writes.
@@ -173,6 +173,15 @@ __global__ void __launch_bounds__(256) spot_eval_kernel(int64_t n, const float *
 #include "spot_eval.inc"
 }
 
+// sphere_light.hpp over arrays (pbrt_hip_sphere_light_eval_device): a sphere light's sample at a shading point and the hit side's density
+__global__ void __launch_bounds__(256) sphere_light_eval_kernel(int64_t n, const float *in, float *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float *x = in + i * (int64_t)PBRT_HIP_SPHERE_LIGHT_EVAL_IN;
+  float *y = out + i * (int64_t)PBRT_HIP_SPHERE_LIGHT_EVAL_OUT;
+#include "sphere_light_eval.inc"
+}
+
 // light_map.hpp over arrays (pbrt_hip_light_map_eval_device): a mapped light's sample at a shading point.  rows = the image
 // slot's three rows, map = {a row of world_to_light, inv_tan / sx / sy} x 3
 __global__ void __launch_bounds__(256) light_map_eval_kernel(uint32_t e_kind, float4 e_r0, float4 e_r1, float4 e_r2, const float4 *rows, const float4 *e_pool, int64_t n,
@@ -295,6 +304,24 @@ extern "C" int pbrt_hip_spot_eval_device(int device, int64_t n, const float *in,
     hipLaunchKernelGGL(spot_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, d_in.p, d_out.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, d_out.p, 4 * PBRT_HIP_SPOT_EVAL_OUT * (size_t)n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PBRT_HIP_OK;
+  });
+}
+
+extern "C" int pbrt_hip_sphere_light_eval_device(int device, int64_t n, const float *in, float *out) {
+  if (n < 0 || !in || !out) return fail(PBRT_HIP_ERR_INVALID, "sphere_light_eval_device: null argument or negative count");
+  if (n == 0) return PBRT_HIP_OK;
+  return guarded([&]() -> int {
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<float> d_in, d_out;
+    HIP_TRY(d_in.alloc(PBRT_HIP_SPHERE_LIGHT_EVAL_IN * (size_t)n));
+    HIP_TRY(d_out.alloc(PBRT_HIP_SPHERE_LIGHT_EVAL_OUT * (size_t)n));
+    const hipStream_t stream = nullptr;  // the device's default stream
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, 4 * PBRT_HIP_SPHERE_LIGHT_EVAL_IN * (size_t)n, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(sphere_light_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, d_in.p, d_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, 4 * PBRT_HIP_SPHERE_LIGHT_EVAL_OUT * (size_t)n, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return PBRT_HIP_OK;
   });

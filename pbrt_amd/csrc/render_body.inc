@@ -144,6 +144,18 @@
                 const float w = mis_weight_bsdf(pb, pl);
                 P.L = P.L + (P.beta * le) * w;
               }
+            } else if (PLS && SPH && hit) {
+              // 3.25: a sphere that a sphere light names, met from outside: light sampling would have drawn this direction with
+              // pl = pdf_omega(origin) / nL.  A sphere that no light names adds nothing here, as ever
+              const uint32_t si = h.prim - S.n_tris;
+              const V3 le = xyz(m1);
+              if (sphere_listed(S, si) && (le.x > 0.f || le.y > 0.f || le.z > 0.f) && dot(ng, wo) > 0.f) {
+                const float4 cr = S.spheres[kSphereRows * si];
+                const float pb = rec_load(rec, kRecLpend).w;
+                const float pl = sphere_light::pdf_omega(T.o, xyz(cr), cr.w) / nLf;
+                const float w = mis_weight_bsdf(pb, pl);
+                P.L = P.L + (P.beta * le) * w;
+              }
             } else if (!hit && S.has_inf) {
               const float w = (nLf * nLf) / (nLf * nLf + 1.0f);
               P.L = P.L + (P.beta * mk(S.le_inf[0], S.le_inf[1], S.le_inf[2])) * w;
@@ -244,8 +256,9 @@
                   }
                 } else
                 if (PLS && dev_light_beyond_chain(light_type(S, li))) {
-                  // a spot light (3.22) or a mapped light (3.23): taken before sample_light's chain, which does not know them, by ONE compare
+                  // a spot light (3.22), a mapped light (3.23) or a sphere light (3.25): taken before sample_light's chain, which does not know them, by ONE compare
                   if (light_type(S, li) == kDevLightSpot ? sample_light_spot(S, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)
+                      : light_type(S, li) == kDevLightSphere ? sample_light_sphere(S, li, po, nsh, k, u1, u2, nLf, Ld, sh_d, sh_tmax, MIS)
                                                                            : sample_light_mapped(S, R.textures, R.image_texels, li, po, nsh, k, nLf, Ld, sh_d, sh_tmax)) {
                     need_shadow = true;
                     lpend = P.beta * Ld;

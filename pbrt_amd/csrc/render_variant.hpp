@@ -34,7 +34,7 @@ struct RenderVariant {
   bool wide;           // WIDE: a box filter radius other than 0.5
   bool table_sampler;  // SND: samplers 2 and 3 (3.12, 3.13)
   bool mis, textured;  // MIS (3.14) and TEX (3.15)
-  bool glass;          // GLS (3.16, 3.21, 3.22, 3.23): the scene has a glass or a plastic material, or a spot or a mapped light
+  bool glass;          // GLS (3.16, 3.21, 3.22, 3.23, 3.25): the scene has a glass or a plastic material, or a spot, a mapped or a sphere light
   bool env;            // ENV (3.17): the scene has an environment map
   bool normals;        // NRM (3.18): the scene carries shading normals
   RenderCounters counters;

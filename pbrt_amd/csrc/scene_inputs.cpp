@@ -45,6 +45,13 @@ void gather_lights(const pbrt_hip_scene_desc &d, const TextureTable &table, Scen
       in->has_spot = true;
       continue;
     }
+    if (l.type == PBRT_HIP_LIGHT_SPHERE) {  // (the sphere's row is marked for the MIS hit side)
+      const uint32_t si = light_slot(l) - 1u;
+      push_light_sphere(&in->lights, d.spheres[si], l.c);
+      mark_sphere_listed(&in->spheres[kSphereRows * (size_t)si]);
+      in->has_sphere_light = true;
+      continue;
+    }
     push_light_plain(&in->lights, dev_light_type(l.type), l.p, l.c);
     if (dev_light_type(l.type) == kDevLightInfinite) {
       for (int k = 0; k < 3; k++) in->le_inf[k] = in->le_inf[k] + l.c[k];

@@ -46,6 +46,7 @@ struct SceneInputs {
   bool has_inf = false;
   bool has_spot = false;  // a spot light: the scene needs the GLS instantiations
   bool has_mapped = false;  // a mapped light: likewise, and the texture rows and the texel pool go up for its image
+  bool has_sphere_light = false;  // a sphere light: the GLS instantiations likewise
 };
 // the four parts in their order: primitives and sphere proxies, lights, materials, texture rows.  `d` has passed check_scene_desc, `table` is its table
 void gather_inputs(const pbrt_hip_scene_desc &d, const TextureTable &table, SceneInputs *in);

@@ -672,7 +672,15 @@ struct Api {
       s.r = r * std::sqrt(sx[0] * sx[0] + sx[1] * sx[1] + sx[2] * sx[2]);  // uniform scale assumed
       s.mat = mid;
       out->spheres.push_back(s);
-      if (gs.has_area_light && !in_object) warn("sphere area lights emit but are not sampled by the direct-light estimate");
+      if (gs.has_area_light && !in_object && (le[0] > 0.f || le[1] > 0.f || le[2] > 0.f)) {
+        // a sphere light behind the lights so far: it names the sphere by its 1-based number, and c is the le its material got
+        pbrt_hip_light l{};
+        l.type = PBRT_HIP_LIGHT_SPHERE;
+        for (int i = 0; i < 3; i++) l.c[i] = out->mats[mid].le[i];
+        const uint32_t number = (uint32_t)out->spheres.size();
+        std::memcpy(&l.pad, &number, 4);
+        out->lights.push_back(l);
+      }
       if (gs.material.kd_tex) {  // (u, v) = (phi / 2 pi, 1 - theta / pi) about the WORLD's z axis: a sphere is a centre and a radius here
         bool axes_kept = true;
         for (int i = 0; i < 3; i++)
@@ -1514,6 +1522,23 @@ ParseError parse_scene(const char *text, size_t len, const std::string &base_dir
     }
     if (api.any_normals) {
       api.warn("a scene with a \"projection\" / \"goniometric\" light: the meshes' normals \"N\" are ignored (every mesh renders flat)");
+      api.any_normals = false;
+    }
+  }
+  // the sphere lights under the same two family rules: beside a map the lights leave the list -- their spheres still emit,
+  // unsampled, as every emissive sphere did before 3.25 --, beside mesh normals the normals leave
+  {
+    size_t n_sphere_lights = 0;
+    for (const pbrt_hip_light &l : out->lights) n_sphere_lights += l.type == PBRT_HIP_LIGHT_SPHERE;
+    if (n_sphere_lights && !out->env_rgb.empty()) {
+      api.warn("a scene with an environment map (\"mapname\"): its " + std::to_string(n_sphere_lights) +
+               " sphere light(s) are ignored (the spheres emit but are not sampled by the direct-light estimate)");
+      std::vector<pbrt_hip_light> kept;
+      for (const pbrt_hip_light &l : out->lights)
+        if (l.type != PBRT_HIP_LIGHT_SPHERE) kept.push_back(l);
+      out->lights.swap(kept);
+    } else if (n_sphere_lights && api.any_normals) {
+      api.warn("a scene with a sphere light (an AreaLightSource on a Shape \"sphere\"): the meshes' normals \"N\" are ignored (every mesh renders flat)");
       api.any_normals = false;
     }
   }

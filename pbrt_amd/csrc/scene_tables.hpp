@@ -9,13 +9,15 @@
 //     emissive triangle 3                    {3, p0}      {p1, area}             {p2, 0}             {le, 0}                {n, 0}
 //     spot 5                                 {5, p}       {axis, cos_total}      {cos_start, 0 0 0}  {I, 0}                 0
 //     projection 6, goniometric 7            {type, p}    {M row 0, inv_tan}     {M row 1, sx}       {I, image slot bits}   {M row 2, sy}
+//     sphere 8                               {8, centre}  {r, 0 0 0}             0                   {L, 0}                 0
 //     (p: position; distant: the unit direction towards the light; infinite / env: ignored.  c: I or L; env: the factor on the texels.
 //     area = 0.5 |e1 x e2|, n = (e1 x e2) / |e1 x e2|.  M = world_to_light; image slot: the 0-BASED number of the image's texture slot)
 //   mats      kMatRows x 16 B per material: {type, k} {le, kd_tex}; kd_tex = the 1-based texture number of a matte material, else 0; le = 0
 //             for glass, plastic and substrate, which reuse the public record's `le` for a parameter and do not emit
 //   mat_extra 16 B per material, present when some material is glass, plastic or substrate: glass {Kt, eta}, plastic / substrate {Ks, alpha},
 //             every other material's row {0, 0, 0, 1}
-//   spheres   kSphereRows x 16 B per sphere: {c, r} {material id, 0 0 0}
+//   spheres   kSphereRows x 16 B per sphere: {c, r} {material id, listed, 0 0}; listed = 1 where a sphere light names the
+//             sphere -- the MIS hit side weights its emission --, else 0: an unlisted sphere's rows are what they were before 3.25
 #pragma once
 #include <stdint.h>
 
@@ -40,10 +42,11 @@ enum DevLight : uint32_t {
   kDevLightSpot = 5u,
   kDevLightProjection = 6u,  // the mapped lights, by their record's kind
   kDevLightGonio = 7u,
+  kDevLightSphere = 8u,  // a sphere of the scene as an area light
 };
 // the device word of a light of public type `type` (PBRT_HIP_LIGHT_*, 0 .. 2 unnamed there); map_kind: a mapped light's record's kind
 constexpr uint32_t dev_light_type(uint32_t type, uint32_t map_kind = 0u) {
-  return type == PBRT_HIP_LIGHT_ENVMAP ? (uint32_t)kDevLightEnv : (type == PBRT_HIP_LIGHT_MAPPED ? kDevLightProjection + map_kind : type);
+  return type == PBRT_HIP_LIGHT_ENVMAP ? (uint32_t)kDevLightEnv : (type == PBRT_HIP_LIGHT_MAPPED ? kDevLightProjection + map_kind : type);  // (a sphere light keeps its 8)
 }
 // the types that are taken before sample_light's chain, under PLS, are the table's LARGEST (3 is an emissive triangle, 4 the environment map,
 // which no PLS kernel meets): ONE compare finds them, so a scene without them pays what it paid for the spot light's test alone
@@ -56,6 +59,8 @@ static_assert(dev_light_type(PBRT_HIP_LIGHT_MAPPED, PBRT_HIP_LIGHT_MAP_PROJECTIO
               "a mapped light is 6 + its record's kind");
 static_assert(!dev_light_beyond_chain(kDevLightEnv) && dev_light_beyond_chain(kDevLightSpot) && dev_light_beyond_chain(kDevLightProjection) && dev_light_beyond_chain(kDevLightGonio),
               "spot and mapped lights are the table's largest type words");
+static_assert(dev_light_type(PBRT_HIP_LIGHT_SPHERE) == kDevLightSphere && kDevLightSphere == 8u && dev_light_beyond_chain(kDevLightSphere), "a sphere light keeps its 8, beyond the chain");
+static_assert(dev_light_type(PBRT_HIP_LIGHT_MAPPED, PBRT_HIP_LIGHT_MAP_GONIOMETRIC) < kDevLightSphere, "no mapped light's word reaches the sphere light's");
 
 // ---- the type word of a material's row 0: the public PBRT_HIP_MATERIAL_* value; the predicates the kernels and the host go by ----
 constexpr bool mat_is_matte(uint32_t type) { return type == PBRT_HIP_MATERIAL_MATTE; }
@@ -104,6 +109,14 @@ inline void push_light_mapped(std::vector<float4> *t, const float p[3], const fl
   t->push_back(table_row(c[0], c[1], c[2], table_word(map.image - 1u)));
   t->push_back(table_row(m[6], m[7], m[8], map.sy));
 }
+// a sphere light: the sphere's centre and radius as its row of `spheres` holds them, and the radiance L = the material's le
+inline void push_light_sphere(std::vector<float4> *t, const pbrt_hip_sphere &sp, const float L[3]) {
+  t->push_back(table_row(table_word(kDevLightSphere), sp.c[0], sp.c[1], sp.c[2]));
+  t->push_back(table_row(sp.r, 0, 0, 0));
+  t->push_back(table_row(0, 0, 0, 0));
+  t->push_back(table_row(L[0], L[1], L[2], 0));
+  t->push_back(table_row(0, 0, 0, 0));
+}
 // an emissive triangle: cr = (p1 - p0) x (p2 - p0), len = |cr|; a triangle of no area gets the NaN normal of 0 / 0
 inline void push_light_triangle(std::vector<float4> *t, const float p0[3], const float p1[3], const float p2[3], const float le[3]) {
   const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
@@ -132,5 +145,9 @@ inline void write_sphere(float4 *rows, const pbrt_hip_sphere &sp) {
   rows[0] = table_row(sp.c[0], sp.c[1], sp.c[2], sp.r);
   rows[1] = table_row(table_word(sp.mat), 0, 0, 0);
 }
+// ... and the mark of a sphere that a sphere light names, read by sphere_listed
+inline void mark_sphere_listed(float4 *rows) { rows[1].y = table_word(1u); }
+template <class Scene>
+__host__ __device__ __forceinline__ bool sphere_listed(const Scene &S, uint32_t si) { return table_bits(S.spheres[kSphereRows * si + 1u].y) != 0u; }
 
 }  // namespace pbrt_hip

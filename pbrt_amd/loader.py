@@ -8,7 +8,7 @@ import numpy as np
 
 from ._lib import (SLOT_ENVMAP, SLOT_FILTER, SLOT_IMAGE, SLOT_LIGHT_MAP, SLOT_NORMALS, SLOT_SPOT, EnvMap, ImageTexture, LightMap, Normals, PixelFilter, RenderDesc, SceneDesc,
                    SpotCone, check, lib, read_slot)
-from .api import GLASS, LIGHT_MAPPED, LIGHT_SPOT, PLASTIC, SUBSTRATE, SceneData
+from .api import GLASS, LIGHT_MAPPED, LIGHT_SPHERE, LIGHT_SPOT, PLASTIC, SUBSTRATE, SceneData
 
 
 @dataclass
@@ -89,7 +89,9 @@ def _collect(h):
             P=arr(d.P, 3 * d.n_verts, np.float32).reshape(-1, 3), idx=arr(d.idx, 3 * d.n_tris, np.uint32).reshape(-1, 3),
             mat_id=arr(d.mat_id, d.n_tris, np.uint16),
             materials=np.array([[d.mats[i].type, *d.mats[i].k, *d.mats[i].le] for i in range(d.n_mats)], np.float32).reshape(-1, 7),
-            lights=np.array([[d.lights[i].type, *d.lights[i].p, *d.lights[i].c] for i in range(d.n_lights)], np.float32).reshape(-1, 7),
+            # (a sphere light's `pad` holds the bits of its sphere's 1-based number, DESIGN.md 3.25: the row's first word is the 0-based row)
+            lights=np.array([[d.lights[i].type, *([int(np.array([d.lights[i].pad], np.float32).view(np.uint32)[0]) - 1, 0, 0] if d.lights[i].type == LIGHT_SPHERE
+                                                  else d.lights[i].p), *d.lights[i].c] for i in range(d.n_lights)], np.float32).reshape(-1, 7),
             spheres=np.array([[*d.spheres[i].c, d.spheres[i].r, d.spheres[i].mat] for i in range(d.n_spheres)], np.float32).reshape(-1, 5),
             cam_to_world=np.array(list(d.cam_to_world), np.float32).reshape(4, 4), fov=d.fov, xres=d.xres, yres=d.yres,
             crop=tuple(d.crop),

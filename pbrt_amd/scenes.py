@@ -9,6 +9,7 @@
   plastic_scene       a plastic floor and two plastic spheres in a Cornell-style box (= scenes/plastic_spheres.pbrt)
   substrate_scene     a substrate floor and two substrate spheres in a Cornell-style box (= scenes/substrate_spheres.pbrt)
   spot_scene          a plastic and a matte sphere in a Cornell-style box lit by two spot lights (= scenes/spot_cornell.pbrt)
+  sphere_light_scene  the same box lit by two sphere lamps, with a plastic and a mirror sphere (= scenes/sphere_light_cornell.pbrt)
   projector_scene     the same box lit by a projection light that throws a slide onto the back wall and a goniometric light (DESIGN.md 3.23;
                       = scenes/projector_cornell.pbrt)
   envmap_scene        a matte ground, a glass and a mirror sphere under an environment map (= scenes/envmap_spheres.pbrt)
@@ -396,6 +397,40 @@ def spot_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0)):
         spheres=np.array([[-0.45, 0.15, -0.65, 0.35, BLUE], [0.45, -0.2, -0.65, 0.35, ORANGE]], np.float32),
         cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
     ).normalized()
+
+
+def sphere_light_scene(xres=256, yres=256, crop=(0.0, 1.0, 0.0, 1.0)):
+    """The sphere light's scene, array for array what scenes/sphere_light_cornell.pbrt loads to: spot_scene's box -- white
+    floor, ceiling and back wall, red left and green right walls, no emitter quad in the ceiling -- lit by two sphere lamps: a warm one of
+    radius 0.15 under the ceiling and a small cool one of radius 0.05 beside a blue plastic sphere; a mirror sphere shows both lamps.  A
+    matte vertex and a plastic vertex both sample a sphere light, and a specular path sees the lamps through their material."""
+    from .api import plastic_material, sphere_light
+    WHITE, RED, GREEN, WARM, COOL, BLUE, CHROME = range(7)  # (numbered in the order the scene file's shapes first use them)
+    blue, alpha = plastic_material((0.1, 0.2, 0.6), (0.3, 0.3, 0.3), 0.1)
+    mats = [_mat(MATTE, (0.73, 0.73, 0.73)), _mat(MATTE, (0.65, 0.05, 0.05)), _mat(MATTE, (0.12, 0.45, 0.15)), _mat(MATTE, (0, 0, 0), (20, 16, 10)),
+            _mat(MATTE, (0, 0, 0), (30, 40, 60)), blue, _mat(MIRROR, (0.9, 0.9, 0.9))]
+    V, I, M = [], [], []
+
+    def add(q, m):
+        base = len(V)
+        v, t = _quad(*q)
+        V.extend(v)
+        I.extend([[base + a for a in tri] for tri in t])
+        M.extend([m, m])
+
+    add(((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1)), WHITE)  # floor
+    add(((-1, -1, 1), (-1, 1, 1), (1, 1, 1), (1, -1, 1)), WHITE)      # ceiling
+    add(((-1, 1, -1), (1, 1, -1), (1, 1, 1), (-1, 1, 1)), WHITE)      # back wall (y = +1)
+    add(((-1, -1, -1), (-1, 1, -1), (-1, 1, 1), (-1, -1, 1)), RED)    # left
+    add(((1, -1, -1), (1, -1, 1), (1, 1, 1), (1, 1, -1)), GREEN)      # right
+    sd = SceneData(
+        P=np.array(V, np.float32), idx=np.array(I, np.uint32), mat_id=np.array(M, np.uint16),
+        materials=np.array(mats, np.float32), mat_eta=np.array([1.5, 1.5, 1.5, 1.5, 1.5, alpha, 1.5], np.float32),
+        spheres=np.array([[0.0, 0.0, 0.8, 0.15, WARM], [-0.05, -0.45, -0.6, 0.05, COOL], [-0.45, 0.15, -0.65, 0.35, BLUE], [0.45, -0.2, -0.65, 0.35, CHROME]], np.float32),
+        cam_to_world=_camera((0, -3.6, 0), (0, 0, 0), (0, 0, 1)), fov=40.0, xres=xres, yres=yres, crop=crop,
+    ).normalized()
+    sd.lights = np.array([sphere_light(sd, 0), sphere_light(sd, 1)], np.float32)
+    return sd
 
 
 def procedural_slide(width=64, height=48):

@@ -34,6 +34,9 @@ pub const LIGHT_SPOT: u32 = 5;
 // window's half extents sx, sy (all three 0 for a goniometric map)
 pub const LIGHT_MAPPED: u32 = 6;
 #[repr(C)] pub struct HipLightMap { pub kind: u32 /* = 8 */, pub map_kind: u32, pub image: u32, pub world_to_light: [f32; 9], pub inv_tan: f32, pub sx: f32, pub sy: f32, pub pad: [u32; 1] }
+// kind == LIGHT_SPHERE (8; DESIGN.md 3.25: AreaLightSource "diffuse" on a Shape "sphere"): pad = f32::from_bits(n), n = the 1-based number of the sphere in
+// `spheres`; c = L * scale, bit for bit the `le` of that sphere's material; p is not used (keep it finite)
+pub const LIGHT_SPHERE: u32 = 8;
 #[repr(C)] pub struct HipSphere   { pub c: [f32; 3], pub r: f32, pub mat: u32, pub pad: [u32; 3] }
 #[repr(C)] pub struct HipSceneDesc {
     pub p: *const f32, pub idx: *const u32, pub mat_id: *const u16,
